@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sw2d DG right-hand side + LSERK4 stage on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path: ONE fused RHS + LSERK4 stage over the whole mesh.
@@ -105,6 +105,20 @@ def initial_state(x, y):
     h = 10.0 + np.exp(-10 * x * x - 10 * y * y)
     z = np.zeros_like(h)
     return h, z, z.copy()
+
+
+DUMP_BYTES, DUMP_SEED = 48 << 20, 12345
+
+
+def dump_outputs(out_dir, fields):
+    """--dump-outputs: the (Np, K) float64 fields as <out_dir>/<name>.npy. Beyond DUMP_BYTES in all, the same fixed sample of
+    element columns of every field (seed DUMP_SEED, ascending element index), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    np_, k = next(iter(fields.values())).shape
+    keep = min(k, DUMP_BYTES // (len(fields) * np_ * 8))
+    cols = slice(None) if keep == k else np.sort(np.random.default_rng(DUMP_SEED).choice(k, keep, replace=False))
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a[:, cols], dtype=np.float64))
 
 
 def cpu_baseline(order):
@@ -233,6 +247,10 @@ def run_single(args):
         if prev is not None and abs(cur - prev) <= 0.02 * prev:
             break
         prev = cur
+    if ramp_blocks:
+        # the ramp advanced the state by a number of stages that depends on the clocks: warm-up and timed steps start
+        # from the initial state again, so that every run with the same arguments computes the same thing
+        solver.setState(h, hu, hv)
     solver.lserk4Stages(dt, args.warmup)
     solver.synchronize()
     t0 = time.perf_counter()
@@ -240,6 +258,9 @@ def run_single(args):
     solver.synchronize()
     wall = time.perf_counter() - t0
     _, eta_max = solver.computeDt(CFL)  # raises if the run blew up
+    state = solver.getState()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("h", "hu", "hv"), state)))
     # total mass before / after (walls everywhere: conserved to round-off). Computed only now: NumPy's BLAS
     # threads keep spinning for a while after a product and would compete with the launch thread above.
     V = ctx.V
@@ -248,7 +269,7 @@ def run_single(args):
     def total_mass(hh):
         return float((quad @ hh * ctx.J[0]).sum())
     mass0 = total_mass(h)
-    mass_drift = (total_mass(solver.getState()[0]) - mass0) / mass0
+    mass_drift = (total_mass(state[0]) - mass0) / mass0
     probe_ms = solver.probeStageTraffic(20) if solver.usesAffineGeometry else None
     triad = sw2d.streamTriadGBps(0)
 
@@ -500,15 +521,23 @@ def main():
     ap.add_argument("--nodal-geometry", action="store_true", help="force the per-node-geometry kernels")
     ap.add_argument("--rehearse-world", type=int, default=0,
                     help="one-GPU schedule rehearsal of an N-way split (loop-back exchanges; timing only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state they computed (h, hu, hv) as DIR/<name>.npy, float64; "
+                         "a fixed seeded sample of element columns when the whole state exceeds 48 MiB (one GPU only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     ORDER = args.order
     NX, NY = (int(v) for v in args.cells.lower().split("x"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    distributed = args.gpus > 1 or world > 1 or os.environ.get("BDG_BENCH_FORCE_DISTRIBUTED") == "1"
+    if args.dump_outputs and (args.rehearse_world > 1 or distributed):
+        ap.error("--dump-outputs writes the state of the one-GPU run only")
     if args.rehearse_world > 1:
         run_rehearsal(args)
     elif args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)
-    elif args.gpus > 1 or world > 1 or os.environ.get("BDG_BENCH_FORCE_DISTRIBUTED") == "1":
+    elif distributed:
         run_distributed(args)
     else:
         run_single(args)

@@ -13,20 +13,23 @@
 using namespace blitzdg;
 int main(int argc, char** argv) {
     const std::string mshPath = argc > 1 ? argv[1] : "tests/golden/coarse_box.msh";
+    const std::string dir = argc > 2 ? argv[2] : "."; // where the files it writes go (the test's own temporary directory)
+    const std::string boxMsh = dir + "/asan_box.msh", boxCache = dir + "/asan_box.bdgmesh", badCache = dir + "/asan_bad.bdgmesh",
+                      fieldVtu = dir + "/asan_f.vtu";
     MeshManager m;
     m.readMesh(mshPath);
     m.partitionMesh(3);
-    m.writeMesh("/tmp/asan_box.msh");
+    m.writeMesh(boxMsh);
     MeshManager m2;
-    m2.readMesh("/tmp/asan_box.msh");
+    m2.readMesh(boxMsh);
     {   // binary cache: round trip, then a truncated and a corrupted copy (both must throw, under the sanitizers)
-        m.writeCache("/tmp/asan_box.bdgmesh");
+        m.writeCache(boxCache);
         MeshManager c;
-        c.readCache("/tmp/asan_box.bdgmesh");
+        c.readCache(boxCache);
         if (c.get_NumElements() != m.get_NumElements() || c.get_EToE()[5] != m.get_EToE()[5] ||
             c.get_ElementPartitionMap().size() != m.get_ElementPartitionMap().size())
             return 3;
-        std::FILE* f = std::fopen("/tmp/asan_box.bdgmesh", "rb");
+        std::FILE* f = std::fopen(boxCache.c_str(), "rb");
         std::vector<char> raw(1 << 20);
         const size_t n = std::fread(raw.data(), 1, raw.size(), f);
         std::fclose(f);
@@ -34,10 +37,10 @@ int main(int argc, char** argv) {
         for (int variant = 0; variant < 2; ++variant) {
             std::vector<char> bad(raw.begin(), raw.begin() + (variant == 0 ? n / 2 : n));
             if (variant == 1) bad[n / 3] ^= 0x21;
-            f = std::fopen("/tmp/asan_bad.bdgmesh", "wb");
+            f = std::fopen(badCache.c_str(), "wb");
             std::fwrite(bad.data(), 1, bad.size(), f);
             std::fclose(f);
-            try { c.readCache("/tmp/asan_bad.bdgmesh"); } catch (const std::exception&) { ++refused; }
+            try { c.readCache(badCache); } catch (const std::exception&) { ++refused; }
         }
         if (refused != 2) return 4;
     }
@@ -51,7 +54,7 @@ int main(int argc, char** argv) {
             for (index_type k = 0; k < f.cols(); ++k) f(i, k) = ctx.x()(i, k) + 2 * ctx.y()(i, k);
         nodes.splitElements(ctx.x(), ctx.y(), f, xn, yn, fn);
         VtkOutputter out(nodes);
-        out.writeFieldToFile("/tmp/asan_f.vtu", f, "f");
+        out.writeFieldToFile(fieldVtu, f, "f");
         index_vector_type bc = m2.get_BCType();
         nodes.buildBCHash(bc);
     }
@@ -94,7 +97,6 @@ int main(int argc, char** argv) {
     index_type steps = 0;
     const real_type err = advec1d::run(4, 30, -1.0, 4.0, 0.1, 0.8, 2.0, &steps);
     std::printf("host check ok: K=%d, advec1d err %.3e in %d steps\n", box.get_NumElements(), err, steps);
-    std::remove("/tmp/asan_box.msh");
-    std::remove("/tmp/asan_f.vtu");
+    for (const std::string* p : {&boxMsh, &boxCache, &badCache, &fieldVtu}) std::remove(p->c_str());
     return 0;
 }

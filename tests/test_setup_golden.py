@@ -359,7 +359,7 @@ def test_host_setup_code_is_clean_under_address_and_ub_sanitizers(tmp_path):
     if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
         pytest.skip("sanitizer runtime not installed")
     assert build.returncode == 0, build.stderr[-3000:]
-    run = subprocess.run([exe, os.path.join(root, "tests", "golden", "coarse_box.msh")], capture_output=True, text=True,
+    run = subprocess.run([exe, os.path.join(root, "tests", "golden", "coarse_box.msh"), str(tmp_path)], capture_output=True, text=True,
                          timeout=600, env=dict(os.environ, OMP_NUM_THREADS="4", ASAN_OPTIONS="detect_leaks=1"), cwd=str(tmp_path))
     assert run.returncode == 0 and "host check ok" in run.stdout, run.stdout[-2000:] + run.stderr[-4000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
