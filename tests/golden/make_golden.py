@@ -42,6 +42,13 @@ Writes
   advec1d_rhs_N4_K100.npz   advec1dComputeRHS(u, c, nodes1d) of the reference SCRIPT advec1d.py:12-39
   sw2d_rhsC_<case>.npz      sw2dComputeRHS(h,hu,hv,hN,g,H,f,ctx) of the reference SCRIPT sw2d.py:37-146
                             ("variant C"), its two function definitions compiled on their own
+  regimes_<family>_<case>.npz
+                            the same reference functions (family A: sw2dComputeRHS with zero sources; D: with the
+                            sources of the named fixture; C: the script's function; curved: sw2dComputeRHS_curved) on the
+                            states of regime_fields -- a depth that jumps at every face, supercritical flow, deep water,
+                            per-element depth contrast -- on the tables of an existing fixture, whose name it stores
+                            (`tables`); only the states ("<regime>__h", ...; float32, exact) and outputs
+                            ("<regime>__rhs1", ...) are kept
 """
 import os
 import re
@@ -104,6 +111,117 @@ def seeded_fields(x, y, seed=0):
     hu = 0.1 * rng.standard_normal(x.shape)
     hv = 0.1 * rng.standard_normal(x.shape)
     return h, hu, hv
+
+
+REGIMES = ("jumpy", "supercritical", "deep", "contrast")
+
+
+def regime_fields(x, y, regime, seed=0):
+    """tests/regimes.py::regime_fields (same draws): h > 0 everywhere, rounded to float32 values.
+      jumpy          the parity state with 0.5 N(0,1) added to h per node: the depth jumps at every face
+      supercritical  h in [0.05, 0.1], u and v of 1..2 with random signs
+      deep           h = 4000 +- 50, hu, hv ~ 20 N(0,1)
+      contrast       h constant per element, 10^U(0, 1.5), O(1) velocities"""
+    rng = np.random.default_rng([seed, REGIMES.index(regime)])
+    shape = np.shape(x)
+    if regime == "jumpy":
+        h, hu, hv = seeded_fields(x, y, seed)
+        h = h + 0.5 * rng.standard_normal(shape)
+    elif regime == "supercritical":
+        h = rng.uniform(0.05, 0.1, shape)
+        u = rng.choice([-1.0, 1.0], shape) * rng.uniform(1.0, 2.0, shape)
+        v = rng.choice([-1.0, 1.0], shape) * rng.uniform(1.0, 2.0, shape)
+        hu, hv = h * u, h * v
+    elif regime == "deep":
+        h = 4000.0 + rng.uniform(-50.0, 50.0, shape)
+        hu, hv = 20.0 * rng.standard_normal(shape), 20.0 * rng.standard_normal(shape)
+    elif regime == "contrast":
+        h = np.tile(10.0 ** rng.uniform(0.0, 1.5, shape[1]), (shape[0], 1))
+        hu, hv = h * rng.standard_normal(shape), h * rng.standard_normal(shape)
+    else:
+        raise ValueError(regime)
+    h, hu, hv = (np.asarray(a, dtype=np.float32).astype(np.float64) for a in (h, hu, hv))
+    assert h.min() > 0
+    return h, hu, hv
+
+
+def regime_tracer(h, x, y, seed=0):
+    """A noisy tracer hN for the four-field regime fixtures (float32 values)."""
+    rng = np.random.default_rng([seed, 99])
+    hN = h * (0.5 + 0.3 * np.sin(2 * x) * np.cos(3 * y) + 0.05 * rng.standard_normal(np.shape(x)))
+    return np.asarray(hN, dtype=np.float32).astype(np.float64)
+
+
+def regime_case(family, fixture, regimes):
+    """regimes_<family>_<case>.npz: the reference function of `family` on regime states over the tables of the existing
+    fixture tests/golden/<fixture>.npz."""
+    sys.path.insert(0, REF)
+    if not hasattr(np, "float"):
+        np.float = float
+    from swhelpers.rhs import sw2dComputeRHS, sw2dComputeRHS_curved
+    d = np.load(os.path.join(HERE, fixture + ".npz"))
+    case = fixture.split("_", 2)[2]
+    if family == "curved":
+        case = fixture[len("sw2d_rhs_curved_"):]
+    x, y = d["x"], d["y"]
+    out = {"tables": fixture}
+    for regime in regimes:
+        h, hu, hv = regime_fields(x, y, regime)
+        hN = regime_tracer(h, x, y)
+        if family in ("A", "D", "C"):
+            order = int(d["order"])
+            mapW = [int(i) for i in d["mapW"]]
+            ref_ctx = types.SimpleNamespace(BCmap={3: mapW}, nx=d["nx"], ny=d["ny"], rx=d["rx"], sx=d["sx"], ry=d["ry"],
+                                            sy=d["sy"], Dr=d["Dr"], Ds=d["Ds"], numFacePoints=order + 1,
+                                            numElements=d["rx"].shape[1], numFaces=3, Lift=d["Lift"], Fscale=d["Fscale"],
+                                            vmapM=d["vmapM"], vmapP=d["vmapP"])
+        if family == "A":
+            z = np.zeros_like(h)
+            r = sw2dComputeRHS(h, hu, hv, z.copy(), z, z, float(d["g"]), 10.0 + z, 0.0, 0.0, ref_ctx, d["vmapM"], d["vmapP"])
+            assert np.all(r[3] == 0.0)
+            r, state = r[:3], dict(h=h, hu=hu, hv=hv)
+        elif family == "D":
+            r = sw2dComputeRHS(h, hu, hv, hN, d["zx"], d["zy"], float(d["g"]), d["H"], d["f"], float(d["CD"]), ref_ctx,
+                               d["vmapM"], d["vmapP"])
+            state = dict(h=h, hu=hu, hv=hv, hN=hN)
+        elif family == "C":
+            scope = script_functions(os.path.join(REF, "sw2d.py"), ("sw2dComputeFluxes", "sw2dComputeRHS"))
+            scope["K"] = d["rx"].shape[1]
+            r = scope["sw2dComputeRHS"](h, hu, hv, hN, float(d["g"]), d["H"], float(d["f"]), ref_ctx)
+            state = dict(h=h, hu=hu, hv=hv, hN=hN)
+        else:
+            ref_ctx = types.SimpleNamespace(numLocalPoints=d["V"].shape[0], numElements=d["J"].shape[1], V=d["V"])
+            ref_cub = types.SimpleNamespace(V=d["cubV"], Dr=d["cubDr"], Ds=d["cubDs"], W=d["cubW"], rx=d["cubrx"], ry=d["cubry"],
+                                            sx=d["cubsx"], sy=d["cubsy"], MMChol=d["MMChol"])
+            ref_gauss = types.SimpleNamespace(nx=d["gnx"], ny=d["gny"], BCmap={3: [int(i) for i in d["gmapW"]]},
+                                              Interp=d["gInterp"], W=d["gW"])
+            r = sw2dComputeRHS_curved(h, hu, hv, hN, d["zx"], d["zy"], float(d["g"]), d["H"], float(d["f"]), d["CD"], ref_ctx,
+                                      ref_cub, ref_gauss, d["curvedEls"], d["J"], d["gmapM"].copy(), d["gmapP"].copy())
+            state = dict(h=h, hu=hu, hv=hv, hN=hN)
+        for k, v in state.items():
+            out[f"{regime}__{k}"] = v.astype(np.float32)
+        for i, v in enumerate(r):
+            assert np.all(np.isfinite(v))
+            out[f"{regime}__rhs{i + 1}"] = v
+    path = os.path.join(HERE, f"regimes_{family}_{case}.npz")
+    np.savez_compressed(path, **out)
+    print(f"regimes_{family}_{case}.npz ({fixture}): {', '.join(regimes)}; {os.path.getsize(path) / 1e3:.0f} kB")
+
+
+def regime_cases():
+    for case in ("coarse_box_N1", "coarse_box_N2", "coarse_box_N3", "coarse_box_N4", "coarse_box_N5", "coarse_box_N6",
+                 "box6x5_shuffled_N4", "box2x2_N8"):
+        regime_case("A", f"sw2d_rhs_{case}", REGIMES)
+    regime_case("A", "sw2d_rhs4_box6x5_shuffled_N7", REGIMES)     # the N = 7 pin of variant A, on variant D's tables
+    for case in ("coarse_box_N2", "coarse_box_N4", "coarse_box_N6", "box6x5_shuffled_N3", "box6x5_shuffled_N5",
+                 "box6x5_shuffled_N7", "box2x2_N8"):
+        regime_case("D", f"sw2d_rhs4_{case}", ("jumpy", "supercritical"))
+    for case in ("box7x6_N2", "box6x5_N4", "box5x4_N6", "box3x2_N8"):
+        regime_case("D", f"sw2d_rhs4n_{case}", ("jumpy", "supercritical"))
+    for case in ("coarse_box_N3", "box6x5_shuffled_N6"):
+        regime_case("C", f"sw2d_rhsC_{case}", ("jumpy",))
+    for case in ("coarse_box_N3", "coarse_box_N4", "box6x5_periodic_N2", "box6x5_shuffled_N6", "box3x2_N8"):
+        regime_case("curved", f"sw2d_rhs_curved_{case}", ("jumpy",))
 
 
 def rhs_case(name, mesh, order, g=9.81):
@@ -571,6 +689,7 @@ def main():
     curved_cases()
     degenerate_b_cases()
     nodal_cases()
+    regime_cases()
 
 
 def nodal_cases():
@@ -628,5 +747,7 @@ if __name__ == "__main__":
         nodal_cases()
     elif len(sys.argv) > 1 and sys.argv[1] == "degenerate_b":
         degenerate_b_cases()
+    elif len(sys.argv) > 1 and sys.argv[1] == "regimes":
+        regime_cases()
     else:
         main()

@@ -391,3 +391,63 @@ def test_numpy_restatement_reproduces_the_reference_at_production_gravity():
         ref = [d[f"rhs{i}"] for i in (1, 2, 3, 4)]
         scale = max(np.abs(r).max() for r in ref)
         assert max(np.abs(a - b).max() for a, b in zip(got, ref)) <= 1e-13 * scale
+
+
+# ---- the regime fixtures (tests/golden/regimes_*.npz): the reference functions on states where every term of the
+# ---- Lax-Friedrichs flux matters -- a depth that jumps at every face, supercritical flow, deep water, per-element contrast
+
+REGIME_IDS = [(fam, case) for fam, cases in __import__("regimes").REGIME_CASES.items() for case in cases]
+
+
+def _oracle_rhs(family, t, s):
+    from oracle import oracle_np as onp
+    q = (s["h"], s["hu"], s["hv"])
+    if family == "A":
+        return oracle_from(t, g=float(t["g"])).rhs(*q)
+    if family == "D":
+        return onp.sw2d_rhs4(*q, s["hN"], t["zx"], t["zy"], float(t["g"]), t["f"], float(t["CD"]), t)
+    if family == "C":
+        return onp.sw2d_rhs_c(*q, s["hN"], float(t["g"]), float(t["f"]), t)
+    return onp.sw2d_rhs_curved(*q, s["hN"], t["zx"], t["zy"], float(t["g"]), float(t["f"]), t["CD"], t)
+
+
+@pytest.mark.parametrize("family,case", REGIME_IDS, ids=[f"{f}-{c}" for f, c in REGIME_IDS])
+def test_oracle_reproduces_the_regime_fixtures_field_by_field(family, case):
+    """The checkers (the C oracle for variant A, the NumPy restatements for C, D and curved) against the reference functions'
+    output on every regime, each field against its own size (measured: <= 8e-15 on the deep state, where g h^2 / 2 ~ 8e7
+    cancels; 0 for the NumPy restatements, which do the reference's operations in its order)."""
+    from regimes import assert_fields_close, load_regimes
+    t, states = load_regimes(family, case)
+    assert set(states) == {"A": {"jumpy", "supercritical", "deep", "contrast"}, "D": {"jumpy", "supercritical"}}.get(family, {"jumpy"})
+    for regime, s in states.items():
+        ref = [s[f"rhs{i}"] for i in range(1, 4 if family == "A" else 5)]
+        assert_fields_close(_oracle_rhs(family, t, s), ref, 1e-13, what=f"{family} {case} {regime}")
+
+
+@pytest.mark.parametrize("family,case", REGIME_IDS, ids=[f"{f}-{c}" for f, c in REGIME_IDS])
+def test_regime_fixtures_are_discontinuous_and_made_by_regime_fields(family, case):
+    """Every regime state jumps across the faces: on its own tables, max |hM - hP| over the interior face nodes (the Gauss
+    points of the curved faces) is at least 1e-2 of the mean depth -- a fixture regenerated from the smooth parity state
+    (seeded_fields: |hM - hP| ~ 1e-15) fails here. And the states are what regimes.regime_fields draws on those tables."""
+    from regimes import load_regimes, regime_fields
+    t, states = load_regimes(family, case)
+    for regime, s in states.items():
+        h = s["h"]
+        assert h.min() > 0
+        if family == "curved":
+            hg = (t["gInterp"] @ h).flatten("F")
+            mM, mP = np.asarray(t["gmapM"]).reshape(-1), np.asarray(t["gmapP"]).reshape(-1)
+            wall = np.asarray(t["gmapW"])
+        else:
+            hg = h.flatten("F")
+            mM, mP = np.asarray(t["vmapM"]).reshape(-1), np.asarray(t["vmapP"]).reshape(-1)
+            wall = np.asarray(t["mapW"])
+        interior = np.ones(mM.size, dtype=bool)
+        interior[wall] = False
+        interior &= mM != mP
+        assert interior.sum() > 0
+        jump = np.abs(hg[mM[interior]] - hg[mP[interior]]).max()
+        assert jump >= 1e-2 * h.mean(), (regime, jump, h.mean())
+        gen = regime_fields(t["x"], t["y"], regime)
+        for a, b in zip(gen, (s["h"], s["hu"], s["hv"])):
+            assert np.array_equal(a, b), regime

@@ -19,6 +19,7 @@ import blitzdg_amd.pyblitzdg as dg
 from blitzdg_amd import sw2d
 from blitzdg_amd._capi import BdgError, NumericalInstability
 from conftest import launch, load_case, oracle_from, relmax, seeded_fields, tables_from_nodes
+from regimes import assert_fields_close
 
 pytestmark = pytest.mark.gpu
 
@@ -42,13 +43,11 @@ def test_rhs_matches_reference_fixture(case, flags):
     s = solver_from_case(d, flags)  # NODAL_GEOMETRY: the matrix-core kernel with per-node geometry, every order
     assert s.usesAffineGeometry == (not flags & sw2d.NODAL_GEOMETRY)  # all fixtures are straight-sided
     r = s.computeRHS(d["h"], d["hu"], d["hv"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3))
-    for i in range(3):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    ref = [d[f"rhs{i}"] for i in (1, 2, 3)]
+    assert_fields_close(r, ref, RHS_TOL)
     # and the filtered variant against Filter @ reference RHS
     rf = s.computeRHS(d["h"], d["hu"], d["hv"], filter=True)
-    for i in range(3):
-        assert np.abs(rf[i] - d["Filter"] @ d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    assert_fields_close(rf, [d["Filter"] @ x for x in ref], RHS_TOL)
 
 
 def test_drop_in_compute_rhs_signature(coarse_mesh):
@@ -59,9 +58,8 @@ def test_drop_in_compute_rhs_signature(coarse_mesh):
     h, hu, hv = seeded_fields(t["x"], t["y"])
     r = sw2d.computeRHS(h, hu, hv, 9.81, nodes)
     ref = oracle_from(t).rhs(h, hu, hv)
-    scale = max(np.abs(x).max() for x in ref)
     assert all(x.shape == (10, 40) and x.dtype == np.float64 for x in r)
-    assert max(np.abs(a - b).max() for a, b in zip(r, ref)) / scale < RHS_TOL
+    assert_fields_close(r, ref, RHS_TOL)
 
 
 def test_automatic_renumbering_decision():
@@ -180,9 +178,7 @@ def test_non_affine_tables_take_the_nodal_path(coarse_mesh):
     assert not s.usesAffineGeometry
     h, hu, hv = seeded_fields(t["x"], t["y"])
     ref = oracle_from(t).rhs(h, hu, hv)
-    scale = max(np.abs(x).max() for x in ref)
-    r = s.computeRHS(h, hu, hv)
-    assert max(np.abs(a - b).max() for a, b in zip(r, ref)) / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL)
 
 
 def test_instability_is_reported(coarse_mesh):
@@ -232,13 +228,11 @@ def test_medium_box_meshes_vs_oracle(order, nx, ny, seed):
     o = oracle_from(t, threads=4)
     h, hu, hv = seeded_fields(t["x"], t["y"])
     ref = o.rhs(h, hu, hv)
-    scale = max(np.abs(x).max() for x in ref)
     dt = 0.5 * o.dt(h, hu, hv, 0.65, order)
     ref_state = o.step_lserk4(h, hu, hv, dt, 2)
     for flags in (0, sw2d.REORDER, sw2d.KEEP_ORDER, sw2d.NODAL_GEOMETRY):
         s = sw2d.Sw2dSolver(nodes=nodes, flags=flags)
-        r = s.computeRHS(h, hu, hv)
-        assert max(np.abs(a - b).max() for a, b in zip(r, ref)) / scale < RHS_TOL
+        assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL, what=f"flags={flags}")
         s.setState(h, hu, hv)
         s.stepLSERK4(dt, 2)
         for a, b in zip(s.getState(), ref_state):
@@ -407,10 +401,7 @@ def test_variant_d_matches_the_reference_function_output(case):
     zx, zy, f, vmapM, vmapP = d["zx"], d["zy"], d["f"], d["vmapM"], d["vmapP"]
     r = sw2dComputeRHS(d["h"], d["hu"], d["hv"], d["hN"], zx, zy, float(d["g"]), d["H"], f, float(d["CD"]), ctx, vmapM,
                        vmapP)
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in range(1, 5))
-    for i in range(4):
-        assert r[i].shape == d["h"].shape
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL, f"RHS{i + 1}"
+    assert_fields_close(r, [d[f"rhs{i}"] for i in range(1, 5)], RHS_TOL)
 
 
 @pytest.mark.parametrize("case,rolled", [("coarse_box_N2", False), ("coarse_box_N4", False), ("coarse_box_N4", True),
@@ -432,10 +423,7 @@ def test_variant_d_filtered_rhs_and_lserk4_vs_numpy_oracle(case, rolled, monkeyp
     s = sw2d.Sw2dSolver(tables=t, g=g, fields=4, sources={"zx": d["zx"], "zy": d["zy"], "f": f0, "CD": CD})
     q = [d["h"], d["hu"], d["hv"], d["hN"]]
     ref = sw2d_rhs4(*q, d["zx"], d["zy"], g, f0, CD, d)
-    scale = max(np.abs(x).max() for x in ref)
-    got = s.computeRHS4(*q, filter=True)
-    for a, b in zip(got, ref):
-        assert np.abs(a - d["Filter"] @ b).max() / scale < RHS_TOL
+    assert_fields_close(s.computeRHS4(*q, filter=True), [d["Filter"] @ b for b in ref], RHS_TOL)
     # three-field entry points refuse a four-field solver
     with pytest.raises(BdgError, match="4 fields"):
         s.setState(q[0], q[1], q[2])
@@ -463,9 +451,8 @@ def test_tracer_only_equals_three_field_solver(coarse_mesh):
     s4 = sw2d.Sw2dSolver(tables=t, fields=4)
     r4 = s4.computeRHS4(h, hu, hv, 0.25 * h)
     r3 = sw2d.Sw2dSolver(tables=t).computeRHS(h, hu, hv)
-    scale = max(np.abs(x).max() for x in r3)
-    assert max(np.abs(a - b).max() for a, b in zip(r4[:3], r3)) / scale < RHS_TOL
-    assert np.abs(r4[3] - 0.25 * r4[0]).max() / scale < RHS_TOL
+    assert_fields_close(r4[:3], r3, RHS_TOL)
+    assert_fields_close([r4[3]], [0.25 * r4[0]], RHS_TOL)
 
 
 @pytest.mark.parametrize("order,flags", [(3, 0), (3, sw2d.NODAL_GEOMETRY), (6, 0), (8, 0)])
@@ -511,21 +498,19 @@ def test_variant_b_rhs_vs_oracle(order, coarse_mesh):
     Hx, Hy = nodes.bedSlopes(e["H"])
     s = _variant_b_solver(nodes, e, Hx, Hy)
     ref = onp.sw2d_rhs_b(e["h"], e["hu"], e["hv"], e["H"], Hx, Hy, 9.81, e["f"], e["CD"], e["time"], t, e["mapO"])
-    scale = max(np.abs(x).max() for x in ref)
-    r = s.computeRHS(e["h"], e["hu"], e["hv"])
-    assert max(np.abs(a - b).max() for a, b in zip(r, ref)) / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(e["h"], e["hu"], e["hv"]), ref, RHS_TOL)
     # the speed pass: same maximum as the restatement's (contraction-free arithmetic; Newton reciprocal)
     col = lambda a: a.flatten("F")  # noqa: E731
     assert s.globalSpeed > np.sqrt(9.81 * e["h"].min())
     rf = s.computeRHS(e["h"], e["hu"], e["hv"], filter=True)
-    assert max(np.abs(a - t["Filter"] @ b).max() for a, b in zip(rf, ref)) / scale < RHS_TOL
+    assert_fields_close(rf, [t["Filter"] @ b for b in ref], RHS_TOL)
     # a different tide phase changes the answer, and matches again
     s.time = e["time"] + 5000.0
     ref2 = onp.sw2d_rhs_b(e["h"], e["hu"], e["hv"], e["H"], Hx, Hy, 9.81, e["f"], e["CD"], e["time"] + 5000.0, t,
                           e["mapO"])
     r2 = s.computeRHS(e["h"], e["hu"], e["hv"])
     assert np.abs(ref2[0] - ref[0]).max() > 1e-6
-    assert max(np.abs(a - b).max() for a, b in zip(r2, ref2)) / scale < RHS_TOL
+    assert_fields_close(r2, ref2, RHS_TOL)
     del col
 
 
@@ -540,16 +525,16 @@ def test_variant_b_still_water_over_a_bed_that_jumps_between_elements_stays_stil
     H = np.tile(9.0 + 3.0 * np.random.default_rng(4).random(K), (t["x"].shape[0], 1))
     zero = 0 * H
     moving = _variant_b_solver(nodes, e, *nodes.bedSlopes(e["H"])).computeRHS(e["h"], e["hu"], e["hv"])
-    scale = max(np.abs(x).max() for x in moving)
+    moving_max = max(np.abs(x).max() for x in moving)          # the size of a moving state's RHS: what "at rest" is measured by
     for flags in (0, sw2d.NODAL_GEOMETRY):
         s = sw2d.Sw2dSolver(nodes=nodes, flags=flags)
         s.enableVariantB(H, zero, zero, CD=e["CD"], f=e["f"])              # closed basin: no tide enters
         rest = s.computeRHS(H + 0.25, zero, zero)
-        assert max(np.abs(x).max() for x in rest) < 1e-13 * scale
-        assert max(np.abs(x).max() for x in s.computeRHS(H + 0.25, zero, zero, filter=True)) < 1e-13 * scale
+        assert max(np.abs(x).max() for x in rest) < 1e-13 * moving_max
+        assert max(np.abs(x).max() for x in s.computeRHS(H + 0.25, zero, zero, filter=True)) < 1e-13 * moving_max
         h = H + 0.25
         h[:, K // 2] += 0.01
-        assert max(np.abs(x).max() for x in s.computeRHS(h, zero, zero)) > 1e-6 * scale
+        assert max(np.abs(x).max() for x in s.computeRHS(h, zero, zero)) > 1e-6 * moving_max
         s.setState(H + 0.25, zero, zero)                                    # and it stays still through the time stepping
         dt = 0.2 * s.computeDt(0.5)[0]
         s.lserk4Stages(dt, 10)
@@ -565,9 +550,9 @@ def test_variant_b_still_water_over_a_bed_that_jumps_between_elements_stays_stil
         tb.time = e["time"]
         eta = onp.tide_elevation(e["time"])
         assert abs(eta) > 0.1
-        assert max(np.abs(x).max() for x in tb.computeRHS(H + eta, zero, zero)) < 1e-13 * scale
+        assert max(np.abs(x).max() for x in tb.computeRHS(H + eta, zero, zero)) < 1e-13 * moving_max
         off = tb.computeRHS(H + eta + 0.05, zero, zero)
-        touched = np.unique(np.nonzero(np.abs(off[0]) > 1e-9 * scale)[1])
+        touched = np.unique(np.nonzero(np.abs(off[0]) > 1e-9 * moving_max)[1])
         on_boundary = np.unique(t["vmapM"].reshape(-1)[e["mapO"]] // t["x"].shape[0])
         assert len(touched) > 0 and set(touched) <= set(on_boundary)
         tb.close()
@@ -585,10 +570,7 @@ def test_variant_b_matches_the_reference_function_where_it_degenerates_to_it(cas
     s = solver_from_case(d)
     z = np.zeros_like(d["h"])
     s.enableVariantB(d["H"], z, z, mapO=(), CD=0.0, f=float(d["f"]))
-    r = s.computeRHS(d["h"], d["hu"], d["hv"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3))
-    for i in range(3):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(d["h"], d["hu"], d["hv"]), [d[f"rhs{i}"] for i in (1, 2, 3)], RHS_TOL)
     assert abs(s.globalSpeed - (0.8 + np.sqrt(float(d["g"]) * 10.0))) < 1e-12 * s.globalSpeed
 
 
@@ -604,9 +586,13 @@ def test_variant_b_matches_the_reference_function_over_a_continuous_bed(case, ta
     s = solver_from_case(d)
     s.enableVariantB(d["H"], d["Hx"], d["Hy"], mapO=(), CD=float(d["CD"]), f=float(d["f"]))
     r = s.computeRHS(d["h"], d["hu"], d["hv"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3))
-    for i in range(3):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    ref = [d[f"rhs{i}"] for i in (1, 2, 3)]
+    assert_fields_close(r[:1], ref[:1], RHS_TOL, what="mass")
+    # v = 0 here: RHS3 (|RHS3| ~ 55) is what is left of a momentum vector of size |RHS2| ~ 3e4 .. 8e4 once the pressure gradient and
+    # the bed slope cancel, and the kernels' round-off of that vector lands in both components alike (measured on the MI355X: the same
+    # absolute error, 6e-11 .. 1.7e-9, in RHS2 and RHS3, 1.5e-14 of |RHS2|). The y component is held to the momentum vector's size.
+    momentum = max(np.abs(ref[1]).max(), np.abs(ref[2]).max())
+    assert_fields_close(r[1:], ref[1:], RHS_TOL, floor=momentum, what="momentum")
     assert abs(s.globalSpeed - float(d["c0"])) < 1e-12 * s.globalSpeed
 
 
@@ -655,8 +641,7 @@ def test_variant_b_medium_mesh_properties():
     s2 = _variant_b_solver(nodes, e, Hx, Hy)
     ref = onp.sw2d_rhs_b(e["h"], e["hu"], e["hv"], e["H"], Hx, Hy, 9.81, e["f"], e["CD"], e["time"], t, e["mapO"])
     r2 = s2.computeRHS(e["h"], e["hu"], e["hv"])
-    scale = max(np.abs(x).max() for x in ref)
-    assert max(np.abs(a - b).max() for a, b in zip(r2, ref)) / scale < RHS_TOL
+    assert_fields_close(r2, ref, RHS_TOL)
 
 
 def test_variant_b_error_paths(coarse_mesh):
@@ -671,7 +656,7 @@ def test_variant_b_error_paths(coarse_mesh):
         sol.time = e["time"]
     assert not sn.usesAffineGeometry and sa.usesAffineGeometry
     rn, ra = sn.computeRHS(e["h"], e["hu"], e["hv"]), sa.computeRHS(e["h"], e["hu"], e["hv"])
-    assert max(np.abs(a - b).max() for a, b in zip(rn, ra)) < RHS_TOL * max(np.abs(b).max() for b in ra)
+    assert_fields_close(rn, ra, RHS_TOL)
     s = sw2d.Sw2dSolver(nodes=nodes)
     with pytest.raises(BdgError, match="variant B is not enabled"):
         s.globalSpeed
@@ -759,13 +744,10 @@ def test_every_affine_kernel_variant_matches_the_reference_fixture(variant, case
     monkeypatch.setenv("BDG_SW2D_AFFINE_VARIANT", str(variant))
     d = load_case(case)
     s = solver_from_case(d)
-    r = s.computeRHS(d["h"], d["hu"], d["hv"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3))
-    for i in range(3):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    ref = [d[f"rhs{i}"] for i in (1, 2, 3)]
+    assert_fields_close(s.computeRHS(d["h"], d["hu"], d["hv"]), ref, RHS_TOL)
     rf = s.computeRHS(d["h"], d["hu"], d["hv"], filter=True)     # pre-filtered operator image
-    for i in range(3):
-        assert np.abs(rf[i] - d["Filter"] @ d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    assert_fields_close(rf, [d["Filter"] @ x for x in ref], RHS_TOL)
     o = oracle_from(d)
     dt = 0.5 * o.dt(d["h"], d["hu"], d["hv"], 0.65, int(d["order"]))
     s.setState(d["h"], d["hu"], d["hv"])
@@ -819,11 +801,8 @@ def test_non_affine_tables_on_the_matrix_core_kernel(order, nx, ny, vector, monk
     o = oracle_from(t, threads=4)
     h, hu, hv = seeded_fields(x, y, seed=order)
     ref = o.rhs(h, hu, hv)
-    scale = max(np.abs(r).max() for r in ref)
-    got = s.computeRHS(h, hu, hv)
-    assert max(np.abs(a - b).max() for a, b in zip(got, ref)) / scale < RHS_TOL
-    gotf = s.computeRHS(h, hu, hv, filter=True)
-    assert max(np.abs(a - t["Filter"] @ b).max() for a, b in zip(gotf, ref)) / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL)
+    assert_fields_close(s.computeRHS(h, hu, hv, filter=True), [t["Filter"] @ b for b in ref], RHS_TOL)
     dt = 0.3 * o.dt(h, hu, hv, 0.65, order)
     s.setState(h, hu, hv)
     s.lserk4Stages(dt, 9)
@@ -857,17 +836,14 @@ def test_variant_d_on_per_node_geometry_matches_the_reference_function(case):
                                 numElements=d["rx"].shape[1], numFaces=3, Lift=d["Lift"], Fscale=d["Fscale"])
     g, CD = float(d["g"]), float(d["CD"])
     r = sw2dComputeRHS(d["h"], d["hu"], d["hv"], d["hN"], d["zx"], d["zy"], g, d["H"], d["f"], CD, ctx, d["vmapM"], d["vmapP"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in range(1, 5))
-    for i in range(4):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL, f"RHS{i + 1}"
+    assert_fields_close(r, [d[f"rhs{i}"] for i in range(1, 5)], RHS_TOL)
     t = {k: d[k] for k in ("Dr", "Ds", "Lift", "Filter", "rx", "sx", "ry", "sy", "nx", "ny", "Fscale", "vmapM", "vmapP", "mapW")}
     t["order"] = int(d["order"])
     s = sw2d.Sw2dSolver(tables=t, g=g, fields=4, sources={"zx": d["zx"], "zy": d["zy"], "f": d["f"], "CD": CD}, flags=sw2d.KEEP_ORDER)
     assert not s.usesAffineGeometry
     q = [d["h"], d["hu"], d["hv"], d["hN"]]
     ref = [d[f"rhs{i}"] for i in range(1, 5)]
-    for a, b in zip(s.computeRHS4(*q, filter=True), ref):
-        assert np.abs(a - d["Filter"] @ b).max() / scale < RHS_TOL
+    assert_fields_close(s.computeRHS4(*q, filter=True), [d["Filter"] @ b for b in ref], RHS_TOL)
     a_, b_ = lserk4_coefficients()
     dt = 2e-4
     s.setState4(*q)
@@ -923,9 +899,7 @@ def test_variant_b_on_per_node_geometry_matches_the_oracle(case):
     s.enableVariantB(H, Hx, Hy, mapO=mapO, CD=CD, f=f, sponge=sponge)
     s.time = time
     ref = onp.sw2d_rhs_b(h, hu, hv, H, Hx, Hy, g, f, CD, time, t, mapO)
-    scale = max(np.abs(r).max() for r in ref)
-    got = s.computeRHS(h, hu, hv)
-    assert max(np.abs(a - b).max() for a, b in zip(got, ref)) / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL)
     s.setState(h, hu, hv)
     dt = 0.2 * s.computeDt(0.25)[0]
     s.stepSSPRK2(dt, 3)
@@ -977,9 +951,7 @@ def test_variant_c_script_signature_matches_the_reference_function_output(case):
                                                       "vmapM", "vmapP")},
                                 BCmap={3: d["mapW"].tolist()}, numFacePoints=int(d["order"]) + 1)
     r = sw2d.sw2dComputeRHS(d["h"], d["hu"], d["hv"], d["hN"], float(d["g"]), d["H"], float(d["f"]), ctx)
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3, 4))
-    for i in range(4):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    assert_fields_close(r, [d[f"rhs{i}"] for i in (1, 2, 3, 4)], RHS_TOL)
 
 
 def test_python_driver_sw2d_tracer_matches_oracle_replay():
@@ -1007,9 +979,9 @@ def test_python_driver_sw2d_tracer_matches_oracle_replay():
         q = [a + dt * b for a, b in zip(q, r)]
     # momentum here is ~1e-4 while the fluxes it is integrated from are O(g h^2): measure the error
     # against the natural momentum scale h*sqrt(g h), not against the tiny momentum itself
-    scale = 10.0 * np.sqrt(g * 10.0)
+    momentum_scale = 10.0 * np.sqrt(g * 10.0)
     for a, b in zip(solver.getState4(), q):
-        assert np.abs(a - b).max() / max(np.abs(b).max(), scale) < STATE_TOL
+        assert np.abs(a - b).max() / max(np.abs(b).max(), momentum_scale) < STATE_TOL
     assert np.abs(q[1]).max() > 1e-4
 
 
@@ -1100,13 +1072,11 @@ def test_variant_b_rolled_kernels_as_cross_check(order, coarse_mesh, monkeypatch
     nodes, t, e = variant_b_setup(order, coarse_mesh)
     Hx, Hy = nodes.bedSlopes(e["H"])
     ref = onp.sw2d_rhs_b(e["h"], e["hu"], e["hv"], e["H"], Hx, Hy, 9.81, e["f"], e["CD"], e["time"], t, e["mapO"])
-    scale = max(np.abs(x).max() for x in ref)
     fast = _variant_b_solver(nodes, e, Hx, Hy).computeRHS(e["h"], e["hu"], e["hv"], filter=True)
     monkeypatch.setenv("BDG_SW2D_ROLLED_SOURCES", "1")
     rolled = _variant_b_solver(nodes, e, Hx, Hy).computeRHS(e["h"], e["hu"], e["hv"], filter=True)
-    for a, b, c in zip(fast, rolled, ref):
-        assert np.abs(a - t["Filter"] @ c).max() / scale < RHS_TOL
-        assert np.abs(b - t["Filter"] @ c).max() / scale < RHS_TOL
+    assert_fields_close(fast, [t["Filter"] @ c for c in ref], RHS_TOL, what="default")
+    assert_fields_close(rolled, [t["Filter"] @ c for c in ref], RHS_TOL, what="rolled")
 
 
 @pytest.mark.parametrize("order", [1, 4, 8])
@@ -1123,9 +1093,7 @@ def test_smallest_mesh_two_triangles(order):
     o = oracle_from(t)
     s = sw2d.Sw2dSolver(nodes=nodes)
     ref = o.rhs(h, hu, hv)
-    scale = max(np.abs(x).max() for x in ref)
-    got = s.computeRHS(h, hu, hv)
-    assert max(np.abs(a - b).max() for a, b in zip(got, ref)) / scale < RHS_TOL
+    assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL)
     dt = 0.5 * o.dt(h, hu, hv, 0.65, order)
     assert s.setState(h, hu, hv) is None and s.computeDt(0.65)[0] == 2 * dt
     s.stepRK2(dt, 3, filter=True)
@@ -1299,10 +1267,117 @@ def test_tracer_in_its_own_pass_as_cross_check(case, monkeypatch):
     t["order"] = int(d["order"])
     s = sw2d.Sw2dSolver(tables=t, g=float(d["g"]), fields=4,
                         sources={"zx": d["zx"], "zy": d["zy"], "f": d["f"], "CD": float(d["CD"])})
-    r = s.computeRHS4(d["h"], d["hu"], d["hv"], d["hN"])
-    scale = max(np.abs(d[f"rhs{i}"]).max() for i in (1, 2, 3, 4))
-    for i in range(4):
-        assert np.abs(r[i] - d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    ref = [d[f"rhs{i}"] for i in (1, 2, 3, 4)]
+    assert_fields_close(s.computeRHS4(d["h"], d["hu"], d["hv"], d["hN"]), ref, RHS_TOL)
     rf = s.computeRHS4(d["h"], d["hu"], d["hv"], d["hN"], filter=True)
-    for i in range(4):
-        assert np.abs(rf[i] - d["Filter"] @ d[f"rhs{i + 1}"]).max() / scale < RHS_TOL
+    assert_fields_close(rf, [d["Filter"] @ x for x in ref], RHS_TOL)
+
+
+# ---- the regime fixtures (tests/golden/regimes_*.npz, outputs of the reference functions): a depth that jumps at every face,
+# ---- supercritical flow, deep water and per-element depth contrast, so that the depth penalty lambda/2 [h], the pressure jump
+# ---- g/2 [h^2] and every use of the neighbour's depth (u+ = hu+/h+, g h+^2/2, sqrt(g h+)) are pinned, each field to its own size
+
+def _regime_solver_tables(t):
+    tt = {k: t[k] for k in ("Dr", "Ds", "Lift", "Filter", "rx", "sx", "ry", "sy", "nx", "ny", "Fscale", "vmapM", "vmapP", "mapW")}
+    tt["order"] = int(t["order"])
+    return tt
+
+
+def _three_field_configs():
+    """(id, flags, env, cases): every three-field kernel family on the variant-A regime fixtures."""
+    from regimes import REGIME_CASES
+    cases = REGIME_CASES["A"]
+    out = [("default", 0, {}, cases), ("reorder", sw2d.REORDER, {}, cases), ("nodal", sw2d.NODAL_GEOMETRY, {}, cases),
+           ("nodal-vector", sw2d.NODAL_GEOMETRY, {"BDG_SW2D_NODAL_VECTOR": "1"}, [c for c in cases if int(c[-1]) <= 6])]
+    for v in range(8):          # the orders test_every_affine_kernel_variant_matches_the_reference_fixture covers
+        out.append((f"variant{v}", 0, {"BDG_SW2D_AFFINE_VARIANT": str(v)},
+                    ["coarse_box_N3", "box6x5_shuffled_N4", "coarse_box_N6", "box2x2_N8"]))
+    for v in (8, 9):
+        out.append((f"variant{v}", 0, {"BDG_SW2D_AFFINE_VARIANT": str(v)}, ["coarse_box_N2", "coarse_box_N4", "coarse_box_N5"]))
+    return [pytest.param(flags, env, case, id=f"{name}-{case}") for name, flags, env, cs in out for case in cs]
+
+
+@pytest.mark.parametrize("flags,env,case", _three_field_configs())
+def test_three_field_families_on_discontinuous_reference_fixtures(flags, env, case, monkeypatch):
+    """Every three-field kernel family (BDG_SW2D_AFFINE_VARIANT 0-9, per-node geometry on matrix cores and on the vector
+    kernel, internal renumbering) against the reference's sw2dComputeRHS on all four regimes: RHS and Filter @ RHS, each field
+    to 1e-12 of its own size. On the smooth parity state a kernel that reads h- where h+ belongs passes every fixture."""
+    from regimes import load_regimes
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    t, states = load_regimes("A", case)
+    s = sw2d.Sw2dSolver(tables=_regime_solver_tables(t), g=float(t["g"]), flags=flags)
+    assert s.usesAffineGeometry == (not flags & sw2d.NODAL_GEOMETRY)
+    assert set(states) == {"jumpy", "supercritical", "deep", "contrast"}
+    for regime, q in states.items():
+        ref = [q[f"rhs{i}"] for i in (1, 2, 3)]
+        assert_fields_close(s.computeRHS(q["h"], q["hu"], q["hv"]), ref, RHS_TOL, what=regime)
+        assert_fields_close(s.computeRHS(q["h"], q["hu"], q["hv"], filter=True), [t["Filter"] @ r for r in ref], RHS_TOL,
+                            what=regime + " filtered")
+
+
+_SOURCE_ENVS = {"default": {}, "two-wave": {"BDG_SW2D_SOURCES_TWO_WAVE": "1"}, "rolled": {"BDG_SW2D_ROLLED_SOURCES": "1"},
+                "tracer-pass": {"BDG_SW2D_TRACER_PASS": "1"}, "product": {"BDG_SW2D_SOURCES_PRODUCT": "1"}}
+
+
+def _source_configs():
+    from regimes import REGIME_CASES
+    return [pytest.param(fam, case, env, id=f"{fam}-{case}-{name}") for fam in ("C", "D") for case in REGIME_CASES[fam]
+            for name, env in _SOURCE_ENVS.items()]
+
+
+@pytest.mark.parametrize("family,case,env", _source_configs())
+def test_variants_c_and_d_on_discontinuous_reference_fixtures(family, case, env, monkeypatch):
+    """Variants C (the script's function) and D (tracer, Coriolis array, drag, bed slope; on the sw2d_rhs4n tables the per-node
+    geometry kernel) against the reference functions' output on the jumpy and supercritical regimes, through the default kernels
+    and every switch that selects another form: all four fields, plain and filtered, each to 1e-12 of its own size."""
+    from regimes import load_regimes
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    t, states = load_regimes(family, case)
+    if family == "C":
+        src = {"f": float(t["f"]), "CD": 0.0}
+    else:
+        src = {"zx": t["zx"], "zy": t["zy"], "f": t["f"], "CD": float(t["CD"])}
+    s = sw2d.Sw2dSolver(tables=_regime_solver_tables(t), g=float(t["g"]), fields=4, sources=src)
+    assert s.usesAffineGeometry == (np.ptp(t["rx"], axis=0).max() < 1e-3)     # the sw2d_rhs4n tables vary inside the elements
+    for regime, q in states.items():
+        ref = [q[f"rhs{i}"] for i in (1, 2, 3, 4)]
+        qq = (q["h"], q["hu"], q["hv"], q["hN"])
+        assert_fields_close(s.computeRHS4(*qq), ref, RHS_TOL, what=regime)
+        assert_fields_close(s.computeRHS4(*qq, filter=True), [t["Filter"] @ r for r in ref], RHS_TOL, what=regime + " filtered")
+
+
+@pytest.mark.parametrize("order,nx,ny,seed", [(1, 64, 64, 0), (2, 50, 20, 5), (3, 33, 17, 7), (4, 40, 25, 12345), (5, 21, 13, 3),
+                                              (6, 17, 11, 0), (7, 19, 9, 11), (8, 23, 14, 12345)])
+@pytest.mark.parametrize("regime", ["jumpy", "supercritical", "deep", "contrast"])
+def test_flow_regimes_on_medium_meshes_vs_oracle(regime, order, nx, ny, seed):
+    """The shapes of test_medium_box_meshes_vs_oracle (ragged K, shuffled element order) on every regime: the RHS field by field,
+    computeDt bit for bit (lambda from |u| reaches dt too) and, except on the contrast state (which two LSERK4 stages drive to
+    NaN), 4 LSERK4 stages at a quarter of the CFL step with the depth kept positive. Renumbered and in the mesh's order."""
+    from regimes import regime_fields
+    m = dg.MeshManager()
+    m.buildBoxMesh(nx, ny, shuffleSeed=seed)
+    nodes = dg.TriangleNodesProvisioner(order, m)
+    t = tables_from_nodes(nodes)
+    o = oracle_from(t, threads=4)
+    h, hu, hv = regime_fields(t["x"], t["y"], regime, seed=order)
+    ref = o.rhs(h, hu, hv)
+    dt_ref = o.dt(h, hu, hv, 0.65, order)
+    stepped = regime != "contrast"
+    if stepped:
+        dt = 0.25 * dt_ref
+        zero = [np.zeros_like(h) for _ in range(3)]
+        ref_state = o.lserk4_stages(h, hu, hv, zero, dt, 0, 4)[:3]
+        assert ref_state[0].min() > 0
+    for flags in (0, sw2d.KEEP_ORDER):
+        s = sw2d.Sw2dSolver(nodes=nodes, flags=flags)
+        assert_fields_close(s.computeRHS(h, hu, hv), ref, RHS_TOL, what=f"{regime} flags={flags}")
+        s.setState(h, hu, hv)
+        assert s.computeDt(0.65)[0] == dt_ref
+        if stepped:
+            s.lserk4Stages(dt, 4)
+            got = s.getState()
+            assert got[0].min() > 0
+            assert_fields_close(got, ref_state, STATE_TOL, what=f"{regime} 4 stages flags={flags}")
+        s.close()
