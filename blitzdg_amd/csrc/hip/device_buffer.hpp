@@ -1,0 +1,45 @@
+// device_buffer.hpp -- the HIP error check and the owning device buffer of the two sw2d solvers (sw2d_device.hip,
+// sw2d_curved_device.hip).
+#pragma once
+#include "../host/capi_internal.hpp"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <string>
+
+namespace bdg_dev {
+
+inline void hipCheck(hipError_t e, const char* what) {
+    if (e != hipSuccess) throw bdg_detail::hip_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// `total` counts the bytes of the live allocations: replacing a live buffer stops counting its old size; release()
+// on its own leaves the count as it is.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    void alloc(size_t count, size_t& total) {
+        if (p) total -= std::min(total, n * sizeof(T));
+        release();
+        if (count == 0) return;
+        hipCheck(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)), "hipMalloc");
+        n = count;
+        total += count * sizeof(T);
+    }
+    // ... and zeroed on `zeroOn`
+    void alloc(size_t count, size_t& total, hipStream_t zeroOn) {
+        alloc(count, total);
+        zero(zeroOn);
+    }
+    void zero(hipStream_t on) {
+        if (p) hipCheck(hipMemsetAsync(p, 0, n * sizeof(T), on), "hipMemset");
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    ~DevBuf() { release(); }
+};
+
+} // namespace bdg_dev

@@ -4,7 +4,7 @@
 #include "../host/capi_internal.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
-#include "rccl_api.hpp"
+#include "halo_transport.hpp"
 #include "sw2d_curved_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -44,51 +44,8 @@ using bdg_detail::arg_error;
 using bdg_detail::guard;
 using bdg_detail::hip_error;
 
-namespace {
-
-void hipOk(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw hip_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-template <typename T>
-struct Buf {
-    T* p = nullptr;
-    size_t n = 0;
-    void alloc(size_t count, size_t& total, hipStream_t stream) {
-        if (p) total -= std::min(total, n * sizeof(T)); // a replaced buffer no longer counts (repeated set_partition)
-        release();
-        if (count == 0) return;
-        hipOk(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)), "hipMalloc");
-        n = count;
-        total += count * sizeof(T);
-        hipOk(hipMemsetAsync(p, 0, count * sizeof(T), stream), "hipMemset");
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~Buf() { release(); }
-};
-
-// Ghost exchange of a partitioned run: one record of 4 Np doubles ([field][node]) per element. Pack: the elements a
-// neighbour needs, in the order of the send list; unpack: the received records into the ghost columns (num_owned ...).
-__global__ __launch_bounds__(256) void sw2d_curved_pack_kernel(const double* __restrict__ q, long long ld, int rows,
-                                                               const int* __restrict__ sendEls, int numSend, double* __restrict__ out) {
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= static_cast<long long>(numSend) * rows) return;
-    const int rec = static_cast<int>(i / rows), row = static_cast<int>(i - static_cast<long long>(rec) * rows);
-    out[i] = q[static_cast<long long>(row) * ld + sendEls[rec]];
-}
-__global__ __launch_bounds__(256) void sw2d_curved_unpack_kernel(double* __restrict__ q, long long ld, int rows, int firstGhost,
-                                                                 int numGhost, const double* __restrict__ in) {
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= static_cast<long long>(numGhost) * rows) return;
-    const int row = static_cast<int>(i / numGhost), gcol = static_cast<int>(i - static_cast<long long>(row) * numGhost); // coalesced writes
-    q[static_cast<long long>(row) * ld + firstGhost + gcol] = in[static_cast<long long>(gcol) * rows + row];
-}
-
-} // namespace
+using bdg_dev::DevBuf;
+using bdg_dev::hipCheck;
 
 struct bdg_sw2d_curved {
     const bdg_dev::CurvedKernelTable* kt = nullptr;
@@ -98,17 +55,17 @@ struct bdg_sw2d_curved {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t bytes = 0;
-    Buf<double> qA, qB, res, rhs, gq, cubG, gaussG, coef, mmSide, minvSide, ops, filt;
+    DevBuf<double> qA, qB, res, rhs, gq, cubG, gaussG, coef, mmSide, minvSide, ops, filt;
     // nodal coefficient planes inside coef (one allocation: the stage kernel reaches all of them through one buffer
     // descriptor): 1 / J first, then whichever of zx, zy, f, CD the caller gave (nullptr: absent)
     double *rJ = nullptr, *zx = nullptr, *zy = nullptr, *fcor = nullptr, *cd = nullptr;
-    Buf<int> gmapP, gmapM, curvedSlot, curvedEls, affineEl;
-    Buf<double> cubAffine, cubWref;
+    DevBuf<int> gmapP, gmapM, curvedSlot, curvedEls, affineEl;
+    DevBuf<double> cubAffine, cubWref;
     int numAffine = 0;
     // nodal-trace form (sw2d_curved_nt_kernel.hpp): used when the context has the structure it needs (useNT)
     bool useNT = false;
-    Buf<double> opsNT, elAffine, gaussWref;
-    Buf<int> nodeP, faceFlags, faceNodesDev, tileOrder;
+    DevBuf<double> opsNT, elAffine, gaussWref;
+    DevBuf<int> nodeP, faceFlags, faceNodesDev, tileOrder;
     int numAffineNT = 0;
     int prioMode = 2;   // see sw2d_curved_nt_kernel (BDG_SW2D_CURVED_PRIO at creation: A/B switch)
     double g = 9.81, fconst = 0.0, cdconst = 0.0;
@@ -116,46 +73,40 @@ struct bdg_sw2d_curved {
     double bytesPerElement = 0.0;
     // partitioned runs (bdg_sw2d_curved_set_partition / _comm_init): elements [numOwned, K) are ghosts, refreshed from their
     // owners before every evaluation by grouped ncclSend / ncclRecv on the solver's stream
-    struct Peer { int rank, sendStart, sendCount, recvStart, recvCount; };
-    int numOwned = 0, numInterior = 0, numSend = 0, commRank = 0, commWorld = 1;
-    Buf<int> sendEls;
+    int numOwned = 0, numInterior = 0, numSend = 0;
+    DevBuf<int> sendEls;
     // overlapped schedule (nodal-trace form): elements [0, numInterior) have no ghost neighbour and are evaluated on the solver's
-    // stream while the exchange and then the partition-boundary elements [numInterior, numOwned) run on commStream; the curved
+    // stream while the exchange and then the partition-boundary elements [numInterior, numOwned) run on the exchange stream; the curved
     // elements of the two ranges (columns of the side buffer) are listed for the fix-up launches of either chain
     std::vector<int> curvedHost;          // element of each side-buffer column
     std::vector<int> maxNeighbourHost;    // largest element index a face of element k is paired with (from gmapP, kept for set_partition)
-    Buf<int> slotsInterior, slotsBoundary;
+    DevBuf<int> slotsInterior, slotsBoundary;
     int numSlotsInterior = 0, numSlotsBoundary = 0;
-    hipStream_t commStream = nullptr;
+    bdg_halo::Transport halo;
     hipEvent_t evA[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr}, evEntry = nullptr;
-    Buf<double> sendBuf, recvBuf, scalarBuf;
-    std::vector<Peer> peers;
-    ncclComm_t comm = nullptr;
 
     ~bdg_sw2d_curved() {
-        if (comm) (void)bdg_rccl::rccl().CommDestroy(comm);
         for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evEntry})
             if (e) (void)hipEventDestroy(e);
-        if (commStream) (void)hipStreamDestroy(commStream);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
     }
-    void use() const { hipOk(hipSetDevice(device), "hipSetDevice"); }
+    void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
     size_t plane() const { return static_cast<size_t>(Np) * static_cast<size_t>(ld); }
 
     // host (rows, K) row-major -> device rows [row0, row0 + rows) of a (., ld) plane
     template <typename T>
     void uploadRows(const T* host, T* dev, int rows, int row0 = 0) {
-        hipOk(hipMemcpy2DAsync(dev + static_cast<size_t>(row0) * ld, static_cast<size_t>(ld) * sizeof(T), host,
+        hipCheck(hipMemcpy2DAsync(dev + static_cast<size_t>(row0) * ld, static_cast<size_t>(ld) * sizeof(T), host,
                                static_cast<size_t>(K) * sizeof(T), static_cast<size_t>(K) * sizeof(T), rows,
                                hipMemcpyHostToDevice, stream), "H2D copy");
-        hipOk(hipStreamSynchronize(stream), "upload sync");
+        hipCheck(hipStreamSynchronize(stream), "upload sync");
     }
     void downloadRows(const double* dev, double* host, int rows) {
-        hipOk(hipMemcpy2DAsync(host, static_cast<size_t>(K) * sizeof(double), dev, static_cast<size_t>(ld) * sizeof(double),
+        hipCheck(hipMemcpy2DAsync(host, static_cast<size_t>(K) * sizeof(double), dev, static_cast<size_t>(ld) * sizeof(double),
                                static_cast<size_t>(K) * sizeof(double), rows, hipMemcpyDeviceToHost, stream), "D2H copy");
-        hipOk(hipStreamSynchronize(stream), "download sync");
+        hipCheck(hipStreamSynchronize(stream), "download sync");
     }
 
     bdg_dev::CurvedParams params() const {
@@ -187,9 +138,9 @@ struct bdg_sw2d_curved {
         p.qin = qin; p.qbase = qbase; p.qout = qout; p.res = res.p; p.rhs = rhs.p; p.ca = ca; p.cb = cb; p.cc = cc;
         p.kbegin = kbegin; p.K = kend; p.gridReserve = gridReserve;
         p.tileOrder = nullptr;  // (the list is built for the tiles of [0, K))
-        hipOk(kt->stageNT(mode, filter, p, on), "sw2d_curved_nt_kernel");
+        hipCheck(kt->stageNT(mode, filter, p, on), "sw2d_curved_nt_kernel");
         p.slotList = slotList; p.numCurved = numSlots;
-        hipOk(kt->fixup(mode, filter, p, on), "sw2d_curved_fixup_kernel");
+        hipCheck(kt->fixup(mode, filter, p, on), "sw2d_curved_fixup_kernel");
     }
 
     void evaluate(int mode, bool filter, const double* qin, const double* qbase, double* qout, double ca, double cb,
@@ -199,12 +150,12 @@ struct bdg_sw2d_curved {
         p.qin = qin; p.qbase = qbase; p.qout = qout; p.res = res.p; p.rhs = rhs.p; p.ca = ca; p.cb = cb; p.cc = cc;
         if (useNT) { // one launch: the neighbours' traces are products of their nodal values (no Gauss-trace planes)
             if (qin == qout) throw arg_error("bdg_sw2d_curved: the nodal-trace kernel cannot update the state it gathers from in place");
-            hipOk(kt->stageNT(mode, filter, p, stream), "sw2d_curved_nt_kernel");
+            hipCheck(kt->stageNT(mode, filter, p, stream), "sw2d_curved_nt_kernel");
         } else {
-            hipOk(kt->gauss(p, stream), "sw2d_curved_gauss_kernel");
-            hipOk(kt->stage(mode, filter, p, stream), "sw2d_curved_stage_kernel");
+            hipCheck(kt->gauss(p, stream), "sw2d_curved_gauss_kernel");
+            hipCheck(kt->stage(mode, filter, p, stream), "sw2d_curved_stage_kernel");
         }
-        hipOk(kt->fixup(mode, filter, p, stream), "sw2d_curved_fixup_kernel");
+        hipCheck(kt->fixup(mode, filter, p, stream), "sw2d_curved_fixup_kernel");
     }
 
     // one LSERK4 stage: res = a res + dt RHS(q); q += b res. The first form updates q in place (it reads neighbours
@@ -222,33 +173,11 @@ struct bdg_sw2d_curved {
     // ghost columns of `state` from their owners (pack -> grouped send / receive with every neighbour -> unpack), in stream order
     void exchange(double* state) { exchangeOn(state, stream); }
     void exchangeOn(double* state, hipStream_t stream) {
-        if (!comm) throw arg_error("bdg_sw2d_curved: no communicator (call bdg_sw2d_curved_comm_init first)");
-        const int rows = 4 * Np, ghosts = K - numOwned;
-        if (numSend > 0) {
-            const long long n = static_cast<long long>(numSend) * rows;
-            hipLaunchKernelGGL(sw2d_curved_pack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, state, ld,
-                               rows, sendEls.p, numSend, sendBuf.p);
-            hipOk(hipGetLastError(), "sw2d_curved_pack_kernel");
-        }
-        if (!peers.empty()) {
-            bdg_rccl::RcclApi& nc = bdg_rccl::rccl();
-            bdg_rccl::ncclCheck(nc.GroupStart(), "ncclGroupStart");
-            for (const Peer& pr : peers) {
-                if (pr.recvCount > 0)
-                    bdg_rccl::ncclCheck(nc.Recv(recvBuf.p + static_cast<size_t>(pr.recvStart) * rows, static_cast<size_t>(pr.recvCount) * rows,
-                                                ncclDouble, pr.rank, comm, stream), "ncclRecv");
-                if (pr.sendCount > 0)
-                    bdg_rccl::ncclCheck(nc.Send(sendBuf.p + static_cast<size_t>(pr.sendStart) * rows, static_cast<size_t>(pr.sendCount) * rows,
-                                                ncclDouble, pr.rank, comm, stream), "ncclSend");
-            }
-            bdg_rccl::ncclCheck(nc.GroupEnd(), "ncclGroupEnd");
-        }
-        if (ghosts > 0) {
-            const long long n = static_cast<long long>(ghosts) * rows;
-            hipLaunchKernelGGL(sw2d_curved_unpack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, state, ld,
-                               rows, numOwned, ghosts, recvBuf.p);
-            hipOk(hipGetLastError(), "sw2d_curved_unpack_kernel");
-        }
+        if (!halo.comm) throw arg_error("bdg_sw2d_curved: no communicator (call bdg_sw2d_curved_comm_init first)");
+        const int rows = 4 * Np;
+        bdg_halo::pack(state, ld, rows, sendEls.p, numSend, halo.sendBuf.p, stream);
+        halo.sendRecv(stream, rows);
+        bdg_halo::unpack(state, ld, rows, numOwned, K - numOwned, halo.recvBuf.p, stream);
     }
     // the driver's RK2 step of a partitioned run: an exchange in front of EACH evaluation, of the state that evaluation reads
     //
@@ -265,8 +194,8 @@ struct bdg_sw2d_curved {
         return useNT && numInterior >= 1 && std::getenv("BDG_SW2D_CURVED_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
     }
     void chainsBegin(Chains&) {
-        hipOk(hipEventRecord(evEntry, stream), "hipEventRecord");          // whatever set the state, on A
-        hipOk(hipStreamWaitEvent(commStream, evEntry, 0), "hipStreamWaitEvent");
+        hipCheck(hipEventRecord(evEntry, stream), "hipEventRecord");          // whatever set the state, on A
+        hipCheck(hipStreamWaitEvent(halo.stream, evEntry, 0), "hipStreamWaitEvent");
     }
     // one evaluation on both chains: reads `in` (ghost columns refreshed first), writes the owned columns of `out`
     void chainsEval(Chains& c, int mode, bool filter, double* in, const double* base, double* out, double ca, double cb, double cc) {
@@ -275,21 +204,21 @@ struct bdg_sw2d_curved {
         const int boundaryWgs = (((numOwned - numInterior + 15) / 16 + 3) / 4 + 7) / 8 * 8;
         const int cur = c.e & 1, prev = cur ^ 1;
         // ---- chain A
-        if (c.haveB) hipOk(hipStreamWaitEvent(stream, evB[prev], 0), "hipStreamWaitEvent");
+        if (c.haveB) hipCheck(hipStreamWaitEvent(stream, evB[prev], 0), "hipStreamWaitEvent");
         evaluateRange(mode, filter, in, base, out, ca, cb, cc, 0, numInterior, slotsInterior.p, numSlotsInterior, stream, boundaryWgs);
-        hipOk(hipEventRecord(evA[cur], stream), "hipEventRecord");
+        hipCheck(hipEventRecord(evA[cur], stream), "hipEventRecord");
         // ---- chain B
-        if (c.haveA) hipOk(hipStreamWaitEvent(commStream, evA[prev], 0), "hipStreamWaitEvent");
-        exchangeOn(in, commStream);
-        evaluateRange(mode, filter, in, base, out, ca, cb, cc, numInterior, numOwned, slotsBoundary.p, numSlotsBoundary, commStream);
-        hipOk(hipEventRecord(evB[cur], commStream), "hipEventRecord");
+        if (c.haveA) hipCheck(hipStreamWaitEvent(halo.stream, evA[prev], 0), "hipStreamWaitEvent");
+        exchangeOn(in, halo.stream);
+        evaluateRange(mode, filter, in, base, out, ca, cb, cc, numInterior, numOwned, slotsBoundary.p, numSlotsBoundary, halo.stream);
+        hipCheck(hipEventRecord(evB[cur], halo.stream), "hipEventRecord");
         c.haveA = c.haveB = true;
         ++c.e;
     }
     void chainsEnd(Chains& c) { // join both ways: later work on A sees the last boundary update, later work on B the last interior launch
         if (c.e == 0) return;
-        hipOk(hipStreamWaitEvent(stream, evB[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
-        hipOk(hipStreamWaitEvent(commStream, evA[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
+        hipCheck(hipStreamWaitEvent(stream, evB[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
+        hipCheck(hipStreamWaitEvent(halo.stream, evA[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
     }
     void stepRk2Exchanged(double dt, int steps, bool filter) {
         if (!overlapped()) {
@@ -505,19 +434,19 @@ void buildNodalTraceTables(bdg_sw2d_curved& s, const bdg_sw2d_curved_desc& d, co
     s.uploadRows(ea.data(), s.elAffine.p, 14);
     if (!s.cubWref.p) { // (the first form's reference weights when it found straight elements: the same numbers)
         s.cubWref.alloc(wref.size(), s.bytes, st);
-        hipOk(hipMemcpyAsync(s.cubWref.p, wref.data(), wref.size() * sizeof(double), hipMemcpyHostToDevice, st), "Wref upload");
+        hipCheck(hipMemcpyAsync(s.cubWref.p, wref.data(), wref.size() * sizeof(double), hipMemcpyHostToDevice, st), "Wref upload");
     }
     s.gaussWref.alloc(gwHalf.size(), s.bytes, st);
-    hipOk(hipMemcpyAsync(s.gaussWref.p, gwHalf.data(), gwHalf.size() * sizeof(double), hipMemcpyHostToDevice, st), "gauss Wref upload");
+    hipCheck(hipMemcpyAsync(s.gaussWref.p, gwHalf.data(), gwHalf.size() * sizeof(double), hipMemcpyHostToDevice, st), "gauss Wref upload");
     s.faceFlags.alloc(static_cast<size_t>(ld), s.bytes, st);
-    hipOk(hipMemcpyAsync(s.faceFlags.p, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, st), "face flags upload");
+    hipCheck(hipMemcpyAsync(s.faceFlags.p, flags.data(), flags.size() * sizeof(int), hipMemcpyHostToDevice, st), "face flags upload");
     s.nodeP.alloc(static_cast<size_t>(rowsP) * ld, s.bytes, st);
     s.uploadRows(nodeP.data(), s.nodeP.p, rowsP);
     std::vector<int> fnodes(static_cast<size_t>(rowsP));
     for (int f = 0; f < 3; ++f)
         for (int i = 0; i < KE * 4; ++i) fnodes[static_cast<size_t>(f) * KE * 4 + i] = faceNodes[f][i < Nfp ? i : 0];
     s.faceNodesDev.alloc(fnodes.size(), s.bytes, st);
-    hipOk(hipMemcpyAsync(s.faceNodesDev.p, fnodes.data(), fnodes.size() * sizeof(int), hipMemcpyHostToDevice, st), "face nodes upload");
+    hipCheck(hipMemcpyAsync(s.faceNodesDev.p, fnodes.data(), fnodes.size() * sizeof(int), hipMemcpyHostToDevice, st), "face nodes upload");
 
     // ---- order of the tiles: positions [n x / 8, n (x + 1) / 8) of the list are XCD x's (sw2d_curved_nt_kernel); each eighth gets
     //      an eighth of the general tiles (in mesh order, first), then straight-sided ones (in mesh order)
@@ -543,8 +472,8 @@ void buildNodalTraceTables(bdg_sw2d_curved& s, const bdg_sw2d_curved_desc& d, co
             }
             if (gi == G && si == S && static_cast<int>(order.size()) == ntiles) {
                 s.tileOrder.alloc(order.size(), s.bytes, st);
-                hipOk(hipMemcpyAsync(s.tileOrder.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, st), "tile order upload");
-                hipOk(hipStreamSynchronize(st), "tile order sync"); // (order is a local)
+                hipCheck(hipMemcpyAsync(s.tileOrder.p, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, st), "tile order upload");
+                hipCheck(hipStreamSynchronize(st), "tile order sync"); // (order is a local)
             }
         }
     }
@@ -600,8 +529,8 @@ void buildNodalTraceTables(bdg_sw2d_curved& s, const bdg_sw2d_curved_desc& d, co
             }
     }
     s.opsNT.alloc(img.size(), s.bytes, st);
-    hipOk(hipMemcpyAsync(s.opsNT.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, st), "ops upload");
-    hipOk(hipStreamSynchronize(st), "nodal-trace tables sync");
+    hipCheck(hipMemcpyAsync(s.opsNT.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, st), "ops upload");
+    hipCheck(hipStreamSynchronize(st), "nodal-trace tables sync");
     s.useNT = true;
 }
 
@@ -686,9 +615,9 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
     s->identityM = identityM;
 
     s->use();
-    hipOk(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
-    hipOk(hipEventCreate(&s->ev0), "hipEventCreate");
-    hipOk(hipEventCreate(&s->ev1), "hipEventCreate");
+    hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
+    hipCheck(hipEventCreate(&s->ev0), "hipEventCreate");
+    hipCheck(hipEventCreate(&s->ev1), "hipEventCreate");
     hipStream_t st = s->stream;
 
     // ---- state and work planes
@@ -754,12 +683,12 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
             if (count) {
                 for (long long k = K; k < ld; ++k) flag[k] = flag[K - 1]; // (padding lanes repeat the last element)
                 s->affineEl.alloc(static_cast<size_t>(ld), s->bytes, st);
-                hipOk(hipMemcpyAsync(s->affineEl.p, flag.data(), flag.size() * sizeof(int), hipMemcpyHostToDevice, st), "affine flags upload");
+                hipCheck(hipMemcpyAsync(s->affineEl.p, flag.data(), flag.size() * sizeof(int), hipMemcpyHostToDevice, st), "affine flags upload");
                 s->cubAffine.alloc(static_cast<size_t>(4) * ld, s->bytes, st);
                 s->uploadRows(ca.data(), s->cubAffine.p, 4);
                 s->cubWref.alloc(wref.size(), s->bytes, st);
-                hipOk(hipMemcpyAsync(s->cubWref.p, wref.data(), wref.size() * sizeof(double), hipMemcpyHostToDevice, st), "Wref upload");
-                hipOk(hipStreamSynchronize(st), "affine upload sync");
+                hipCheck(hipMemcpyAsync(s->cubWref.p, wref.data(), wref.size() * sizeof(double), hipMemcpyHostToDevice, st), "Wref upload");
+                hipCheck(hipStreamSynchronize(st), "affine upload sync");
             }
         }
     }
@@ -806,10 +735,10 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
         s->curvedSlot.alloc(ld, s->bytes, st);
         std::vector<int> slots(static_cast<size_t>(ld), -1);
         std::copy(slotOf.begin(), slotOf.end(), slots.begin());
-        hipOk(hipMemcpyAsync(s->curvedSlot.p, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice, st), "slot upload");
+        hipCheck(hipMemcpyAsync(s->curvedSlot.p, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice, st), "slot upload");
         s->curvedHost = curved;
         s->curvedEls.alloc(curved.size(), s->bytes, st);
-        hipOk(hipMemcpyAsync(s->curvedEls.p, curved.data(), curved.size() * sizeof(int), hipMemcpyHostToDevice, st), "curvedEls upload");
+        hipCheck(hipMemcpyAsync(s->curvedEls.p, curved.data(), curved.size() * sizeof(int), hipMemcpyHostToDevice, st), "curvedEls upload");
         // inverse mass matrix of every listed element from its upper Cholesky factor U (M = U^T U): W = U^-1 by back
         // substitution, Minv = W W^T (the reference solves U^T y = b, U x = y per evaluation, rhs.py:157-162)
         std::vector<double> minv(static_cast<size_t>(Np) * Np * curved.size(), 0.0);
@@ -840,9 +769,9 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
         }, 8);
         if (badDiagonal) throw arg_error("bdg_sw2d_curved_create: MMChol has a non-positive diagonal entry on an element of curvedEls");
         s->minvSide.alloc(minv.size(), s->bytes, st);
-        hipOk(hipMemcpyAsync(s->minvSide.p, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, st), "Minv upload");
+        hipCheck(hipMemcpyAsync(s->minvSide.p, minv.data(), minv.size() * sizeof(double), hipMemcpyHostToDevice, st), "Minv upload");
         s->mmSide.alloc(static_cast<size_t>(4) * Np * curved.size(), s->bytes, st);
-        hipOk(hipStreamSynchronize(st), "side upload sync");
+        hipCheck(hipStreamSynchronize(st), "side upload sync");
     }
 
     // ---- operator image in MFMA A-tile order (layout: CurvedOps in sw2d_curved_kernel.hpp)
@@ -899,12 +828,12 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
                 }
         }
         s->ops.alloc(img.size(), s->bytes, st);
-        hipOk(hipMemcpyAsync(s->ops.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, st), "ops upload");
+        hipCheck(hipMemcpyAsync(s->ops.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, st), "ops upload");
         if (d.Filter) {
             s->filt.alloc(static_cast<size_t>(Np) * Np, s->bytes, st);
-            hipOk(hipMemcpyAsync(s->filt.p, d.Filter, static_cast<size_t>(Np) * Np * sizeof(double), hipMemcpyHostToDevice, st), "filter upload");
+            hipCheck(hipMemcpyAsync(s->filt.p, d.Filter, static_cast<size_t>(Np) * Np * sizeof(double), hipMemcpyHostToDevice, st), "filter upload");
         }
-        hipOk(hipStreamSynchronize(st), "ops sync");
+        hipCheck(hipStreamSynchronize(st), "ops sync");
     }
     buildNodalTraceTables(*s, d, slotOf);
     // compulsory bytes of one RHS evaluation per element: state in, RHS out, geometry, maps, traces out and in (twice: both sides)
@@ -916,8 +845,8 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
                                 (identityM ? 2 : 3) * 4 * NG3) +
                          4.0 * (NG3 * (identityM ? 1 : 2) + 2);
     if (s->useNT) { // the Gauss-trace planes and maps belong to the general form only
-        for (Buf<double>* b : {&s->gq}) { s->bytes -= b->n * sizeof(double); b->release(); }
-        for (Buf<int>* b : {&s->gmapP, &s->gmapM}) { s->bytes -= b->n * sizeof(int); b->release(); }
+        for (DevBuf<double>* b : {&s->gq}) { s->bytes -= b->n * sizeof(double); b->release(); }
+        for (DevBuf<int>* b : {&s->gmapP, &s->gmapM}) { s->bytes -= b->n * sizeof(int); b->release(); }
     }
     if (s->useNT) { // state in, update in / out, the neighbours' face nodes, node map + flags, geometry (14 numbers on straight elements), sources
         const double fa = static_cast<double>(s->numAffineNT) / K;
@@ -943,7 +872,7 @@ int bdg_sw2d_curved_create(const bdg_sw2d_curved_desc* desc, bdg_sw2d_curved** o
 void bdg_sw2d_curved_destroy(bdg_sw2d_curved* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    if (s->commStream) (void)hipStreamSynchronize(s->commStream);
+    if (s->halo.stream) (void)hipStreamSynchronize(s->halo.stream);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     delete s;
 }
@@ -970,7 +899,7 @@ int bdg_sw2d_curved_set_state(bdg_sw2d_curved* s, const double* h, const double*
         s->use();
         const double* in[4] = {h, hu, hv, hN};
         for (int c = 0; c < 4; ++c) s->uploadRows(in[c], s->qA.p + c * s->plane(), s->Np);
-        hipOk(hipMemsetAsync(s->res.p, 0, s->res.n * sizeof(double), s->stream), "hipMemset");
+        hipCheck(hipMemsetAsync(s->res.p, 0, s->res.n * sizeof(double), s->stream), "hipMemset");
         s->stageCount = 0;
     });
 }
@@ -1014,12 +943,12 @@ int bdg_sw2d_curved_time_rk2(bdg_sw2d_curved* s, double dt, int num_steps, int f
         requireCurved(s, "bdg_sw2d_curved_time_rk2");
         if (num_steps < 1 || !ms_per_rhs) throw arg_error("bdg_sw2d_curved_time_rk2: bad argument");
         s->use();
-        hipOk(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
+        hipCheck(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
         s->stepRk2(dt, num_steps, filter != 0);
-        hipOk(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
-        hipOk(hipEventSynchronize(s->ev1), "hipEventSynchronize");
+        hipCheck(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
+        hipCheck(hipEventSynchronize(s->ev1), "hipEventSynchronize");
         float ms = 0.f;
-        hipOk(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
+        hipCheck(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
         *ms_per_rhs = ms / (2.0f * static_cast<float>(num_steps));
     });
 }
@@ -1039,9 +968,9 @@ int bdg_sw2d_curved_get_elements(bdg_sw2d_curved* s, int which, int first, int c
         if (count == 0) return;
         if (!out) throw arg_error("bdg_sw2d_curved_get_elements: NULL buffer");
         s->use();
-        hipOk(hipMemcpy2DAsync(out, static_cast<size_t>(count) * sizeof(double), dev, static_cast<size_t>(s->ld) * sizeof(double),
+        hipCheck(hipMemcpy2DAsync(out, static_cast<size_t>(count) * sizeof(double), dev, static_cast<size_t>(s->ld) * sizeof(double),
                                static_cast<size_t>(count) * sizeof(double), static_cast<size_t>(4) * s->Np, hipMemcpyDeviceToHost, s->stream), "D2H copy");
-        hipOk(hipStreamSynchronize(s->stream), "download sync");
+        hipCheck(hipStreamSynchronize(s->stream), "download sync");
     });
 }
 
@@ -1051,9 +980,9 @@ int bdg_sw2d_curved_set_elements(bdg_sw2d_curved* s, int which, int first, int c
         if (count == 0) return;
         if (!in) throw arg_error("bdg_sw2d_curved_set_elements: NULL buffer");
         s->use();
-        hipOk(hipMemcpy2DAsync(dev, static_cast<size_t>(s->ld) * sizeof(double), in, static_cast<size_t>(count) * sizeof(double),
+        hipCheck(hipMemcpy2DAsync(dev, static_cast<size_t>(s->ld) * sizeof(double), in, static_cast<size_t>(count) * sizeof(double),
                                static_cast<size_t>(count) * sizeof(double), static_cast<size_t>(4) * s->Np, hipMemcpyHostToDevice, s->stream), "H2D copy");
-        hipOk(hipStreamSynchronize(s->stream), "upload sync");
+        hipCheck(hipStreamSynchronize(s->stream), "upload sync");
     });
 }
 
@@ -1087,7 +1016,7 @@ int bdg_sw2d_curved_set_partition(bdg_sw2d_curved* s, int num_interior, int num_
             if (send_elements[i] < num_interior)
                 throw arg_error("bdg_sw2d_curved_set_partition: send element " + std::to_string(send_elements[i]) +
                                 " lies in the interior range [0, num_interior)");
-        if (s->comm) throw arg_error("bdg_sw2d_curved_set_partition: the communicator is already initialised");
+        if (s->halo.comm) throw arg_error("bdg_sw2d_curved_set_partition: the communicator is already initialised");
         s->use();
         s->numOwned = num_owned;
         s->numInterior = num_interior;
@@ -1103,15 +1032,15 @@ int bdg_sw2d_curved_set_partition(bdg_sw2d_curved* s, int num_interior, int num_
         s->slotsInterior.alloc(std::max<size_t>(1, inner.size()), s->bytes, s->stream);
         s->slotsBoundary.alloc(std::max<size_t>(1, outer.size()), s->bytes, s->stream);
         if (!inner.empty())
-            hipOk(hipMemcpyAsync(s->slotsInterior.p, inner.data(), inner.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "slot list upload");
+            hipCheck(hipMemcpyAsync(s->slotsInterior.p, inner.data(), inner.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "slot list upload");
         if (!outer.empty())
-            hipOk(hipMemcpyAsync(s->slotsBoundary.p, outer.data(), outer.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "slot list upload");
-        hipOk(hipStreamSynchronize(s->stream), "slot list sync"); // (inner, outer are locals)
+            hipCheck(hipMemcpyAsync(s->slotsBoundary.p, outer.data(), outer.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "slot list upload");
+        hipCheck(hipStreamSynchronize(s->stream), "slot list sync"); // (inner, outer are locals)
         s->sendEls.alloc(static_cast<size_t>(std::max(1, num_send)), s->bytes, s->stream);
         if (num_send > 0)
-            hipOk(hipMemcpyAsync(s->sendEls.p, send_elements, static_cast<size_t>(num_send) * sizeof(int), hipMemcpyHostToDevice, s->stream),
+            hipCheck(hipMemcpyAsync(s->sendEls.p, send_elements, static_cast<size_t>(num_send) * sizeof(int), hipMemcpyHostToDevice, s->stream),
                   "send list upload");
-        hipOk(hipStreamSynchronize(s->stream), "send list sync");
+        hipCheck(hipStreamSynchronize(s->stream), "send list sync");
     });
 }
 
@@ -1123,33 +1052,24 @@ int bdg_sw2d_curved_comm_init(bdg_sw2d_curved* s, int rank, int world, const voi
         if (!unique_id || world < 1 || rank < 0 || rank >= world || num_peers < 0 ||
             (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
             throw arg_error("bdg_sw2d_curved_comm_init: bad argument");
-        if (s->comm) throw arg_error("bdg_sw2d_curved_comm_init: communicator already initialised");
+        if (s->halo.comm) throw arg_error("bdg_sw2d_curved_comm_init: communicator already initialised");
         if (s->numOwned < 1) throw arg_error("bdg_sw2d_curved_comm_init: call bdg_sw2d_curved_set_partition first");
         const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_sw2d_curved::Peer> peers;
+        std::vector<bdg_halo::Peer> peers;
         for (int i = 0; i < num_peers; ++i) {
-            const bdg_sw2d_curved::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank >= world || p.sendStart < 0 || p.sendCount < 0 || p.sendStart + p.sendCount > s->numSend ||
-                p.recvStart < 0 || p.recvCount < 0 || p.recvStart + p.recvCount > ghosts)
+            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
+            if (p.rank < 0 || p.rank >= world || !bdg_halo::rangesFit(p, s->numSend, ghosts))
                 throw arg_error("bdg_sw2d_curved_comm_init: peer ranges do not fit the partition set with bdg_sw2d_curved_set_partition");
             peers.push_back(p);
         }
         s->use();
-        ncclUniqueId id;
-        std::memcpy(&id, unique_id, sizeof(id));
-        bdg_rccl::ncclCheck(bdg_rccl::rccl().CommInitRank(&s->comm, world, id, rank), "ncclCommInitRank");
-        s->commRank = rank;
-        s->commWorld = world;
-        s->peers = peers;
-        hipOk(hipStreamCreateWithFlags(&s->commStream, hipStreamNonBlocking), "hipStreamCreate");
+        s->halo.connect(unique_id, rank, world, static_cast<size_t>(4) * s->Np, s->numSend, ghosts, s->bytes);
+        s->halo.peers = peers;
         // (events that only order kernels of this device's two streams: no system-scope fence, as in bdg_sw2d_comm_init)
         for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1], &s->evEntry})
-            hipOk(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate");
-        const size_t rows = static_cast<size_t>(4) * s->Np;
-        s->sendBuf.alloc(std::max<size_t>(1, static_cast<size_t>(s->numSend) * rows), s->bytes, s->stream);
-        s->recvBuf.alloc(std::max<size_t>(1, static_cast<size_t>(ghosts) * rows), s->bytes, s->stream);
-        s->scalarBuf.alloc(2, s->bytes, s->stream);
-        hipOk(hipStreamSynchronize(s->stream), "exchange buffers");
+            hipCheck(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate");
+        for (DevBuf<double>* b : {&s->halo.sendBuf, &s->halo.recvBuf, &s->halo.scalarBuf}) b->zero(s->stream);
+        hipCheck(hipStreamSynchronize(s->stream), "exchange buffers");
     });
 }
 
@@ -1157,7 +1077,7 @@ int bdg_sw2d_curved_step_rk2_exchanged(bdg_sw2d_curved* s, double dt, int num_st
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_step_rk2_exchanged");
         if (num_steps < 0) throw arg_error("bdg_sw2d_curved_step_rk2_exchanged: num_steps < 0");
-        if (!s->comm) throw arg_error("bdg_sw2d_curved_step_rk2_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
+        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_step_rk2_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
         s->use();
         s->stepRk2Exchanged(dt, num_steps, filter != 0);
     });
@@ -1167,7 +1087,7 @@ int bdg_sw2d_curved_lserk4_stages_exchanged(bdg_sw2d_curved* s, double dt, int n
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_lserk4_stages_exchanged");
         if (num_stages < 0) throw arg_error("bdg_sw2d_curved_lserk4_stages_exchanged: num_stages < 0");
-        if (!s->comm) throw arg_error("bdg_sw2d_curved_lserk4_stages_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
+        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_lserk4_stages_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
         s->use();
         s->lserkStagesExchanged(dt, num_stages);
     });
@@ -1184,12 +1104,12 @@ int bdg_sw2d_curved_exchange(bdg_sw2d_curved* s, int intermediate) {
 int bdg_sw2d_curved_barrier(bdg_sw2d_curved* s) {
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_barrier");
-        if (!s->comm) throw arg_error("bdg_sw2d_curved_barrier: no communicator");
+        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_barrier: no communicator");
         s->use();
-        hipOk(hipStreamSynchronize(s->commStream), "hipStreamSynchronize");
-        hipOk(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(s->scalarBuf.p, s->scalarBuf.p, 1, ncclDouble, ncclMax, s->comm, s->stream), "ncclAllReduce");
-        hipOk(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(s->halo.scalarBuf.p, s->halo.scalarBuf.p, 1, ncclDouble, ncclMax, s->halo.comm, s->stream), "ncclAllReduce");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
 
@@ -1197,7 +1117,7 @@ int bdg_sw2d_curved_synchronize(bdg_sw2d_curved* s) {
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_synchronize");
         s->use();
-        hipOk(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
 

@@ -15,7 +15,7 @@
 #include "../host/capi_internal.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
-#include "rccl_api.hpp"
+#include "halo_transport.hpp"
 #include "sw2d_launch.hpp"
 #include <algorithm>
 #include <atomic>
@@ -104,25 +104,6 @@ __global__ void gather_rows_kernel(const T* __restrict__ src, T* __restrict__ ds
     dst[t] = src[r * ld + (perm ? perm[k] : k)];
 }
 
-// Halo exchange staging: element-major buffers of 3*Np doubles per element.
-//   pack:   buf[i*rows + r] = q[r*ld + slots[i]]        (owned elements a neighbour rank needs)
-//   unpack: q[r*ld + first + i] = buf[i*rows + r]       (ghost elements, stored after the owned ones)
-__global__ void halo_pack_kernel(const double* __restrict__ q, double* __restrict__ buf, const int* __restrict__ slots,
-                                 int count, int rows, long long ld) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(count) * rows) return;
-    const long long r = t / count, i = t % count; // consecutive lanes read consecutive elements of one row
-    buf[i * rows + r] = q[r * ld + slots[i]];
-}
-
-__global__ void halo_unpack_kernel(double* __restrict__ q, const double* __restrict__ buf, int first, int count,
-                                   int rows, long long ld) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(count) * rows) return;
-    const long long r = t / count, i = t % count;
-    q[r * ld + first + i] = buf[i * rows + r];
-}
-
 // ---- bandwidth probes (measurement aids, not part of the solver)
 // STREAM triad a = b + s*c on 16-byte lanes: the practical HBM roof of this device.
 __global__ __launch_bounds__(256) void triad_kernel(double2* __restrict__ a, const double2* __restrict__ b,
@@ -162,36 +143,10 @@ using bdg_detail::guard;
 using bdg_detail::hip_error;
 using bdg_detail::unstable_error;
 
-namespace {
-
-void hipCheck(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw hip_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
+using bdg_dev::DevBuf;
+using bdg_dev::hipCheck;
 using bdg_rccl::ncclCheck;
 using bdg_rccl::rccl;
-using bdg_rccl::RcclApi;
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void alloc(size_t count, size_t& total) {
-        release();
-        if (count == 0) return;
-        hipCheck(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)), "hipMalloc");
-        n = count;
-        total += count * sizeof(T);
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
-
-} // namespace
 
 namespace {
 std::vector<double> matmulHost(const double* A, const double* B, int n, int c);
@@ -235,15 +190,10 @@ struct bdg_sw2d {
     bool haloFusable = false;  // every sent element is a partition-boundary element with at most three records
     int numInterior = 0, numOwned = 0, numSend = 0; // element partition: [interior | boundary | ghost]
     // native halo exchange (RCCL over xGMI): one send and one receive range per neighbour rank
-    struct Peer { int rank, sendStart, sendCount, recvStart, recvCount; };
-    std::vector<Peer> peers;
-    ncclComm_t comm = nullptr;
-    int commRank = 0, commWorld = 1;
-    hipStream_t commStream = nullptr;
+    bdg_halo::Transport halo;
     hipEvent_t evA[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr};
     hipEvent_t evPacked[2] = {nullptr, nullptr}, evCopied[2] = {nullptr, nullptr}; // in-process group transport
     bool localGroup = false;
-    DevBuf<double> sendBuf, recvBuf, scalarBuf;
     // In-kernel dependencies between the two chains of an exchanged stage (round 4): two device counters --
     // [0] ring tiles of interior launches finished, [1] workgroups of boundary launches finished, [2] a word a bounded wait
     // sets when it gives up -- and what the host expects them to reach after the launches issued so far
@@ -258,10 +208,8 @@ struct bdg_sw2d {
     std::vector<int> permHost; // caller element -> device slot (empty = identity)
 
     ~bdg_sw2d() {
-        if (comm) (void)rccl().CommDestroy(comm);
         for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evPacked[0], evPacked[1], evCopied[0], evCopied[1]})
             if (e) (void)hipEventDestroy(e);
-        if (commStream) (void)hipStreamDestroy(commStream);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -572,44 +520,20 @@ struct bdg_sw2d {
 
     // `state`: the planes whose boundary elements are packed / whose ghost columns are filled (default: the current state)
     void launchPack(double* buf, hipStream_t on = nullptr, const double* state = nullptr) {
-        if (numSend == 0) return;
-        const int rows = nf * Np;
-        const long long n = static_cast<long long>(numSend) * rows;
-        hipLaunchKernelGGL(bdg_dev::halo_pack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           on ? on : stream, state ? state : qcur, buf, sendSlots.p, numSend, rows, ld);
-        hipCheck(hipGetLastError(), "halo_pack_kernel");
+        bdg_halo::pack(state ? state : qcur, ld, nf * Np, sendSlots.p, numSend, buf, on ? on : stream);
     }
     void launchUnpack(const double* buf, hipStream_t on = nullptr, double* state = nullptr) {
-        const int ghosts = K - numOwned;
-        if (ghosts == 0) return;
-        const int rows = nf * Np;
-        const long long n = static_cast<long long>(ghosts) * rows;
-        hipLaunchKernelGGL(bdg_dev::halo_unpack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           on ? on : stream, state ? state : qcur, buf, numOwned, ghosts, rows, ld);
-        hipCheck(hipGetLastError(), "halo_unpack_kernel");
+        bdg_halo::unpack(state ? state : qcur, ld, nf * Np, numOwned, K - numOwned, buf, on ? on : stream);
     }
 
     // ---- plain (not overlapped) exchange for the steppers whose RHS needs more than the neighbours' traces of the
     //      previous stage: every evaluation of the midpoint / Heun schemes reads another state, and variant B also
     //      needs ONE Lax-Friedrichs speed over all ranks (reference src/sw2d/main.cpp:414) before any element starts.
     void exchangeGhostsOf(double* state) {
-        if (!comm) throw arg_error("no communicator: call bdg_sw2d_comm_init first");
-        const int rows = nf * Np;
-        launchPack(sendBuf.p, stream, state);
-        if (!peers.empty()) {
-            RcclApi& nc = rccl();
-            ncclCheck(nc.GroupStart(), "ncclGroupStart");
-            for (const Peer& pr : peers) {
-                if (pr.recvCount > 0)
-                    ncclCheck(nc.Recv(recvBuf.p + static_cast<size_t>(pr.recvStart) * rows, static_cast<size_t>(pr.recvCount) * rows,
-                                      ncclDouble, pr.rank, comm, stream), "ncclRecv");
-                if (pr.sendCount > 0)
-                    ncclCheck(nc.Send(sendBuf.p + static_cast<size_t>(pr.sendStart) * rows, static_cast<size_t>(pr.sendCount) * rows,
-                                      ncclDouble, pr.rank, comm, stream), "ncclSend");
-            }
-            ncclCheck(nc.GroupEnd(), "ncclGroupEnd");
-        }
-        launchUnpack(recvBuf.p, stream, state);
+        if (!halo.comm) throw arg_error("no communicator: call bdg_sw2d_comm_init first");
+        launchPack(halo.sendBuf.p, stream, state);
+        halo.sendRecv(stream, nf * Np);
+        launchUnpack(halo.recvBuf.p, stream, state);
     }
     // variant B: speed of `state` over this rank's owned elements (their '+' traces include the ghosts just received),
     // then the maximum over all ranks, left in lamBuf on the device: one 8-byte all-reduce per RHS evaluation
@@ -619,8 +543,8 @@ struct bdg_sw2d {
         vb.tide = tideAt(timeNow);
         vb.lam = lamBuf.p;
         hipCheck(kt->stageVb(bdg_dev::MODE_RHS, p, vb, vbPartials.p, lamBuf.p, 4, nullptr, stream), "sw2d_vb_speed_kernel");
-        if (comm && commWorld > 1)
-            ncclCheck(rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, comm, stream), "ncclAllReduce");
+        if (halo.comm && halo.world > 1)
+            ncclCheck(rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, halo.comm, stream), "ncclAllReduce");
     }
     // one evaluation of a partitioned run: ghosts of `state`, the all-rank speed (variant B), then fn launches the stage
     template <typename Fn>
@@ -730,7 +654,7 @@ struct bdg_sw2d {
     //   the send / receive buffers and the ghost slots. Events alternate by stage parity so that a
     //   wait issued for stage s-1 is not re-armed by the record of stage s.
     void launchLserkStagesExchanged(double dt, int numStages) {
-        if (!comm) throw arg_error("no communicator: call bdg_sw2d_comm_init first");
+        if (!halo.comm) throw arg_error("no communicator: call bdg_sw2d_comm_init first");
         if (numStages <= 0) return;
         const int rows = nf * Np;
         dtStage = dt;
@@ -740,7 +664,7 @@ struct bdg_sw2d {
         }
         // chain B starts after everything already queued on A (state upload, earlier steps)
         hipCheck(hipEventRecord(evA[1], stream), "hipEventRecord");
-        hipCheck(hipStreamWaitEvent(commStream, evA[1], 0), "hipStreamWaitEvent");
+        hipCheck(hipStreamWaitEvent(halo.stream, evA[1], 0), "hipStreamWaitEvent");
         bool haveA = false, haveB = false;
         // With the staging folded into the boundary kernel, chain B is: exchange -> boundary kernel (which reads
         // the received records and writes the next send records); only the very first exchange needs a pack.
@@ -756,7 +680,7 @@ struct bdg_sw2d {
         // are a few dozen waves, so the boundary launch and RCCL's kernel always find free compute units (interiorGridCap keeps
         // them free at N >= 5), and every wait is bounded (sync_wait) -- a wave that gives up marks the run invalid.
         const bool flags = fold && flagSyncUsable();
-        if (fold) launchPack(sendBuf.p, commStream);
+        if (fold) launchPack(halo.sendBuf.p, halo.stream);
         for (int i = 0; i < numStages; ++i) {
             const int cur = i & 1, prev = cur ^ 1;
             const bool last = i == numStages - 1;
@@ -765,26 +689,12 @@ struct bdg_sw2d {
             if (!flags && haveB) hipCheck(hipStreamWaitEvent(stream, evB[prev], 0), "hipStreamWaitEvent");
             launchLserkStage(0, nullptr, true, flags ? nullptr : evA[cur], flags);
             // ---- chain B
-            if (!fold) launchPack(sendBuf.p, commStream);
-            if (!peers.empty()) {
-                RcclApi& nc = rccl();
-                ncclCheck(nc.GroupStart(), "ncclGroupStart");
-                for (const Peer& pr : peers) {
-                    if (pr.recvCount > 0)
-                        ncclCheck(nc.Recv(recvBuf.p + static_cast<size_t>(pr.recvStart) * rows,
-                                          static_cast<size_t>(pr.recvCount) * rows, ncclDouble, pr.rank, comm, commStream),
-                                  "ncclRecv");
-                    if (pr.sendCount > 0)
-                        ncclCheck(nc.Send(sendBuf.p + static_cast<size_t>(pr.sendStart) * rows,
-                                          static_cast<size_t>(pr.sendCount) * rows, ncclDouble, pr.rank, comm, commStream),
-                                  "ncclSend");
-                }
-                ncclCheck(nc.GroupEnd(), "ncclGroupEnd");
-            }
-            if (!fold) launchUnpack(recvBuf.p, commStream);
-            if (!flags && haveA) hipCheck(hipStreamWaitEvent(commStream, evA[prev], 0), "hipStreamWaitEvent");
-            if (fold) launchBoundaryStageFolded(commStream, recvBuf.p, sendBuf.p, (!flags || last) ? evB[cur] : nullptr, flags, ringBefore);
-            else launchLserkStage(1, commStream, true, evB[cur]); // partition-boundary elements, advance
+            if (!fold) launchPack(halo.sendBuf.p, halo.stream);
+            halo.sendRecv(halo.stream, rows);
+            if (!fold) launchUnpack(halo.recvBuf.p, halo.stream);
+            if (!flags && haveA) hipCheck(hipStreamWaitEvent(halo.stream, evA[prev], 0), "hipStreamWaitEvent");
+            if (fold) launchBoundaryStageFolded(halo.stream, halo.recvBuf.p, halo.sendBuf.p, (!flags || last) ? evB[cur] : nullptr, flags, ringBefore);
+            else launchLserkStage(1, halo.stream, true, evB[cur]); // partition-boundary elements, advance
             haveA = haveB = true;
         }
         // later work on A (dt reduction, downloads, plain stages) sees the last boundary update
@@ -793,12 +703,12 @@ struct bdg_sw2d {
 
     // max (or min) of one double over all ranks, through the device
     double allReduceScalar(double v, bool takeMax, bool sum = false) {
-        if (!comm || commWorld == 1) return v;
-        hipCheck(hipMemcpyAsync(scalarBuf.p, &v, sizeof(double), hipMemcpyHostToDevice, stream), "H2D copy");
-        ncclCheck(rccl().AllReduce(scalarBuf.p, scalarBuf.p + 1, 1, ncclDouble, sum ? ncclSum : (takeMax ? ncclMax : ncclMin),
-                                   comm, stream), "ncclAllReduce");
+        if (!halo.comm || halo.world == 1) return v;
+        hipCheck(hipMemcpyAsync(halo.scalarBuf.p, &v, sizeof(double), hipMemcpyHostToDevice, stream), "H2D copy");
+        ncclCheck(rccl().AllReduce(halo.scalarBuf.p, halo.scalarBuf.p + 1, 1, ncclDouble, sum ? ncclSum : (takeMax ? ncclMax : ncclMin),
+                                   halo.comm, stream), "ncclAllReduce");
         double out = 0.0;
-        hipCheck(hipMemcpyAsync(&out, scalarBuf.p + 1, sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
+        hipCheck(hipMemcpyAsync(&out, halo.scalarBuf.p + 1, sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
         hipCheck(hipStreamSynchronize(stream), "allreduce sync");
         return out;
     }
@@ -1861,28 +1771,17 @@ int bdg_sw2d_halo_pack(bdg_sw2d* s, void* send_buffer) {
         if (s->numSend == 0) return;
         if (!send_buffer) throw arg_error("bdg_sw2d_halo_pack: buffer is NULL");
         s->use();
-        const int rows = s->nf * s->Np;
-        const long long n = static_cast<long long>(s->numSend) * rows;
-        hipLaunchKernelGGL(bdg_dev::halo_pack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           s->stream, s->qcur, static_cast<double*>(send_buffer), s->sendSlots.p, s->numSend, rows,
-                           s->ld);
-        hipCheck(hipGetLastError(), "halo_pack_kernel");
+        s->launchPack(static_cast<double*>(send_buffer));
     });
 }
 
 int bdg_sw2d_halo_unpack(bdg_sw2d* s, const void* recv_buffer) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_halo_unpack");
-        const int ghosts = s->K - s->numOwned;
-        if (ghosts == 0) return;
+        if (s->K == s->numOwned) return;
         if (!recv_buffer) throw arg_error("bdg_sw2d_halo_unpack: buffer is NULL");
         s->use();
-        const int rows = s->nf * s->Np;
-        const long long n = static_cast<long long>(ghosts) * rows;
-        hipLaunchKernelGGL(bdg_dev::halo_unpack_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           s->stream, s->qcur, static_cast<const double*>(recv_buffer), s->numOwned, ghosts, rows,
-                           s->ld);
-        hipCheck(hipGetLastError(), "halo_unpack_kernel");
+        s->launchUnpack(static_cast<const double*>(recv_buffer));
     });
 }
 
@@ -1928,27 +1827,21 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
         if (!unique_id || world < 1 || rank < 0 || rank >= world || num_peers < 0 ||
             (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
             throw arg_error("bdg_sw2d_comm_init: bad argument");
-        if (s->comm) throw arg_error("bdg_sw2d_comm_init: communicator already initialised");
+        if (s->halo.comm) throw arg_error("bdg_sw2d_comm_init: communicator already initialised");
         const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_sw2d::Peer> peers;
+        std::vector<bdg_halo::Peer> peers;
         for (int i = 0; i < num_peers; ++i) {
-            const bdg_sw2d::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank >= world || p.sendStart < 0 || p.sendCount < 0 ||
-                p.sendStart + p.sendCount > s->numSend || p.recvStart < 0 || p.recvCount < 0 ||
-                p.recvStart + p.recvCount > ghosts)
+            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
+            if (p.rank < 0 || p.rank >= world || !bdg_halo::rangesFit(p, s->numSend, ghosts))
                 throw arg_error("bdg_sw2d_comm_init: peer ranges do not fit the partition set with bdg_sw2d_set_partition");
             peers.push_back(p);
         }
         s->use();
-        ncclUniqueId id;
-        std::memcpy(&id, unique_id, sizeof(id));
-        ncclCheck(rccl().CommInitRank(&s->comm, world, id, rank), "ncclCommInitRank");
-        s->commRank = rank;
-        s->commWorld = world;
-        s->peers = peers;
-        // (default priority: at the highest priority every stage of every order took about twice as long -- 8-way N=4 0.0958 against 0.0483 ms,
-        // N=8 0.113 against 0.052, 2-way 0.293 against 0.205: profiles/r04_rehearsal_experiments.txt, call 28)
-        hipCheck(hipStreamCreateWithFlags(&s->commStream, hipStreamNonBlocking), "hipStreamCreate");
+        const size_t rows = static_cast<size_t>(s->nf) * s->Np;
+        s->halo.connect(unique_id, rank, world, rows, s->numSend, ghosts, s->bytes);
+        s->halo.peers = peers;
+        hipCheck(hipMemset(s->halo.sendBuf.p, 0, s->halo.sendBuf.n * sizeof(double)), "hipMemset");
+        hipCheck(hipMemset(s->halo.recvBuf.p, 0, s->halo.recvBuf.n * sizeof(double)), "hipMemset");
         // These four events only order kernels of the two streams of THIS device against each other (a kernel's own
         // end-of-kernel release is device-wide, and data from another GPU is made visible by the RCCL kernel that received
         // it, on the stream that then runs the boundary kernel): the system-scope fence of a default event record is not
@@ -1961,12 +1854,6 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
         const unsigned evFlags = hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence);
         for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1]})
             hipCheck(hipEventCreateWithFlags(e, evFlags), "hipEventCreate");
-        const size_t rows = static_cast<size_t>(s->nf) * s->Np;
-        s->sendBuf.alloc(std::max<size_t>(1, static_cast<size_t>(s->numSend) * rows), s->bytes);
-        s->recvBuf.alloc(std::max<size_t>(1, static_cast<size_t>(ghosts) * rows), s->bytes);
-        hipCheck(hipMemset(s->sendBuf.p, 0, s->sendBuf.n * sizeof(double)), "hipMemset");
-        hipCheck(hipMemset(s->recvBuf.p, 0, s->recvBuf.n * sizeof(double)), "hipMemset");
-        s->scalarBuf.alloc(2, s->bytes);
         s->syncBuf.alloc(8, s->bytes);
         hipCheck(hipMemset(s->syncBuf.p, 0, 8 * sizeof(unsigned long long)), "hipMemset");
         s->expectRing = s->expectStrip = 0;
@@ -1974,17 +1861,9 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
         // slower of the two gets there). Do that HERE, where every rank is anyway and nothing is in flight: one double each way with
         // every neighbour, in the buffers and with the pairing of the stage exchange. Otherwise it would happen in the first exchanged
         // stage, behind interior launches whose ring tiles wait -- with a bound -- for the launches queued behind that exchange.
-        if (!s->peers.empty() && !std::getenv("BDG_SW2D_NO_COMM_WARMUP")) {
-            RcclApi& nc = rccl();
-            ncclCheck(nc.GroupStart(), "ncclGroupStart");
-            for (const bdg_sw2d::Peer& pr : s->peers) {
-                if (pr.recvCount > 0)
-                    ncclCheck(nc.Recv(s->recvBuf.p + static_cast<size_t>(pr.recvStart) * rows, 1, ncclDouble, pr.rank, s->comm, s->commStream), "ncclRecv");
-                if (pr.sendCount > 0)
-                    ncclCheck(nc.Send(s->sendBuf.p + static_cast<size_t>(pr.sendStart) * rows, 1, ncclDouble, pr.rank, s->comm, s->commStream), "ncclSend");
-            }
-            ncclCheck(nc.GroupEnd(), "ncclGroupEnd");
-            hipCheck(hipStreamSynchronize(s->commStream), "hipStreamSynchronize");
+        if (!s->halo.peers.empty() && !std::getenv("BDG_SW2D_NO_COMM_WARMUP")) {
+            s->halo.sendRecv(s->halo.stream, rows, 1);
+            hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
         }
     });
 }
@@ -2001,26 +1880,22 @@ int bdg_sw2d_local_peers(bdg_sw2d* s, int rank, const int* peer_ranks, const int
         if (rank < 0 || num_peers < 0 ||
             (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
             throw arg_error("bdg_sw2d_local_peers: bad argument");
-        if (s->comm || s->localGroup) throw arg_error("bdg_sw2d_local_peers: a transport is already initialised");
+        if (s->halo.comm || s->localGroup) throw arg_error("bdg_sw2d_local_peers: a transport is already initialised");
         const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_sw2d::Peer> peers;
+        std::vector<bdg_halo::Peer> peers;
         for (int i = 0; i < num_peers; ++i) {
-            const bdg_sw2d::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank == rank || p.sendStart < 0 || p.sendCount < 0 || p.sendStart + p.sendCount > s->numSend ||
-                p.recvStart < 0 || p.recvCount < 0 || p.recvStart + p.recvCount > ghosts)
+            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
+            if (p.rank < 0 || p.rank == rank || !bdg_halo::rangesFit(p, s->numSend, ghosts))
                 throw arg_error("bdg_sw2d_local_peers: peer ranges do not fit the partition set with bdg_sw2d_set_partition");
             peers.push_back(p);
         }
         s->use();
-        s->commRank = rank;
-        s->peers = peers;
-        hipCheck(hipStreamCreateWithFlags(&s->commStream, hipStreamNonBlocking), "hipStreamCreate");
+        s->halo.rank = rank;
+        s->halo.peers = peers;
+        s->halo.open(static_cast<size_t>(s->nf) * s->Np, s->numSend, ghosts, s->bytes);
         for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1], &s->evPacked[0], &s->evPacked[1],
                               &s->evCopied[0], &s->evCopied[1]})
             hipCheck(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate");
-        const size_t rows = static_cast<size_t>(s->nf) * s->Np;
-        s->sendBuf.alloc(std::max<size_t>(1, static_cast<size_t>(s->numSend) * rows), s->bytes);
-        s->recvBuf.alloc(std::max<size_t>(1, static_cast<size_t>(ghosts) * rows), s->bytes);
         s->localGroup = true;
     });
 }
@@ -2029,12 +1904,12 @@ int bdg_sw2d_group_lserk4_stages(bdg_sw2d** parts, int num_parts, double dt, int
     return guard([&] {
         if (!parts || num_parts < 1 || num_stages < 0) throw arg_error("bdg_sw2d_group_lserk4_stages: bad argument");
         for (int r = 0; r < num_parts; ++r) {
-            if (!parts[r] || !parts[r]->localGroup || parts[r]->commRank != r)
+            if (!parts[r] || !parts[r]->localGroup || parts[r]->halo.rank != r)
                 throw arg_error("bdg_sw2d_group_lserk4_stages: parts[r] must be the part given rank r in bdg_sw2d_local_peers");
-            for (const bdg_sw2d::Peer& pr : parts[r]->peers) {
+            for (const bdg_halo::Peer& pr : parts[r]->halo.peers) {
                 if (pr.rank >= num_parts) throw arg_error("bdg_sw2d_group_lserk4_stages: peer rank outside the group");
                 bool matched = false;
-                for (const bdg_sw2d::Peer& back : parts[pr.rank]->peers)
+                for (const bdg_halo::Peer& back : parts[pr.rank]->halo.peers)
                     matched = matched || (back.rank == r && back.sendCount == pr.recvCount && back.recvCount == pr.sendCount);
                 if (!matched) throw arg_error("bdg_sw2d_group_lserk4_stages: neighbour tables of two parts do not match");
             }
@@ -2043,7 +1918,7 @@ int bdg_sw2d_group_lserk4_stages(bdg_sw2d** parts, int num_parts, double dt, int
         }
         if (num_stages == 0) return;
         for (int r = 0; r < num_parts; ++r)          // direct access between the GPUs that exchange ghosts
-            for (const bdg_sw2d::Peer& pr : parts[r]->peers)
+            for (const bdg_halo::Peer& pr : parts[r]->halo.peers)
                 if (parts[pr.rank]->device != parts[r]->device) {
                     parts[r]->use();
                     const hipError_t e = hipDeviceEnablePeerAccess(parts[pr.rank]->device, 0);
@@ -2056,7 +1931,7 @@ int bdg_sw2d_group_lserk4_stages(bdg_sw2d** parts, int num_parts, double dt, int
             s->use();
             s->dtStage = dt;
             hipCheck(hipEventRecord(s->evA[1], s->stream), "hipEventRecord");
-            hipCheck(hipStreamWaitEvent(s->commStream, s->evA[1], 0), "hipStreamWaitEvent");
+            hipCheck(hipStreamWaitEvent(s->halo.stream, s->evA[1], 0), "hipStreamWaitEvent");
         }
         // pack / unpack folded into the boundary kernel where every part can do it (see launchLserkStagesExchanged)
         bool fold = true;
@@ -2072,46 +1947,46 @@ int bdg_sw2d_group_lserk4_stages(bdg_sw2d** parts, int num_parts, double dt, int
                 hipCheck(hipEventRecord(s->evA[cur], s->stream), "hipEventRecord");
                 if (!fold || first) {
                     if (!first)                               // neighbours are done reading our send buffer
-                        for (const bdg_sw2d::Peer& pr : s->peers)
-                            hipCheck(hipStreamWaitEvent(s->commStream, parts[pr.rank]->evCopied[prev], 0), "hipStreamWaitEvent");
-                    s->launchPack(s->sendBuf.p, s->commStream);
+                        for (const bdg_halo::Peer& pr : s->halo.peers)
+                            hipCheck(hipStreamWaitEvent(s->halo.stream, parts[pr.rank]->evCopied[prev], 0), "hipStreamWaitEvent");
+                    s->launchPack(s->halo.sendBuf.p, s->halo.stream);
                 }                                             // (folded: boundary(i-1) wrote the records, same stream)
-                hipCheck(hipEventRecord(s->evPacked[cur], s->commStream), "hipEventRecord");
+                hipCheck(hipEventRecord(s->evPacked[cur], s->halo.stream), "hipEventRecord");
             }
             for (int r = 0; r < num_parts; ++r) {           // pull the ghosts
                 bdg_sw2d* s = parts[r];
                 s->use();
-                for (const bdg_sw2d::Peer& pr : s->peers) {
+                for (const bdg_halo::Peer& pr : s->halo.peers) {
                     if (pr.recvCount == 0) continue;
                     bdg_sw2d* src = parts[pr.rank];
-                    const bdg_sw2d::Peer* back = nullptr;
-                    for (const bdg_sw2d::Peer& b : src->peers)
+                    const bdg_halo::Peer* back = nullptr;
+                    for (const bdg_halo::Peer& b : src->halo.peers)
                         if (b.rank == r) back = &b;
-                    hipCheck(hipStreamWaitEvent(s->commStream, src->evPacked[cur], 0), "hipStreamWaitEvent");
-                    double* dst = s->recvBuf.p + static_cast<size_t>(pr.recvStart) * rows;
-                    const double* from = src->sendBuf.p + static_cast<size_t>(back->sendStart) * rows;
+                    hipCheck(hipStreamWaitEvent(s->halo.stream, src->evPacked[cur], 0), "hipStreamWaitEvent");
+                    double* dst = s->halo.recvBuf.p + static_cast<size_t>(pr.recvStart) * rows;
+                    const double* from = src->halo.sendBuf.p + static_cast<size_t>(back->sendStart) * rows;
                     const size_t bytes = static_cast<size_t>(pr.recvCount) * rows * sizeof(double);
                     if (src->device == s->device)
-                        hipCheck(hipMemcpyAsync(dst, from, bytes, hipMemcpyDeviceToDevice, s->commStream), "ghost copy");
+                        hipCheck(hipMemcpyAsync(dst, from, bytes, hipMemcpyDeviceToDevice, s->halo.stream), "ghost copy");
                     else  // another GPU of the node: the copy engine pulls over xGMI
-                        hipCheck(hipMemcpyPeerAsync(dst, s->device, from, src->device, bytes, s->commStream), "ghost peer copy");
+                        hipCheck(hipMemcpyPeerAsync(dst, s->device, from, src->device, bytes, s->halo.stream), "ghost peer copy");
                 }
-                hipCheck(hipEventRecord(s->evCopied[cur], s->commStream), "hipEventRecord");
+                hipCheck(hipEventRecord(s->evCopied[cur], s->halo.stream), "hipEventRecord");
             }
             for (int r = 0; r < num_parts; ++r) {           // chain B: unpack, boundary elements
                 bdg_sw2d* s = parts[r];
                 s->use();
-                if (!fold) s->launchUnpack(s->recvBuf.p, s->commStream);
-                if (!first) hipCheck(hipStreamWaitEvent(s->commStream, s->evA[prev], 0), "hipStreamWaitEvent");
+                if (!fold) s->launchUnpack(s->halo.recvBuf.p, s->halo.stream);
+                if (!first) hipCheck(hipStreamWaitEvent(s->halo.stream, s->evA[prev], 0), "hipStreamWaitEvent");
                 if (fold) {
                     // the kernel overwrites the send records: every neighbour must have pulled this stage's first
-                    for (const bdg_sw2d::Peer& pr : s->peers)
-                        hipCheck(hipStreamWaitEvent(s->commStream, parts[pr.rank]->evCopied[cur], 0), "hipStreamWaitEvent");
-                    s->launchBoundaryStageFolded(s->commStream, s->recvBuf.p, s->sendBuf.p);
+                    for (const bdg_halo::Peer& pr : s->halo.peers)
+                        hipCheck(hipStreamWaitEvent(s->halo.stream, parts[pr.rank]->evCopied[cur], 0), "hipStreamWaitEvent");
+                    s->launchBoundaryStageFolded(s->halo.stream, s->halo.recvBuf.p, s->halo.sendBuf.p);
                 } else {
-                    s->launchLserkStage(1, s->commStream);
+                    s->launchLserkStage(1, s->halo.stream);
                 }
-                hipCheck(hipEventRecord(s->evB[cur], s->commStream), "hipEventRecord");
+                hipCheck(hipEventRecord(s->evB[cur], s->halo.stream), "hipEventRecord");
             }
         }
         for (int r = 0; r < num_parts; ++r) {
@@ -2119,7 +1994,7 @@ int bdg_sw2d_group_lserk4_stages(bdg_sw2d** parts, int num_parts, double dt, int
             s->use();
             hipCheck(hipStreamWaitEvent(s->stream, s->evB[(num_stages - 1) & 1], 0), "hipStreamWaitEvent");
             // the neighbours' last copies read this part's send buffer: order them before anything later on A
-            for (const bdg_sw2d::Peer& pr : s->peers)
+            for (const bdg_halo::Peer& pr : s->halo.peers)
                 hipCheck(hipStreamWaitEvent(s->stream, parts[pr.rank]->evCopied[(num_stages - 1) & 1], 0), "hipStreamWaitEvent");
         }
     });
@@ -2174,7 +2049,7 @@ int bdg_sw2d_barrier(bdg_sw2d* s) {
         requireSolver(s, "bdg_sw2d_barrier");
         s->use();
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        if (s->commStream) hipCheck(hipStreamSynchronize(s->commStream), "hipStreamSynchronize");
+        if (s->halo.stream) hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
         // every rank arrives before anyone leaves -- and a wait that gave up on ANY rank is reported by ALL of them here (a rank that
         // threw before the reduction would leave the others inside it), so that the callers can react together
         const bool mine = s->takeSyncMark();

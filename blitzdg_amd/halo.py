@@ -48,6 +48,22 @@ class HaloPlan:
     def local_to_global(self):
         return np.concatenate([self.own_global, self.halo_global])
 
+    def peer_tables(self, loopback=False):
+        """The five int32 tables of the native transports (bdg_sw2d_comm_init and friends): neighbour rank, send start,
+        send count, receive start, receive count, one entry per neighbour in ascending rank order. loopback=True: every
+        neighbour becomes rank 0 with min(send, receive) records each way (a send-to-self of the same size)."""
+        recv_of = {peer: (start, count) for peer, start, count in self.recv_slices}
+        send_of = {peer: (start, count) for peer, start, count in self.send_slices}
+        peers = sorted(set(recv_of) | set(send_of))
+        arr = lambda vals: np.ascontiguousarray(vals, dtype=np.int32)  # noqa: E731
+        pr = arr(peers)
+        ss, sc = arr([send_of.get(p, (0, 0))[0] for p in peers]), arr([send_of.get(p, (0, 0))[1] for p in peers])
+        rs, rc = arr([recv_of.get(p, (0, 0))[0] for p in peers]), arr([recv_of.get(p, (0, 0))[1] for p in peers])
+        if loopback:
+            pr = arr([0] * len(peers))
+            sc = rc = np.minimum(sc, rc)
+        return pr, ss, sc, rs, rc
+
 
 def build_plan(EToV, Vert, EToE, epart, rank, world, bctype=None):
     """Halo plan of `rank` from the global mesh tables and an element partition vector."""
@@ -152,7 +168,7 @@ def file_rendezvous(rank, world, make_id, timeout=300.0):
     unlinks whatever an earlier, crashed launch left under that name and creates the file with
     O_EXCL, mode 0600; the record carries rank 0's clock, and a reader only accepts a record written
     after its launcher started (a recycled launcher pid cannot match a stale record). Rank 0 removes
-    the file once every rank has joined (see NativeDistributedSw2d)."""
+    the file once every rank has joined (native_comm, remove_id_file)."""
     import os
     import struct
     import time
@@ -189,6 +205,38 @@ def file_rendezvous(rank, world, make_id, timeout=300.0):
     raise TimeoutError(f"rank {rank}: no fresh RCCL id at {path} after {timeout} s")
 
 
+def native_comm(plan, unique_id=None, loopback=False):
+    """Communicator of `plan.rank` for the native transports: (rank, world, 128-byte id buffer, rendezvous file).
+    unique_id=None: rank 0's id reaches the others through file_rendezvous, and the file is returned to rank 0, which
+    removes it (remove_id_file) once every rank has joined; otherwise the file is None. loopback=True: a communicator of
+    one rank with a fresh id, for the send-to-self rehearsal of the exchange."""
+    import ctypes
+
+    from ._capi import check, lib
+
+    def make_id():
+        buf = ctypes.create_string_buffer(128)
+        check(lib.bdg_comm_unique_id(buf, 128))
+        return buf.raw
+    rank, world, id_path = plan.rank, plan.world, None
+    if loopback:
+        rank, world, unique_id = 0, 1, make_id()
+    if unique_id is None:
+        unique_id, id_path = file_rendezvous(plan.rank, plan.world, make_id)
+    return rank, world, ctypes.create_string_buffer(unique_id, 128), id_path if plan.rank == 0 else None
+
+
+def remove_id_file(path):
+    """Rank 0's clean-up of the rendezvous file native_comm returned (None: nothing to remove)."""
+    import os
+    if path is None:
+        return
+    try:
+        os.remove(path)
+    except OSError:
+        pass
+
+
 class NativeDistributedSw2d:
     """sw2d on `world` GPUs with the exchange driven entirely by the C++ library: grouped
     ncclSend/ncclRecv on a communication stream, overlapped with the interior elements, whole
@@ -199,9 +247,6 @@ class NativeDistributedSw2d:
         """loopback=True: schedule rehearsal on ONE GPU -- this process computes `plan.rank`'s share
         of a `plan.world`-way split, and every neighbour exchange is a send-to-self of the same size
         (ghost values are then not the neighbours' -- timing only, never results)."""
-        import ctypes
-        import os
-
         from . import pyblitzdg as dg
         from . import sw2d
         from ._capi import byref, c_double, check, lib, ptr
@@ -225,38 +270,12 @@ class NativeDistributedSw2d:
         send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
         check(lib.bdg_sw2d_set_partition(self.solver._h, plan.num_interior, plan.num_owned, ptr(send), send.size))
 
-        id_path = None
-        comm_rank, comm_world = plan.rank, plan.world
-        if loopback:
-            comm_rank, comm_world = 0, 1
-            buf = ctypes.create_string_buffer(128)
-            check(lib.bdg_comm_unique_id(buf, 128))
-            unique_id = buf.raw
-        if unique_id is None:
-            def make_id():
-                buf = ctypes.create_string_buffer(128)
-                check(lib.bdg_comm_unique_id(buf, 128))
-                return buf.raw
-            unique_id, id_path = file_rendezvous(plan.rank, plan.world, make_id)
-        recv_of = {peer: (start, count) for peer, start, count in plan.recv_slices}
-        send_of = {peer: (start, count) for peer, start, count in plan.send_slices}
-        peers = sorted(set(recv_of) | set(send_of))
-        arr = lambda vals: np.ascontiguousarray(vals, dtype=np.int32)  # noqa: E731
-        pr = arr(peers)
-        ss, sc = arr([send_of.get(p, (0, 0))[0] for p in peers]), arr([send_of.get(p, (0, 0))[1] for p in peers])
-        rs, rc = arr([recv_of.get(p, (0, 0))[0] for p in peers]), arr([recv_of.get(p, (0, 0))[1] for p in peers])
-        if loopback:
-            pr = arr([0] * len(peers))
-            sc = rc = np.minimum(sc, rc)
-        idbuf = ctypes.create_string_buffer(unique_id, 128)
+        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
+        pr, ss, sc, rs, rc = plan.peer_tables(loopback)
         check(lib.bdg_sw2d_comm_init(self.solver._h, comm_rank, comm_world, idbuf, ptr(pr), ptr(ss), ptr(sc), ptr(rs),
-                                     ptr(rc), len(peers)))
+                                     ptr(rc), pr.size))
         self.barrier()
-        if id_path is not None and plan.rank == 0:
-            try:
-                os.remove(id_path)
-            except OSError:
-                pass
+        remove_id_file(id_path)
         self.global_elements = None
 
     @classmethod
@@ -495,22 +514,16 @@ class LocalGroupSw2d:
         self.world, self.order = world, order
         self.global_elements = mesh.numElements
         self.plans, self.meshes, self.nodes, self.solvers = [], [], [], []
-        arr = lambda vals: np.ascontiguousarray(vals, dtype=np.int32)  # noqa: E731
         for r in range(world):
             plan = build_plan(mesh.elements, mesh.vertices, mesh.EToE, epart, r, world, bctype=mesh.bcType)
             lm = build_local_mesh(plan)
             nd = dg.TriangleNodesProvisioner(order, lm)
             dev = devices[r] if devices is not None else 0
             s = sw2d.Sw2dSolver(nodes=nd, g=g, device=dev, flags=sw2d.KEEP_ORDER)
-            send = arr(plan.send_local)
+            send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
             check(lib.bdg_sw2d_set_partition(s._h, plan.num_interior, plan.num_owned, ptr(send), send.size))
-            recv_of = {peer: (start, count) for peer, start, count in plan.recv_slices}
-            send_of = {peer: (start, count) for peer, start, count in plan.send_slices}
-            peers = sorted(set(recv_of) | set(send_of))
-            pr = arr(peers)
-            ss, sc = arr([send_of.get(p, (0, 0))[0] for p in peers]), arr([send_of.get(p, (0, 0))[1] for p in peers])
-            rs, rc = arr([recv_of.get(p, (0, 0))[0] for p in peers]), arr([recv_of.get(p, (0, 0))[1] for p in peers])
-            check(lib.bdg_sw2d_local_peers(s._h, r, ptr(pr), ptr(ss), ptr(sc), ptr(rs), ptr(rc), len(peers)))
+            pr, ss, sc, rs, rc = plan.peer_tables()
+            check(lib.bdg_sw2d_local_peers(s._h, r, ptr(pr), ptr(ss), ptr(sc), ptr(rs), ptr(rc), pr.size))
             self.plans.append(plan)
             self.meshes.append(lm)
             self.nodes.append(nd)

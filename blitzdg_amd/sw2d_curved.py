@@ -236,11 +236,8 @@ class NativeDistributedSw2dCurved(DistributedSw2dCurved):
         """loopback=True: this one process computes plan.rank's share of a plan.world-way split and every neighbour exchange
         is a send-to-self of the same size through the real transport (ghost values are then this rank's own boundary
         elements, not the neighbours': a rehearsal of the exchange on one GPU, not a partitioned result)."""
-        import ctypes
-        import os
-
         from ._capi import ptr
-        from .halo import file_rendezvous
+        from .halo import native_comm, remove_id_file
 
         class _NoDist:                    # the base class only asks its transport for the backend name
             @staticmethod
@@ -250,36 +247,11 @@ class NativeDistributedSw2dCurved(DistributedSw2dCurved):
         h = self.solver._h
         send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
         check(lib.bdg_sw2d_curved_set_partition(h, plan.num_interior, plan.num_owned, ptr(send), send.size))
-        id_path = None
-        comm_rank, comm_world = plan.rank, plan.world
-
-        def make_id():
-            buf = ctypes.create_string_buffer(128)
-            check(lib.bdg_comm_unique_id(buf, 128))
-            return buf.raw
-        if loopback:
-            comm_rank, comm_world, unique_id = 0, 1, make_id()
-        if unique_id is None:
-            unique_id, id_path = file_rendezvous(plan.rank, plan.world, make_id)
-        recv_of = {peer: (start, count) for peer, start, count in plan.recv_slices}
-        send_of = {peer: (start, count) for peer, start, count in plan.send_slices}
-        peers = sorted(set(recv_of) | set(send_of))
-        arr = lambda vals: np.ascontiguousarray(vals, dtype=np.int32)  # noqa: E731
-        pr = arr(peers)
-        ss, sc = arr([send_of.get(p, (0, 0))[0] for p in peers]), arr([send_of.get(p, (0, 0))[1] for p in peers])
-        rs, rc = arr([recv_of.get(p, (0, 0))[0] for p in peers]), arr([recv_of.get(p, (0, 0))[1] for p in peers])
-        if loopback:
-            pr = arr([0] * len(peers))
-            sc = rc = np.minimum(sc, rc)
-        self.peer_table = (pr, ss, sc, rs, rc)
-        idbuf = ctypes.create_string_buffer(unique_id, 128)
-        check(lib.bdg_sw2d_curved_comm_init(h, comm_rank, comm_world, idbuf, ptr(pr), ptr(ss), ptr(sc), ptr(rs), ptr(rc), len(peers)))
+        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
+        pr, ss, sc, rs, rc = self.peer_table = plan.peer_tables(loopback)
+        check(lib.bdg_sw2d_curved_comm_init(h, comm_rank, comm_world, idbuf, ptr(pr), ptr(ss), ptr(sc), ptr(rs), ptr(rc), pr.size))
         self.barrier()
-        if id_path is not None and plan.rank == 0:
-            try:
-                os.remove(id_path)
-            except OSError:
-                pass
+        remove_id_file(id_path)
 
     def _exchange(self, intermediate):
         check(lib.bdg_sw2d_curved_exchange(self.solver._h, int(bool(intermediate))))

@@ -299,3 +299,51 @@ def test_plan_orders_owned_elements_deep_ring_boundary(world, mesh_args):
             assert len(back) == 1 and back[0][1] == count
             sent = plans[peer].own_global[plans[peer].send_local[back[0][0]:back[0][0] + count]]
             assert np.array_equal(sent, p.halo_global[start:start + count])
+
+
+def _strip_epart(mesh, world):
+    """A hand-made split into `world` vertical strips by element centroid (not METIS / RCB)."""
+    EToV = np.asarray(mesh.elements).reshape(-1, 3)
+    V = np.asarray(mesh.vertices).reshape(-1, 3)
+    cx = V[EToV, 0].mean(axis=1)
+    edges = np.linspace(cx.min(), cx.max(), world + 1)[1:-1]
+    return np.searchsorted(edges, cx).astype(np.int32)
+
+
+@pytest.mark.parametrize("split", ["partitionMesh", "strips"])
+def test_peer_tables_of_a_plan(split):
+    """HaloPlan.peer_tables, the neighbour tables every native transport is opened with (bdg_sw2d_comm_init,
+    bdg_sw2d_local_peers, bdg_sw2d_curved_comm_init): one int32 entry per neighbour in ascending rank order, send
+    ranges that cover the send list, receive ranges that tile the ghost slots, and loop-back tables that talk to
+    rank 0 with min(send, receive) records each way."""
+    import blitzdg_amd.pyblitzdg as dg
+    from blitzdg_amd.halo import build_plan
+    world = 4
+    mesh = dg.MeshManager()
+    mesh.buildBoxMesh(12, 9, shuffleSeed=3)
+    if split == "partitionMesh":
+        mesh.partitionMesh(world)
+        epart = np.asarray(mesh.elementPartitionMap).reshape(-1)
+    else:
+        epart = _strip_epart(mesh, world)
+    assert sorted(set(epart.tolist())) == list(range(world))
+    for rank in range(world):
+        plan = build_plan(mesh.elements, mesh.vertices, mesh.EToE, epart, rank, world, bctype=mesh.bcType)
+        pr, ss, sc, rs, rc = plan.peer_tables()
+        for t in (pr, ss, sc, rs, rc):
+            assert t.dtype == np.int32 and t.flags.c_contiguous and t.shape == pr.shape
+        assert pr.size > 0 and rank not in pr.tolist()
+        assert np.array_equal(pr, np.sort(pr)) and np.unique(pr).size == pr.size
+        assert set(pr.tolist()) == {p for p, _, _ in plan.send_slices} | {p for p, _, _ in plan.recv_slices}
+        assert int(sc.sum()) == len(plan.send_local)
+        assert ((ss >= 0) & (ss + sc <= len(plan.send_local))).all()
+        order = np.argsort(rs, kind="stable")                       # receive ranges tile [0, num_halo)
+        ends = np.concatenate([[0], (rs + rc)[order]])
+        assert np.array_equal(rs[order], ends[:-1]) and ends[-1] == plan.num_halo
+        for p, start, count in plan.recv_slices:
+            i = pr.tolist().index(p)
+            assert (rs[i], rc[i]) == (start, count)
+        lr, ls, lsc, lrs, lrc = plan.peer_tables(loopback=True)
+        assert lr.dtype == np.int32 and (lr == 0).all() and lr.size == pr.size
+        assert np.array_equal(ls, ss) and np.array_equal(lrs, rs)
+        assert np.array_equal(lsc, np.minimum(sc, rc)) and np.array_equal(lrc, lsc)
