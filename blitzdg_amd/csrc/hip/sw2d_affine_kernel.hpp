@@ -19,8 +19,12 @@
 //     while it runs;
 //   * the modal filter folds into the operators (Filt*Dr, Filt*Ds, Filt*Lift are
 //     prepared on the host), so a filtered RHS costs nothing extra.
-// HBM traffic per element and stage: q 360 + res 360 in, res 360 + q 360 out,
+// HBM traffic per element and stage at N = 4: q 360 + res 360 in, res 360 + q 360 out,
 // geometry 104, gather index 60 (+ neighbour traces through L2) = 1604 bytes.
+// The LSERK instances that gather through the face links (KIND = a StageKind, FaceLink in
+// sw2d_kernels.hpp) read 12 bytes of index instead of 60, skip the residual rows at the first
+// stage of a step and the residual store at the last: 1196 / 1556 / 1196 bytes for the first /
+// middle three / last stage, 1412 bytes on average over a step.
 #pragma once
 #include "sw2d_kernels.hpp"
 
@@ -92,13 +96,35 @@ struct PhysParams {
     double tide;
 };
 
+// Volume node that node n of a face linked with code (f' | reversed << 2) gathers: the Nfp compile-time choices of
+// each of the six codes, picked per lane.
+template <int N>
+__device__ __forceinline__ unsigned link_node(unsigned code, int n) {
+    using E = Elem<N>;
+    const bool rev = (code & 4u) != 0;
+    const unsigned f = code & 3u;
+    const unsigned m0 = rev ? E::fmask(0, N - n) : E::fmask(0, n);
+    const unsigned m1 = rev ? E::fmask(1, N - n) : E::fmask(1, n);
+    const unsigned m2 = rev ? E::fmask(2, N - n) : E::fmask(2, n);
+    return f == 0u ? m0 : (f == 1u ? m1 : m2);
+}
+
+// KIND of the unrolled kernel: gather through vmapP, residual in and out (every mode and family)
+constexpr int STAGE_VMAP = -1;
+
 // TRACER: the passive tracer hN (field 3; F4 = hN u, G4 = hN v, no sources) in the same pass.
 // SPONGE (MODE_COMBINE only): the momentum relaxation of the SSP-RK2 + sponge scheme is applied after the update; a
 // launch with StageParams::sponge == 0 takes the instance without it.
-template <int N, int MODE, int PHYS = 0, bool TRACER = false, bool SPONGE = false>
+// KIND: STAGE_VMAP, or a StageKind (three-field LSERK stage without sources): the neighbour traces are gathered through
+// the face links (p.faceLink), and the residual is neither read at STAGE_FIRST nor written at STAGE_LAST.
+template <int N, int MODE, int PHYS = 0, bool TRACER = false, bool SPONGE = false, int KIND = STAGE_VMAP>
 __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParams p, const PhysParams ph) {
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp, NFN = E::NFN;
+    constexpr bool kLinks = KIND != STAGE_VMAP;
+    static_assert(!kLinks || (MODE == MODE_LSERK && PHYS == 0 && !TRACER && !SPONGE), "face links: three-field LSERK stages");
+    constexpr bool kReadRes = MODE == MODE_LSERK && KIND != STAGE_FIRST;
+    constexpr bool kWriteRes = KIND != STAGE_LAST;
 
     const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
     const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
@@ -112,10 +138,17 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
     const double* __restrict__ ops = p.opsAffine; // wave-uniform reads -> scalar loads
     const double* __restrict__ qin = p.qin;
 
-    // ---- issue the independent loads: gather indices, own state, element geometry
-    int idx[NFN];
+    // ---- issue the independent loads: gather indices (or face links), own state, element geometry
+    int idx[kLinks ? 1 : NFN];
+    unsigned lnk[kLinks ? 3 : 1];
+    if constexpr (kLinks) {
+        const unsigned* __restrict__ fl = reinterpret_cast<const unsigned*>(p.faceLink);
 #pragma unroll
-    for (int j = 0; j < NFN; ++j) idx[j] = ld_row(p.vmapP + j * ld, k4);
+        for (int f = 0; f < 3; ++f) lnk[f] = ld_row(fl + f * ld, k4);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NFN; ++j) idx[j] = ld_row(p.vmapP + j * ld, k4);
+    }
     double h[Np], hu[Np], hv[Np], hN[TRACER ? Np : 1];
 #pragma unroll
     for (int n = 0; n < Np; ++n) {
@@ -177,6 +210,17 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
     if constexpr (kLateFace) {
         gatherFace(0);
         gatherFace(1);
+    } else if constexpr (kLinks) { // the same requests in the same order, offsets from the links
+        const unsigned uld = static_cast<unsigned>(ld);
+#pragma unroll
+        for (int j = 0; j < NFN; ++j) {
+            const int f = j / Nfp, n = j % Nfp;
+            const unsigned code = lnk[f] >> FaceLink::FACE_SHIFT & 7u;
+            const unsigned o8 = (link_node<N>(code, n) * uld + (lnk[f] & FaceLink::SLOT_MASK)) * 8u;
+            hP[j] = ld_row(qin, o8);
+            huP[j] = ld_row(qin + plane, o8);
+            hvP[j] = ld_row(qin + 2 * plane, o8);
+        }
     } else { // (the loop as it always was: the register allocation of these kernels is sensitive to the very order of requests)
 #pragma unroll
         for (int j = 0; j < NFN; ++j) {
@@ -225,7 +269,10 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
             hq[n] = hP[j];
             huq[n] = huP[j];
             hvq[n] = hvP[j];
-            if (idx[j] < 0) { // reflective wall: no normal flow
+            bool wall;
+            if constexpr (kLinks) wall = (lnk[f] & FaceLink::WALL) != 0u;
+            else wall = idx[j] < 0;
+            if (wall) { // reflective wall: no normal flow
                 const double un = hu[m] * nxf + hv[m] * nyf;
                 huq[n] = hu[m] - 2 * nxf * un;
                 hvq[n] = hv[m] - 2 * nyf * un;
@@ -270,7 +317,7 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
 
     // ---- stage inputs that are only needed at the very end: issue now, land during the volume loop
     double old1[Np], old2[Np], old3[Np], old4[TRACER ? Np : 1];
-    if constexpr (MODE == MODE_LSERK) {
+    if constexpr (kReadRes) {
         const double* __restrict__ rs = p.res;
 #pragma unroll
         for (int i = 0; i < Np; ++i) {
@@ -371,12 +418,29 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
         const double a = p.ca, b = p.cb, dt = p.cc;
 #pragma unroll
         for (int i = 0; i < Np; ++i) {
-            const double n1 = a * old1[i] + dt * R1[i];
-            const double n2 = a * old2[i] + dt * R2[i];
-            const double n3 = a * old3[i] + dt * R3[i];
-            st_row(rs + i * ld, k8, n1);
-            st_row(rs + plane + i * ld, k8, n2);
-            st_row(rs + 2 * plane + i * ld, k8, n3);
+            // The face-link instances spell out the contraction the vmapP instance gets from the compiler, a * old rounded and
+            // dt R fused (left to the compiler, a different instance of the same expression fused the other product at some
+            // nodes: N = 1 differed in the last bit). STAGE_FIRST: a = 0, and fma(dt, R, 0 * old) is dt R up to the sign of
+            // an exact zero.
+            double n1, n2, n3;
+            if constexpr (!kLinks) {
+                n1 = a * old1[i] + dt * R1[i];
+                n2 = a * old2[i] + dt * R2[i];
+                n3 = a * old3[i] + dt * R3[i];
+            } else if constexpr (kReadRes) {
+                n1 = fma(dt, R1[i], a * old1[i]);
+                n2 = fma(dt, R2[i], a * old2[i]);
+                n3 = fma(dt, R3[i], a * old3[i]);
+            } else {
+                n1 = dt * R1[i];
+                n2 = dt * R2[i];
+                n3 = dt * R3[i];
+            }
+            if constexpr (kWriteRes) {
+                st_row(rs + i * ld, k8, n1);
+                st_row(rs + plane + i * ld, k8, n2);
+                st_row(rs + 2 * plane + i * ld, k8, n3);
+            }
             st_row(o + i * ld, k8, h[i] + b * n1);
             st_row(o + plane + i * ld, k8, hu[i] + b * n2);
             st_row(o + 2 * plane + i * ld, k8, hv[i] + b * n3);

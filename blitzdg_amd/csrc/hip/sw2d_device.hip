@@ -118,20 +118,22 @@ __global__ __launch_bounds__(256) void triad_kernel(double2* __restrict__ a, con
 // Same rows, same 8-byte-per-lane accesses and same read/write mix as one fused LSERK stage of
 // the affine kernel (reads: state 3Np rows, residual 3Np rows, 13 geometry rows, 3Nfp index rows;
 // writes: residual and state, 6Np rows), with no gathers and almost no arithmetic: the time of
-// this launch is the memory-system floor for the stage kernel's own access pattern.
+// this launch is the memory-system floor for the stage kernel's own access pattern. With face
+// links: 3 index rows, no residual read (readRes = 0, first stage of a step) or no residual
+// write (writeRes = 0, last stage).
 __global__ __launch_bounds__(256) void stage_traffic_probe_kernel(const double* __restrict__ qin, double* __restrict__ qout,
                                                                  double* __restrict__ res, const double* __restrict__ ageo,
                                                                  const int* __restrict__ vmapP, int rows, int idxRows,
-                                                                 long long ld, int K) {
+                                                                 long long ld, int K, int readRes, int writeRes) {
     const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= static_cast<unsigned>(K)) return;
     double acc = 0.0;
     for (int r = 0; r < 13; ++r) acc += ageo[r * ld + k];
     for (int r = 0; r < idxRows; ++r) acc += vmapP[r * ld + k];
     for (int r = 0; r < rows; ++r) {
-        const double q = qin[r * ld + k], o = res[r * ld + k];
+        const double q = qin[r * ld + k], o = readRes ? res[r * ld + k] : 0.0;
         const double n = 0.5 * o + 1e-300 * (q + acc);
-        res[r * ld + k] = n;
+        if (writeRes) res[r * ld + k] = n;
         qout[r * ld + k] = q + 1e-300 * n;
     }
 }
@@ -187,6 +189,10 @@ struct bdg_sw2d {
                            // per SIMD; 1: rolled, one field per wave; 4: rolled, three fields per lane; 5: matrix cores (MFMA f64),
                            // whole tile unrolled; 6: matrix cores, face-by-face / chunked schedule at 2 waves per SIMD
     DevBuf<int> vmapP, perm, istage, sendSlots, haloSendOf;
+    // (3, ld) face links (bdg_dev::FaceLink) of the LSERK stages on the unrolled kernel; empty when the switch
+    // BDG_SW2D_FULL_STAGE_TRAFFIC is set, when that kernel does not serve the solver, or when a face's vmapP rows are not
+    // a neighbour face (or the face itself) in Fmask order
+    DevBuf<int> faceLink;
     bool haloFusable = false;  // every sent element is a partition-boundary element with at most three records
     int numInterior = 0, numOwned = 0, numSend = 0; // element partition: [interior | boundary | ghost]
     // native halo exchange (RCCL over xGMI): one send and one receive range per neighbour rank
@@ -507,6 +513,9 @@ struct bdg_sw2d {
         p.cc = dtStage;
         // model time (the tide phase of variant B) is frozen over the five stages and moves on after the last
         const bool lastOfStep = s == blitzdg::LSERK4::numStages - 1;
+        // the unrolled kernel's face-link instances (launchAffine, sw2d_order.hip); every other kernel ignores both
+        p.faceLink = faceLink.p;
+        p.stageKind = p.ca == 0.0 ? bdg_dev::STAGE_FIRST : (lastOfStep ? bdg_dev::STAGE_LAST : bdg_dev::STAGE_MID);
         nextEvalTime = lastOfStep ? timeNow + dtStage : timeNow;
         launchStage(bdg_dev::MODE_LSERK, false, p, "sw2d stage kernel <LSERK>", on);
         expectRing += signals;
@@ -1296,6 +1305,53 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
                            s->vmapP.p, NFN, K, ld, s->permDev());
         hipCheck(hipGetLastError(), "scatter_rows_kernel<int>");
         hipCheck(hipStreamSynchronize(s->stream), "vmapP sync");
+
+        // ---- face links: every face of every element must reproduce its Nfp rows above exactly (address and wall
+        //      flag); one face that does not (periodic maps, non-conforming meshes, hand-made tables) keeps the whole
+        //      solver on the vmapP gather
+        const char* full = std::getenv("BDG_SW2D_FULL_STAGE_TRAFFIC");
+        if (s->affine && s->N <= 4 && !s->variantD && !(full && full[0] != '0')) {
+            int fm[3][5]; // (N <= 4)
+            for (int f = 0; f < 3; ++f)
+                for (int n = 0; n < Nfp; ++n) fm[f][n] = kt->fmask(f, n);
+            std::vector<int> links(static_cast<size_t>(3) * K);
+            std::atomic<bool> ok{true};
+            blitzdg::detail::parallelChunks(K, [&](int kBegin, int kEnd) {
+                for (int k = kBegin; k < kEnd && ok.load(std::memory_order_relaxed); ++k)
+                    for (int f = 0; f < 3; ++f) {
+                        const int k2 = d.vmapP[static_cast<size_t>(k) * NFN + f * Nfp] / Np;
+                        const long long slot = perm ? perm[k2] : k2;
+                        const bool wall = rows[static_cast<size_t>(f * Nfp) * K + k] < 0;
+                        int code = -1;
+                        for (int c = 0; c < 6 && code < 0; ++c) {
+                            const int f2 = c % 3;
+                            const bool rev = c >= 3;
+                            bool same = true;
+                            for (int n = 0; n < Nfp && same; ++n) {
+                                const long long off = fm[f2][rev ? Nfp - 1 - n : n] * ld + slot;
+                                same = rows[static_cast<size_t>(f * Nfp + n) * K + k] == (wall ? -(off + 1) : off);
+                            }
+                            if (same) code = f2 | (rev ? 4 : 0);
+                        }
+                        if (code < 0) {
+                            ok = false;
+                            break;
+                        }
+                        links[static_cast<size_t>(f) * K + k] = static_cast<int>(
+                            bdg_dev::FaceLink::make(static_cast<unsigned>(slot), code & 3, code >= 4, wall));
+                    }
+            });
+            if (ok) {
+                s->faceLink.alloc(static_cast<size_t>(3) * ld, s->bytes);
+                hipCheck(hipMemsetAsync(s->faceLink.p, 0, s->faceLink.n * sizeof(int), s->stream), "hipMemset");
+                hipCheck(hipMemcpyAsync(s->istage.p, links.data(), links.size() * sizeof(int), hipMemcpyHostToDevice, s->stream),
+                         "face link upload");
+                hipLaunchKernelGGL((bdg_dev::scatter_rows_kernel<int>), dim3(static_cast<unsigned>((links.size() + 255) / 256)),
+                                   dim3(256), 0, s->stream, s->istage.p, s->faceLink.p, 3, K, ld, s->permDev());
+                hipCheck(hipGetLastError(), "scatter_rows_kernel<int>");
+                hipCheck(hipStreamSynchronize(s->stream), "face link sync");
+            }
+        }
     }
     s->istage.release();
     return s.release();
@@ -2098,14 +2154,18 @@ int bdg_sw2d_probe_stage_traffic(bdg_sw2d* s, int repeats, float* ms_per_launch)
         if (!s->affine) throw arg_error("bdg_sw2d_probe_stage_traffic: affine geometry only");
         s->use();
         const unsigned grid = static_cast<unsigned>((s->K + 255) / 256);
-        auto launch = [&] {
+        // with face links the launches cycle through the five stages of a step, as the stage kernel's do
+        const bool links = s->faceLink.p != nullptr;
+        auto launch = [&](int stage) {
+            const int last = blitzdg::LSERK4::numStages - 1;
             // aux / qalt are scratch here: the resident state is not modified
             hipLaunchKernelGGL(bdg_dev::stage_traffic_probe_kernel, dim3(grid), dim3(256), 0, s->stream, s->qcur, s->qalt,
-                               s->aux.p, s->ageo.p, s->vmapP.p, 3 * s->Np, s->NFN, s->ld, s->K);
+                               s->aux.p, s->ageo.p, links ? s->faceLink.p : s->vmapP.p, 3 * s->Np, links ? 3 : s->NFN, s->ld,
+                               s->K, !links || stage != 0 ? 1 : 0, !links || stage != last ? 1 : 0);
         };
-        launch();
+        launch(1);
         hipCheck(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
-        for (int i = 0; i < repeats; ++i) launch();
+        for (int i = 0; i < repeats; ++i) launch(i % blitzdg::LSERK4::numStages);
         hipCheck(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
         hipCheck(hipEventSynchronize(s->ev1), "hipEventSynchronize");
         float ms = 0.f;

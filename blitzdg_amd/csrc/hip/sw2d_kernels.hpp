@@ -47,6 +47,29 @@ struct Elem {
     static constexpr int LDS_DOUBLES = OFF_FILT + Np * Np;
 };
 
+// Face link: one int32 per element and face that reproduces the face's Nfp gather offsets. Bits 0-27: the neighbour's slot
+// k'; 28-29: its face f'; 30: the neighbour's face nodes run in the opposite sense; 31: reflective wall. Node n of the face
+// gathers node Fmask(f', reversed ? N - n : n) of slot k' (a boundary face links to itself). k' < 2^28 follows from
+// Np * ld < 2^29 (Np >= 3).
+struct FaceLink {
+    static constexpr unsigned SLOT_MASK = 0x0FFFFFFFu;
+    static constexpr int FACE_SHIFT = 28;
+    static constexpr unsigned REVERSED = 1u << 30;
+    static constexpr unsigned WALL = 1u << 31;
+    __host__ __device__ static constexpr unsigned make(unsigned slot, unsigned face, bool reversed, bool wall) {
+        return slot | (face << FACE_SHIFT) | (reversed ? REVERSED : 0u) | (wall ? WALL : 0u);
+    }
+};
+
+// LSERK stage kinds of the face-link instances of the unrolled kernel. rk4a[0] = 0: the first stage of a step does not read
+// the residual (res = dt R); the residual the last stage writes is read by nothing but the next step's first stage, which
+// multiplies it by 0: the last stage does not write it.
+enum StageKind {
+    STAGE_FIRST = 0, // no residual load
+    STAGE_MID = 1,   // residual in and out
+    STAGE_LAST = 2   // no residual store
+};
+
 enum StageMode {
     MODE_RHS = 0,    // rhs = R(qin)
     MODE_LSERK = 1,  // res = ca*res + cc*R(qin); qout = qin + cb*res
@@ -62,6 +85,10 @@ struct StageParams {
     const double* geo;   // rx, sx, ry, sy: 4 planes of Np*ld
     const double* fgeo;  // nx, ny, Fscale: 3 planes of NFN*ld
     const int* vmapP;    // NFN*ld gather offsets n'*ld + k'; wall nodes stored as -(offset+1)
+    // MODE_LSERK, unrolled kernel: 3 rows of ld face links (FaceLink below) or nullptr (gather through vmapP), and the
+    // StageKind of this launch (read only when faceLink is set)
+    const int* faceLink;
+    int stageKind;
     const double* ops;   // global image of the LDS block (Elem<N>::LDS_DOUBLES doubles)
     const double* ageo;  // affine path: 13 planes of ld: rx, sx, ry, sy, nx[3], ny[3], Fscale[3]
     const double* opsAffine; // affine path: AffineOps<N> image (plain or pre-filtered operators)

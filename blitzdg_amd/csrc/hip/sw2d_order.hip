@@ -106,6 +106,23 @@ hipError_t launchAffine(const StageParams& p, hipStream_t stream) {
         }
     }
     if (p.syncSignal) return hipErrorNotSupported; // (no SYNC instance of the unrolled kernel: see flagSyncUsable in sw2d_device.hip)
+    if constexpr (MODE == MODE_LSERK && kN <= 4) {
+        if (p.faceLink) { // gathers through the face links; the residual rows only where the stage needs them
+            switch (p.stageKind) {
+            case STAGE_FIRST:
+                BDG_LAUNCH_EV((sw2d_stage_affine_kernel<kN, MODE, 0, false, false, STAGE_FIRST>), dim3(grid), dim3(kUnrolledBlock), 0, stream, p, PhysParams{});
+                break;
+            case STAGE_MID:
+                BDG_LAUNCH_EV((sw2d_stage_affine_kernel<kN, MODE, 0, false, false, STAGE_MID>), dim3(grid), dim3(kUnrolledBlock), 0, stream, p, PhysParams{});
+                break;
+            case STAGE_LAST:
+                BDG_LAUNCH_EV((sw2d_stage_affine_kernel<kN, MODE, 0, false, false, STAGE_LAST>), dim3(grid), dim3(kUnrolledBlock), 0, stream, p, PhysParams{});
+                break;
+            default: return hipErrorInvalidValue;
+            }
+            return hipGetLastError();
+        }
+    }
     BDG_LAUNCH_EV((sw2d_stage_affine_kernel<kN, MODE>), dim3(grid), dim3(kUnrolledBlock), 0, stream, p, PhysParams{});
     return hipGetLastError();
     }
