@@ -55,6 +55,11 @@ REGIME_CASES = {
 }
 
 
+# the switches that select another kernel form of the four-field solvers (variants C and D), each against the default
+SOURCE_ENVS = {"default": {}, "two-wave": {"BDG_SW2D_SOURCES_TWO_WAVE": "1"}, "rolled": {"BDG_SW2D_ROLLED_SOURCES": "1"},
+               "tracer-pass": {"BDG_SW2D_TRACER_PASS": "1"}, "product": {"BDG_SW2D_SOURCES_PRODUCT": "1"}}
+
+
 def load_regimes(family, case):
     """A regime fixture tests/golden/regimes_<family>_<case>.npz and the tables it was made on (the existing fixture named in
     it). Returns (tables, {regime: {"h": .., "hu": .., "hv": .., ["hN": ..,] "rhs1": .., ...}})."""

@@ -290,6 +290,30 @@ def _dist_sources(x, y):
     return {"zx": 0.05 + 0 * x, "zy": -0.04 * y, "f": 0.0788, "CD": 2.5e-3 * (1.0 + 0.5 * np.cos(x))}
 
 
+def _rank_store(rank, world, out_dir, timeout=300.0):
+    """The process group's TCP store. Rank 0 listens on a port the system picks as it binds and publishes the number in
+    out_dir (so it cannot wait for the others in the constructor); the other ranks wait for the number. (A port probed free
+    beforehand can be taken by another process before rank 0 listens on it: EADDRINUSE.)"""
+    import datetime
+    import time
+
+    import torch.distributed as dist
+    path = os.path.join(out_dir, "store_port")
+    wait = datetime.timedelta(seconds=timeout)
+    if rank == 0:
+        store = dist.TCPStore("127.0.0.1", 0, world, True, timeout=wait, wait_for_workers=False)
+        with open(path + ".tmp", "w") as f:
+            f.write(str(store.port))
+        os.replace(path + ".tmp", path)
+        return store
+    deadline = time.monotonic() + timeout
+    while not os.path.exists(path):
+        assert time.monotonic() < deadline, "rank 0 did not publish its store port"
+        time.sleep(0.05)
+    with open(path) as f:
+        return dist.TCPStore("127.0.0.1", int(f.read()), world, False, timeout=wait)
+
+
 def _curved_rank_worker(rank, world, port, out_dir, general, native_env=None, stepper="rk2"):
     import sys
     from blitzdg_amd.halo import build_plan
@@ -316,7 +340,7 @@ def _curved_rank_worker(rank, world, port, out_dir, general, native_env=None, st
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
             torch.cuda.set_device(0)
         pg = {"device_id": torch.device("cuda", 0)} if backend == "nccl" else {}
-        dist.init_process_group(backend, init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world, **pg)
+        dist.init_process_group(backend, store=_rank_store(rank, world, out_dir), rank=rank, world_size=world, **pg)
         d = DistributedSw2dCurved(plan, DIST_ORDER, _dist_deform, dist, device=0, **kw)
         assert d._on_device == (backend == "nccl") and d.device == 0
     try:
@@ -348,7 +372,7 @@ def test_partitioned_curved_solver_matches_the_single_domain_run(tmp_path, world
     bit for bit)."""
     import socket
     from conftest import launch_ranks
-    with socket.socket() as sk:
+    with socket.socket() as sk:   # the native transports' MASTER_PORT: it names their rendezvous file, nothing listens on it
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     launch_ranks("test_sw2d_curved_gpu", "_curved_rank_worker", world,

@@ -1316,14 +1316,10 @@ def test_three_field_families_on_discontinuous_reference_fixtures(flags, env, ca
                             what=regime + " filtered")
 
 
-_SOURCE_ENVS = {"default": {}, "two-wave": {"BDG_SW2D_SOURCES_TWO_WAVE": "1"}, "rolled": {"BDG_SW2D_ROLLED_SOURCES": "1"},
-                "tracer-pass": {"BDG_SW2D_TRACER_PASS": "1"}, "product": {"BDG_SW2D_SOURCES_PRODUCT": "1"}}
-
-
 def _source_configs():
-    from regimes import REGIME_CASES
+    from regimes import REGIME_CASES, SOURCE_ENVS
     return [pytest.param(fam, case, env, id=f"{fam}-{case}-{name}") for fam in ("C", "D") for case in REGIME_CASES[fam]
-            for name, env in _SOURCE_ENVS.items()]
+            for name, env in SOURCE_ENVS.items()]
 
 
 @pytest.mark.parametrize("family,case,env", _source_configs())
