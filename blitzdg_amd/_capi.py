@@ -22,6 +22,7 @@ BDG_F64, BDG_I32 = 0, 1
 BDG_SW2D_REORDER = 1
 BDG_SW2D_NODAL_GEOMETRY = 2
 BDG_SW2D_KEEP_ORDER = 4
+BDG_SW2DQ_GENERAL_GEOMETRY = 1
 
 # enum values, in header order
 (MESH_VERTICES, MESH_ELEMENTS, MESH_ETOE, MESH_ETOF, MESH_BCTYPE, MESH_EPART, MESH_NPART) = range(7)
@@ -61,6 +62,15 @@ class Sw2dDesc(Structure):
                 ("g", c_double), ("device", c_int), ("flags", c_int),
                 ("num_fields", c_int), ("sources", c_int), ("zx", c_void_p), ("zy", c_void_p),
                 ("coriolis", c_void_p), ("coriolis_const", c_double), ("drag", c_double)]
+
+
+class Sw2dqDesc(Structure):
+    _fields_ = [("order", c_int), ("num_elements", c_int),
+                ("Dr", c_void_p), ("Ds", c_void_p), ("Lift", c_void_p), ("Filter", c_void_p),
+                ("rx", c_void_p), ("sx", c_void_p), ("ry", c_void_p), ("sy", c_void_p),
+                ("nx", c_void_p), ("ny", c_void_p), ("Fscale", c_void_p),
+                ("vmapM", c_void_p), ("vmapP", c_void_p), ("mapW", c_void_p), ("num_wall", c_int),
+                ("g", c_double), ("device", c_int), ("flags", c_int)]
 
 
 class Sw2dVbDesc(Structure):
@@ -106,6 +116,8 @@ _SIGNATURES = {
     "bdg_mesh_build_box": (c_int, [_P, c_int, c_int, c_double, c_double, c_double, c_double, c_ulonglong]),
     "bdg_mesh_set_bctype": (c_int, [_P, _P, c_int]),
     "bdg_mesh_partition": (c_int, [_P, c_int]),
+    "bdg_mesh_build_quads": (c_int, [_P, _P, c_int, _P, c_int, c_int]),
+    "bdg_mesh_num_faces": (c_int, [_P]),
     "bdg_mesh_num_elements": (c_int, [_P]),
     "bdg_mesh_num_verts": (c_int, [_P]),
     "bdg_mesh_table": (c_int, [_P, c_int, POINTER(Table)]),
@@ -119,6 +131,15 @@ _SIGNATURES = {
     "bdg_trinodes_bcmap_num_tags": (c_int, [_P]),
     "bdg_trinodes_bcmap_tags": (c_int, [_P, POINTER(c_int), c_int]),
     "bdg_trinodes_bcmap_nodes": (c_int, [_P, c_int, POINTER(POINTER(c_int)), POINTER(c_int)]),
+    "bdg_quadnodes_create": (c_int, [c_int, _P, POINTER(_P)]),
+    "bdg_quadnodes_destroy": (None, [_P]),
+    "bdg_quadnodes_build_filter": (c_int, [_P, c_double, c_int]),
+    "bdg_quadnodes_build_bchash": (c_int, [_P, _P, c_int]),
+    "bdg_quadnodes_dims": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "bdg_quadnodes_table": (c_int, [_P, c_int, POINTER(Table)]),
+    "bdg_quadnodes_bcmap_num_tags": (c_int, [_P]),
+    "bdg_quadnodes_bcmap_tags": (c_int, [_P, POINTER(c_int), c_int]),
+    "bdg_quadnodes_bcmap_nodes": (c_int, [_P, c_int, POINTER(POINTER(c_int)), POINTER(c_int)]),
     "bdg_trinodes_split_count": (c_int, [_P]),
     "bdg_trinodes_split_operators": (c_int, [_P, _P, _P]),
     "bdg_trinodes_split_elements": (c_int, [_P, _P, _P, _P, _P]),
@@ -174,6 +195,18 @@ _SIGNATURES = {
     "bdg_sw2d_global_speed": (c_int, [_P, POINTER(c_double)]),
     "bdg_trinodes_bed_slopes": (c_int, [_P, _P, _P, _P]),
     "bdg_trinodes_sponge_coeff": (c_int, [_P, _P, c_int, c_double, c_double, _P]),
+    "bdg_sw2dq_create": (c_int, [POINTER(Sw2dqDesc), POINTER(_P)]),
+    "bdg_sw2dq_create_from_nodes": (c_int, [_P, c_double, c_int, c_int, POINTER(_P)]),
+    "bdg_sw2dq_destroy": (None, [_P]),
+    "bdg_sw2dq_set_state": (c_int, [_P, _P, _P, _P]),
+    "bdg_sw2dq_get_state": (c_int, [_P, _P, _P, _P]),
+    "bdg_sw2dq_rhs": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int]),
+    "bdg_sw2dq_step_rk2": (c_int, [_P, c_double, c_int, c_int]),
+    "bdg_sw2dq_lserk4_stages": (c_int, [_P, c_double, c_int]),
+    "bdg_sw2dq_time": (c_int, [_P, c_int, c_double, c_int, POINTER(c_float)]),
+    "bdg_sw2dq_synchronize": (c_int, [_P]),
+    "bdg_sw2dq_device_bytes": (c_size_t, [_P]),
+    "bdg_sw2dq_uses_parallelogram_geometry": (c_int, [_P]),
     "bdg_sw2d_step_lserk4": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_lserk4_stages": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_step_rk2": (c_int, [_P, c_double, c_int, c_int]),

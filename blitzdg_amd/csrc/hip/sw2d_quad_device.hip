@@ -1,0 +1,466 @@
+// sw2d_quad_device.hip -- the device-resident quadrilateral sw2d solver behind the bdg_sw2dq_* C ABI
+// (include/blitzdg_hip.h). Host side: checks that Dr, Ds and Lift have the Gauss-Lobatto tensor form and extracts
+// their 1-D factors, chooses the geometry form, builds the gather index; then launches sw2d_quad_stage_kernel
+// (sw2d_quad_kernel.hpp) on its own stream. One device, one stream; results come back in the caller's numbering.
+#include "device_buffer.hpp"
+#include "sw2d_quad_kernel.hpp"
+#include "blitzdg/LSERK4.hpp"
+#include "blitzdg/MeshManager.hpp"
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+using bdg_detail::arg_error;
+using bdg_detail::guard;
+using bdg_detail::unstable_error;
+using namespace bdg_dev;
+
+namespace bdg_dev {
+
+hipError_t sw2d_quad_stage(int order, int mode, bool filter, bool general, const QuadParams& p, hipStream_t stream) {
+    switch (order) {
+    case 1: return sw2d_quad_launch<1>(mode, filter, general, p, stream);
+    case 2: return sw2d_quad_launch<2>(mode, filter, general, p, stream);
+    case 3: return sw2d_quad_launch<3>(mode, filter, general, p, stream);
+    case 4: return sw2d_quad_launch<4>(mode, filter, general, p, stream);
+    case 5: return sw2d_quad_launch<5>(mode, filter, general, p, stream);
+    case 6: return sw2d_quad_launch<6>(mode, filter, general, p, stream);
+    case 7: return sw2d_quad_launch<7>(mode, filter, general, p, stream);
+    case 8: return sw2d_quad_launch<8>(mode, filter, general, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+int sw2d_quad_tile(int order) {
+    switch (order) {
+    case 1: return QuadElem<1>::E;
+    case 2: return QuadElem<2>::E;
+    default: return QuadElem<3>::E;
+    }
+}
+
+} // namespace bdg_dev
+
+namespace {
+
+// |h| maximum and NaN count of plane 0 over [0, K): two doubles per block
+__global__ __launch_bounds__(256) void sw2d_quad_hmax_kernel(const double* h, long long ld, int Np, int K, double* partials) {
+    __shared__ double smax[256], snan[256];
+    double mx = 0.0, nn = 0.0;
+    const long long total = static_cast<long long>(Np) * K;
+    for (long long t = blockIdx.x * 256LL + threadIdx.x; t < total; t += 256LL * gridDim.x) {
+        const long long n = t / K, k = t % K;
+        const double v = h[n * ld + k];
+        if (v != v) nn += 1.0;
+        else mx = fabs(v) > mx ? fabs(v) : mx;
+    }
+    smax[threadIdx.x] = mx;
+    snan[threadIdx.x] = nn;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + s]);
+            snan[threadIdx.x] += snan[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = smax[0];
+        partials[2 * blockIdx.x + 1] = snan[0];
+    }
+}
+
+constexpr int kHmaxBlocks = 512;
+
+} // namespace
+
+struct bdg_sw2dq {
+    int N = 0, Np = 0, Nfp = 0, NFN = 0, K = 0, device = 0;
+    long long ld = 0;
+    double g = 9.81;
+    bool general = true, hasFilter = false;
+    hipStream_t stream = nullptr;
+    size_t bytes = 0;
+    long long stageCount = 0;
+    DevBuf<double> q, q1, res, io, ioOut, geo, fgeo, ageo, ops, filt, partials;
+    DevBuf<int> gidx;
+    std::vector<double> hostPartials;
+
+    void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
+    long long plane() const { return static_cast<long long>(Np) * ld; }
+
+    // host (rows, K) -> device planes of stride ld
+    void upload(double* dst, const double* src, int rows) {
+        hipCheck(hipMemcpy2DAsync(dst, ld * sizeof(double), src, K * sizeof(double), K * sizeof(double), rows,
+                                  hipMemcpyHostToDevice, stream), "hipMemcpy2D (upload)");
+    }
+    void download(double* dst, const double* src, int rows) {
+        hipCheck(hipMemcpy2DAsync(dst, K * sizeof(double), src, ld * sizeof(double), K * sizeof(double), rows,
+                                  hipMemcpyDeviceToHost, stream), "hipMemcpy2D (download)");
+    }
+
+    QuadParams params() const {
+        QuadParams p{};
+        p.geo = geo.p; p.fgeo = fgeo.p; p.ageo = ageo.p; p.gidx = gidx.p; p.ops = ops.p; p.filt = filt.p;
+        p.ld = ld; p.K = K; p.g = g;
+        return p;
+    }
+    void launch(int mode, bool filter, const QuadParams& p) {
+        hipCheck(sw2d_quad_stage(N, mode, filter, general, p, stream), "sw2d_quad_stage_kernel launch");
+    }
+    void rk2Step(double dt, bool filter) {
+        QuadParams p = params();
+        p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.cc = 0.5 * dt;        // predictor: q1 = q + dt/2 F R(q)
+        launch(QMODE_COMBINE, filter, p);
+        p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;              // corrector: q += dt F R(q1)
+        launch(QMODE_COMBINE, filter, p);
+    }
+    void lserkStage(double dt) {
+        const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
+        QuadParams p = params();
+        p.qin = q.p; p.qout = q1.p; p.res = res.p;
+        p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
+        launch(QMODE_LSERK, false, p);
+        std::swap(q.p, q1.p); // neighbours read the old traces during the launch: double-buffered
+        ++stageCount;
+    }
+    // the reference script's check after every step: max|h| > 1e8 or NaN
+    void checkBlowUp() {
+        hipLaunchKernelGGL(sw2d_quad_hmax_kernel, dim3(kHmaxBlocks), dim3(256), 0, stream, q.p, ld, Np, K, partials.p);
+        hipCheck(hipGetLastError(), "sw2d_quad_hmax_kernel launch");
+        hostPartials.resize(2 * kHmaxBlocks);
+        hipCheck(hipMemcpyAsync(hostPartials.data(), partials.p, 2 * kHmaxBlocks * sizeof(double), hipMemcpyDeviceToHost,
+                                stream), "hipMemcpy (partials)");
+        hipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        double mx = 0.0, nans = 0.0;
+        for (int b = 0; b < kHmaxBlocks; ++b) {
+            mx = std::max(mx, hostPartials[2 * b]);
+            nans += hostPartials[2 * b + 1];
+        }
+        if (nans > 0 || mx > 1e8) throw unstable_error("A numerical instability has occurred!");
+    }
+    ~bdg_sw2dq() {
+        if (stream) {
+            (void)hipSetDevice(device);
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+};
+
+namespace {
+
+void requireSolver(const bdg_sw2dq* s, const char* fn) {
+    if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
+}
+
+double maxAbs(const double* a, size_t n) {
+    double m = 0.0;
+    for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(a[i]));
+    return m;
+}
+
+// Dr = D1 (x) I, Ds = I (x) D1 and the face-wise lift structure, each to 1e-13 max|entry|; returns the ops image.
+std::vector<double> tensorFactors(int N, const double* Dr, const double* Ds, const double* Lift) {
+    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
+    std::vector<double> ops(Nq * Nq + 2 * Nq);
+    double* D1 = ops.data();
+    double* l0 = D1 + Nq * Nq;
+    double* lN = l0 + Nq;
+    for (int j = 0; j < Nq; ++j)
+        for (int m = 0; m < Nq; ++m) D1[j * Nq + m] = Dr[static_cast<size_t>(Nq * j) * Np + Nq * m];
+    for (int i = 0; i < Nq; ++i) l0[i] = Lift[static_cast<size_t>(i) * NFN + 0];          // face 0, q = j = 0
+    for (int j = 0; j < Nq; ++j) lN[j] = Lift[static_cast<size_t>(Nq * j) * NFN + Nq];    // face 1, q = i = 0
+    const double tolD = 1e-13 * std::max(maxAbs(Dr, static_cast<size_t>(Np) * Np), maxAbs(Ds, static_cast<size_t>(Np) * Np));
+    const double tolL = 1e-13 * maxAbs(Lift, static_cast<size_t>(Np) * NFN);
+    double errD = 0.0, errL = 0.0;
+    for (int j = 0; j < Nq; ++j)
+        for (int i = 0; i < Nq; ++i) {
+            const size_t row = static_cast<size_t>(Nq * j + i);
+            for (int jj = 0; jj < Nq; ++jj)
+                for (int ii = 0; ii < Nq; ++ii) {
+                    const int col = Nq * jj + ii;
+                    const double er = (ii == i ? D1[j * Nq + jj] : 0.0), es = (jj == j ? D1[i * Nq + ii] : 0.0);
+                    errD = std::max(errD, std::fabs(Dr[row * Np + col] - er));
+                    errD = std::max(errD, std::fabs(Ds[row * Np + col] - es));
+                }
+            for (int q = 0; q < Nq; ++q) {
+                const double e0 = q == j ? l0[i] : 0.0, e1 = q == i ? lN[j] : 0.0;
+                const double e2 = q == j ? lN[i] : 0.0, e3 = q == i ? l0[j] : 0.0;
+                errL = std::max(errL, std::fabs(Lift[row * NFN + q] - e0));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + Nq + q] - e1));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + 2 * Nq + q] - e2));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + 3 * Nq + q] - e3));
+            }
+        }
+    if (!(errD <= tolD))
+        throw arg_error("bdg_sw2dq_create: Dr / Ds are not the Gauss-Lobatto tensor operators D1 (x) I, I (x) D1 (deviation " +
+                        std::to_string(errD) + "); the quadrilateral kernel has no dense-operator form");
+    if (!(errL <= tolL))
+        throw arg_error("bdg_sw2dq_create: Lift does not have the face-wise tensor form of the Gauss-Lobatto element (deviation " +
+                        std::to_string(errL) + "); the quadrilateral kernel has no dense-operator form");
+    return ops;
+}
+
+bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d) {
+    const int N = d.order, K = d.num_elements;
+    if (N < 1 || N > BDG_SW2DQ_MAX_ORDER)
+        throw arg_error("bdg_sw2dq_create: order " + std::to_string(N) + " is outside 1.." + std::to_string(BDG_SW2DQ_MAX_ORDER));
+    if (K < 1) throw arg_error("bdg_sw2dq_create: num_elements < 1");
+    if (!d.Dr || !d.Ds || !d.Lift || !d.rx || !d.sx || !d.ry || !d.sy || !d.nx || !d.ny || !d.Fscale || !d.vmapP)
+        throw arg_error("bdg_sw2dq_create: NULL table");
+    if (d.num_wall < 0 || (d.num_wall > 0 && !d.mapW)) throw arg_error("bdg_sw2dq_create: bad wall list");
+    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
+    if (static_cast<long long>(Np) * (K + 64) >= (1LL << 31)) throw arg_error("bdg_sw2dq_create: mesh too large for int32 gathers");
+    std::vector<double> opsHost = tensorFactors(N, d.Dr, d.Ds, d.Lift);
+
+    if (d.vmapM) {
+        for (int k = 0; k < K; ++k)
+            for (int f = 0; f < 4; ++f)
+                for (int n = 0; n < Nq; ++n) {
+                    const int fm = f == 0 ? Nq * n : (f == 1 ? Nq * N + n : (f == 2 ? Nq * n + N : n));
+                    if (d.vmapM[(static_cast<size_t>(k) * 4 + f) * Nq + n] != fm + Np * k)
+                        throw arg_error("bdg_sw2dq_create: vmapM is not the Gauss-Lobatto face numbering (faces s=-1, r=+1, s=+1, r=-1)");
+                }
+    }
+
+    std::unique_ptr<bdg_sw2dq> s(new bdg_sw2dq());
+    s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->g = d.g; s->device = d.device;
+    s->ld = (static_cast<long long>(K) + 63) / 64 * 64;
+    const long long ld = s->ld;
+
+    // gather index, [fn][ld]: vmapP entry of face node fn of element k, wall nodes with the sign bit
+    std::vector<int> gi(static_cast<size_t>(NFN) * ld, 0);
+    std::vector<char> wall(static_cast<size_t>(NFN) * K, 0);
+    for (int w = 0; w < d.num_wall; ++w) {
+        if (d.mapW[w] < 0 || d.mapW[w] >= NFN * K) throw arg_error("bdg_sw2dq_create: mapW entry out of range");
+        wall[d.mapW[w]] = 1;
+    }
+    for (int k = 0; k < K; ++k)
+        for (int fn = 0; fn < NFN; ++fn) {
+            const size_t g = static_cast<size_t>(k) * NFN + fn;
+            const int v = d.vmapP[g];
+            if (v < 0 || v >= Np * K) throw arg_error("bdg_sw2dq_create: vmapP entry out of range");
+            const long long off = static_cast<long long>(v % Np) * ld + v / Np;
+            gi[static_cast<size_t>(fn) * ld + k] = wall[g] ? static_cast<int>(-(off + 1)) : static_cast<int>(off);
+        }
+
+    // geometry form: parallelograms (metric terms constant per element, nx, ny, Fscale per face, to 1e-10 relative)
+    bool para = (d.flags & BDG_SW2DQ_GENERAL_GEOMETRY) == 0;
+    std::vector<double> ag;
+    if (para) {
+        ag.assign(static_cast<size_t>(16) * ld, 0.0);
+        const double* met[4] = {d.rx, d.sx, d.ry, d.sy};
+        const double* fg[3] = {d.nx, d.ny, d.Fscale};
+        for (int k = 0; k < K && para; ++k) {
+            double scale = 0.0;
+            for (int a = 0; a < 4; ++a)
+                for (int n = 0; n < Np; ++n) scale = std::max(scale, std::fabs(met[a][static_cast<size_t>(n) * K + k]));
+            for (int a = 0; a < 4 && para; ++a) {
+                double mean = 0.0;
+                for (int n = 0; n < Np; ++n) mean += met[a][static_cast<size_t>(n) * K + k];
+                mean /= Np;
+                for (int n = 0; n < Np; ++n)
+                    if (std::fabs(met[a][static_cast<size_t>(n) * K + k] - mean) > 1e-10 * scale) para = false;
+                ag[static_cast<size_t>(a) * ld + k] = mean;
+            }
+            for (int c = 0; c < 3 && para; ++c)
+                for (int f = 0; f < 4 && para; ++f) {
+                    double mean = 0.0, sc = 0.0;
+                    for (int n = 0; n < Nq; ++n) {
+                        const double v = fg[c][static_cast<size_t>(f * Nq + n) * K + k];
+                        mean += v;
+                        sc = std::max(sc, std::fabs(v));
+                    }
+                    mean /= Nq;
+                    if (c < 2) sc = 1.0;
+                    for (int n = 0; n < Nq; ++n)
+                        if (std::fabs(fg[c][static_cast<size_t>(f * Nq + n) * K + k] - mean) > 1e-10 * sc) para = false;
+                    ag[static_cast<size_t>(4 + 4 * c + f) * ld + k] = mean;
+                }
+        }
+    }
+    s->general = !para;
+
+    s->use();
+    hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
+    const long long plane = s->plane();
+    s->q.alloc(3 * plane, s->bytes, s->stream);
+    s->q1.alloc(3 * plane, s->bytes, s->stream);
+    s->res.alloc(3 * plane, s->bytes, s->stream);
+    s->gidx.alloc(gi.size(), s->bytes);
+    hipCheck(hipMemcpyAsync(s->gidx.p, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "hipMemcpy (gidx)");
+    s->ops.alloc(opsHost.size(), s->bytes);
+    hipCheck(hipMemcpyAsync(s->ops.p, opsHost.data(), opsHost.size() * sizeof(double), hipMemcpyHostToDevice, s->stream),
+             "hipMemcpy (ops)");
+    if (d.Filter) {
+        s->filt.alloc(static_cast<size_t>(Np) * Np, s->bytes);
+        hipCheck(hipMemcpyAsync(s->filt.p, d.Filter, static_cast<size_t>(Np) * Np * sizeof(double), hipMemcpyHostToDevice,
+                                s->stream), "hipMemcpy (Filter)");
+        s->hasFilter = true;
+    }
+    if (para) {
+        s->ageo.alloc(ag.size(), s->bytes);
+        hipCheck(hipMemcpyAsync(s->ageo.p, ag.data(), ag.size() * sizeof(double), hipMemcpyHostToDevice, s->stream),
+                 "hipMemcpy (ageo)");
+    } else {
+        s->geo.alloc(4 * plane, s->bytes, s->stream);
+        s->fgeo.alloc(3LL * NFN * ld, s->bytes, s->stream);
+        const double* met[4] = {d.rx, d.sx, d.ry, d.sy};
+        for (int a = 0; a < 4; ++a) s->upload(s->geo.p + a * plane, met[a], Np);
+        s->upload(s->fgeo.p, d.nx, NFN);
+        s->upload(s->fgeo.p + static_cast<long long>(NFN) * ld, d.ny, NFN);
+        s->upload(s->fgeo.p + 2LL * NFN * ld, d.Fscale, NFN);
+    }
+    s->partials.alloc(2 * kHmaxBlocks, s->bytes);
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize (create)"); // host staging vectors die here
+    return s.release();
+}
+
+} // namespace
+
+extern "C" {
+
+int bdg_sw2dq_create(const bdg_sw2dq_desc* desc, bdg_sw2dq** out) {
+    return guard([&] {
+        if (!desc || !out) throw arg_error("bdg_sw2dq_create: NULL argument");
+        *out = createQuad(*desc);
+    });
+}
+
+int bdg_sw2dq_create_from_nodes(const bdg_quadnodes* nodes, double g, int device, int flags, bdg_sw2dq** out) {
+    return guard([&] {
+        if (!nodes || !out) throw arg_error("bdg_sw2dq_create_from_nodes: NULL argument");
+        const blitzdg::QuadNodesProvisioner& p = nodes->prov;
+        bdg_sw2dq_desc d{};
+        d.order = p.get_NOrder();
+        d.num_elements = p.get_NumElements();
+        d.Dr = p.get_Dr().data(); d.Ds = p.get_Ds().data(); d.Lift = p.get_Lift().data();
+        d.Filter = nodes->hasFilter ? p.get_Filter().data() : nullptr;
+        d.rx = p.get_rx().data(); d.sx = p.get_sx().data(); d.ry = p.get_ry().data(); d.sy = p.get_sy().data();
+        d.nx = p.get_nx().data(); d.ny = p.get_ny().data(); d.Fscale = p.get_Fscale().data();
+        d.vmapM = p.get_vmapM().data(); d.vmapP = p.get_vmapP().data();
+        const auto& bc = p.get_bcMap();
+        const auto it = bc.find(blitzdg::BCTag::Wall);
+        if (it != bc.end()) { d.mapW = it->second.data(); d.num_wall = static_cast<int>(it->second.size()); }
+        d.g = g; d.device = device; d.flags = flags;
+        *out = createQuad(d);
+    });
+}
+
+void bdg_sw2dq_destroy(bdg_sw2dq* s) { delete s; }
+
+int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const double* hv) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_set_state");
+        if (!h || !hu || !hv) throw arg_error("bdg_sw2dq_set_state: NULL field");
+        s->use();
+        const long long plane = s->plane();
+        s->upload(s->q.p, h, s->Np);
+        s->upload(s->q.p + plane, hu, s->Np);
+        s->upload(s->q.p + 2 * plane, hv, s->Np);
+        s->res.zero(s->stream);
+        s->stageCount = 0;
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_get_state(bdg_sw2dq* s, double* h, double* hu, double* hv) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_get_state");
+        s->use();
+        const long long plane = s->plane();
+        if (h) s->download(h, s->q.p, s->Np);
+        if (hu) s->download(hu, s->q.p + plane, s->Np);
+        if (hv) s->download(hv, s->q.p + 2 * plane, s->Np);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, double* rhs1, double* rhs2,
+                  double* rhs3, int filter) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_rhs");
+        if (!h || !hu || !hv || !rhs1 || !rhs2 || !rhs3) throw arg_error("bdg_sw2dq_rhs: NULL argument");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_rhs: filter requested but the solver has no Filter");
+        s->use();
+        const long long plane = s->plane();
+        if (!s->io.p) {
+            s->io.alloc(3 * plane, s->bytes, s->stream);
+            s->ioOut.alloc(3 * plane, s->bytes, s->stream);
+        }
+        s->upload(s->io.p, h, s->Np);
+        s->upload(s->io.p + plane, hu, s->Np);
+        s->upload(s->io.p + 2 * plane, hv, s->Np);
+        QuadParams p = s->params();
+        p.qin = s->io.p; p.rhs = s->ioOut.p;
+        s->launch(QMODE_RHS, filter != 0, p);
+        s->download(rhs1, s->ioOut.p, s->Np);
+        s->download(rhs2, s->ioOut.p + plane, s->Np);
+        s->download(rhs3, s->ioOut.p + 2 * plane, s->Np);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_step_rk2");
+        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2: num_steps < 0");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2: filter requested but the solver has no Filter");
+        s->use();
+        for (int i = 0; i < num_steps; ++i) s->rk2Step(dt, filter != 0);
+        s->checkBlowUp();
+    });
+}
+
+int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_lserk4_stages");
+        if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages: num_stages < 0");
+        s->use();
+        for (int i = 0; i < num_stages; ++i) s->lserkStage(dt);
+        s->checkBlowUp();
+    });
+}
+
+int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_time");
+        if (!ms || count < 1 || kind < 0 || kind > 1) throw arg_error("bdg_sw2dq_time: bad argument");
+        if (kind == 1 && !s->hasFilter) throw arg_error("bdg_sw2dq_time: RK2 + filter needs a Filter");
+        s->use();
+        hipEvent_t a, b;
+        hipCheck(hipEventCreate(&a), "hipEventCreate");
+        hipCheck(hipEventCreate(&b), "hipEventCreate");
+        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
+        for (int i = 0; i < count; ++i) {
+            if (kind == 0) s->lserkStage(dt);
+            else s->rk2Step(dt, true);
+        }
+        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
+        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
+        float t = 0.0f;
+        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        *ms = t / count;
+        s->checkBlowUp();
+    });
+}
+
+int bdg_sw2dq_synchronize(bdg_sw2dq* s) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_synchronize");
+        s->use();
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+size_t bdg_sw2dq_device_bytes(const bdg_sw2dq* s) { return s ? s->bytes : 0; }
+
+int bdg_sw2dq_uses_parallelogram_geometry(const bdg_sw2dq* s) { return s ? (s->general ? 0 : 1) : -1; }
+
+} // extern "C"

@@ -110,6 +110,14 @@ int bdg_mesh_partition(bdg_mesh* mesh, int nparts) {
     });
 }
 
+int bdg_mesh_build_quads(bdg_mesh* mesh, const int* etov, int K, const double* vert, int Nv, int dim) {
+    return guard([&] {
+        if (!mesh || !etov || !vert || K < 1 || Nv < 4) throw bdg_detail::arg_error("bdg_mesh_build_quads: bad argument");
+        mesh->mgr.buildMesh(etov, K, 4, vert, Nv, dim);
+    });
+}
+
+int bdg_mesh_num_faces(const bdg_mesh* mesh) { return mesh ? mesh->mgr.get_NumFaces() : -1; }
 int bdg_mesh_num_elements(const bdg_mesh* mesh) { return mesh ? mesh->mgr.get_NumElements() : -1; }
 int bdg_mesh_num_verts(const bdg_mesh* mesh) { return mesh ? mesh->mgr.get_NumVerts() : -1; }
 
@@ -119,10 +127,10 @@ int bdg_mesh_table(const bdg_mesh* mesh, int which, bdg_table* out) {
         const MeshManager& m = mesh->mgr;
         switch (which) {
         case BDG_MESH_VERTICES: *out = {m.get_Vertices().data(), m.get_NumVerts(), m.get_Dim(), BDG_F64}; break;
-        case BDG_MESH_ELEMENTS: view2(out, m.get_Elements(), 3); break;
-        case BDG_MESH_ETOE: view2(out, m.get_EToE(), 3); break;
-        case BDG_MESH_ETOF: view2(out, m.get_EToF(), 3); break;
-        case BDG_MESH_BCTYPE: view2(out, m.get_BCType(), 3); break;
+        case BDG_MESH_ELEMENTS: view2(out, m.get_Elements(), m.get_NumFaces()); break;
+        case BDG_MESH_ETOE: view2(out, m.get_EToE(), m.get_NumFaces()); break;
+        case BDG_MESH_ETOF: view2(out, m.get_EToF(), m.get_NumFaces()); break;
+        case BDG_MESH_BCTYPE: view2(out, m.get_BCType(), m.get_NumFaces()); break;
         case BDG_MESH_EPART: view(out, m.get_ElementPartitionMap()); break;
         case BDG_MESH_NPART: view(out, m.get_VertexPartitionMap()); break;
         default: throw bdg_detail::arg_error("bdg_mesh_table: unknown table id");
@@ -360,6 +368,109 @@ int bdg_trinodes_bcmap_tags(const bdg_trinodes* nodes, int* tags, int capacity) 
 int bdg_trinodes_bcmap_nodes(const bdg_trinodes* nodes, int tag, const int** out, int* count) {
     return guard([&] {
         if (!nodes || !out || !count) throw bdg_detail::arg_error("bdg_trinodes_bcmap_nodes: NULL argument");
+        const auto& map = nodes->prov.get_bcMap();
+        const auto it = map.find(tag);
+        if (it == map.end()) { *out = nullptr; *count = 0; return; }
+        *out = it->second.data();
+        *count = static_cast<int>(it->second.size());
+    });
+}
+
+// ------------------------------------------------------------------ quadrilateral nodes
+// The bdg_trinodes_* shape over QuadNodesProvisioner. Tables use the BDG_TRI_* ids; the ones a quadrilateral
+// provisioner does not build are refused.
+int bdg_quadnodes_create(int order, const bdg_mesh* mesh, bdg_quadnodes** out) {
+    return guard([&] {
+        if (!mesh || !out) throw bdg_detail::arg_error("bdg_quadnodes_create: NULL argument");
+        if (mesh->mgr.get_NumElements() < 1) throw bdg_detail::arg_error("bdg_quadnodes_create: mesh is empty");
+        if (mesh->mgr.get_NumFaces() != 4)
+            throw bdg_detail::arg_error("bdg_quadnodes_create: the mesh holds triangles (use bdg_trinodes_create)");
+        if (order < 1) throw bdg_detail::arg_error("bdg_quadnodes_create: order must be >= 1");
+        *out = new bdg_quadnodes{QuadNodesProvisioner(order, mesh->mgr)};
+    });
+}
+
+void bdg_quadnodes_destroy(bdg_quadnodes* nodes) { delete nodes; }
+
+int bdg_quadnodes_build_filter(bdg_quadnodes* nodes, double Nc, int s) {
+    return guard([&] {
+        if (!nodes) throw bdg_detail::arg_error("bdg_quadnodes_build_filter: nodes is NULL");
+        nodes->prov.buildFilter(Nc, s);
+        nodes->hasFilter = true;
+    });
+}
+
+int bdg_quadnodes_build_bchash(bdg_quadnodes* nodes, const int* bctype, int n) {
+    return guard([&] {
+        if (!nodes || !bctype) throw bdg_detail::arg_error("bdg_quadnodes_build_bchash: NULL argument");
+        index_vector_type bc(n);
+        std::copy(bctype, bctype + n, bc.begin());
+        nodes->prov.buildBCHash(bc);
+    });
+}
+
+int bdg_quadnodes_dims(const bdg_quadnodes* nodes, int* order, int* np, int* nfp, int* K) {
+    return guard([&] {
+        if (!nodes) throw bdg_detail::arg_error("bdg_quadnodes_dims: nodes is NULL");
+        if (order) *order = nodes->prov.get_NOrder();
+        if (np) *np = nodes->prov.get_NumLocalPoints();
+        if (nfp) *nfp = nodes->prov.get_NumFacePoints();
+        if (K) *K = nodes->prov.get_NumElements();
+    });
+}
+
+int bdg_quadnodes_table(const bdg_quadnodes* nodes, int which, bdg_table* out) {
+    return guard([&] {
+        if (!nodes || !out) throw bdg_detail::arg_error("bdg_quadnodes_table: NULL argument");
+        const QuadNodesProvisioner& p = nodes->prov;
+        switch (which) {
+        case BDG_TRI_R: view(out, p.get_rGrid()); break;
+        case BDG_TRI_S: view(out, p.get_sGrid()); break;
+        case BDG_TRI_X: view(out, p.get_xGrid()); break;
+        case BDG_TRI_Y: view(out, p.get_yGrid()); break;
+        case BDG_TRI_V: view(out, p.get_V()); break;
+        case BDG_TRI_VINV: view(out, p.get_Vinv()); break;
+        case BDG_TRI_DR: view(out, p.get_Dr()); break;
+        case BDG_TRI_DS: view(out, p.get_Ds()); break;
+        case BDG_TRI_LIFT: view(out, p.get_Lift()); break;
+        case BDG_TRI_FILTER: view(out, p.get_Filter()); break;
+        case BDG_TRI_J: view(out, p.get_J()); break;
+        case BDG_TRI_RX: view(out, p.get_rx()); break;
+        case BDG_TRI_RY: view(out, p.get_ry()); break;
+        case BDG_TRI_SX: view(out, p.get_sx()); break;
+        case BDG_TRI_SY: view(out, p.get_sy()); break;
+        case BDG_TRI_NX: view(out, p.get_nx()); break;
+        case BDG_TRI_NY: view(out, p.get_ny()); break;
+        case BDG_TRI_FSCALE: view(out, p.get_Fscale()); break;
+        case BDG_TRI_FMASK: view(out, p.get_Fmask()); break;
+        case BDG_TRI_VMAPM: view(out, p.get_vmapM()); break;
+        case BDG_TRI_VMAPP: view(out, p.get_vmapP()); break;
+        case BDG_TRI_MAPP: view(out, p.get_mapP()); break;
+        case BDG_TRI_VMAPB: view(out, p.get_vmapB()); break;
+        case BDG_TRI_MAPB: view(out, p.get_mapB()); break;
+        default: throw bdg_detail::arg_error("bdg_quadnodes_table: table not built for quadrilaterals");
+        }
+    });
+}
+
+int bdg_quadnodes_bcmap_num_tags(const bdg_quadnodes* nodes) {
+    return nodes ? static_cast<int>(nodes->prov.get_bcMap().size()) : -1;
+}
+
+int bdg_quadnodes_bcmap_tags(const bdg_quadnodes* nodes, int* tags, int capacity) {
+    return guard([&] {
+        if (!nodes || !tags) throw bdg_detail::arg_error("bdg_quadnodes_bcmap_tags: NULL argument");
+        std::vector<int> keys;
+        for (const auto& kv : nodes->prov.get_bcMap()) keys.push_back(kv.first);
+        std::sort(keys.begin(), keys.end());
+        if (static_cast<int>(keys.size()) > capacity) throw bdg_detail::arg_error("bdg_quadnodes_bcmap_tags: capacity too small");
+        std::copy(keys.begin(), keys.end(), tags);
+    });
+}
+
+int bdg_quadnodes_bcmap_nodes(const bdg_quadnodes* nodes, int tag, const int** out, int* count) {
+    return guard([&] {
+        if (!nodes || !out || !count) throw bdg_detail::arg_error("bdg_quadnodes_bcmap_nodes: NULL argument");
         const auto& map = nodes->prov.get_bcMap();
         const auto it = map.find(tag);
         if (it == map.end()) { *out = nullptr; *count = 0; return; }

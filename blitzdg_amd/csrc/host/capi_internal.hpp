@@ -4,6 +4,7 @@
 #include "blitzdg_hip.h"
 #include "blitzdg/MeshManager.hpp"
 #include "blitzdg/Nodes1DProvisioner.hpp"
+#include "blitzdg/QuadNodesProvisioner.hpp"
 #include "blitzdg/TriangleNodesProvisioner.hpp"
 #include <exception>
 #include <stdexcept>
@@ -15,6 +16,11 @@ struct bdg_mesh {
 
 struct bdg_trinodes {
     blitzdg::TriangleNodesProvisioner prov;
+    bool hasFilter = false;
+};
+
+struct bdg_quadnodes {
+    blitzdg::QuadNodesProvisioner prov;
     bool hasFilter = false;
 };
 

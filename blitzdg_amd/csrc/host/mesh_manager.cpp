@@ -112,9 +112,10 @@ void MeshManager::readMesh(const std::string& gmshInputFile) {
     requireLine(in, line, "element count");
     const index_type numRows = std::stoi(line);
 
-    std::vector<index_type> tris;
+    // Triangles (type 2) or quadrangles (type 3, the reference's :300-307); points and lines are skipped. A file with
+    // both is refused: the reference keeps the quads and silently drops the triangles.
+    std::vector<index_type> tris, quads;
     tris.reserve(static_cast<std::size_t>(numRows) * 3);
-    bool sawQuads = false;
     for (index_type i = 0; i < numRows; ++i) {
         requireLine(in, line, "elements");
         tokenize(line, tok);
@@ -131,16 +132,20 @@ void MeshManager::readMesh(const std::string& gmshInputFile) {
         }
         if (nLocal == 4) {
             if (elemType != 3) throw std::runtime_error("Incorrect Element Type for quadrangle element!");
-            sawQuads = true;
+            if (tok.size() < 9) throw std::runtime_error("Quadrangle row with fewer than two tags is not supported!");
+            for (int v = 5; v <= 8; ++v) quads.push_back(std::stoi(tok[v]) - 1);
         }
     }
-    if (sawQuads)
-        throw std::runtime_error("Quadrangle meshes are outside the scope of the MI355X sw2d path (triangles only).");
+    if (!tris.empty() && !quads.empty())
+        throw std::runtime_error("Mixed triangle/quadrangle meshes are not supported: the file holds " +
+                                 std::to_string(tris.size() / 3) + " triangles and " + std::to_string(quads.size() / 4) +
+                                 " quadrangles.");
 
-    NumFaces = 3;
-    NumElements = static_cast<index_type>(tris.size() / 3);
+    const std::vector<index_type>& elems = quads.empty() ? tris : quads;
+    NumFaces = quads.empty() ? 3 : 4;
+    NumElements = static_cast<index_type>(elems.size() / NumFaces);
     EToV.resize(NumElements * NumFaces);
-    std::copy(tris.begin(), tris.end(), EToV.begin());
+    std::copy(elems.begin(), elems.end(), EToV.begin());
     for (index_type i = 0; i < EToV.size(); ++i)
         if (EToV(i) < 0 || EToV(i) >= NumVerts) throw std::runtime_error("Element references a vertex out of range!");
 
@@ -150,6 +155,7 @@ void MeshManager::readMesh(const std::string& gmshInputFile) {
 }
 
 void MeshManager::writeMesh(const std::string& gmshOutputFile) const {
+    if (NumFaces != 3) throw std::runtime_error("writeMesh: triangle meshes only (this mesh has quadrangles)");
     std::FILE* f = std::fopen(gmshOutputFile.c_str(), "w");
     if (!f) throw std::runtime_error("Unable to open mesh file for writing: " + gmshOutputFile);
     std::fprintf(f, "$MeshFormat\n2.2 0 8\n$EndMeshFormat\n$Nodes\n%d\n", NumVerts);
@@ -199,6 +205,7 @@ void getTable(std::FILE* f, V& v, std::uint64_t n, std::uint64_t& sum) {
 } // namespace
 
 void MeshManager::writeCache(const std::string& cacheFile) const {
+    if (NumFaces != 3) throw std::runtime_error("writeCache: triangle meshes only (this mesh has quadrangles)");
     std::FILE* f = std::fopen(cacheFile.c_str(), "wb");
     if (!f) throw std::runtime_error("Unable to open mesh cache for writing: " + cacheFile);
     CacheHeader h{};
@@ -282,18 +289,24 @@ void MeshManager::readElements(const std::string& E2VFile) {
 }
 
 void MeshManager::buildMesh(const index_type* e2v, index_type K, const real_type* vert, index_type Nv, index_type dim) {
+    buildMesh(e2v, K, 3, vert, Nv, dim);
+}
+
+void MeshManager::buildMesh(const index_type* e2v, index_type K, index_type numFaces, const real_type* vert, index_type Nv,
+                            index_type dim) {
     if (dim != 2 && dim != 3) throw std::runtime_error("buildMesh: vertices must have 2 or 3 coordinates");
+    if (numFaces != 3 && numFaces != 4) throw std::runtime_error("buildMesh: elements must have 3 or 4 vertices");
     // Vertices are always stored (x,y,z)-interleaved: the nodes provisioner
     // indexes them with stride 3 (reference src/TriangleNodesProvisioner.cpp:755-760).
-    Dim = 3; NumVerts = Nv; NumFaces = 3; NumElements = K;
+    Dim = 3; NumVerts = Nv; NumFaces = numFaces; NumElements = K;
     Vert.resize(Nv * 3);
     for (index_type i = 0; i < Nv; ++i) {
         Vert(3 * i) = vert[dim * i];
         Vert(3 * i + 1) = vert[dim * i + 1];
         Vert(3 * i + 2) = dim == 3 ? vert[dim * i + 2] : 0.0;
     }
-    EToV.resize(K * 3);
-    for (index_type i = 0; i < K * 3; ++i) {
+    EToV.resize(K * numFaces);
+    for (index_type i = 0; i < K * numFaces; ++i) {
         if (e2v[i] < 0 || e2v[i] >= Nv) throw std::runtime_error("buildMesh: vertex index out of range");
         EToV(i) = e2v[i];
     }
@@ -353,16 +366,23 @@ void MeshManager::enforceCounterClockwise() {
         const real_type bx = Vert(b * Dim), by = Vert(b * Dim + 1);
         const real_type cx = Vert(c * Dim), cy = Vert(c * Dim + 1);
         const real_type det = (ax - cx) * (by - cy) - (bx - cx) * (ay - cy);
-        if (det < 0) std::swap(EToV(NumFaces * k + 1), EToV(NumFaces * k + 2));
+        if (det >= 0) continue;
+        if (NumFaces == 3) {
+            std::swap(EToV(NumFaces * k + 1), EToV(NumFaces * k + 2));
+        } else {
+            // (a, b, c, d) -> (a, d, c, b): the reference swaps b and c here too, which turns a quadrangle into a
+            // bow-tie; reversing keeps it a quadrangle (identical to the reference on counter-clockwise input).
+            std::swap(EToV(NumFaces * k + 1), EToV(NumFaces * k + 3));
+        }
     }
 }
 
 void MeshManager::buildConnectivity() {
-    if (NumFaces != 3) throw std::runtime_error("buildConnectivity: triangles only");
+    if (NumFaces != 3 && NumFaces != 4) throw std::runtime_error("buildConnectivity: triangles or quadrangles only");
     const index_type totalFaces = NumFaces * NumElements;
     EToE.resize(totalFaces);
     EToF.resize(totalFaces);
-    // Face f of element k joins local vertices (f, (f+1)%3); two faces are
+    // Face f of element k joins local vertices (f, (f+1)%NumFaces); two faces are
     // connected iff they share both vertices. Boundary faces stay self-connected.
     std::vector<std::pair<std::uint64_t, index_type>> keys(static_cast<std::size_t>(totalFaces));
     for (index_type k = 0; k < NumElements; ++k)

@@ -3,9 +3,9 @@
 Same class, method and property names as the reference's boost::python module
 (src/pyblitzdg/pyblitzdg.cpp:59-201) for the objects the sw2d / advec1d path uses:
 ``MeshManager``, ``TriangleNodesProvisioner`` (+ ``dgContext()`` -> ``DGContext2D``),
-``Nodes1DProvisioner``, ``LSERK4``, ``BCType``. As in the reference every property
-access returns a FRESH C-order ndarray (float64 / int32). Objects outside the hot
-path (quads, Poisson) are not provided. ``GaussFaceContext2D`` / ``CubatureContext2D`` (the curved,
+``Nodes1DProvisioner``, ``LSERK4``, ``BCType``, and ``QuadNodesProvisioner`` for the
+quadrilateral path (sw2dquads.py). As in the reference every property access returns a
+FRESH C-order ndarray (float64 / int32). Objects outside the hot path (Poisson) are not provided. ``GaussFaceContext2D`` / ``CubatureContext2D`` (the curved,
 over-integrated RHS's tables) come from ``buildGaussFaceNodes`` / ``buildCubatureVolumeMesh``.
 """
 import numpy as np
@@ -113,13 +113,14 @@ class MeshManager:
         check(lib.bdg_mesh_read_cache(self._h, str(cacheFile).encode()))
 
     def buildMesh(self, EToV, Vert):
-        """EToV: (K, 3) vertex ids (any numeric dtype, as the reference accepts float64);
-        Vert: (Nv, 2|3) coordinates."""
+        """EToV: (K, 3) triangles or (K, 4) quadrangles, vertex ids (any numeric dtype, as the reference accepts
+        float64); Vert: (Nv, 2|3) coordinates."""
         e = C.as_i32(np.asarray(EToV).astype(np.int64))
         v = C.as_f64(Vert)
-        if e.ndim != 2 or e.shape[1] != 3 or v.ndim != 2:
-            raise ValueError("buildMesh: EToV must be (K,3) and Vert (Nv,2|3)")
-        check(lib.bdg_mesh_build(self._h, C.ptr(e), e.shape[0], C.ptr(v), v.shape[0], v.shape[1]))
+        if e.ndim != 2 or e.shape[1] not in (3, 4) or v.ndim != 2:
+            raise ValueError("buildMesh: EToV must be (K,3) or (K,4) and Vert (Nv,2|3)")
+        build = lib.bdg_mesh_build if e.shape[1] == 3 else lib.bdg_mesh_build_quads
+        check(build(self._h, C.ptr(e), e.shape[0], C.ptr(v), v.shape[0], v.shape[1]))
 
     def buildBoxMesh(self, nx, ny, x0=-1.0, x1=1.0, y0=-1.0, y1=1.0, shuffleSeed=0):
         """Synthetic structured box, K = 2*nx*ny CCW triangles (benchmark configurations)."""
@@ -138,6 +139,7 @@ class MeshManager:
         return C.table_to_numpy(t)
 
     numElements = property(lambda self: lib.bdg_mesh_num_elements(self._h))
+    numFaces = property(lambda self: lib.bdg_mesh_num_faces(self._h))
     numVerts = property(lambda self: lib.bdg_mesh_num_verts(self._h))
     vertices = property(lambda self: self._table(C.MESH_VERTICES))
     elements = property(lambda self: self._table(C.MESH_ELEMENTS))
@@ -149,7 +151,7 @@ class MeshManager:
 
 
 class DGContext2D:
-    """Read-only view of a TriangleNodesProvisioner's tables.
+    """Read-only view of a TriangleNodesProvisioner's or QuadNodesProvisioner's tables.
     reference: include/DGContext2D.hpp:9-258; python names at pyblitzdg.cpp:160-187."""
 
     _TABLES = {
@@ -183,7 +185,7 @@ class DGContext2D:
 
     @property
     def numFaces(self):
-        return 3
+        return self._nodes._numFaces
 
     @property
     def order(self):
@@ -275,6 +277,8 @@ class CubatureContext2D:
 
 class TriangleNodesProvisioner:
     """reference: include/TriangleNodesProvisioner.hpp:32-427; python names at pyblitzdg.cpp:114-119"""
+
+    _numFaces = 3
 
     def __init__(self, NOrder, meshManager):
         h = c_void_p()
@@ -376,6 +380,61 @@ class TriangleNodesProvisioner:
             p, cnt = C.POINTER(c_int)(), c_int()
             check(lib.bdg_trinodes_bcmap_nodes(self._h, tags[i], byref(p), byref(cnt)))
             out[int(tags[i])] = [int(p[j]) for j in range(cnt.value)]
+        return out
+
+
+class QuadNodesProvisioner:
+    """reference: include/QuadNodesProvisioner.hpp:90-206; python names at pyblitzdg.cpp:120-122. Gauss-Lobatto
+    tensor nodes on a quadrangle mesh; ``dgContext()`` reports ``numFaces == 4``."""
+
+    _numFaces = 4
+
+    def __init__(self, NOrder, meshManager):
+        h = c_void_p()
+        check(lib.bdg_quadnodes_create(int(NOrder), meshManager._h, byref(h)))
+        self._h = h
+        self._mesh = meshManager  # the C++ object borrows the mesh
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.bdg_quadnodes_destroy(h)
+
+    _tables_version = 0
+
+    def buildFilter(self, Nc, s):
+        """The reference's construction (src/QuadNodesProvisioner.cpp:170-202), quirk included: the exponential
+        weights run over the triangle index set i + j <= N and fill only the first (N+1)(N+2)/2 diagonal entries."""
+        check(lib.bdg_quadnodes_build_filter(self._h, float(Nc), int(s)))
+        self._tables_version += 1
+
+    def buildBCHash(self, bcType):
+        b = C.as_i32(bcType).reshape(-1)
+        check(lib.bdg_quadnodes_build_bchash(self._h, C.ptr(b), b.size))
+        self._tables_version += 1
+
+    def dgContext(self):
+        return DGContext2D(self)
+
+    def _dims(self):
+        o, np_, nfp, k = c_int(), c_int(), c_int(), c_int()
+        check(lib.bdg_quadnodes_dims(self._h, byref(o), byref(np_), byref(nfp), byref(k)))
+        return o.value, np_.value, nfp.value, k.value
+
+    def _table(self, which, copy=True):
+        t = C.Table()
+        check(lib.bdg_quadnodes_table(self._h, which, byref(t)))
+        return C.table_to_numpy(t, copy=copy)
+
+    def _bcmap(self):
+        n = lib.bdg_quadnodes_bcmap_num_tags(self._h)
+        tags = (c_int * max(n, 1))()
+        check(lib.bdg_quadnodes_bcmap_tags(self._h, tags, n))
+        out = {}
+        for i in range(n):
+            p, cnt = C.POINTER(c_int)(), c_int()
+            check(lib.bdg_quadnodes_bcmap_nodes(self._h, tags[i], byref(p), byref(cnt)))
+            out[int(tags[i])] = np.ctypeslib.as_array(p, shape=(cnt.value,)).tolist() if cnt.value else []
         return out
 
 

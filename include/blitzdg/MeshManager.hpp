@@ -1,4 +1,4 @@
-// MeshManager: reads/holds a 2-D triangle mesh and its connectivity tables.
+// MeshManager: reads/holds a 2-D triangle or quadrangle mesh and its connectivity tables.
 //
 // Keeps the public surface of the reference's include/MeshManager.hpp:23-232
 // (readMesh, buildMesh, buildConnectivity, partitionMesh, get_* accessors) so a
@@ -30,16 +30,17 @@ public:
     MeshManager(MeshManager&&) = default;
     MeshManager& operator=(MeshManager&&) = default;
 
-    /// Reads a Gmsh 2.2 ASCII .msh file (triangles; quads are rejected here).
+    /// Reads a Gmsh 2.2 ASCII .msh file of triangles (NumFaces = 3) or quadrangles (NumFaces = 4); a file
+    /// holding both is refused. A clockwise quadrangle (a, b, c, d) is stored reversed as (a, d, c, b).
     void readMesh(const std::string& gmshInputFile);
-    /// Writes the triangles as Gmsh 2.2 ASCII (two tags per element, coordinates with 17 significant
+    /// Triangle meshes only. Writes the triangles as Gmsh 2.2 ASCII (two tags per element, coordinates with 17 significant
     /// digits) -- the format readMesh takes; not in the reference, which only reads.
     void writeMesh(const std::string& gmshOutputFile) const;
     /// Binary cache of everything this class holds (vertices, EToV, EToE, EToF, BCType, partition maps): one file,
     /// little-endian, checksummed. readCache restores the object without reading ASCII or rebuilding connectivity (the
     /// step before the hot path at 10^6-10^7 elements); it refuses a file whose magic, version, sizes,
     /// index ranges or checksum do not fit. Not in the reference, which re-reads the .msh file every run.
-    void writeCache(const std::string& cacheFile) const;
+    void writeCache(const std::string& cacheFile) const; // triangle meshes only
     void readCache(const std::string& cacheFile);
     /// Reads whitespace/comma separated vertex table (rows of Dim reals).
     void readVertices(const std::string& vertFile);
@@ -49,6 +50,9 @@ public:
     /// Enforces CCW ordering, builds connectivity and the default Wall BC table
     /// (as the reference's numpy buildMesh, src/MeshManager.cpp:74-122).
     void buildMesh(const index_type* EToV, index_type K, const real_type* Vert, index_type Nv, index_type dim);
+    /// The same with numFaces = 3 (triangles) or 4 (quadrangles: EToV is K x 4).
+    void buildMesh(const index_type* EToV, index_type K, index_type numFaces, const real_type* Vert, index_type Nv,
+                   index_type dim);
     /// Structured box [x0,x1]x[y0,y1], nx*ny cells, each split into 2 CCW triangles
     /// (K = 2*nx*ny). shuffleSeed != 0 applies a Fisher-Yates element shuffle.
     void buildBoxMesh(index_type nx, index_type ny, real_type x0, real_type x1, real_type y0, real_type y1,

@@ -43,10 +43,12 @@ extern "C" {
 
 typedef struct bdg_mesh bdg_mesh;
 typedef struct bdg_trinodes bdg_trinodes;
+typedef struct bdg_quadnodes bdg_quadnodes;
 typedef struct bdg_nodes1d bdg_nodes1d;
 typedef struct bdg_gaussctx bdg_gaussctx;
 typedef struct bdg_cubctx bdg_cubctx;
 typedef struct bdg_sw2d bdg_sw2d;
+typedef struct bdg_sw2dq bdg_sw2dq;
 
 const char* bdg_last_error(void);
 int bdg_version(void);
@@ -90,6 +92,9 @@ int bdg_mesh_build_box(bdg_mesh* mesh, int nx, int ny, double x0, double x1, dou
                        unsigned long long shuffle_seed);                  /* synthetic box, K = 2*nx*ny */
 int bdg_mesh_set_bctype(bdg_mesh* mesh, const int* bctype, int n);        /* setBCType  */
 int bdg_mesh_partition(bdg_mesh* mesh, int num_partitions);               /* partitionMesh */
+/* buildMesh of quadrangles: etov is (num_elements, 4); a clockwise quadrangle (a, b, c, d) is stored as (a, d, c, b) */
+int bdg_mesh_build_quads(bdg_mesh* mesh, const int* etov, int num_elements, const double* vert, int num_verts, int dim);
+int bdg_mesh_num_faces(const bdg_mesh* mesh); /* 3: triangles, 4: quadrangles (the mesh tables have this many columns) */
 int bdg_mesh_num_elements(const bdg_mesh* mesh);
 int bdg_mesh_num_verts(const bdg_mesh* mesh);
 int bdg_mesh_table(const bdg_mesh* mesh, int which, bdg_table* out);
@@ -113,6 +118,20 @@ int bdg_trinodes_table(const bdg_trinodes* nodes, int which, bdg_table* out);
 int bdg_trinodes_bcmap_num_tags(const bdg_trinodes* nodes);
 int bdg_trinodes_bcmap_tags(const bdg_trinodes* nodes, int* tags, int capacity);
 int bdg_trinodes_bcmap_nodes(const bdg_trinodes* nodes, int tag, const int** nodes_out, int* count);
+
+/* ---------------------------------------------------------------- QuadNodesProvisioner / DGContext2D
+ * reference: include/QuadNodesProvisioner.hpp:90-206, src/QuadNodesProvisioner.cpp. Same shape as bdg_trinodes_*;
+ * bdg_quadnodes_table takes the BDG_TRI_* ids (DRW, DSW, FX, FY, GATHER, SCATTER are not built for quadrilaterals).
+ * The mesh must hold quadrangles and outlive the handle. */
+int bdg_quadnodes_create(int order, const bdg_mesh* mesh, bdg_quadnodes** out);
+void bdg_quadnodes_destroy(bdg_quadnodes* nodes);
+int bdg_quadnodes_build_filter(bdg_quadnodes* nodes, double Nc, int s); /* the reference's construction, quirk included */
+int bdg_quadnodes_build_bchash(bdg_quadnodes* nodes, const int* bctype, int n); /* appends, as the reference */
+int bdg_quadnodes_dims(const bdg_quadnodes* nodes, int* order, int* np, int* nfp, int* num_elements);
+int bdg_quadnodes_table(const bdg_quadnodes* nodes, int which, bdg_table* out);
+int bdg_quadnodes_bcmap_num_tags(const bdg_quadnodes* nodes);
+int bdg_quadnodes_bcmap_tags(const bdg_quadnodes* nodes, int* tags, int capacity);
+int bdg_quadnodes_bcmap_nodes(const bdg_quadnodes* nodes, int tag, const int** nodes_out, int* count);
 
 /* Output step after the path (reference TriangleNodesProvisioner::splitElements,
  * src/TriangleNodesProvisioner.cpp:1154-1264, and VtkOutputter, include/VtkOutputter.hpp:30-99).
@@ -316,6 +335,60 @@ int bdg_sw2d_global_speed(bdg_sw2d* s, double* lam);
 int bdg_trinodes_bed_slopes(const bdg_trinodes* nodes, const double* H, double* Hx, double* Hy);
 int bdg_trinodes_sponge_coeff(const bdg_trinodes* nodes, const int* mapO, int num_out, double strength,
                               double radius, double* coeff);
+
+/* ---------------------------------------------------------------- quadrilateral sw2d solver (HIP, gfx950)
+ * The reference script sw2dquads.py: sw2dComputeRHS (:24-133; local Lax-Friedrichs flux with one speed per face,
+ * reflective walls on mapW, strong form) and its midpoint-RK2 + filter loop (:183-213), plus LSERK4 stages.
+ * Dr, Ds and Lift must have the Gauss-Lobatto tensor form of QuadNodesProvisioner to 1e-13 max|entry| (create
+ * refuses anything else: the kernel only keeps their 1-D factors); Filter stays a dense (Np, Np) matrix.
+ * Tables as bdg_sw2d_desc with Nfp = order + 1 and 4 faces: Lift (Np, 4 Nfp), nx, ny, Fscale (4 Nfp, K). */
+typedef struct bdg_sw2dq_desc {
+    int order;          /* 1..BDG_SW2DQ_MAX_ORDER                                   */
+    int num_elements;
+    const double* Dr;   /* (Np, Np), Np = (order + 1)^2                             */
+    const double* Ds;
+    const double* Lift; /* (Np, 4 Nfp)                                              */
+    const double* Filter; /* (Np, Np) or NULL (then no filtered modes)              */
+    const double* rx;   /* (Np, K)                                                  */
+    const double* sx;
+    const double* ry;
+    const double* sy;
+    const double* nx;   /* (4 Nfp, K)                                               */
+    const double* ny;
+    const double* Fscale;
+    const int* vmapM;   /* 4 Nfp K, checked against the Gauss-Lobatto face numbering; NULL = that numbering */
+    const int* vmapP;   /* 4 Nfp K                                                  */
+    const int* mapW;    /* reflective-wall face nodes (BCmap[3])                    */
+    int num_wall;
+    double g;
+    int device;
+    int flags;          /* BDG_SW2DQ_*                                              */
+} bdg_sw2dq_desc;
+
+#define BDG_SW2DQ_MAX_ORDER 8
+#define BDG_SW2DQ_GENERAL_GEOMETRY 1u /* always read rx..sy per node and nx, ny, Fscale per face node. Default: if
+                               every element is a parallelogram (metric terms constant per element, normals and
+                               Fscale per face, to 1e-10 relative), 16 values per element are kept instead. */
+
+int bdg_sw2dq_create(const bdg_sw2dq_desc* desc, bdg_sw2dq** out);
+/* every table from a quadrilateral provisioner (wall nodes = BCmap[3]; Filter if buildFilter was called) */
+int bdg_sw2dq_create_from_nodes(const bdg_quadnodes* nodes, double g, int device, int flags, bdg_sw2dq** out);
+void bdg_sw2dq_destroy(bdg_sw2dq* s);
+int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const double* hv); /* also zeroes the LSERK residual */
+int bdg_sw2dq_get_state(bdg_sw2dq* s, double* h, double* hu, double* hv);
+/* host fields in, host RHS out; does not disturb the resident state. filter != 0: Filter applied to the RHS */
+int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, double* rhs1, double* rhs2,
+                  double* rhs3, int filter);
+/* The script's loop body: q1 = q + dt/2 F R(q); q += dt F R(q1) (F = Filter if filter != 0, else identity).
+ * After the steps, BDG_ERR_UNSTABLE if max|h| > 1e8 or h has a NaN (the script's check). */
+int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter);
+/* LSERK4 stages (stage i = count % 5, count reset by set_state), same blow-up check at the end */
+int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages);
+/* HIP-event milliseconds per LSERK4 stage (kind 0) or per RK2 + filter step (kind 1), averaged over count */
+int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms);
+int bdg_sw2dq_synchronize(bdg_sw2dq* s);
+size_t bdg_sw2dq_device_bytes(const bdg_sw2dq* s);
+int bdg_sw2dq_uses_parallelogram_geometry(const bdg_sw2dq* s);
 
 /* Resident time stepping (state stays in HBM). */
 int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps);          /* 5 fused stages per step */

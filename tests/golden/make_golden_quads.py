@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Generates the quadrilateral fixtures under tests/golden/. Run in the BUILD container only (needs the reference
+checkout, as make_golden.py); what it writes is plain data.
+
+  python tests/golden/make_golden_quads.py
+
+Writes
+  coarse_box_quads.msh, coarse_box_quads_fine.msh
+                          copies of the reference's input meshes (input/*.msh; data files)
+  quad_known_answers.npz  the literals of the reference's src/test/QuadNodesProvisionerTests.cpp (N = 3 on
+                          coarse_box_quads.msh): r, s, V2Dr, V2Ds, Fmask, Lift
+  sw2dq_rhs_<case>.npz    a quadrangle mesh (EToV, Vert: THIS repo's MeshManager / QuadNodesProvisioner rebuild the
+                          tables from them), the order, seeded fields h, hu, hv and the RHS of the REFERENCE script's
+                          sw2dComputeRHS (sw2dquads.py:24-133, its two function definitions compiled on their own)
+                          evaluated on those tables (rhs1, rhs2, rhs3)
+Cases: coarse_box_quads_fine at N = 1..8; a 5x4 box with randomly displaced interior vertices (convex, not
+parallelograms) at N = 2, 5, 8; a 6x5 box with shuffled elements and rotated local vertex order (parallelograms) at
+N = 4 and 7; a state whose depth jumps across every face on coarse_box_quads_fine at N = 3.
+"""
+import os
+import shutil
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+REF = "/root/reference"
+sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+sys.dont_write_bytecode = True
+
+from make_golden import literals, script_functions  # noqa: E402
+
+
+def known_answers():
+    src = open(os.path.join(REF, "src/test/QuadNodesProvisionerTests.cpp")).read()
+    names = {"r": "rExpected", "s": "sExpected", "V2Dr": "V2DrExpected", "V2Ds": "V2DsExpected", "Fmask": "FmExpected",
+             "Lift": "liftExpected"}
+    out = {key: literals(src, name) for key, name in names.items()}
+    out["V2Dr"] = out["V2Dr"].reshape(16, 16)
+    out["V2Ds"] = out["V2Ds"].reshape(16, 16)
+    out["Fmask"] = out["Fmask"].astype(np.int32).reshape(4, 4)
+    out["Lift"] = out["Lift"].reshape(16, 16)
+    np.savez_compressed(os.path.join(HERE, "quad_known_answers.npz"), **out)
+    print("quad_known_answers.npz:", {k: v.shape for k, v in out.items()})
+
+
+def _np_proxy():
+    """numpy with the script's spelling np.dtype('Float64') (accepted by the NumPy the reference targeted)."""
+    proxy = types.ModuleType("np_proxy")
+    proxy.__dict__.update(np.__dict__)
+    proxy.dtype = lambda name, *a, **k: np.dtype("float64" if name == "Float64" else name, *a, **k)
+    return proxy
+
+
+SCRIPT = script_functions(os.path.join(REF, "sw2dquads.py"), ["sw2dComputeFluxes", "sw2dComputeRHS"])
+SCRIPT["np"] = _np_proxy()
+
+
+def mesh_tables(path=None, EToV=None, Vert=None):
+    import blitzdg_amd.pyblitzdg as dg
+    m = dg.MeshManager()
+    if path is not None:
+        m.readMesh(path)
+    else:
+        m.buildMesh(EToV, Vert)
+    return m, m.elements.astype(np.int32), m.vertices[:, :2].copy()
+
+
+def box(nx, ny, jitter=0.0, shuffle=False, seed=0):
+    rng = np.random.default_rng(seed)
+    xs, ys = np.linspace(-1, 1, nx + 1), np.linspace(-1, 1, ny + 1)
+    X, Y = np.meshgrid(xs, ys)
+    V = np.stack([X.ravel(), Y.ravel()], axis=1)
+    if jitter:
+        inner = (np.abs(V[:, 0]) < 1) & (np.abs(V[:, 1]) < 1)
+        V[inner] += jitter * rng.uniform(-1, 1, (inner.sum(), 2)) * np.array([2 / nx, 2 / ny])
+    E = []
+    for j in range(ny):
+        for i in range(nx):
+            a = j * (nx + 1) + i
+            E.append([a, a + 1, a + nx + 2, a + nx + 1])
+    E = np.array(E)
+    if shuffle:
+        E = E[rng.permutation(len(E))]
+        E = np.array([np.roll(e, rng.integers(4)) for e in E])
+    return E, V
+
+
+def case(name, order, EToV, Vert, regime=False, seed=1):
+    import blitzdg_amd.pyblitzdg as dg
+    m = dg.MeshManager()
+    m.buildMesh(EToV, Vert)
+    nodes = dg.QuadNodesProvisioner(order, m)
+    ctx = nodes.dgContext()
+    x, y = ctx.x, ctx.y
+    rng = np.random.default_rng(seed)
+    Np, K = x.shape
+    if regime:
+        h = np.repeat(rng.uniform(1.0, 10.0, (1, K)), Np, axis=0) + 0.05 * rng.standard_normal((Np, K))
+        hu = h * rng.uniform(-3, 3, (1, K))
+        hv = h * rng.uniform(-3, 3, (1, K))
+    else:
+        h = 10.0 + np.exp(-10 * x * x - 10 * y * y) + 0.1 * rng.standard_normal((Np, K))
+        hu = 0.5 * rng.standard_normal((Np, K))
+        hv = 0.5 * rng.standard_normal((Np, K))
+    rhs = SCRIPT["sw2dComputeRHS"](h, hu, hv, 9.81, 10.0 * np.ones_like(h), ctx)
+    np.savez_compressed(os.path.join(HERE, f"sw2dq_rhs_{name}.npz"), EToV=m.elements.astype(np.int32),
+                        Vert=m.vertices[:, :2].copy(), order=order, g=9.81, h=h, hu=hu, hv=hv,
+                        rhs1=rhs[0], rhs2=rhs[1], rhs3=rhs[2])
+    print(f"sw2dq_rhs_{name}.npz: K={K} Np={Np} max|rhs|={max(np.abs(r).max() for r in rhs):.3e}")
+
+
+def main():
+    for f in ("coarse_box_quads.msh", "coarse_box_quads_fine.msh"):
+        shutil.copyfile(os.path.join(REF, "input", f), os.path.join(HERE, f))
+    known_answers()
+    _, E, V = mesh_tables(path=os.path.join(HERE, "coarse_box_quads_fine.msh"))
+    for N in range(1, 9):
+        case(f"coarse_box_quads_fine_N{N}", N, E, V, seed=N)
+    Ej, Vj = box(5, 4, jitter=0.15, seed=3)
+    for N in (2, 5, 8):
+        case(f"jitter_box5x4_N{N}", N, Ej, Vj, seed=10 + N)
+    Es, Vs = box(6, 5, shuffle=True, seed=5)
+    for N in (4, 7):
+        case(f"box6x5_shuffled_N{N}", N, Es, Vs, seed=20 + N)
+    case("regime_coarse_box_quads_fine_N3", 3, E, V, regime=True, seed=33)
+
+
+if __name__ == "__main__":
+    main()
