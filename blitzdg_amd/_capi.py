@@ -207,6 +207,12 @@ _SIGNATURES = {
     "bdg_sw2dq_synchronize": (c_int, [_P]),
     "bdg_sw2dq_device_bytes": (c_size_t, [_P]),
     "bdg_sw2dq_uses_parallelogram_geometry": (c_int, [_P]),
+    "bdg_sw2dq_set_partition": (c_int, [_P, c_int, c_int, _P, c_int]),
+    "bdg_sw2dq_comm_init": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int]),
+    "bdg_sw2dq_exchange": (c_int, [_P, c_int]),
+    "bdg_sw2dq_step_rk2_exchanged": (c_int, [_P, c_double, c_int, c_int]),
+    "bdg_sw2dq_lserk4_stages_exchanged": (c_int, [_P, c_double, c_int]),
+    "bdg_sw2dq_barrier": (c_int, [_P]),
     "bdg_sw2d_step_lserk4": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_lserk4_stages": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_step_rk2": (c_int, [_P, c_double, c_int, c_int]),

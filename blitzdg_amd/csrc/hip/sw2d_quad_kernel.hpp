@@ -10,8 +10,9 @@
 // Node (N+1) j + i sits at r = r1d[j], s = s1d[i]; faces are s=-1 (i = 0), r=+1 (j = N), s=+1 (i = N), r=-1 (j = 0).
 //
 // Mapping to the hardware: one 256-thread workgroup owns a tile of E consecutive elements (E = 64 / 32 / 16 for
-// N = 1 / 2 / >= 3, so every access to one nodal row of a tile is a contiguous run of E doubles, >= 128 bytes). Three
-// phases, separated by workgroup barriers:
+// N = 1 / 2 / >= 3, so every access to one nodal row of a tile is a contiguous run of E doubles, >= 128 bytes) of the
+// element range [kBegin, kEnd): tile kBegin + blockIdx.x * E, one workgroup per tile (a single domain evaluates [0, K); a
+// partitioned run its interior and partition-boundary ranges, never its ghosts). Three phases, separated by workgroup barriers:
 //   A  node items (n, e): load h, hu, hv, write hu, hv, F2, G2, G3 to LDS;
 //   B  face-node items (f, n, e): own trace and neighbour trace (gathered through vmapP; the wall flag rides in the sign
 //      bit of the gather index), node speeds to LDS, barrier, per-face maximum speed, lifted flux jump * Fscale to LDS;
@@ -64,7 +65,7 @@ struct QuadParams {
     const double* ops;   // QuadElem<N>::OPS_DOUBLES
     const double* filt;  // Np x Np, row-major (filtered modes)
     long long ld;        // plane stride (multiple of 64)
-    int K;
+    int kBegin, kEnd;    // the elements evaluated; every other column is only read, as a neighbour
     double g, ca, cb, cc;
 };
 
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
     double* const surf = lds + Q::OFF_SURF;
 
     const int tid = threadIdx.x;
-    const int k0 = blockIdx.x * E;
+    const int k0 = p.kBegin + static_cast<int>(blockIdx.x) * E;
     const long long ld = p.ld;
     const long long plane = static_cast<long long>(Np) * ld;
     const double g = p.g;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
         if (idx < Np * E) {
             const int n = idx / E, e = idx % E, k = k0 + e;
             double h = 1.0, hu = 0.0, hv = 0.0;
-            if (k < p.K) {
+            if (k < p.kEnd) {
                 const long long o = n * ld + k;
                 h = p.qin[o];
                 hu = p.qin[plane + o];
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
         if (idx < NFN * E) {
             const int fn = idx / E, e = idx % E, k = k0 + e;
             double lam = 0.0;
-            if (k < p.K) {
+            if (k < p.kEnd) {
                 const int f = fn / Nq, nn = fn % Nq;
                 const long long oM = Q::fmask(f, nn) * ld + k;
                 const double hM = p.qin[oM], huM = p.qin[plane + oM], hvM = p.qin[2 * plane + oM];
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
                 ds[a] = ss;
             }
             double rx, sx, ry, sy;
-            const int kk = k < p.K ? k : 0;
+            const int kk = k < p.kEnd ? k : p.kBegin;
             if (GEN) {
                 rx = p.geo[n * ld + kk];
                 sx = p.geo[plane + n * ld + kk];
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
                   a3 * surf[2 * NFN * E + s3];
             if (FILT) {
                 r1[m] = v1; r2[m] = v2; r3[m] = v3;
-            } else if (k < p.K) {
+            } else if (k < p.kEnd) {
                 store<MODE>(p, n * ld + k, plane, v1, v2, v3);
             }
         }
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
             const int idx = tid + T * m;
             if (idx >= Np * E) continue;
             const int n = idx / E, e = idx % E, k = k0 + e;
-            if (k < p.K) store<MODE>(p, n * ld + k, plane, r1[m], r2[m], r3[m]);
+            if (k < p.kEnd) store<MODE>(p, n * ld + k, plane, r1[m], r2[m], r3[m]);
         }
     }
 }

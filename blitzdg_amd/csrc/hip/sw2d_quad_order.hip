@@ -12,7 +12,8 @@ namespace {
 template <int N, int MODE, bool FILT>
 hipError_t launchForm(bool general, const QuadParams& p, hipStream_t stream) {
     using Q = QuadElem<N>;
-    const dim3 grid((p.K + Q::E - 1) / Q::E), block(Q::THREADS);
+    if (p.kEnd <= p.kBegin) return hipSuccess; // (an empty range: a share without interior elements)
+    const dim3 grid((p.kEnd - p.kBegin + Q::E - 1) / Q::E), block(Q::THREADS);
     if (general)
         hipLaunchKernelGGL((sw2d_quad_stage_kernel<N, MODE, FILT, true>), grid, block, 0, stream, p);
     else

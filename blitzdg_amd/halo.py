@@ -32,9 +32,9 @@ class HaloPlan:
     send_local: np.ndarray        # (n_send,) local slots of owned elements to send, grouped by peer
     send_slices: list = field(default_factory=list)   # [(peer, start, count)] into send_local
     recv_slices: list = field(default_factory=list)   # [(peer, start, count)] into the ghost slots
-    local_EToV: np.ndarray = None  # (K_own + K_halo, 3) local vertex ids
+    local_EToV: np.ndarray = None  # (K_own + K_halo, Nfaces) local vertex ids (3: triangles, 4: quadrangles)
     local_verts: np.ndarray = None  # (Nv_loc, 3)
-    local_bctype: np.ndarray = None  # (K_loc, 3) BC tags of the GLOBAL mesh for owned elements, 0 for ghosts
+    local_bctype: np.ndarray = None  # (K_loc, Nfaces) BC tags of the GLOBAL mesh for owned elements, 0 for ghosts
 
     @property
     def num_owned(self):
@@ -66,13 +66,18 @@ class HaloPlan:
 
 
 def build_plan(EToV, Vert, EToE, epart, rank, world, bctype=None):
-    """Halo plan of `rank` from the global mesh tables and an element partition vector."""
-    EToV = np.asarray(EToV).reshape(-1, 3)
-    EToE = np.asarray(EToE).reshape(-1, 3)
+    """Halo plan of `rank` from the global mesh tables and an element partition vector. The faces per element are the
+    second dimension of a 2-D EToV: 3 (triangles) or 4 (quadrangles); a flat EToV holds triangles."""
+    EToV = np.asarray(EToV)
+    nf = EToV.shape[1] if EToV.ndim == 2 else 3
+    if nf not in (3, 4):
+        raise ValueError(f"build_plan: EToV must have 3 or 4 columns, not {nf}")
+    EToV = EToV.reshape(-1, nf)
+    EToE = np.asarray(EToE).reshape(-1, nf)
     Vert = np.asarray(Vert, dtype=np.float64)
     epart = np.asarray(epart).reshape(-1)
     own = np.flatnonzero(epart == rank)
-    nb = EToE[own]                    # (K_own, 3) neighbour elements (self on physical boundaries)
+    nb = EToE[own]                    # (K_own, nf) neighbour elements (self on physical boundaries)
     nb_owner = epart[nb]
     remote = nb_owner != rank
     is_boundary = remote.any(axis=1)
@@ -112,9 +117,9 @@ def build_plan(EToV, Vert, EToE, epart, rank, world, bctype=None):
     verts_used, inv = np.unique(ev, return_inverse=True)
     local_EToV = inv.reshape(ev.shape).astype(np.int32)
     local_verts = Vert.reshape(-1, Vert.shape[-1] if Vert.ndim == 2 else 3)[verts_used]
-    local_bc = np.zeros((loc2glob.size, 3), dtype=np.int32)
+    local_bc = np.zeros((loc2glob.size, nf), dtype=np.int32)
     if bctype is not None:
-        local_bc[:own_order.size] = np.asarray(bctype).reshape(-1, 3)[own_order]
+        local_bc[:own_order.size] = np.asarray(bctype).reshape(-1, nf)[own_order]
     return HaloPlan(rank=rank, world=world, own_global=own_order.astype(np.int64), halo_global=ghost_ids.astype(np.int64),
                     num_interior=num_interior, send_local=send_local, send_slices=send_slices,
                     recv_slices=recv_slices, local_EToV=local_EToV, local_verts=local_verts, local_bctype=local_bc)
@@ -132,9 +137,9 @@ def exchange_ops(plan, sendbuf, recvbuf, dist):
 
 
 def build_local_mesh(plan):
-    """MeshManager of the rank-local mesh (owned + ghost elements). Ghost elements' outer faces
-    become walls of the local mesh; they are never updated, so that is immaterial. Owned
-    elements keep the BC tags of the global mesh."""
+    """MeshManager of the rank-local mesh (owned + ghost elements; triangles or quadrangles, as the plan's
+    local_EToV). Ghost elements' outer faces become walls of the local mesh; they are never updated, so that is
+    immaterial. Owned elements keep the BC tags of the global mesh."""
     from . import pyblitzdg as dg
     mesh = dg.MeshManager()
     mesh.buildMesh(plan.local_EToV, plan.local_verts)

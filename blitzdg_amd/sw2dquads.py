@@ -2,7 +2,8 @@
 
 ``sw2dComputeRHS(h, hu, hv, g, H, ctx)`` is a drop-in for the script's function (sw2dquads.py:24-133: same signature,
 three (Np, K) arrays out; ``H`` is accepted and unused, as there). ``Sw2dQuadSolver`` keeps the state resident in HBM
-and runs the script's midpoint-RK2 + filter loop body (:183-213) and LSERK4 stages. Everything here calls the HIP
+and runs the script's midpoint-RK2 + filter loop body (:183-213) and LSERK4 stages. ``NativeDistributedSw2dQuad`` runs the
+same on an element partition, one process per GPU, with the ghost exchange over RCCL. Everything here calls the HIP
 library (bdg_sw2dq_*); there is no CPU implementation behind it.
 """
 import weakref
@@ -129,3 +130,73 @@ def sw2dComputeRHS(h, hu, hv, g, H, ctx):
             _script_cache.pop(next(iter(_script_cache)))
         _script_cache[key] = entry
     return entry[0].computeRHS(h, hu, hv)
+
+
+class NativeDistributedSw2dQuad:
+    """Sw2dQuadSolver on an element partition, one process per rank: this rank's owned elements plus one layer of ghost
+    elements (``halo.build_plan`` of a quadrangle mesh), the ghost exchange driven by the library (pack kernel, grouped
+    ncclSend / ncclRecv with every neighbour, unpack kernel: device to device over RCCL, no PyTorch). Elements without a ghost
+    neighbour are evaluated beside the exchange (two streams), as in ``sw2d_curved.NativeDistributedSw2dCurved``. Rank 0's RCCL
+    id reaches the others through ``halo.file_rendezvous`` (or pass ``unique_id``)."""
+
+    def __init__(self, plan, order, g=9.81, filter_args=None, device=0, flags=0, unique_id=None, loopback=False):
+        """filter_args: (Nc, s) of QuadNodesProvisioner.buildFilter (the script's filter: (0.99 N, 4)); flags as
+        Sw2dQuadSolver. loopback=True: this one process computes plan.rank's share of a plan.world-way split and every
+        neighbour exchange is a send-to-self of the same size through the real transport (the ghosts then hold this rank's
+        own boundary elements: a rehearsal of the exchange on one GPU, not a partitioned result)."""
+        from . import pyblitzdg as dg
+        from .halo import build_local_mesh, native_comm, remove_id_file
+
+        self.plan, self.order = plan, order
+        self.mesh = build_local_mesh(plan)
+        self.nodes = dg.QuadNodesProvisioner(order, self.mesh)
+        if filter_args is not None:
+            self.nodes.buildFilter(*filter_args)
+        self.filtered = filter_args is not None
+        self.solver = Sw2dQuadSolver(nodes=self.nodes, g=g, device=device, flags=flags)
+        h = self.solver._h
+        send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
+        check(lib.bdg_sw2dq_set_partition(h, plan.num_interior, plan.num_owned, C.ptr(send), send.size))
+        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
+        pr, ss, sc, rs, rc = self.peer_table = plan.peer_tables(loopback)
+        check(lib.bdg_sw2dq_comm_init(h, comm_rank, comm_world, idbuf, C.ptr(pr), C.ptr(ss), C.ptr(sc), C.ptr(rs), C.ptr(rc),
+                                      pr.size))
+        self.barrier()
+        remove_id_file(id_path)
+
+    def close(self):
+        solver, self.solver = getattr(self, "solver", None), None
+        if solver is not None:
+            solver.close()
+
+    def set_initial_state(self, fn):
+        """fn(x, y) -> (h, hu, hv) on the rank-local nodes (owned and ghost elements: the ghosts start current)."""
+        ctx = self.nodes.dgContext()
+        self.solver.setState(*fn(ctx.x, ctx.y))
+
+    def step_rk2(self, dt, nsteps=1, filter=True):
+        """The script's predictor / corrector, ghosts refreshed before each evaluation; every rank raises
+        NumericalInstability together when max|h| > 1e8 or h has a NaN on any rank's owned elements."""
+        check(lib.bdg_sw2dq_step_rk2_exchanged(self.solver._h, float(dt), int(nsteps), int(bool(filter))))
+
+    def lserk4_stages(self, dt, nstages):
+        """LSERK4 stages with an exchange in front of every stage (same collective check)."""
+        check(lib.bdg_sw2dq_lserk4_stages_exchanged(self.solver._h, float(dt), int(nstages)))
+
+    def owned_state(self):
+        """(global ids, h, hu, hv) of the owned elements."""
+        n = self.plan.num_owned
+        return (self.plan.own_global,) + tuple(a[:, :n] for a in self.solver.getState())
+
+    def owned_mass(self):
+        """Integral of h over the owned elements: sum of w J h with w the tensor Gauss-Lobatto weights."""
+        from . import pyblitzdg as dg
+        ctx = self.nodes.dgContext()
+        V1 = dg.VandermondeBuilder().buildVandermondeMatrix(ctx.s[:self.order + 1])[0]
+        w1 = np.linalg.inv(V1 @ V1.T).sum(axis=1)          # 1-D Gauss-Lobatto mass-matrix row sums = weights
+        w = np.outer(w1, w1).ravel()[:, None]              # node (N+1) j + i: w1[j] w1[i]
+        n = self.plan.num_owned
+        return float((w * ctx.J[:, :n] * self.solver.getState()[0][:, :n]).sum())
+
+    def barrier(self):
+        check(lib.bdg_sw2dq_barrier(self.solver._h))

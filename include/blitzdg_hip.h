@@ -389,6 +389,29 @@ int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms);
 int bdg_sw2dq_synchronize(bdg_sw2dq* s);
 size_t bdg_sw2dq_device_bytes(const bdg_sw2dq* s);
 int bdg_sw2dq_uses_parallelogram_geometry(const bdg_sw2dq* s);
+/* Element-partitioned runs, as bdg_sw2d_curved_set_partition and friends (same argument order, refusals and error codes):
+ * the solver's mesh is ordered [elements without a ghost neighbour: num_interior | partition-boundary elements: up to
+ * num_owned | ghosts: up to K]; set_partition refuses (BDG_ERR_ARGUMENT) a bad range, an element of [0, num_interior) whose
+ * gather reaches a ghost or that is in the send list, and any call after comm_init. */
+int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const int* send_elements, int num_send);
+/* The RCCL communicator (bdg_comm_unique_id) and the neighbour tables: peer i is sent the elements send_elements[send_start[i]
+ * .. + send_count[i]) and its recv_count[i] elements arrive in ghost slots recv_start[i] .. (relative to num_owned); one record
+ * of 3 Np doubles per element. Refused before set_partition, a second time, or with peer ranges that do not fit. */
+int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id, const int* peer_ranks, const int* send_start,
+                        const int* send_count, const int* recv_start, const int* recv_count, int num_peers);
+/* one ghost refresh of the state (intermediate = 0) or of the RK2 intermediate / other LSERK4 buffer (1), on the solver's stream */
+int bdg_sw2dq_exchange(bdg_sw2dq* s, int intermediate);
+/* bdg_sw2dq_step_rk2 with the ghosts of q refreshed before the predictor and those of q1 before the corrector. With interior
+ * elements the interior range runs on the solver's stream beside the exchange, and the partition-boundary range after it on the
+ * exchange stream (two chains joined by events); without (or with BDG_SW2DQ_NO_OVERLAP set) the exchange and then every owned
+ * element run in stream order. Ghost elements are not evaluated: the ghost columns bdg_sw2dq_get_state returns hold whatever
+ * was last received. The blow-up check covers the owned columns and is all-reduced, so every rank returns BDG_ERR_UNSTABLE
+ * together. */
+int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int filter);
+/* bdg_sw2dq_lserk4_stages with an exchange of the state in front of every stage; schedule and check as above */
+int bdg_sw2dq_lserk4_stages_exchanged(bdg_sw2dq* s, double dt, int num_stages);
+/* drains both streams, meets every rank (an 8-byte all-reduce), drains again */
+int bdg_sw2dq_barrier(bdg_sw2dq* s);
 
 /* Resident time stepping (state stays in HBM). */
 int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps);          /* 5 fused stages per step */
