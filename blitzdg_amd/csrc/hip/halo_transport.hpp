@@ -1,6 +1,8 @@
-// halo_transport.hpp -- the ghost exchange of a partitioned run, shared by the straight-element solver (sw2d_device.hip)
-// and the curved one (sw2d_curved_device.hip): the neighbour table, the pack / unpack kernels, the grouped RCCL send /
-// receive, and the communicator, exchange stream and staging buffers. Events and stage schedules stay with each solver.
+// halo_transport.hpp -- the ghost exchange of a partitioned run, shared by the straight-element solver (sw2d_device.hip),
+// the curved one (sw2d_curved_device.hip) and the quadrilateral one (sw2d_quad_device.hip): the neighbour table and its
+// parse, the pack / unpack kernels, the grouped RCCL send / receive, and the communicator, exchange stream and staging
+// buffers. The straight-element solver keeps its own events and stage schedule; the other two share the two-chain
+// schedule of partition_schedule.hpp.
 //
 // A record is the `rows` doubles of one element, [field][node]. Records go out in the order of the send list and come
 // in as the ghost elements, stored after the owned ones; each neighbour rank has one contiguous range of either.
@@ -8,8 +10,10 @@
 #include "device_buffer.hpp"
 #include "rccl_api.hpp"
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace bdg_halo {
@@ -23,6 +27,21 @@ struct Peer { int rank, sendStart, sendCount, recvStart, recvCount; };
 inline bool rangesFit(const Peer& p, int numSend, int ghosts) {
     return p.sendStart >= 0 && p.sendCount >= 0 && p.sendStart + p.sendCount <= numSend && p.recvStart >= 0 &&
            p.recvCount >= 0 && p.recvStart + p.recvCount <= ghosts;
+}
+
+// the peer table of `fn` from its five arrays. Refused: a rank outside [0, rankEnd) or equal to notRank, ranges that do
+// not fit a partition of numSend send records and `ghosts` ghost elements (set with `prefix`_set_partition)
+inline std::vector<Peer> parsePeers(const std::string& prefix, const char* fn, const int* ranks, const int* sendStart,
+                                    const int* sendCount, const int* recvStart, const int* recvCount, int numPeers,
+                                    int numSend, int ghosts, int rankEnd, int notRank = -1) {
+    std::vector<Peer> peers;
+    for (int i = 0; i < numPeers; ++i) {
+        const Peer p{ranks[i], sendStart[i], sendCount[i], recvStart[i], recvCount[i]};
+        if (p.rank < 0 || p.rank >= rankEnd || p.rank == notRank || !rangesFit(p, numSend, ghosts))
+            throw bdg_detail::arg_error(prefix + "_" + fn + ": peer ranges do not fit the partition set with " + prefix + "_set_partition");
+        peers.push_back(p);
+    }
+    return peers;
 }
 
 // internal linkage: each solver's translation unit has its own copy, and the library exports no symbol for them

@@ -4,7 +4,7 @@
 #include "../host/capi_internal.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
-#include "halo_transport.hpp"
+#include "partition_schedule.hpp"
 #include "sw2d_curved_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -71,23 +71,21 @@ struct bdg_sw2d_curved {
     double g = 9.81, fconst = 0.0, cdconst = 0.0;
     long long stageCount = 0;
     double bytesPerElement = 0.0;
-    // partitioned runs (bdg_sw2d_curved_set_partition / _comm_init): elements [numOwned, K) are ghosts, refreshed from their
-    // owners before every evaluation by grouped ncclSend / ncclRecv on the solver's stream
-    int numOwned = 0, numInterior = 0, numSend = 0;
-    DevBuf<int> sendEls;
-    // overlapped schedule (nodal-trace form): elements [0, numInterior) have no ghost neighbour and are evaluated on the solver's
-    // stream while the exchange and then the partition-boundary elements [numInterior, numOwned) run on the exchange stream; the curved
-    // elements of the two ranges (columns of the side buffer) are listed for the fix-up launches of either chain
+    // partitioned runs (bdg_sw2d_curved_set_partition / _comm_init): partition_schedule.hpp. The two-chain schedule needs the
+    // nodal-trace form; the curved elements of the interior and the partition-boundary range (columns of the side buffer) are
+    // listed for the fix-up launches of either chain
     std::vector<int> curvedHost;          // element of each side-buffer column
     std::vector<int> maxNeighbourHost;    // largest element index a face of element k is paired with (from gmapP, kept for set_partition)
     DevBuf<int> slotsInterior, slotsBoundary;
     int numSlotsInterior = 0, numSlotsBoundary = 0;
+    bdg_halo::Partition part;
     bdg_halo::Transport halo;
-    hipEvent_t evA[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr}, evEntry = nullptr;
+    bdg_halo::TwoChains chains;
 
-    ~bdg_sw2d_curved() {
-        for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evEntry})
-            if (e) (void)hipEventDestroy(e);
+    ~bdg_sw2d_curved() { // both streams drained before the members destroy the events, the communicator and the exchange stream
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (halo.stream) (void)hipStreamSynchronize(halo.stream);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
@@ -170,55 +168,30 @@ struct bdg_sw2d_curved {
         }
     }
 
-    // ghost columns of `state` from their owners (pack -> grouped send / receive with every neighbour -> unpack), in stream order
     void exchange(double* state) { exchangeOn(state, stream); }
-    void exchangeOn(double* state, hipStream_t stream) {
-        if (!halo.comm) throw arg_error("bdg_sw2d_curved: no communicator (call bdg_sw2d_curved_comm_init first)");
-        const int rows = 4 * Np;
-        bdg_halo::pack(state, ld, rows, sendEls.p, numSend, halo.sendBuf.p, stream);
-        halo.sendRecv(stream, rows);
-        bdg_halo::unpack(state, ld, rows, numOwned, K - numOwned, halo.recvBuf.p, stream);
-    }
+    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, 4 * Np, K, on); }
     // the driver's RK2 step of a partitioned run: an exchange in front of EACH evaluation, of the state that evaluation reads
     //
-    // Nodal-trace form with interior elements: two chains, as the straight-element solver's stage loop (sw2d_device.hip):
-    //   solver stream A:  wait B(e-1) -> [elements without a ghost neighbour of evaluation e] -> signal A(e)
-    //   comm stream   B:  wait A(e-1) -> pack, grouped send / receive, unpack of the state e reads -> [partition-boundary
-    //                     elements of e] -> signal B(e)
-    // interior(e) reads the boundary elements' columns boundary(e-1) wrote and overwrites columns boundary(e-1) read: it waits
-    // for B(e-1); boundary(e) and its pack read / overwrite columns interior(e-1) wrote / read: B waits for A(e-1). Ghost
-    // columns are written by the unpack and read by the boundary launch only, both on B. Ghost elements are not evaluated.
-    // Otherwise (general form, or no interior elements): exchange, then every element, in stream order.
-    struct Chains { bool haveA = false, haveB = false; int e = 0; };
+    // Nodal-trace form with interior elements: the two-chain schedule of partition_schedule.hpp. Otherwise (general form, no
+    // interior elements, or BDG_SW2D_CURVED_NO_OVERLAP): exchange, then every element, in stream order.
     bool overlapped() const {
-        return useNT && numInterior >= 1 && std::getenv("BDG_SW2D_CURVED_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
-    }
-    void chainsBegin(Chains&) {
-        hipCheck(hipEventRecord(evEntry, stream), "hipEventRecord");          // whatever set the state, on A
-        hipCheck(hipStreamWaitEvent(halo.stream, evEntry, 0), "hipStreamWaitEvent");
+        return useNT && part.numInterior >= 1 && std::getenv("BDG_SW2D_CURVED_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
     }
     // one evaluation on both chains: reads `in` (ghost columns refreshed first), writes the owned columns of `out`
-    void chainsEval(Chains& c, int mode, bool filter, double* in, const double* base, double* out, double ca, double cb, double cc) {
+    void chainsEval(int mode, bool filter, double* in, const double* base, double* out, double ca, double cb, double cc) {
         // the interior launch is one resident round of workgroups that loop over their tiles: it leaves the slots the
         // partition-boundary launch needs (a workgroup per four tiles, rounded up to the eight XCDs), or that launch would wait
-        const int boundaryWgs = (((numOwned - numInterior + 15) / 16 + 3) / 4 + 7) / 8 * 8;
-        const int cur = c.e & 1, prev = cur ^ 1;
-        // ---- chain A
-        if (c.haveB) hipCheck(hipStreamWaitEvent(stream, evB[prev], 0), "hipStreamWaitEvent");
-        evaluateRange(mode, filter, in, base, out, ca, cb, cc, 0, numInterior, slotsInterior.p, numSlotsInterior, stream, boundaryWgs);
-        hipCheck(hipEventRecord(evA[cur], stream), "hipEventRecord");
-        // ---- chain B
-        if (c.haveA) hipCheck(hipStreamWaitEvent(halo.stream, evA[prev], 0), "hipStreamWaitEvent");
-        exchangeOn(in, halo.stream);
-        evaluateRange(mode, filter, in, base, out, ca, cb, cc, numInterior, numOwned, slotsBoundary.p, numSlotsBoundary, halo.stream);
-        hipCheck(hipEventRecord(evB[cur], halo.stream), "hipEventRecord");
-        c.haveA = c.haveB = true;
-        ++c.e;
-    }
-    void chainsEnd(Chains& c) { // join both ways: later work on A sees the last boundary update, later work on B the last interior launch
-        if (c.e == 0) return;
-        hipCheck(hipStreamWaitEvent(stream, evB[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
-        hipCheck(hipStreamWaitEvent(halo.stream, evA[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
+        const int boundaryWgs = (((part.numOwned - part.numInterior + 15) / 16 + 3) / 4 + 7) / 8 * 8;
+        chains.eval(stream, halo.stream,
+                    [&](hipStream_t a) {
+                        evaluateRange(mode, filter, in, base, out, ca, cb, cc, 0, part.numInterior, slotsInterior.p, numSlotsInterior, a,
+                                      boundaryWgs);
+                    },
+                    [&](hipStream_t b) {
+                        exchangeOn(in, b);
+                        evaluateRange(mode, filter, in, base, out, ca, cb, cc, part.numInterior, part.numOwned, slotsBoundary.p,
+                                      numSlotsBoundary, b);
+                    });
     }
     void stepRk2Exchanged(double dt, int steps, bool filter) {
         if (!overlapped()) {
@@ -230,25 +203,23 @@ struct bdg_sw2d_curved {
             }
             return;
         }
-        Chains c;
-        chainsBegin(c);
+        chains.begin(stream, halo.stream);
         for (int i = 0; i < steps; ++i) {
-            chainsEval(c, bdg_dev::CMODE_COMBINE, filter, qA.p, qA.p, qB.p, 1.0, 0.0, 0.5 * dt);
-            chainsEval(c, bdg_dev::CMODE_COMBINE, filter, qB.p, qA.p, qA.p, 1.0, 0.0, dt);
+            chainsEval(bdg_dev::CMODE_COMBINE, filter, qA.p, qA.p, qB.p, 1.0, 0.0, 0.5 * dt);
+            chainsEval(bdg_dev::CMODE_COMBINE, filter, qB.p, qA.p, qA.p, 1.0, 0.0, dt);
         }
-        chainsEnd(c);
+        chains.end(stream, halo.stream);
     }
     // LSERK4 stages of a partitioned run (reference src/advec1d/main.cpp:92-102 per stage): res = a res + dt RHS(q); q += b res,
     // an exchange of q in front of every stage; the nodal-trace form writes the other state buffer and the two swap roles
     void lserkStagesExchanged(double dt, int numStages) {
-        Chains c;
         const bool two = overlapped();
-        if (two) chainsBegin(c);
+        if (two) chains.begin(stream, halo.stream);
         for (int i = 0; i < numStages; ++i) {
             const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
             const double a = blitzdg::LSERK4::rk4a[st], b = blitzdg::LSERK4::rk4b[st];
             if (two) {
-                chainsEval(c, bdg_dev::CMODE_LSERK, false, qA.p, nullptr, qB.p, a, b, dt);
+                chainsEval(bdg_dev::CMODE_LSERK, false, qA.p, nullptr, qB.p, a, b, dt);
                 std::swap(qA.p, qB.p);
             } else {
                 exchange(qA.p);
@@ -256,7 +227,7 @@ struct bdg_sw2d_curved {
             }
             ++stageCount;
         }
-        if (two) chainsEnd(c);
+        if (two) chains.end(stream, halo.stream);
     }
     void stepRk2(double dt, int steps, bool filter) {
         for (int i = 0; i < steps; ++i) {
@@ -270,6 +241,10 @@ namespace {
 
 void requireCurved(const bdg_sw2d_curved* s, const char* fn) {
     if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
+}
+void requireComm(const bdg_sw2d_curved* s, const char* fn) {
+    requireCurved(s, fn);
+    bdg_halo::requireComm(s->halo, "bdg_sw2d_curved", fn);
 }
 
 std::vector<double> matmul(const double* A, const double* B, int n, int m, int c) { // (n,m) (m,c)
@@ -869,13 +844,7 @@ int bdg_sw2d_curved_create(const bdg_sw2d_curved_desc* desc, bdg_sw2d_curved** o
     });
 }
 
-void bdg_sw2d_curved_destroy(bdg_sw2d_curved* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->halo.stream) (void)hipStreamSynchronize(s->halo.stream);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
+void bdg_sw2d_curved_destroy(bdg_sw2d_curved* s) { delete s; }
 
 int bdg_sw2d_curved_rhs(bdg_sw2d_curved* s, const double* h, const double* hu, const double* hv, const double* hN,
                         double* r1, double* r2, double* r3, double* r4, int filter) {
@@ -999,28 +968,9 @@ int bdg_sw2d_curved_rk2_phase(bdg_sw2d_curved* s, double dt, int phase, int filt
 int bdg_sw2d_curved_set_partition(bdg_sw2d_curved* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_set_partition");
-        if (num_owned < 1 || num_owned > s->K || num_interior < 0 || num_interior > num_owned || num_send < 0 ||
-            (num_send > 0 && !send_elements))
-            throw arg_error("bdg_sw2d_curved_set_partition: bad argument");
-        for (int i = 0; i < num_send; ++i)
-            if (send_elements[i] < 0 || send_elements[i] >= num_owned)
-                throw arg_error("bdg_sw2d_curved_set_partition: a send element is not an owned element");
-        // The two-chain schedule evaluates [0, num_interior) beside the exchange: it is race-free only if no such element
-        // reads a ghost column and none of them is packed for a neighbour. A plan that breaks either is refused here
-        // (it would otherwise give stale ghost reads, not an error).
-        for (int k = 0; k < num_interior; ++k)
-            if (s->maxNeighbourHost[static_cast<size_t>(k)] >= num_owned)
-                throw arg_error("bdg_sw2d_curved_set_partition: element " + std::to_string(k) +
-                                " is listed as interior but has a ghost neighbour (elements >= num_owned)");
-        for (int i = 0; i < num_send; ++i)
-            if (send_elements[i] < num_interior)
-                throw arg_error("bdg_sw2d_curved_set_partition: send element " + std::to_string(send_elements[i]) +
-                                " lies in the interior range [0, num_interior)");
-        if (s->halo.comm) throw arg_error("bdg_sw2d_curved_set_partition: the communicator is already initialised");
         s->use();
-        s->numOwned = num_owned;
-        s->numInterior = num_interior;
-        s->numSend = num_send;
+        s->part.set("bdg_sw2d_curved", s->K, s->maxNeighbourHost, num_interior, num_owned, send_elements, num_send,
+                    s->halo.comm != nullptr, s->bytes, s->stream);
         std::vector<int> inner, outer; // columns of the side buffer whose element is an interior / a partition-boundary one
         for (size_t c = 0; c < s->curvedHost.size(); ++c) {
             const int k = s->curvedHost[c];
@@ -1036,11 +986,6 @@ int bdg_sw2d_curved_set_partition(bdg_sw2d_curved* s, int num_interior, int num_
         if (!outer.empty())
             hipCheck(hipMemcpyAsync(s->slotsBoundary.p, outer.data(), outer.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "slot list upload");
         hipCheck(hipStreamSynchronize(s->stream), "slot list sync"); // (inner, outer are locals)
-        s->sendEls.alloc(static_cast<size_t>(std::max(1, num_send)), s->bytes, s->stream);
-        if (num_send > 0)
-            hipCheck(hipMemcpyAsync(s->sendEls.p, send_elements, static_cast<size_t>(num_send) * sizeof(int), hipMemcpyHostToDevice, s->stream),
-                  "send list upload");
-        hipCheck(hipStreamSynchronize(s->stream), "send list sync");
     });
 }
 
@@ -1049,35 +994,16 @@ int bdg_sw2d_curved_comm_init(bdg_sw2d_curved* s, int rank, int world, const voi
                               int num_peers) {
     return guard([&] {
         requireCurved(s, "bdg_sw2d_curved_comm_init");
-        if (!unique_id || world < 1 || rank < 0 || rank >= world || num_peers < 0 ||
-            (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
-            throw arg_error("bdg_sw2d_curved_comm_init: bad argument");
-        if (s->halo.comm) throw arg_error("bdg_sw2d_curved_comm_init: communicator already initialised");
-        if (s->numOwned < 1) throw arg_error("bdg_sw2d_curved_comm_init: call bdg_sw2d_curved_set_partition first");
-        const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_halo::Peer> peers;
-        for (int i = 0; i < num_peers; ++i) {
-            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank >= world || !bdg_halo::rangesFit(p, s->numSend, ghosts))
-                throw arg_error("bdg_sw2d_curved_comm_init: peer ranges do not fit the partition set with bdg_sw2d_curved_set_partition");
-            peers.push_back(p);
-        }
         s->use();
-        s->halo.connect(unique_id, rank, world, static_cast<size_t>(4) * s->Np, s->numSend, ghosts, s->bytes);
-        s->halo.peers = peers;
-        // (events that only order kernels of this device's two streams: no system-scope fence, as in bdg_sw2d_comm_init)
-        for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1], &s->evEntry})
-            hipCheck(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate");
-        for (DevBuf<double>* b : {&s->halo.sendBuf, &s->halo.recvBuf, &s->halo.scalarBuf}) b->zero(s->stream);
-        hipCheck(hipStreamSynchronize(s->stream), "exchange buffers");
+        bdg_halo::commInit("bdg_sw2d_curved", s->halo, s->part, s->chains, s->K, static_cast<size_t>(4) * s->Np, rank, world, unique_id,
+                           peer_ranks, send_start, send_count, recv_start, recv_count, num_peers, s->bytes, s->stream);
     });
 }
 
 int bdg_sw2d_curved_step_rk2_exchanged(bdg_sw2d_curved* s, double dt, int num_steps, int filter) {
     return guard([&] {
-        requireCurved(s, "bdg_sw2d_curved_step_rk2_exchanged");
+        requireComm(s, "bdg_sw2d_curved_step_rk2_exchanged");
         if (num_steps < 0) throw arg_error("bdg_sw2d_curved_step_rk2_exchanged: num_steps < 0");
-        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_step_rk2_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
         s->use();
         s->stepRk2Exchanged(dt, num_steps, filter != 0);
     });
@@ -1085,9 +1011,8 @@ int bdg_sw2d_curved_step_rk2_exchanged(bdg_sw2d_curved* s, double dt, int num_st
 
 int bdg_sw2d_curved_lserk4_stages_exchanged(bdg_sw2d_curved* s, double dt, int num_stages) {
     return guard([&] {
-        requireCurved(s, "bdg_sw2d_curved_lserk4_stages_exchanged");
+        requireComm(s, "bdg_sw2d_curved_lserk4_stages_exchanged");
         if (num_stages < 0) throw arg_error("bdg_sw2d_curved_lserk4_stages_exchanged: num_stages < 0");
-        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_lserk4_stages_exchanged: no communicator (call bdg_sw2d_curved_comm_init first)");
         s->use();
         s->lserkStagesExchanged(dt, num_stages);
     });
@@ -1095,7 +1020,7 @@ int bdg_sw2d_curved_lserk4_stages_exchanged(bdg_sw2d_curved* s, double dt, int n
 
 int bdg_sw2d_curved_exchange(bdg_sw2d_curved* s, int intermediate) {
     return guard([&] {
-        requireCurved(s, "bdg_sw2d_curved_exchange");
+        requireComm(s, "bdg_sw2d_curved_exchange");
         s->use();
         s->exchange(intermediate ? s->qB.p : s->qA.p);
     });
@@ -1103,13 +1028,9 @@ int bdg_sw2d_curved_exchange(bdg_sw2d_curved* s, int intermediate) {
 
 int bdg_sw2d_curved_barrier(bdg_sw2d_curved* s) {
     return guard([&] {
-        requireCurved(s, "bdg_sw2d_curved_barrier");
-        if (!s->halo.comm) throw arg_error("bdg_sw2d_curved_barrier: no communicator");
+        requireComm(s, "bdg_sw2d_curved_barrier");
         s->use();
-        hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(s->halo.scalarBuf.p, s->halo.scalarBuf.p, 1, ncclDouble, ncclMax, s->halo.comm, s->stream), "ncclAllReduce");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        bdg_halo::barrier(s->halo, s->stream);
     });
 }
 

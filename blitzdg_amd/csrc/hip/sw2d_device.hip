@@ -1885,13 +1885,8 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
             throw arg_error("bdg_sw2d_comm_init: bad argument");
         if (s->halo.comm) throw arg_error("bdg_sw2d_comm_init: communicator already initialised");
         const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_halo::Peer> peers;
-        for (int i = 0; i < num_peers; ++i) {
-            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank >= world || !bdg_halo::rangesFit(p, s->numSend, ghosts))
-                throw arg_error("bdg_sw2d_comm_init: peer ranges do not fit the partition set with bdg_sw2d_set_partition");
-            peers.push_back(p);
-        }
+        std::vector<bdg_halo::Peer> peers = bdg_halo::parsePeers("bdg_sw2d", "comm_init", peer_ranks, send_start, send_count, recv_start,
+                                                                 recv_count, num_peers, s->numSend, ghosts, world);
         s->use();
         const size_t rows = static_cast<size_t>(s->nf) * s->Np;
         s->halo.connect(unique_id, rank, world, rows, s->numSend, ghosts, s->bytes);
@@ -1938,13 +1933,9 @@ int bdg_sw2d_local_peers(bdg_sw2d* s, int rank, const int* peer_ranks, const int
             throw arg_error("bdg_sw2d_local_peers: bad argument");
         if (s->halo.comm || s->localGroup) throw arg_error("bdg_sw2d_local_peers: a transport is already initialised");
         const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_halo::Peer> peers;
-        for (int i = 0; i < num_peers; ++i) {
-            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank == rank || !bdg_halo::rangesFit(p, s->numSend, ghosts))
-                throw arg_error("bdg_sw2d_local_peers: peer ranges do not fit the partition set with bdg_sw2d_set_partition");
-            peers.push_back(p);
-        }
+        // (no world here: any other rank of the group)
+        std::vector<bdg_halo::Peer> peers = bdg_halo::parsePeers("bdg_sw2d", "local_peers", peer_ranks, send_start, send_count, recv_start,
+                                                                 recv_count, num_peers, s->numSend, ghosts, INT_MAX, rank);
         s->use();
         s->halo.rank = rank;
         s->halo.peers = peers;

@@ -2,9 +2,10 @@
 // (include/blitzdg_hip.h). Host side: checks that Dr, Ds and Lift have the Gauss-Lobatto tensor form and extracts
 // their 1-D factors, chooses the geometry form, builds the gather index; then launches sw2d_quad_stage_kernel
 // (sw2d_quad_kernel.hpp) on its own stream. One device; results come back in the caller's numbering.
-// Partitioned runs (bdg_sw2dq_set_partition / _comm_init) add the ghost exchange of halo_transport.hpp on a second stream.
+// Partitioned runs (bdg_sw2dq_set_partition / _comm_init) add the ghost exchange and the two-chain schedule of
+// partition_schedule.hpp on a second stream.
 #include "device_buffer.hpp"
-#include "halo_transport.hpp"
+#include "partition_schedule.hpp"
 #include "sw2d_quad_kernel.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "blitzdg/MeshManager.hpp"
@@ -91,13 +92,11 @@ struct bdg_sw2dq {
     DevBuf<double> q, q1, res, io, ioOut, geo, fgeo, ageo, ops, filt, partials;
     DevBuf<int> gidx;
     std::vector<double> hostPartials;
-    // partitioned runs (bdg_sw2dq_set_partition / _comm_init): the mesh is ordered [interior: numInterior | partition boundary:
-    // up to numOwned | ghosts: up to K]; ghost columns are refreshed from their owners before every evaluation, never evaluated
-    int numOwned = 0, numInterior = 0, numSend = 0;
+    // partitioned runs (bdg_sw2dq_set_partition / _comm_init): partition_schedule.hpp
     std::vector<int> maxNeighbourHost; // largest element a face node of element k gathers from (from vmapP, kept for set_partition)
-    DevBuf<int> sendEls;
+    bdg_halo::Partition part;
     bdg_halo::Transport halo;
-    hipEvent_t evA[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr}, evEntry = nullptr;
+    bdg_halo::TwoChains chains;
 
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
     long long plane() const { return static_cast<long long>(Np) * ld; }
@@ -164,102 +163,69 @@ struct bdg_sw2dq {
     }
 
     // ---- partitioned runs
-    // ghost columns of `state` from their owners (pack -> grouped send / receive with every neighbour -> unpack), in stream order
-    void exchangeOn(double* state, hipStream_t on) {
-        const int rows = 3 * Np;
-        bdg_halo::pack(state, ld, rows, sendEls.p, numSend, halo.sendBuf.p, on);
-        halo.sendRecv(on, static_cast<size_t>(rows));
-        bdg_halo::unpack(state, ld, rows, numOwned, K - numOwned, halo.recvBuf.p, on);
-    }
+    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, 3 * Np, K, on); }
     // one evaluation of the elements [kBegin, kEnd) on `on`
     void evaluateRange(int mode, bool filter, QuadParams p, int kBegin, int kEnd, hipStream_t on) {
         p.kBegin = kBegin; p.kEnd = kEnd;
         launchOn(mode, filter, p, on);
     }
-    // Two chains, as the curved solver's partitioned schedule (sw2d_curved_device.hip), ordered by events only:
-    //   solver stream A:  wait B(e-1) -> [interior elements of evaluation e] -> signal A(e)
-    //   exchange stream B: wait A(e-1) -> pack, grouped send / receive, unpack of the state e reads -> [partition-boundary
-    //                      elements of e] -> signal B(e)
-    // interior(e) reads the columns boundary(e-1) wrote and overwrites columns boundary(e-1) read: it waits for B(e-1);
-    // boundary(e) and its pack read / overwrite columns interior(e-1) wrote / read: B waits for A(e-1). Ghost columns are
-    // written by the unpack and read by the boundary launch only, both on B. Ghost elements are not evaluated.
-    // Otherwise (no interior element, or BDG_SW2DQ_NO_OVERLAP): exchange, then every owned element, in stream order.
-    struct Chains { bool haveA = false, haveB = false; int e = 0; };
+    // The two-chain schedule of partition_schedule.hpp; without an interior element, or with BDG_SW2DQ_NO_OVERLAP:
+    // exchange, then every owned element, in stream order.
     bool overlapped() const {
-        return numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
-    }
-    void chainsBegin(Chains&) {
-        hipCheck(hipEventRecord(evEntry, stream), "hipEventRecord"); // whatever set the state, on A
-        hipCheck(hipStreamWaitEvent(halo.stream, evEntry, 0), "hipStreamWaitEvent");
+        return part.numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
     }
     // one evaluation: reads p.qin (ghost columns refreshed first), writes the owned columns of its outputs
-    void evaluateExchanged(Chains* c, int mode, bool filter, const QuadParams& p) {
+    void evaluateExchanged(bool two, int mode, bool filter, const QuadParams& p) {
         double* in = const_cast<double*>(p.qin);
-        if (!c) {
+        if (!two) {
             exchangeOn(in, stream);
-            evaluateRange(mode, filter, p, 0, numOwned, stream);
+            evaluateRange(mode, filter, p, 0, part.numOwned, stream);
             return;
         }
         // (the interior launch is the plain grid of one workgroup per tile: a capped grid of workgroups looping over tiles,
         // which leaves room for the boundary launch, measured slower at every split and order: DESIGN section 3.8)
-        const int cur = c->e & 1, prev = cur ^ 1;
-        // ---- chain A
-        if (c->haveB) hipCheck(hipStreamWaitEvent(stream, evB[prev], 0), "hipStreamWaitEvent");
-        evaluateRange(mode, filter, p, 0, numInterior, stream);
-        hipCheck(hipEventRecord(evA[cur], stream), "hipEventRecord");
-        // ---- chain B
-        if (c->haveA) hipCheck(hipStreamWaitEvent(halo.stream, evA[prev], 0), "hipStreamWaitEvent");
-        exchangeOn(in, halo.stream);
-        evaluateRange(mode, filter, p, numInterior, numOwned, halo.stream);
-        hipCheck(hipEventRecord(evB[cur], halo.stream), "hipEventRecord");
-        c->haveA = c->haveB = true;
-        ++c->e;
-    }
-    void chainsEnd(Chains& c) { // join both ways: later work on A sees the last boundary update, later work on B the last interior launch
-        if (c.e == 0) return;
-        hipCheck(hipStreamWaitEvent(stream, evB[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
-        hipCheck(hipStreamWaitEvent(halo.stream, evA[(c.e - 1) & 1], 0), "hipStreamWaitEvent");
+        chains.eval(stream, halo.stream,
+                    [&](hipStream_t a) { evaluateRange(mode, filter, p, 0, part.numInterior, a); },
+                    [&](hipStream_t b) {
+                        exchangeOn(in, b);
+                        evaluateRange(mode, filter, p, part.numInterior, part.numOwned, b);
+                    });
     }
     // the script's RK2 step with an exchange of q before the predictor and of q1 before the corrector
     void stepRk2Exchanged(double dt, int steps, bool filter) {
-        Chains c;
-        Chains* cp = overlapped() ? &c : nullptr;
-        if (cp) chainsBegin(c);
+        const bool two = overlapped();
+        if (two) chains.begin(stream, halo.stream);
         for (int i = 0; i < steps; ++i) {
             QuadParams p = params();
             p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.cc = 0.5 * dt;
-            evaluateExchanged(cp, QMODE_COMBINE, filter, p);
+            evaluateExchanged(two, QMODE_COMBINE, filter, p);
             p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;
-            evaluateExchanged(cp, QMODE_COMBINE, filter, p);
+            evaluateExchanged(two, QMODE_COMBINE, filter, p);
         }
-        if (cp) chainsEnd(c);
+        if (two) chains.end(stream, halo.stream);
     }
     // LSERK4 stages with an exchange of the state each stage reads; q and q1 swap roles after every stage, and the next stage's
     // exchange refreshes the ghosts of the new q
     void lserkStagesExchanged(double dt, int stages) {
-        Chains c;
-        Chains* cp = overlapped() ? &c : nullptr;
-        if (cp) chainsBegin(c);
+        const bool two = overlapped();
+        if (two) chains.begin(stream, halo.stream);
         for (int i = 0; i < stages; ++i) {
             const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
             QuadParams p = params();
             p.qin = q.p; p.qout = q1.p; p.res = res.p;
             p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
-            evaluateExchanged(cp, QMODE_LSERK, false, p);
+            evaluateExchanged(two, QMODE_LSERK, false, p);
             std::swap(q.p, q1.p);
             ++stageCount;
         }
-        if (cp) chainsEnd(c);
+        if (two) chains.end(stream, halo.stream);
     }
-    ~bdg_sw2dq() {
-        if (stream) {
-            (void)hipSetDevice(device);
-            (void)hipStreamSynchronize(stream);
-            if (halo.stream) (void)hipStreamSynchronize(halo.stream);
-        }
-        for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evEntry})
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
+    ~bdg_sw2dq() { // both streams drained before the members destroy the events, the communicator and the exchange stream
+        if (!stream) return;
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        if (halo.stream) (void)hipStreamSynchronize(halo.stream);
+        (void)hipStreamDestroy(stream);
     }
 };
 
@@ -576,33 +542,9 @@ int bdg_sw2dq_synchronize(bdg_sw2dq* s) {
 int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_partition");
-        if (num_owned < 1 || num_owned > s->K || num_interior < 0 || num_interior > num_owned || num_send < 0 ||
-            (num_send > 0 && !send_elements))
-            throw arg_error("bdg_sw2dq_set_partition: bad argument");
-        for (int i = 0; i < num_send; ++i)
-            if (send_elements[i] < 0 || send_elements[i] >= num_owned)
-                throw arg_error("bdg_sw2dq_set_partition: a send element is not an owned element");
-        // The two-chain schedule evaluates [0, num_interior) beside the exchange: it is race-free only if no such element
-        // reads a ghost column and none of them is packed for a neighbour. A plan that breaks either is refused here
-        // (it would otherwise give stale ghost reads, not an error).
-        for (int k = 0; k < num_interior; ++k)
-            if (s->maxNeighbourHost[static_cast<size_t>(k)] >= num_owned)
-                throw arg_error("bdg_sw2dq_set_partition: element " + std::to_string(k) +
-                                " is listed as interior but has a ghost neighbour (elements >= num_owned)");
-        for (int i = 0; i < num_send; ++i)
-            if (send_elements[i] < num_interior)
-                throw arg_error("bdg_sw2dq_set_partition: send element " + std::to_string(send_elements[i]) +
-                                " lies in the interior range [0, num_interior)");
-        if (s->halo.comm) throw arg_error("bdg_sw2dq_set_partition: the communicator is already initialised");
         s->use();
-        s->numOwned = num_owned;
-        s->numInterior = num_interior;
-        s->numSend = num_send;
-        s->sendEls.alloc(static_cast<size_t>(std::max(1, num_send)), s->bytes, s->stream);
-        if (num_send > 0)
-            hipCheck(hipMemcpyAsync(s->sendEls.p, send_elements, static_cast<size_t>(num_send) * sizeof(int), hipMemcpyHostToDevice,
-                                    s->stream), "send list upload");
-        hipCheck(hipStreamSynchronize(s->stream), "send list sync");
+        s->part.set("bdg_sw2dq", s->K, s->maxNeighbourHost, num_interior, num_owned, send_elements, num_send, s->halo.comm != nullptr,
+                    s->bytes, s->stream);
     });
 }
 
@@ -610,34 +552,16 @@ int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id
                         const int* send_count, const int* recv_start, const int* recv_count, int num_peers) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_comm_init");
-        if (!unique_id || world < 1 || rank < 0 || rank >= world || num_peers < 0 ||
-            (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
-            throw arg_error("bdg_sw2dq_comm_init: bad argument");
-        if (s->halo.comm) throw arg_error("bdg_sw2dq_comm_init: communicator already initialised");
-        if (s->numOwned < 1) throw arg_error("bdg_sw2dq_comm_init: call bdg_sw2dq_set_partition first");
-        const int ghosts = s->K - s->numOwned;
-        std::vector<bdg_halo::Peer> peers;
-        for (int i = 0; i < num_peers; ++i) {
-            const bdg_halo::Peer p{peer_ranks[i], send_start[i], send_count[i], recv_start[i], recv_count[i]};
-            if (p.rank < 0 || p.rank >= world || !bdg_halo::rangesFit(p, s->numSend, ghosts))
-                throw arg_error("bdg_sw2dq_comm_init: peer ranges do not fit the partition set with bdg_sw2dq_set_partition");
-            peers.push_back(p);
-        }
         s->use();
-        s->halo.connect(unique_id, rank, world, static_cast<size_t>(3) * s->Np, s->numSend, ghosts, s->bytes);
-        s->halo.peers = peers;
-        // (events that only order kernels of this device's two streams: no system-scope fence, as in bdg_sw2d_comm_init)
-        for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1], &s->evEntry})
-            hipCheck(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate");
-        for (DevBuf<double>* b : {&s->halo.sendBuf, &s->halo.recvBuf, &s->halo.scalarBuf}) b->zero(s->stream);
-        hipCheck(hipStreamSynchronize(s->stream), "exchange buffers");
+        bdg_halo::commInit("bdg_sw2dq", s->halo, s->part, s->chains, s->K, static_cast<size_t>(3) * s->Np, rank, world, unique_id,
+                           peer_ranks, send_start, send_count, recv_start, recv_count, num_peers, s->bytes, s->stream);
     });
 }
 
 namespace {
 void requireComm(const bdg_sw2dq* s, const char* fn) {
     requireSolver(s, fn);
-    if (!s->halo.comm) throw arg_error(std::string(fn) + ": no communicator (call bdg_sw2dq_comm_init first)");
+    bdg_halo::requireComm(s->halo, "bdg_sw2dq", fn);
 }
 } // namespace
 
@@ -656,7 +580,7 @@ int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int fil
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2_exchanged: filter requested but the solver has no Filter");
         s->use();
         s->stepRk2Exchanged(dt, num_steps, filter != 0);
-        s->checkBlowUp(s->numOwned, true);
+        s->checkBlowUp(s->part.numOwned, true);
     });
 }
 
@@ -666,7 +590,7 @@ int bdg_sw2dq_lserk4_stages_exchanged(bdg_sw2dq* s, double dt, int num_stages) {
         if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages_exchanged: num_stages < 0");
         s->use();
         s->lserkStagesExchanged(dt, num_stages);
-        s->checkBlowUp(s->numOwned, true);
+        s->checkBlowUp(s->part.numOwned, true);
     });
 }
 
@@ -674,11 +598,7 @@ int bdg_sw2dq_barrier(bdg_sw2dq* s) {
     return guard([&] {
         requireComm(s, "bdg_sw2dq_barrier");
         s->use();
-        hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(s->halo.scalarBuf.p, s->halo.scalarBuf.p, 1, ncclDouble, ncclMax, s->halo.comm,
-                                                       s->stream), "ncclAllReduce");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        bdg_halo::barrier(s->halo, s->stream);
     });
 }
 

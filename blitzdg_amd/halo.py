@@ -242,6 +242,22 @@ def remove_id_file(path):
         pass
 
 
+def attach_native(handle, prefix, plan, unique_id=None, loopback=False):
+    """Puts the native solver `handle` on `plan`'s share: `prefix`_set_partition, the communicator (native_comm),
+    `prefix`_comm_init with the plan's peer tables, a first `prefix`_barrier, then rank 0's clean-up of the rendezvous
+    file. prefix: "bdg_sw2d", "bdg_sw2d_curved" or "bdg_sw2dq". Returns the peer tables."""
+    from ._capi import check, lib, ptr
+
+    send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
+    check(getattr(lib, prefix + "_set_partition")(handle, plan.num_interior, plan.num_owned, ptr(send), send.size))
+    comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
+    peers = plan.peer_tables(loopback)
+    check(getattr(lib, prefix + "_comm_init")(handle, comm_rank, comm_world, idbuf, *map(ptr, peers), peers[0].size))
+    check(getattr(lib, prefix + "_barrier")(handle))
+    remove_id_file(id_path)
+    return peers
+
+
 class NativeDistributedSw2d:
     """sw2d on `world` GPUs with the exchange driven entirely by the C++ library: grouped
     ncclSend/ncclRecv on a communication stream, overlapped with the interior elements, whole
@@ -254,7 +270,7 @@ class NativeDistributedSw2d:
         (ghost values are then not the neighbours' -- timing only, never results)."""
         from . import pyblitzdg as dg
         from . import sw2d
-        from ._capi import byref, c_double, check, lib, ptr
+        from ._capi import byref, c_double, check, lib
 
         self._lib, self._check, self._byref, self._c_double = lib, check, byref, c_double
         self.plan, self.order = plan, order
@@ -272,15 +288,7 @@ class NativeDistributedSw2d:
         else:
             self.solver = sw2d.Sw2dSolver(nodes=self.nodes, g=g, device=device, flags=sw2d.KEEP_ORDER)
         self.Np = self.solver.Np
-        send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
-        check(lib.bdg_sw2d_set_partition(self.solver._h, plan.num_interior, plan.num_owned, ptr(send), send.size))
-
-        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
-        pr, ss, sc, rs, rc = plan.peer_tables(loopback)
-        check(lib.bdg_sw2d_comm_init(self.solver._h, comm_rank, comm_world, idbuf, ptr(pr), ptr(ss), ptr(sc), ptr(rs),
-                                     ptr(rc), pr.size))
-        self.barrier()
-        remove_id_file(id_path)
+        attach_native(self.solver._h, "bdg_sw2d", plan, unique_id, loopback)
         self.global_elements = None
 
     @classmethod

@@ -236,22 +236,14 @@ class NativeDistributedSw2dCurved(DistributedSw2dCurved):
         """loopback=True: this one process computes plan.rank's share of a plan.world-way split and every neighbour exchange
         is a send-to-self of the same size through the real transport (ghost values are then this rank's own boundary
         elements, not the neighbours': a rehearsal of the exchange on one GPU, not a partitioned result)."""
-        from ._capi import ptr
-        from .halo import native_comm, remove_id_file
+        from .halo import attach_native
 
         class _NoDist:                    # the base class only asks its transport for the backend name
             @staticmethod
             def get_backend():
                 return "native"
         super().__init__(plan, order, deform, _NoDist(), g=g, filter_args=filter_args, sources=sources, device=device)
-        h = self.solver._h
-        send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
-        check(lib.bdg_sw2d_curved_set_partition(h, plan.num_interior, plan.num_owned, ptr(send), send.size))
-        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
-        pr, ss, sc, rs, rc = self.peer_table = plan.peer_tables(loopback)
-        check(lib.bdg_sw2d_curved_comm_init(h, comm_rank, comm_world, idbuf, ptr(pr), ptr(ss), ptr(sc), ptr(rs), ptr(rc), pr.size))
-        self.barrier()
-        remove_id_file(id_path)
+        self.peer_table = attach_native(self.solver._h, "bdg_sw2d_curved", plan, unique_id, loopback)
 
     def _exchange(self, intermediate):
         check(lib.bdg_sw2d_curved_exchange(self.solver._h, int(bool(intermediate))))

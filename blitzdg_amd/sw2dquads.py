@@ -145,7 +145,7 @@ class NativeDistributedSw2dQuad:
         neighbour exchange is a send-to-self of the same size through the real transport (the ghosts then hold this rank's
         own boundary elements: a rehearsal of the exchange on one GPU, not a partitioned result)."""
         from . import pyblitzdg as dg
-        from .halo import build_local_mesh, native_comm, remove_id_file
+        from .halo import attach_native, build_local_mesh
 
         self.plan, self.order = plan, order
         self.mesh = build_local_mesh(plan)
@@ -154,15 +154,7 @@ class NativeDistributedSw2dQuad:
             self.nodes.buildFilter(*filter_args)
         self.filtered = filter_args is not None
         self.solver = Sw2dQuadSolver(nodes=self.nodes, g=g, device=device, flags=flags)
-        h = self.solver._h
-        send = np.ascontiguousarray(plan.send_local, dtype=np.int32)
-        check(lib.bdg_sw2dq_set_partition(h, plan.num_interior, plan.num_owned, C.ptr(send), send.size))
-        comm_rank, comm_world, idbuf, id_path = native_comm(plan, unique_id, loopback)
-        pr, ss, sc, rs, rc = self.peer_table = plan.peer_tables(loopback)
-        check(lib.bdg_sw2dq_comm_init(h, comm_rank, comm_world, idbuf, C.ptr(pr), C.ptr(ss), C.ptr(sc), C.ptr(rs), C.ptr(rc),
-                                      pr.size))
-        self.barrier()
-        remove_id_file(id_path)
+        self.peer_table = attach_native(self.solver._h, "bdg_sw2dq", plan, unique_id, loopback)
 
     def close(self):
         solver, self.solver = getattr(self, "solver", None), None
