@@ -207,6 +207,14 @@ _SIGNATURES = {
     "bdg_sw2dq_synchronize": (c_int, [_P]),
     "bdg_sw2dq_device_bytes": (c_size_t, [_P]),
     "bdg_sw2dq_uses_parallelogram_geometry": (c_int, [_P]),
+    "bdg_sw2dq_create_fields": (c_int, [POINTER(Sw2dqDesc), c_int, POINTER(_P)]),
+    "bdg_sw2dq_create_from_nodes_fields": (c_int, [_P, c_double, c_int, c_int, c_int, POINTER(_P)]),
+    "bdg_sw2dq_num_fields": (c_int, [_P]),
+    "bdg_sw2dq_set_sources": (c_int, [_P, _P, _P, c_double, _P, c_double]),
+    "bdg_sw2dq_set_state4": (c_int, [_P, _P, _P, _P, _P]),
+    "bdg_sw2dq_get_state4": (c_int, [_P, _P, _P, _P, _P]),
+    "bdg_sw2dq_rhs4": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
+    "bdg_sw2dq_compute_dt": (c_int, [_P, c_double, POINTER(c_double), POINTER(c_double)]),
     "bdg_sw2dq_set_partition": (c_int, [_P, c_int, c_int, _P, c_int]),
     "bdg_sw2dq_comm_init": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2dq_exchange": (c_int, [_P, c_int]),

@@ -3,15 +3,17 @@
 // their 1-D factors, chooses the geometry form, builds the gather index; then launches sw2d_quad_stage_kernel
 // (sw2d_quad_kernel.hpp) on its own stream. One device; results come back in the caller's numbering.
 // Partitioned runs (bdg_sw2dq_set_partition / _comm_init) add the ghost exchange and the two-chain schedule of
-// partition_schedule.hpp on a second stream.
+// partition_schedule.hpp on a second stream. A solver created with four fields (bdg_sw2dq_create_fields) launches
+// sw2d_quad4_stage_kernel (sw2d_quad4_kernel.hpp) instead, with the sources of bdg_sw2dq_set_sources if there are any.
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
-#include "sw2d_quad_kernel.hpp"
+#include "sw2d_quad4_kernel.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "blitzdg/MeshManager.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <limits>
 #include <memory>
 #include <string>
 #include <utility>
@@ -34,6 +36,21 @@ hipError_t sw2d_quad_stage(int order, int mode, bool filter, bool general, const
     case 6: return sw2d_quad_launch<6>(mode, filter, general, p, stream);
     case 7: return sw2d_quad_launch<7>(mode, filter, general, p, stream);
     case 8: return sw2d_quad_launch<8>(mode, filter, general, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t sw2d_quad4_stage(int order, int mode, bool filter, bool general, bool sources, const Quad4Params& p,
+                            hipStream_t stream) {
+    switch (order) {
+    case 1: return sw2d_quad4_launch<1>(mode, filter, general, sources, p, stream);
+    case 2: return sw2d_quad4_launch<2>(mode, filter, general, sources, p, stream);
+    case 3: return sw2d_quad4_launch<3>(mode, filter, general, sources, p, stream);
+    case 4: return sw2d_quad4_launch<4>(mode, filter, general, sources, p, stream);
+    case 5: return sw2d_quad4_launch<5>(mode, filter, general, sources, p, stream);
+    case 6: return sw2d_quad4_launch<6>(mode, filter, general, sources, p, stream);
+    case 7: return sw2d_quad4_launch<7>(mode, filter, general, sources, p, stream);
+    case 8: return sw2d_quad4_launch<8>(mode, filter, general, sources, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -79,10 +96,50 @@ __global__ __launch_bounds__(256) void sw2d_quad_hmax_kernel(const double* h, lo
 
 constexpr int kHmaxBlocks = 512;
 
+// Face-node maximum of |Fscale| (sqrt(u^2 + v^2) + sqrt(g h)) over the elements [0, K), for the drivers' time step
+// dt = CFL / ((N + 1)^2 / 2 * maximum); one partial per block, NaN if any value is NaN. Contraction is off, and division
+// and square root are the correctly rounded ones, so the value is bit-identical to the host formula.
+__global__ __launch_bounds__(256) void sw2d_quad_dt_kernel(const double* __restrict__ q, const double* __restrict__ fgeo,
+                                                           const double* __restrict__ ageo, long long ld, int N, int K,
+                                                           double g, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
+    const long long plane = static_cast<long long>(Np) * ld, total = static_cast<long long>(NFN) * K;
+    double mx = 0.0;
+    bool bad = false;
+    for (long long t = blockIdx.x * 256LL + threadIdx.x; t < total; t += 256LL * gridDim.x) {
+        const int fn = static_cast<int>(t / K), k = static_cast<int>(t % K), f = fn / Nq, n = fn % Nq;
+        const int node = f == 0 ? Nq * n : (f == 1 ? Nq * N + n : (f == 2 ? Nq * n + N : n));
+        const long long o = node * ld + k;
+        const double h = q[o], u = q[plane + o] / h, v = q[2 * plane + o] / h;
+        const double fsc = fgeo ? fgeo[(2LL * NFN + fn) * ld + k] : ageo[(12 + f) * ld + k];
+        const double val = fabs(fsc) * (sqrt(u * u + v * v) + sqrt(g * h));
+        if (val != val) bad = true;
+        mx = fmax(mx, val);
+    }
+    __shared__ double smax[256];
+    __shared__ int sBad;
+    if (threadIdx.x == 0) sBad = 0;
+    __syncthreads();
+    if (bad) sBad = 1;
+    smax[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (static_cast<int>(threadIdx.x) < s) smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = sBad ? __builtin_nan("") : smax[0];
+}
+
 } // namespace
 
 struct bdg_sw2dq {
     int N = 0, Np = 0, Nfp = 0, NFN = 0, K = 0, device = 0;
+    int fields = 3;           // 4: the tracer plane hN and sw2d_quad4_stage_kernel
+    bool hasSources = false;  // bdg_sw2dq_set_sources
+    bool evaluated = false;   // a stage kernel has been launched: the sources are fixed from then on
+    double fconst = 0.0, CD = 0.0;
+    DevBuf<double> zx, zy, fcor;
     long long ld = 0;
     double g = 9.81;
     bool general = true, hasFilter = false;
@@ -119,6 +176,12 @@ struct bdg_sw2dq {
     }
     void launch(int mode, bool filter, const QuadParams& p) { launchOn(mode, filter, p, stream); }
     void launchOn(int mode, bool filter, const QuadParams& p, hipStream_t on) {
+        evaluated = true;
+        if (fields == 4) {
+            const Quad4Params p4{p, zx.p, zy.p, fcor.p, fconst, CD};
+            hipCheck(sw2d_quad4_stage(N, mode, filter, general, hasSources, p4, on), "sw2d_quad4_stage_kernel launch");
+            return;
+        }
         hipCheck(sw2d_quad_stage(N, mode, filter, general, p, on), "sw2d_quad_stage_kernel launch");
     }
     void rk2Step(double dt, bool filter) {
@@ -162,8 +225,25 @@ struct bdg_sw2dq {
         if (v[1] > 0 || v[0] > 1e8) throw unstable_error("A numerical instability has occurred!");
     }
 
+    // max over the face nodes of the columns [0, count) of |Fscale| (|u| + sqrt(g h)); NaN if any value is NaN
+    double maxFaceSpeed(int count) {
+        hipLaunchKernelGGL(sw2d_quad_dt_kernel, dim3(kHmaxBlocks), dim3(256), 0, stream, q.p, general ? fgeo.p : nullptr, ageo.p, ld,
+                           N, count, g, partials.p);
+        hipCheck(hipGetLastError(), "sw2d_quad_dt_kernel launch");
+        hostPartials.resize(2 * kHmaxBlocks);
+        hipCheck(hipMemcpyAsync(hostPartials.data(), partials.p, kHmaxBlocks * sizeof(double), hipMemcpyDeviceToHost, stream),
+                 "hipMemcpy (partials)");
+        hipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        double m = 0.0;
+        for (int b = 0; b < kHmaxBlocks; ++b) {
+            if (std::isnan(hostPartials[b])) return hostPartials[b];
+            m = std::max(m, hostPartials[b]);
+        }
+        return m;
+    }
+
     // ---- partitioned runs
-    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, 3 * Np, K, on); }
+    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, fields * Np, K, on); }
     // one evaluation of the elements [kBegin, kEnd) on `on`
     void evaluateRange(int mode, bool filter, QuadParams p, int kBegin, int kEnd, hipStream_t on) {
         p.kBegin = kBegin; p.kEnd = kEnd;
@@ -235,6 +315,13 @@ void requireSolver(const bdg_sw2dq* s, const char* fn) {
     if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
 }
 
+// the three-field calls are for three-field solvers and the *4 calls for four-field ones
+void requireFields(const bdg_sw2dq* s, int fields, const char* fn) {
+    if (s->fields != fields)
+        throw arg_error(std::string(fn) + ": the solver was created with " + std::to_string(s->fields) + " fields; use " +
+                        (s->fields == 4 ? "the *4 calls (h, hu, hv, hN)" : "the three-field calls (h, hu, hv)"));
+}
+
 double maxAbs(const double* a, size_t n) {
     double m = 0.0;
     for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(a[i]));
@@ -283,8 +370,9 @@ std::vector<double> tensorFactors(int N, const double* Dr, const double* Ds, con
     return ops;
 }
 
-bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d) {
+bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
     const int N = d.order, K = d.num_elements;
+    if (fields != 3 && fields != 4) throw arg_error("bdg_sw2dq_create: num_fields must be 3 or 4");
     if (N < 1 || N > BDG_SW2DQ_MAX_ORDER)
         throw arg_error("bdg_sw2dq_create: order " + std::to_string(N) + " is outside 1.." + std::to_string(BDG_SW2DQ_MAX_ORDER));
     if (K < 1) throw arg_error("bdg_sw2dq_create: num_elements < 1");
@@ -306,7 +394,7 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d) {
     }
 
     std::unique_ptr<bdg_sw2dq> s(new bdg_sw2dq());
-    s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->g = d.g; s->device = d.device;
+    s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->g = d.g; s->device = d.device; s->fields = fields;
     s->ld = (static_cast<long long>(K) + 63) / 64 * 64;
     const long long ld = s->ld;
 
@@ -368,9 +456,9 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d) {
     s->use();
     hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
     const long long plane = s->plane();
-    s->q.alloc(3 * plane, s->bytes, s->stream);
-    s->q1.alloc(3 * plane, s->bytes, s->stream);
-    s->res.alloc(3 * plane, s->bytes, s->stream);
+    s->q.alloc(fields * plane, s->bytes, s->stream);
+    s->q1.alloc(fields * plane, s->bytes, s->stream);
+    s->res.alloc(fields * plane, s->bytes, s->stream);
     s->gidx.alloc(gi.size(), s->bytes);
     hipCheck(hipMemcpyAsync(s->gidx.p, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "hipMemcpy (gidx)");
     s->ops.alloc(opsHost.size(), s->bytes);
@@ -407,11 +495,23 @@ extern "C" {
 int bdg_sw2dq_create(const bdg_sw2dq_desc* desc, bdg_sw2dq** out) {
     return guard([&] {
         if (!desc || !out) throw arg_error("bdg_sw2dq_create: NULL argument");
-        *out = createQuad(*desc);
+        *out = createQuad(*desc, 3);
+    });
+}
+
+int bdg_sw2dq_create_fields(const bdg_sw2dq_desc* desc, int num_fields, bdg_sw2dq** out) {
+    return guard([&] {
+        if (!desc || !out) throw arg_error("bdg_sw2dq_create_fields: NULL argument");
+        *out = createQuad(*desc, num_fields);
     });
 }
 
 int bdg_sw2dq_create_from_nodes(const bdg_quadnodes* nodes, double g, int device, int flags, bdg_sw2dq** out) {
+    return bdg_sw2dq_create_from_nodes_fields(nodes, g, device, flags, 3, out);
+}
+
+int bdg_sw2dq_create_from_nodes_fields(const bdg_quadnodes* nodes, double g, int device, int flags, int num_fields,
+                                       bdg_sw2dq** out) {
     return guard([&] {
         if (!nodes || !out) throw arg_error("bdg_sw2dq_create_from_nodes: NULL argument");
         const blitzdg::QuadNodesProvisioner& p = nodes->prov;
@@ -427,7 +527,7 @@ int bdg_sw2dq_create_from_nodes(const bdg_quadnodes* nodes, double g, int device
         const auto it = bc.find(blitzdg::BCTag::Wall);
         if (it != bc.end()) { d.mapW = it->second.data(); d.num_wall = static_cast<int>(it->second.size()); }
         d.g = g; d.device = device; d.flags = flags;
-        *out = createQuad(d);
+        *out = createQuad(d, num_fields);
     });
 }
 
@@ -436,6 +536,7 @@ void bdg_sw2dq_destroy(bdg_sw2dq* s) { delete s; }
 int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const double* hv) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_state");
+        requireFields(s, 3, "bdg_sw2dq_set_state");
         if (!h || !hu || !hv) throw arg_error("bdg_sw2dq_set_state: NULL field");
         s->use();
         const long long plane = s->plane();
@@ -451,6 +552,7 @@ int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const d
 int bdg_sw2dq_get_state(bdg_sw2dq* s, double* h, double* hu, double* hv) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_get_state");
+        requireFields(s, 3, "bdg_sw2dq_get_state");
         s->use();
         const long long plane = s->plane();
         if (h) s->download(h, s->q.p, s->Np);
@@ -464,6 +566,7 @@ int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double*
                   double* rhs3, int filter) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_rhs");
+        requireFields(s, 3, "bdg_sw2dq_rhs");
         if (!h || !hu || !hv || !rhs1 || !rhs2 || !rhs3) throw arg_error("bdg_sw2dq_rhs: NULL argument");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_rhs: filter requested but the solver has no Filter");
         s->use();
@@ -482,6 +585,108 @@ int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double*
         s->download(rhs2, s->ioOut.p + plane, s->Np);
         s->download(rhs3, s->ioOut.p + 2 * plane, s->Np);
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_num_fields(const bdg_sw2dq* s) { return s ? s->fields : -1; }
+
+int bdg_sw2dq_set_sources(bdg_sw2dq* s, const double* zx, const double* zy, double f_scalar, const double* f_array, double CD) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_set_sources");
+        requireFields(s, 4, "bdg_sw2dq_set_sources");
+        if (s->evaluated)
+            throw arg_error("bdg_sw2dq_set_sources: the solver has evaluated a right-hand side already; sources are set before the "
+                            "first evaluation");
+        if (!zx || !zy) throw arg_error("bdg_sw2dq_set_sources: zx / zy is NULL");
+        s->use();
+        const long long plane = s->plane();
+        s->zx.alloc(plane, s->bytes, s->stream);
+        s->zy.alloc(plane, s->bytes, s->stream);
+        s->upload(s->zx.p, zx, s->Np);
+        s->upload(s->zy.p, zy, s->Np);
+        if (f_array) {
+            s->fcor.alloc(plane, s->bytes, s->stream);
+            s->upload(s->fcor.p, f_array, s->Np);
+        } else if (s->fcor.p) {
+            s->fcor.alloc(0, s->bytes);
+        }
+        s->fconst = f_scalar;
+        s->CD = CD;
+        s->hasSources = true;
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_set_state4");
+        requireFields(s, 4, "bdg_sw2dq_set_state4");
+        if (!h || !hu || !hv || !hN) throw arg_error("bdg_sw2dq_set_state4: NULL field");
+        s->use();
+        const long long plane = s->plane();
+        const double* in[4] = {h, hu, hv, hN};
+        for (int c = 0; c < 4; ++c) s->upload(s->q.p + c * plane, in[c], s->Np);
+        s->res.zero(s->stream);
+        s->stageCount = 0;
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_get_state4(bdg_sw2dq* s, double* h, double* hu, double* hv, double* hN) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_get_state4");
+        requireFields(s, 4, "bdg_sw2dq_get_state4");
+        s->use();
+        const long long plane = s->plane();
+        double* out[4] = {h, hu, hv, hN};
+        for (int c = 0; c < 4; ++c)
+            if (out[c]) s->download(out[c], s->q.p + c * plane, s->Np);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_rhs4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN, double* rhs1, double* rhs2,
+                   double* rhs3, double* rhs4, int filter) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_rhs4");
+        requireFields(s, 4, "bdg_sw2dq_rhs4");
+        if (!h || !hu || !hv || !hN || !rhs1 || !rhs2 || !rhs3 || !rhs4) throw arg_error("bdg_sw2dq_rhs4: NULL argument");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_rhs4: filter requested but the solver has no Filter");
+        s->use();
+        const long long plane = s->plane();
+        if (!s->io.p) {
+            s->io.alloc(4 * plane, s->bytes, s->stream);
+            s->ioOut.alloc(4 * plane, s->bytes, s->stream);
+        }
+        const double* in[4] = {h, hu, hv, hN};
+        double* out[4] = {rhs1, rhs2, rhs3, rhs4};
+        for (int c = 0; c < 4; ++c) s->upload(s->io.p + c * plane, in[c], s->Np);
+        QuadParams p = s->params();
+        p.qin = s->io.p; p.rhs = s->ioOut.p;
+        s->launch(QMODE_RHS, filter != 0, p);
+        for (int c = 0; c < 4; ++c) s->download(out[c], s->ioOut.p + c * plane, s->Np);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_compute_dt(bdg_sw2dq* s, double cfl, double* dt, double* speed) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_compute_dt");
+        s->use();
+        const bool collective = s->halo.comm != nullptr;
+        double m = s->maxFaceSpeed(collective ? s->part.numOwned : s->K);
+        if (collective) { // NaN does not survive a max-reduction reliably: send it as +inf
+            double v[2] = {std::isnan(m) ? std::numeric_limits<double>::infinity() : m, 0.0};
+            hipCheck(hipMemcpyAsync(s->halo.scalarBuf.p, v, sizeof(v), hipMemcpyHostToDevice, s->stream), "hipMemcpy (compute_dt)");
+            bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(s->halo.scalarBuf.p, s->halo.scalarBuf.p, 2, ncclDouble, ncclMax,
+                                                           s->halo.comm, s->stream), "ncclAllReduce");
+            hipCheck(hipMemcpyAsync(v, s->halo.scalarBuf.p, sizeof(v), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (compute_dt)");
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+            m = v[0];
+        }
+        if (speed) *speed = m;
+        if (dt) *dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * m);
+        if (std::isnan(m) || std::isinf(m)) throw unstable_error("A numerical instability has occurred!");
     });
 }
 
@@ -553,7 +758,7 @@ int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_comm_init");
         s->use();
-        bdg_halo::commInit("bdg_sw2dq", s->halo, s->part, s->chains, s->K, static_cast<size_t>(3) * s->Np, rank, world, unique_id,
+        bdg_halo::commInit("bdg_sw2dq", s->halo, s->part, s->chains, s->K, static_cast<size_t>(s->fields) * s->Np, rank, world, unique_id,
                            peer_ranks, send_start, send_count, recv_start, recv_count, num_peers, s->bytes, s->stream);
     });
 }

@@ -1,6 +1,7 @@
 // One polynomial order of the quadrilateral sw2d kernel (compiled once per order with -DBDG_ORDER=N, as
-// sw2d_order.hip): every (mode, filter, geometry form) instance of sw2d_quad_stage_kernel<N>.
-#include "sw2d_quad_kernel.hpp"
+// sw2d_order.hip): every (mode, filter, geometry form) instance of sw2d_quad_stage_kernel<N>, and every
+// (mode, filter, geometry form, sources) instance of the four-field sw2d_quad4_stage_kernel<N>.
+#include "sw2d_quad4_kernel.hpp"
 
 #ifndef BDG_ORDER
 #error "compile with -DBDG_ORDER=N"
@@ -34,6 +35,43 @@ hipError_t sw2d_quad_launch<BDG_ORDER>(int mode, bool filter, bool general, cons
     case QMODE_LSERK:
         if (filter) return hipErrorInvalidValue; // LSERK4 stages are unfiltered
         return launchForm<N, QMODE_LSERK, false>(general, p, stream);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+namespace {
+template <int N, int MODE, bool FILT>
+hipError_t launchForm4(bool general, bool sources, const Quad4Params& p, hipStream_t stream) {
+    using Q = Quad4Elem<N>;
+    if (p.q.kEnd <= p.q.kBegin) return hipSuccess;
+    const dim3 grid((p.q.kEnd - p.q.kBegin + Q::E - 1) / Q::E), block(Q::THREADS);
+    if (general && sources)
+        hipLaunchKernelGGL((sw2d_quad4_stage_kernel<N, MODE, FILT, true, true>), grid, block, 0, stream, p);
+    else if (general)
+        hipLaunchKernelGGL((sw2d_quad4_stage_kernel<N, MODE, FILT, true, false>), grid, block, 0, stream, p);
+    else if (sources)
+        hipLaunchKernelGGL((sw2d_quad4_stage_kernel<N, MODE, FILT, false, true>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((sw2d_quad4_stage_kernel<N, MODE, FILT, false, false>), grid, block, 0, stream, p);
+    return hipGetLastError();
+}
+} // namespace
+
+template <>
+hipError_t sw2d_quad4_launch<BDG_ORDER>(int mode, bool filter, bool general, bool sources, const Quad4Params& p,
+                                        hipStream_t stream) {
+    constexpr int N = BDG_ORDER;
+    switch (mode) {
+    case QMODE_RHS:
+        return filter ? launchForm4<N, QMODE_RHS, true>(general, sources, p, stream)
+                      : launchForm4<N, QMODE_RHS, false>(general, sources, p, stream);
+    case QMODE_COMBINE:
+        return filter ? launchForm4<N, QMODE_COMBINE, true>(general, sources, p, stream)
+                      : launchForm4<N, QMODE_COMBINE, false>(general, sources, p, stream);
+    case QMODE_LSERK:
+        if (filter) return hipErrorInvalidValue; // LSERK4 stages are unfiltered
+        return launchForm4<N, QMODE_LSERK, false>(general, sources, p, stream);
     default:
         return hipErrorInvalidValue;
     }

@@ -3,15 +3,17 @@
 ``sw2dComputeRHS(h, hu, hv, g, H, ctx)`` is a drop-in for the script's function (sw2dquads.py:24-133: same signature,
 three (Np, K) arrays out; ``H`` is accepted and unused, as there). ``Sw2dQuadSolver`` keeps the state resident in HBM
 and runs the script's midpoint-RK2 + filter loop body (:183-213) and LSERK4 stages. ``NativeDistributedSw2dQuad`` runs the
-same on an element partition, one process per GPU, with the ghost exchange over RCCL. Everything here calls the HIP
-library (bdg_sw2dq_*); there is no CPU implementation behind it.
+same on an element partition, one process per GPU, with the ghost exchange over RCCL. ``fields=4`` adds the passive tracer
+hN and, with ``sources``, the Coriolis / drag / bed-slope terms of the reference's ``swhelpers.rhs.sw2dComputeRHS``
+(rhs.py:178-311), whose arithmetic a four-field solver follows. Everything here calls the HIP library (bdg_sw2dq_*); there
+is no CPU implementation behind it.
 """
 import weakref
 
 import numpy as np
 
 from . import _capi as C
-from ._capi import byref, c_float, c_void_p, check, lib
+from ._capi import byref, c_double, c_float, c_void_p, check, lib
 
 GENERAL_GEOMETRY = C.BDG_SW2DQ_GENERAL_GEOMETRY
 
@@ -19,13 +21,22 @@ GENERAL_GEOMETRY = C.BDG_SW2DQ_GENERAL_GEOMETRY
 class Sw2dQuadSolver:
     """Device-resident quadrilateral shallow-water DG solver (one HIP device, one stream)."""
 
-    def __init__(self, nodes=None, g=9.81, device=0, flags=0, tables=None):
+    def __init__(self, nodes=None, g=9.81, device=0, flags=0, tables=None, fields=3, sources=None):
         """Create from a ``pyblitzdg.QuadNodesProvisioner`` (``nodes``) or from a dict of host tables (``tables``:
         order, Dr, Ds, Lift, rx, sx, ry, sy, nx, ny, Fscale, vmapP, mapW and optionally vmapM, Filter).
-        ``flags=GENERAL_GEOMETRY`` forces the per-node geometry form even on parallelograms."""
+        ``flags=GENERAL_GEOMETRY`` forces the per-node geometry form even on parallelograms.
+
+        ``fields=4`` adds the passive tracer hN (setState4 / getState4 / computeRHS4); ``sources=dict(zx=, zy=, f=, CD=)``
+        switches on the bed-slope (``zx, zy``: (Np, K)), Coriolis (``f``: scalar or (Np, K)) and drag (``CD``: scalar) terms of
+        the reference's Python RHS (swhelpers/rhs.py:300-309) and needs ``fields=4``. A missing entry is zero."""
         h = c_void_p()
+        self.fields = int(fields)
+        if self.fields not in (3, 4):
+            raise ValueError("fields must be 3 or 4")
+        if sources is not None and self.fields != 4:
+            raise ValueError("sources need fields=4")
         if nodes is not None:
-            check(lib.bdg_sw2dq_create_from_nodes(nodes._h, float(g), int(device), int(flags), byref(h)))
+            check(lib.bdg_sw2dq_create_from_nodes_fields(nodes._h, float(g), int(device), int(flags), self.fields, byref(h)))
             self.order, self.Np, self.Nfp, self.K = nodes._dims()
         elif tables is not None:
             t = dict(tables)
@@ -54,17 +65,36 @@ class Sw2dQuadSolver:
                             C.ptr(a["nx"]), C.ptr(a["ny"]), C.ptr(a["Fscale"]), C.ptr(vmapM),
                             C.ptr(a["vmapP"]), C.ptr(a["mapW"]) if a["mapW"].size else None, a["mapW"].size,
                             float(g), int(device), int(flags))
-            check(lib.bdg_sw2dq_create(byref(d), byref(h)))
+            check(lib.bdg_sw2dq_create_fields(byref(d), self.fields, byref(h)))
             self.order, self.Np, self.Nfp, self.K = order, Np, order + 1, K
         else:
             raise ValueError("Sw2dQuadSolver needs `nodes` or `tables`")
         self._h = h
         self.g = float(g)
         self._finalizer = weakref.finalize(self, lib.bdg_sw2dq_destroy, h)
+        if sources is not None:
+            try:
+                self.setSources(**dict(sources))
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         self._finalizer()
         self._h = None
+
+    def setSources(self, zx=None, zy=None, f=0.0, CD=0.0):
+        """Bed slope, Coriolis and drag of a four-field solver; before its first evaluation only (the library refuses a
+        later call). Wrong shapes raise ValueError."""
+        shape = (self.Np, self.K)
+        zx = np.zeros(shape) if zx is None else C.as_f64(zx, shape, "zx")
+        zy = np.zeros(shape) if zy is None else C.as_f64(zy, shape, "zy")
+        f = 0.0 if f is None else f
+        farr = None if np.ndim(f) == 0 else C.as_f64(f, shape, "f")
+        if np.ndim(CD) != 0:
+            raise ValueError("CD: expected a scalar")
+        check(lib.bdg_sw2dq_set_sources(self._h, C.ptr(zx), C.ptr(zy), 0.0 if farr is not None else float(f), C.ptr(farr),
+                                        float(CD)))
 
     def _field(self, a, name):
         return C.as_f64(a, (self.Np, self.K), name)
@@ -85,6 +115,30 @@ class Sw2dQuadSolver:
         out = [np.empty((self.Np, self.K)) for _ in range(3)]
         check(lib.bdg_sw2dq_rhs(self._h, C.ptr(h), C.ptr(hu), C.ptr(hv), *[C.ptr(o) for o in out], int(bool(filter))))
         return tuple(out)
+
+    def setState4(self, h, hu, hv, hN):
+        f = [self._field(a, n) for a, n in zip((h, hu, hv, hN), ("h", "hu", "hv", "hN"))]
+        check(lib.bdg_sw2dq_set_state4(self._h, *[C.ptr(a) for a in f]))
+
+    def getState4(self):
+        out = [np.empty((self.Np, self.K)) for _ in range(4)]
+        check(lib.bdg_sw2dq_get_state4(self._h, *[C.ptr(o) for o in out]))
+        return tuple(out)
+
+    def computeRHS4(self, h, hu, hv, hN, filter=False):
+        """(RHS1, RHS2, RHS3, RHS4) of the reference's swhelpers.rhs.sw2dComputeRHS with this solver's sources;
+        ``filter=True`` returns Filter @ RHS."""
+        f = [self._field(a, n) for a, n in zip((h, hu, hv, hN), ("h", "hu", "hv", "hN"))]
+        out = [np.empty((self.Np, self.K)) for _ in range(4)]
+        check(lib.bdg_sw2dq_rhs4(self._h, *[C.ptr(a) for a in f], *[C.ptr(o) for o in out], int(bool(filter))))
+        return tuple(out)
+
+    def computeDt(self, CFL):
+        """(dt, speed) from the resident state: dt = CFL / ((N+1)^2 * 0.5 * speed), speed the face-node maximum of
+        |Fscale| (|u| + sqrt(g h)); on a partition the maximum over every rank. Raises NumericalInstability on NaN."""
+        dt, sp = c_double(), c_double()
+        check(lib.bdg_sw2dq_compute_dt(self._h, float(CFL), byref(dt), byref(sp)))
+        return dt.value, sp.value
 
     def stepRK2(self, dt, nsteps=1, filter=True):
         """``nsteps`` of the script's predictor / corrector; raises NumericalInstability if afterwards max|h| > 1e8
@@ -139,11 +193,14 @@ class NativeDistributedSw2dQuad:
     neighbour are evaluated beside the exchange (two streams), as in ``sw2d_curved.NativeDistributedSw2dCurved``. Rank 0's RCCL
     id reaches the others through ``halo.file_rendezvous`` (or pass ``unique_id``)."""
 
-    def __init__(self, plan, order, g=9.81, filter_args=None, device=0, flags=0, unique_id=None, loopback=False):
+    def __init__(self, plan, order, g=9.81, filter_args=None, device=0, flags=0, unique_id=None, loopback=False, fields=3,
+                 sources=None):
         """filter_args: (Nc, s) of QuadNodesProvisioner.buildFilter (the script's filter: (0.99 N, 4)); flags as
         Sw2dQuadSolver. loopback=True: this one process computes plan.rank's share of a plan.world-way split and every
         neighbour exchange is a send-to-self of the same size through the real transport (the ghosts then hold this rank's
-        own boundary elements: a rehearsal of the exchange on one GPU, not a partitioned result)."""
+        own boundary elements: a rehearsal of the exchange on one GPU, not a partitioned result). fields, sources as
+        Sw2dQuadSolver, the sources on the rank-local nodes (owned and ghost elements): a dict of arrays, or a function
+        (x, y) -> dict of the rank-local node coordinates."""
         from . import pyblitzdg as dg
         from .halo import attach_native, build_local_mesh
 
@@ -153,7 +210,11 @@ class NativeDistributedSw2dQuad:
         if filter_args is not None:
             self.nodes.buildFilter(*filter_args)
         self.filtered = filter_args is not None
-        self.solver = Sw2dQuadSolver(nodes=self.nodes, g=g, device=device, flags=flags)
+        self.fields = int(fields)
+        if callable(sources):
+            ctx = self.nodes.dgContext()
+            sources = sources(ctx.x, ctx.y)
+        self.solver = Sw2dQuadSolver(nodes=self.nodes, g=g, device=device, flags=flags, fields=fields, sources=sources)
         self.peer_table = attach_native(self.solver._h, "bdg_sw2dq", plan, unique_id, loopback)
 
     def close(self):
@@ -162,9 +223,17 @@ class NativeDistributedSw2dQuad:
             solver.close()
 
     def set_initial_state(self, fn):
-        """fn(x, y) -> (h, hu, hv) on the rank-local nodes (owned and ghost elements: the ghosts start current)."""
+        """fn(x, y) -> (h, hu, hv) (four fields: (h, hu, hv, hN)) on the rank-local nodes (owned and ghost elements: the
+        ghosts start current)."""
         ctx = self.nodes.dgContext()
-        self.solver.setState(*fn(ctx.x, ctx.y))
+        (self.solver.setState4 if self.fields == 4 else self.solver.setState)(*fn(ctx.x, ctx.y))
+
+    def _state(self):
+        return self.solver.getState4() if self.fields == 4 else self.solver.getState()
+
+    def compute_dt(self, CFL):
+        """(dt, speed) over every rank's owned elements (collective): the same values on every rank."""
+        return self.solver.computeDt(CFL)
 
     def step_rk2(self, dt, nsteps=1, filter=True):
         """The script's predictor / corrector, ghosts refreshed before each evaluation; every rank raises
@@ -176,19 +245,20 @@ class NativeDistributedSw2dQuad:
         check(lib.bdg_sw2dq_lserk4_stages_exchanged(self.solver._h, float(dt), int(nstages)))
 
     def owned_state(self):
-        """(global ids, h, hu, hv) of the owned elements."""
+        """(global ids, h, hu, hv) of the owned elements; with four fields (global ids, h, hu, hv, hN)."""
         n = self.plan.num_owned
-        return (self.plan.own_global,) + tuple(a[:, :n] for a in self.solver.getState())
+        return (self.plan.own_global,) + tuple(a[:, :n] for a in self._state())
 
-    def owned_mass(self):
-        """Integral of h over the owned elements: sum of w J h with w the tensor Gauss-Lobatto weights."""
+    def owned_mass(self, field=0):
+        """Integral of h (field=3: of the tracer hN) over the owned elements: sum of w J h with w the tensor Gauss-Lobatto
+        weights."""
         from . import pyblitzdg as dg
         ctx = self.nodes.dgContext()
         V1 = dg.VandermondeBuilder().buildVandermondeMatrix(ctx.s[:self.order + 1])[0]
         w1 = np.linalg.inv(V1 @ V1.T).sum(axis=1)          # 1-D Gauss-Lobatto mass-matrix row sums = weights
         w = np.outer(w1, w1).ravel()[:, None]              # node (N+1) j + i: w1[j] w1[i]
         n = self.plan.num_owned
-        return float((w * ctx.J[:, :n] * self.solver.getState()[0][:, :n]).sum())
+        return float((w * ctx.J[:, :n] * self._state()[field][:, :n]).sum())
 
     def barrier(self):
         check(lib.bdg_sw2dq_barrier(self.solver._h))

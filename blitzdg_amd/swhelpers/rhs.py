@@ -6,12 +6,14 @@ evaluated on the MI355X through the C ABI (4 fields: h, hu, hv and the tracer hN
 ``f`` (scalar or (Np, K)), drag ``CD``, bed slope ``zx, zy``). ``H`` is accepted and, as in the
 reference (rhs.py:207-210, eta is computed but unused), does not enter the result. ``ctx`` is any
 object with the DGContext2D attributes the reference function reads (BCmap, nx, ny, rx, sx, ry,
-sy, Dr, Ds, numFacePoints, numElements, numFaces, Lift, Fscale).
+sy, Dr, Ds, numFacePoints, numElements, numFaces, Lift, Fscale). The element family is read from ``ctx.numFaces``, as
+the reference function does (rhs.py:261-274): 3 runs the triangle solver, 4 the quadrilateral one.
 """
 import numpy as np
 
 from ..sw2d import Sw2dSolver
 from ..sw2d_curved import Sw2dCurvedSolver
+from ..sw2dquads import Sw2dQuadSolver
 
 _cache = {}
 _curved_cache = {}
@@ -50,11 +52,15 @@ def sw2dComputeRHS(h, hu, hv, hN, zx, zy, g, H, f, CD, ctx, vmapM, vmapP):
     key = _key(ctx, vmapM, vmapP, zx, zy, g, f, CD)
     entry = _cache.get(key)
     if entry is None:
+        faces = int(ctx.numFaces)
+        if faces not in (3, 4):
+            raise ValueError(f"sw2dComputeRHS: ctx.numFaces = {faces}; triangles (3) and quadrilaterals (4) are supported")
         Nfp = int(ctx.numFacePoints)
         tables = {"order": Nfp - 1, "Dr": ctx.Dr, "Ds": ctx.Ds, "Lift": ctx.Lift, "rx": ctx.rx, "sx": ctx.sx,
                   "ry": ctx.ry, "sy": ctx.sy, "nx": ctx.nx, "ny": ctx.ny, "Fscale": ctx.Fscale, "vmapM": vmapM,
                   "vmapP": vmapP, "mapW": np.asarray(ctx.BCmap.get(3, []), dtype=np.int32)}
-        solver = Sw2dSolver(tables=tables, g=g, fields=4, sources={"zx": zx, "zy": zy, "f": f, "CD": CD})
+        solver = (Sw2dSolver if faces == 3 else Sw2dQuadSolver)(tables=tables, g=g, fields=4,
+                                                                  sources={"zx": zx, "zy": zy, "f": f, "CD": CD})
         # keep the keyed objects alive so ids are not recycled while the entry exists
         entry = (solver, (ctx, vmapM, vmapP, zx, zy, f))
         if len(_cache) >= 8:

@@ -389,6 +389,27 @@ int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms);
 int bdg_sw2dq_synchronize(bdg_sw2dq* s);
 size_t bdg_sw2dq_device_bytes(const bdg_sw2dq* s);
 int bdg_sw2dq_uses_parallelogram_geometry(const bdg_sw2dq* s);
+/* Four fields and sources: the reference's Python right-hand side (swhelpers/rhs.py:178-311, fluxes of swhelpers/flux.py)
+ * on quadrilaterals: passive tracer hN as a fourth field, and optionally Coriolis f, quadratic drag CD and bed slope zx, zy
+ * (RHS2 += f hv - CD |u| u - g h zx; RHS3 -= f hu - CD |u| v; RHS3 -= g h zy, the reference's signs). num_fields is 3 (what
+ * bdg_sw2dq_create builds) or 4. A four-field solver is driven by the *4 calls below and by step_rk2, lserk4_stages, time,
+ * compute_dt and the partition calls (one exchanged record is then 4 Np doubles); the three-field set_state / get_state / rhs
+ * are refused on it with BDG_ERR_ARGUMENT, and the *4 calls and set_sources on a three-field solver. */
+int bdg_sw2dq_create_fields(const bdg_sw2dq_desc* desc, int num_fields, bdg_sw2dq** out);
+int bdg_sw2dq_create_from_nodes_fields(const bdg_quadnodes* nodes, double g, int device, int flags, int num_fields,
+                                       bdg_sw2dq** out);
+int bdg_sw2dq_num_fields(const bdg_sw2dq* s);
+/* zx, zy: (Np, K); Coriolis: f_array (Np, K), or f_scalar where f_array is NULL; CD scalar. Once, before the solver's first
+ * evaluation (rhs4, a step, a stage, a timing): afterwards BDG_ERR_ARGUMENT. A solver without this call compiles no source term. */
+int bdg_sw2dq_set_sources(bdg_sw2dq* s, const double* zx, const double* zy, double f_scalar, const double* f_array, double CD);
+int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN);
+int bdg_sw2dq_get_state4(bdg_sw2dq* s, double* h, double* hu, double* hv, double* hN);
+int bdg_sw2dq_rhs4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN, double* rhs1, double* rhs2,
+                   double* rhs3, double* rhs4, int filter);
+/* The drivers' time step from the resident state: dt = CFL / ((N+1)^2 * 0.5 * speed), speed = max over face nodes of
+ * |Fscale| (sqrt(u^2 + v^2) + sqrt(g h)) (a device reduction in IEEE-exact operations). Either kind of solver. After comm_init
+ * the maximum covers the owned elements and is all-reduced, so every rank gets the same dt. BDG_ERR_UNSTABLE on NaN. */
+int bdg_sw2dq_compute_dt(bdg_sw2dq* s, double cfl, double* dt, double* speed);
 /* Element-partitioned runs, as bdg_sw2d_curved_set_partition and friends (same argument order, refusals and error codes):
  * the solver's mesh is ordered [elements without a ghost neighbour: num_interior | partition-boundary elements: up to
  * num_owned | ghosts: up to K]; set_partition refuses (BDG_ERR_ARGUMENT) a bad range, an element of [0, num_interior) whose
@@ -396,7 +417,7 @@ int bdg_sw2dq_uses_parallelogram_geometry(const bdg_sw2dq* s);
 int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const int* send_elements, int num_send);
 /* The RCCL communicator (bdg_comm_unique_id) and the neighbour tables: peer i is sent the elements send_elements[send_start[i]
  * .. + send_count[i]) and its recv_count[i] elements arrive in ghost slots recv_start[i] .. (relative to num_owned); one record
- * of 3 Np doubles per element. Refused before set_partition, a second time, or with peer ranges that do not fit. */
+ * of 3 Np (four fields: 4 Np) doubles per element. Refused before set_partition, a second time, or with peer ranges that do not fit. */
 int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id, const int* peer_ranks, const int* send_start,
                         const int* send_count, const int* recv_start, const int* recv_count, int num_peers);
 /* one ghost refresh of the state (intermediate = 0) or of the RK2 intermediate / other LSERK4 buffer (1), on the solver's stream */

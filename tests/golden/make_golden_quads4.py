@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Generates the four-field quadrilateral fixtures under tests/golden/. Run in the BUILD container only (needs the
+reference checkout, as make_golden_quads.py); what it writes is plain data.
+
+  python tests/golden/make_golden_quads4.py
+
+Writes
+  sw2dq_rhs4_<case>.npz   a quadrangle mesh (EToV, Vert: THIS repo's MeshManager / QuadNodesProvisioner rebuild the tables
+                          from them), the order, g, seeded fields h, hu, hv, hN, the sources zx, zy, f, CD and the output
+                          rhs1..rhs4 of the REFERENCE's own swhelpers.rhs.sw2dComputeRHS (swhelpers/rhs.py:178-311),
+                          imported as it is (only the alias np.float = float, which NumPy removed, is set), evaluated on
+                          those quadrilateral tables: the function takes numFaces and numFacePoints from the context.
+Cases (meshes as make_golden_quads.py): coarse_box_quads_fine at N = 1..8; the jittered 5x4 box (general geometry) at
+N = 2, 5, 8; the shuffled 6x5 box (parallelograms) at N = 4, 7, all with tracer, Coriolis array, drag and bed slope as
+make_golden.py's sw2d_rhs4_* cases; scalarf_*: scalar f; nosrc_*: f = CD = 0, zx = zy = 0; regime_*: a state whose depth
+jumps across every face and whose flow is supercritical (|u| > sqrt(g h)), N = 3. h >= 1 everywhere.
+"""
+import os
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+REF = "/root/reference"
+sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+sys.dont_write_bytecode = True
+
+from make_golden import seeded_fields  # noqa: E402
+from make_golden_quads import box, mesh_tables  # noqa: E402
+
+
+def case(name, order, EToV, Vert, kind="full", seed=1):
+    import blitzdg_amd.pyblitzdg as dg
+    sys.path.insert(0, REF)
+    if not hasattr(np, "float"):
+        np.float = float  # swhelpers/rhs.py:262 uses the alias NumPy removed in 1.24
+    from swhelpers.rhs import sw2dComputeRHS  # the reference's own NumPy RHS
+
+    m = dg.MeshManager()
+    m.buildMesh(EToV, Vert)
+    nodes = dg.QuadNodesProvisioner(order, m)
+    ctx = nodes.dgContext()
+    x, y = ctx.x, ctx.y
+    Np, K = x.shape
+    rng = np.random.default_rng(seed)
+    g = 9.81
+    if kind == "regime":
+        h = np.repeat(rng.uniform(1.3, 3.0, (1, K)), Np, axis=0) + 0.05 * rng.standard_normal((Np, K))
+        hu = h * rng.choice([-1.0, 1.0], (1, K)) * rng.uniform(6.0, 9.0, (1, K))
+        hv = h * rng.choice([-1.0, 1.0], (1, K)) * rng.uniform(6.0, 9.0, (1, K))
+        assert (np.hypot(hu, hv) / h > np.sqrt(g * h)).all()
+    else:
+        h, hu, hv = seeded_fields(x, y, seed)
+    assert h.min() >= 1.0
+    hN = h * (1.0 + 0.3 * np.sin(2 * x) * np.cos(3 * y)) + 0.05 * rng.standard_normal(x.shape)
+    H = 10.0 - 0.5 * x + 0.25 * y * y
+    zx, zy = -0.5 + 0 * x, 0.5 * y
+    f = 1e-1 * (1.0 + 0.5 * y)
+    CD = 2.5e-2
+    if kind == "scalarf":
+        f = 0.1
+    elif kind == "nosrc":
+        zx, zy, f, CD = 0 * x, 0 * x, 0.0, 0.0
+    ref_ctx = types.SimpleNamespace(BCmap=ctx.BCmap, nx=ctx.nx, ny=ctx.ny, rx=ctx.rx, sx=ctx.sx, ry=ctx.ry, sy=ctx.sy,
+                                    Dr=ctx.Dr, Ds=ctx.Ds, numFacePoints=ctx.numFacePoints, numElements=ctx.numElements,
+                                    numFaces=ctx.numFaces, Lift=ctx.Lift, Fscale=ctx.Fscale)
+    assert ref_ctx.numFaces == 4
+    r = sw2dComputeRHS(h, hu, hv, hN, zx, zy, g, H, f, CD, ref_ctx, ctx.vmapM, ctx.vmapP)
+    assert all(np.all(np.isfinite(a)) for a in r)
+    path = os.path.join(HERE, f"sw2dq_rhs4_{name}.npz")
+    np.savez_compressed(path, EToV=m.elements.astype(np.int32), Vert=m.vertices[:, :2].copy(), order=order, g=g, h=h, hu=hu,
+                        hv=hv, hN=hN, zx=zx, zy=zy, f=f, CD=CD, rhs1=r[0], rhs2=r[1], rhs3=r[2], rhs4=r[3])
+    print(f"sw2dq_rhs4_{name}.npz: K={K} Np={Np} max|rhs|={[float('%.3e' % np.abs(a).max()) for a in r]} "
+          f"{os.path.getsize(path) / 1e3:.0f} kB")
+
+
+def main():
+    _, E, V = mesh_tables(path=os.path.join(HERE, "coarse_box_quads_fine.msh"))
+    for N in range(1, 9):
+        case(f"coarse_box_quads_fine_N{N}", N, E, V, seed=N)
+    Ej, Vj = box(5, 4, jitter=0.15, seed=3)
+    for N in (2, 5, 8):
+        case(f"jitter_box5x4_N{N}", N, Ej, Vj, seed=10 + N)
+    Es, Vs = box(6, 5, shuffle=True, seed=5)
+    for N in (4, 7):
+        case(f"box6x5_shuffled_N{N}", N, Es, Vs, seed=20 + N)
+    case("scalarf_jitter_box5x4_N4", 4, Ej, Vj, kind="scalarf", seed=41)
+    case("nosrc_box6x5_shuffled_N5", 5, Es, Vs, kind="nosrc", seed=42)
+    case("regime_coarse_box_quads_fine_N3", 3, E, V, kind="regime", seed=33)
+
+
+if __name__ == "__main__":
+    main()
