@@ -144,6 +144,10 @@ _SIGNATURES = {
     "bdg_trinodes_split_operators": (c_int, [_P, _P, _P]),
     "bdg_trinodes_split_elements": (c_int, [_P, _P, _P, _P, _P]),
     "bdg_trinodes_write_vtu": (c_int, [_P, c_char_p, _P, c_char_p]),
+    "bdg_quadnodes_split_count": (c_int, [_P]),
+    "bdg_quadnodes_split_operators": (c_int, [_P, _P, _P, _P]),
+    "bdg_quadnodes_split_elements": (c_int, [_P, _P, _P, _P, _P]),
+    "bdg_quadnodes_write_vtu": (c_int, [_P, c_char_p, _P, c_char_p]),
     "bdg_trinodes_build_gauss_face_nodes": (c_int, [_P, c_int, POINTER(_P)]),
     "bdg_gaussctx_destroy": (None, [_P]),
     "bdg_gaussctx_ngauss": (c_int, [_P]),
@@ -184,6 +188,7 @@ _SIGNATURES = {
     "bdg_sw2d_output_fields": (c_int, [_P, _P, _P, _P, _P]),
     "bdg_sw2d_output_tracer": (c_int, [_P, _P, _P]),
     "bdg_write_vtu_triangles": (c_int, [c_char_p, _P, _P, _P, c_int, c_char_p]),
+    "bdg_write_vtu_quads": (c_int, [c_char_p, _P, _P, _P, c_int, c_char_p]),
     "bdg_sw2d_rhs": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2d_set_state4": (c_int, [_P, _P, _P, _P, _P]),
     "bdg_sw2d_get_state4": (c_int, [_P, _P, _P, _P, _P]),
@@ -215,6 +220,8 @@ _SIGNATURES = {
     "bdg_sw2dq_get_state4": (c_int, [_P, _P, _P, _P, _P]),
     "bdg_sw2dq_rhs4": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2dq_compute_dt": (c_int, [_P, c_double, POINTER(c_double), POINTER(c_double)]),
+    "bdg_sw2dq_output_fields": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2dq_time_output": (c_int, [_P, _P, _P, c_int, POINTER(c_float)]),
     "bdg_sw2dq_set_partition": (c_int, [_P, c_int, c_int, _P, c_int]),
     "bdg_sw2dq_comm_init": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2dq_exchange": (c_int, [_P, c_int]),

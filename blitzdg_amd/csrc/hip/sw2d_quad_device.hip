@@ -5,9 +5,11 @@
 // Partitioned runs (bdg_sw2dq_set_partition / _comm_init) add the ghost exchange and the two-chain schedule of
 // partition_schedule.hpp on a second stream. A solver created with four fields (bdg_sw2dq_create_fields) launches
 // sw2d_quad4_stage_kernel (sw2d_quad4_kernel.hpp) instead, with the sources of bdg_sw2dq_set_sources if there are any.
+// The output step (bdg_sw2dq_output_fields) is one launch of sw2d_quad_output_kernel (sw2d_quad_output_kernel.hpp).
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_output_kernel.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "blitzdg/MeshManager.hpp"
 #include <algorithm>
@@ -51,6 +53,20 @@ hipError_t sw2d_quad4_stage(int order, int mode, bool filter, bool general, bool
     case 6: return sw2d_quad4_launch<6>(mode, filter, general, sources, p, stream);
     case 7: return sw2d_quad4_launch<7>(mode, filter, general, sources, p, stream);
     case 8: return sw2d_quad4_launch<8>(mode, filter, general, sources, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t sw2d_quad_output(int order, int fields, const QuadOutParams& p, hipStream_t stream) {
+    switch (order) {
+    case 1: return sw2d_quad_output_launch<1>(fields, p, stream);
+    case 2: return sw2d_quad_output_launch<2>(fields, p, stream);
+    case 3: return sw2d_quad_output_launch<3>(fields, p, stream);
+    case 4: return sw2d_quad_output_launch<4>(fields, p, stream);
+    case 5: return sw2d_quad_output_launch<5>(fields, p, stream);
+    case 6: return sw2d_quad_output_launch<6>(fields, p, stream);
+    case 7: return sw2d_quad_output_launch<7>(fields, p, stream);
+    case 8: return sw2d_quad_output_launch<8>(fields, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -147,6 +163,7 @@ struct bdg_sw2dq {
     size_t bytes = 0;
     long long stageCount = 0;
     DevBuf<double> q, q1, res, io, ioOut, geo, fgeo, ageo, ops, filt, partials;
+    DevBuf<double> outH, outI1; // output step: the caller's H and I1
     DevBuf<int> gidx;
     std::vector<double> hostPartials;
     // partitioned runs (bdg_sw2dq_set_partition / _comm_init): partition_schedule.hpp
@@ -240,6 +257,25 @@ struct bdg_sw2dq {
             m = std::max(m, hostPartials[b]);
         }
         return m;
+    }
+
+    // ---- output step: q1 is written whole by every step and stage before it is read, so between steps it is free and
+    // takes the output planes. Returns the number of columns computed (a partitioned run: the owned elements).
+    // staged = false: H and I1 are on the device already (a repeated launch).
+    int outputLaunch(const double* H, const double* lattice, int mask, bool staged = true) {
+        const int count = part.numOwned > 0 ? part.numOwned : K;
+        if (H && staged) {
+            if (!outH.p) outH.alloc(plane(), bytes, stream);
+            upload(outH.p, H, Np);
+        }
+        if (lattice && staged) {
+            if (!outI1.p) outI1.alloc(static_cast<size_t>(Nfp) * Nfp, bytes);
+            hipCheck(hipMemcpyAsync(outI1.p, lattice, static_cast<size_t>(Nfp) * Nfp * sizeof(double), hipMemcpyHostToDevice, stream),
+                     "hipMemcpy (I1)");
+        }
+        const QuadOutParams p{q.p, H ? outH.p : nullptr, lattice ? outI1.p : nullptr, q1.p, ld, count, mask};
+        hipCheck(sw2d_quad_output(N, fields, p, stream), "sw2d_quad_output_kernel launch");
+        return count;
     }
 
     // ---- partitioned runs
@@ -687,6 +723,47 @@ int bdg_sw2dq_compute_dt(bdg_sw2dq* s, double cfl, double* dt, double* speed) {
         if (speed) *speed = m;
         if (dt) *dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * m);
         if (std::isnan(m) || std::isinf(m)) throw unstable_error("A numerical instability has occurred!");
+    });
+}
+
+int bdg_sw2dq_output_fields(bdg_sw2dq* s, const double* H, const double* lattice, double* eta, double* u, double* v, double* N) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_output_fields");
+        if (N && s->fields != 4) throw arg_error("bdg_sw2dq_output_fields: N = hN / h needs a solver with four fields");
+        double* out[4] = {eta, u, v, N};
+        int mask = 0;
+        for (int c = 0; c < 4; ++c) mask |= out[c] ? 1 << c : 0;
+        if (!mask) return;
+        s->use();
+        const int count = s->outputLaunch(H, lattice, mask);
+        const long long plane = s->plane();
+        for (int c = 0; c < 4; ++c)
+            if (out[c]) // the columns [0, count) of each row
+                hipCheck(hipMemcpy2DAsync(out[c], s->K * sizeof(double), s->q1.p + c * plane, s->ld * sizeof(double),
+                                          count * sizeof(double), s->Np, hipMemcpyDeviceToHost, s->stream), "hipMemcpy2D (download)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_time_output(bdg_sw2dq* s, const double* H, const double* lattice, int count, float* ms) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_time_output");
+        if (!ms || count < 1) throw arg_error("bdg_sw2dq_time_output: bad argument");
+        s->use();
+        const int mask = (1 << s->fields) - 1;
+        s->outputLaunch(H, lattice, mask); // uploads H and I1; not timed
+        hipEvent_t a, b;
+        hipCheck(hipEventCreate(&a), "hipEventCreate");
+        hipCheck(hipEventCreate(&b), "hipEventCreate");
+        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
+        for (int i = 0; i < count; ++i) s->outputLaunch(H, lattice, mask, false);
+        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
+        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
+        float t = 0.0f;
+        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        *ms = t / count;
     });
 }
 

@@ -1,7 +1,9 @@
 // One polynomial order of the quadrilateral sw2d kernel (compiled once per order with -DBDG_ORDER=N, as
 // sw2d_order.hip): every (mode, filter, geometry form) instance of sw2d_quad_stage_kernel<N>, and every
-// (mode, filter, geometry form, sources) instance of the four-field sw2d_quad4_stage_kernel<N>.
+// (mode, filter, geometry form, sources) instance of the four-field sw2d_quad4_stage_kernel<N>; and the output step
+// sw2d_quad_output_kernel<N> for three and four fields, with and without the lattice interpolation.
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_output_kernel.hpp"
 
 #ifndef BDG_ORDER
 #error "compile with -DBDG_ORDER=N"
@@ -75,6 +77,27 @@ hipError_t sw2d_quad4_launch<BDG_ORDER>(int mode, bool filter, bool general, boo
     default:
         return hipErrorInvalidValue;
     }
+}
+
+namespace {
+template <int N, int NF>
+hipError_t launchOutput(const QuadOutParams& p, hipStream_t stream) {
+    if (p.kEnd <= 0) return hipSuccess;
+    const dim3 grid((p.kEnd + 63) / 64), block(64 * (N + 1));
+    if (p.I1)
+        hipLaunchKernelGGL((sw2d_quad_output_kernel<N, NF, true>), grid, block, 0, stream, p.q, p.H, p.I1, p.out, p.ld, p.kEnd, p.mask);
+    else
+        hipLaunchKernelGGL((sw2d_quad_output_kernel<N, NF, false>), grid, block, 0, stream, p.q, p.H, p.I1, p.out, p.ld, p.kEnd,
+                           p.mask);
+    return hipGetLastError();
+}
+} // namespace
+
+template <>
+hipError_t sw2d_quad_output_launch<BDG_ORDER>(int fields, const QuadOutParams& p, hipStream_t stream) {
+    if (fields == 3) return launchOutput<BDG_ORDER, 3>(p, stream);
+    if (fields == 4) return launchOutput<BDG_ORDER, 4>(p, stream);
+    return hipErrorInvalidValue;
 }
 
 } // namespace bdg_dev

@@ -293,6 +293,66 @@ int bdg_write_vtu_triangles(const char* path, const double* x, const double* y, 
     });
 }
 
+// ---- the same output step on quadrilaterals (reference QuadNodesProvisioner::splitElements + VtkOutputter's VTK_QUAD branch)
+int bdg_quadnodes_split_count(const bdg_quadnodes* nodes) {
+    if (!nodes) return -1;
+    const int N = nodes->prov.get_NOrder();
+    return N * N;
+}
+
+int bdg_quadnodes_split_operators(const bdg_quadnodes* nodes, double* IM, double* I1, int* local_quads) {
+    return guard([&] {
+        if (!nodes || !IM || !I1 || !local_quads) throw bdg_detail::arg_error("bdg_quadnodes_split_operators: NULL argument");
+        real_matrix_type im, i1;
+        std::vector<index_type> quads;
+        nodes->prov.splitOperators(im, i1, quads);
+        std::copy(im.data(), im.data() + static_cast<size_t>(im.rows()) * im.cols(), IM);
+        std::copy(i1.data(), i1.data() + static_cast<size_t>(i1.rows()) * i1.cols(), I1);
+        std::copy(quads.begin(), quads.end(), local_quads);
+    });
+}
+
+int bdg_quadnodes_split_elements(const bdg_quadnodes* nodes, const double* field, double* xnew, double* ynew,
+                                 double* fieldnew) {
+    return guard([&] {
+        if (!nodes || !field || !xnew || !ynew || !fieldnew) throw bdg_detail::arg_error("bdg_quadnodes_split_elements: NULL argument");
+        const auto& p = nodes->prov;
+        const int Np = p.get_NumLocalPoints(), K = p.get_NumElements();
+        real_matrix_type f(Np, K), xn, yn, fn;
+        std::copy(field, field + static_cast<size_t>(Np) * K, f.data());
+        p.splitElements(p.get_xGrid(), p.get_yGrid(), f, xn, yn, fn);
+        const size_t n = static_cast<size_t>(4) * xn.cols();
+        std::copy(xn.data(), xn.data() + n, xnew);
+        std::copy(yn.data(), yn.data() + n, ynew);
+        std::copy(fn.data(), fn.data() + n, fieldnew);
+    });
+}
+
+int bdg_quadnodes_write_vtu(const bdg_quadnodes* nodes, const char* path, const double* field, const char* field_name) {
+    return guard([&] {
+        if (!nodes || !path || !field || !field_name) throw bdg_detail::arg_error("bdg_quadnodes_write_vtu: NULL argument");
+        const auto& p = nodes->prov;
+        const int Np = p.get_NumLocalPoints(), K = p.get_NumElements();
+        real_matrix_type f(Np, K);
+        std::copy(field, field + static_cast<size_t>(Np) * K, f.data());
+        blitzdg::VtkOutputter(p).writeFieldToFile(path, f, field_name);
+    });
+}
+
+int bdg_write_vtu_quads(const char* path, const double* x, const double* y, const double* field, int num_quads,
+                        const char* field_name) {
+    return guard([&] {
+        if (!path || !x || !y || !field || !field_name || num_quads < 0)
+            throw bdg_detail::arg_error("bdg_write_vtu_quads: bad argument");
+        real_matrix_type xm(4, num_quads), ym(4, num_quads), fm(4, num_quads);
+        const size_t n = static_cast<size_t>(4) * num_quads;
+        std::copy(x, x + n, xm.data());
+        std::copy(y, y + n, ym.data());
+        std::copy(field, field + n, fm.data());
+        blitzdg::VtkOutputter::writeQuads(path, xm, ym, fm, field_name);
+    });
+}
+
 int bdg_trinodes_set_coordinates(bdg_trinodes* nodes, const double* x, const double* y) {
     return guard([&] {
         if (!nodes || !x || !y) throw bdg_detail::arg_error("bdg_trinodes_set_coordinates: NULL argument");

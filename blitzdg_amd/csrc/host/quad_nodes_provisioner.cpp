@@ -1,6 +1,7 @@
 // QuadNodesProvisioner implementation (setup path; CPU only). The tables follow the reference's
 // src/QuadNodesProvisioner.cpp conventions (nodes :230-243, Fmask :245-295, Vandermonde :72-89, bilinear map and
-// normals :277-447, coordinate-matched maps :449-560, filter :170-202); they are assembled from 1-D factors.
+// normals :277-447, coordinate-matched maps :449-560, filter :170-202, splitElements :721-838); they are assembled from
+// 1-D factors.
 #include "blitzdg/QuadNodesProvisioner.hpp"
 #include "parallel_for.hpp"
 #include <algorithm>
@@ -73,6 +74,69 @@ void QuadNodesProvisioner::computeInterpMatrix(const real_vector_type& rout, con
             for (index_type m = 0; m < Np; ++m) acc += Vout(a, m) * Vinv(m, b);
             IM(a, b) = acc;
         }
+}
+
+void QuadNodesProvisioner::splitOperators(real_matrix_type& IM, real_matrix_type& I1,
+                                          std::vector<index_type>& localE2V) const {
+    const index_type N = NOrder, Nq = N + 1, Np = NumLocalPoints;
+    real_vector_type rout(Np), sout(Np), equi(Nq);
+    for (index_type m = 0; m < Nq; ++m) equi(m) = -1.0 + 2.0 * static_cast<real_type>(m) / static_cast<real_type>(N);
+    for (index_type n = 0; n < Nq; ++n)
+        for (index_type m = 0; m < Nq; ++m) {
+            rout(n * Nq + m) = equi(m);
+            sout(n * Nq + m) = equi(n);
+        }
+    computeInterpMatrix(rout, sout, IM);
+    // I1 = V1(equispaced) V1^-1
+    VandermondeBuilders vb;
+    real_matrix_type Vequi(Nq, Nq), unused;
+    vb.computeVandermondeMatrix(equi, Vequi, unused, false);
+    I1.resize(Nq, Nq);
+    for (index_type a = 0; a < Nq; ++a)
+        for (index_type b = 0; b < Nq; ++b) {
+            real_type acc = 0;
+            for (index_type m = 0; m < Nq; ++m) acc += Vequi(a, m) * V1inv(m, b);
+            I1(a, b) = acc;
+        }
+    localE2V.clear();
+    for (index_type n = 0; n < N; ++n)
+        for (index_type m = 0; m < N; ++m)
+            localE2V.insert(localE2V.end(), {n * Nq + m, n * Nq + m + 1, (n + 1) * Nq + m, (n + 1) * Nq + m + 1});
+}
+
+void QuadNodesProvisioner::splitElements(const real_matrix_type& x, const real_matrix_type& y, const real_matrix_type& field,
+                                         real_matrix_type& xnew, real_matrix_type& ynew, real_matrix_type& fieldnew) const {
+    const index_type Np = field.rows(), K = field.cols();
+    if (Np != NumLocalPoints || x.rows() != Np || y.rows() != Np || x.cols() != K || y.cols() != K)
+        throw std::runtime_error("splitElements: x, y and field must be (Np, K)");
+    real_matrix_type IM, I1;
+    std::vector<index_type> quads;
+    splitOperators(IM, I1, quads);
+    const index_type nLocal = static_cast<index_type>(quads.size() / 4);
+    auto interpolate = [&](const real_matrix_type& f) { // (Np, Np) x (Np, K), K contiguous
+        real_matrix_type out(Np, K);
+        detail::parallelFor(Np, [&](index_type i) {
+            real_type* o = out.data() + static_cast<std::size_t>(i) * K;
+            for (index_type m = 0; m < Np; ++m) {
+                const real_type a = IM(i, m);
+                const real_type* src = f.data() + static_cast<std::size_t>(m) * K;
+                for (index_type k = 0; k < K; ++k) o[k] += a * src[k];
+            }
+        }, 1);
+        return out;
+    };
+    const real_matrix_type lx = interpolate(x), ly = interpolate(y), lf = interpolate(field);
+    xnew.resize(4, nLocal * K);
+    ynew.resize(4, nLocal * K);
+    fieldnew.resize(4, nLocal * K);
+    for (index_type k = 0; k < K; ++k)
+        for (index_type l = 0; l < nLocal; ++l)
+            for (index_type c = 0; c < 4; ++c) {
+                const index_type v = quads[4 * l + c], i = k * nLocal + l;
+                xnew(c, i) = lx(v, k);
+                ynew(c, i) = ly(v, k);
+                fieldnew(c, i) = lf(v, k);
+            }
 }
 
 void QuadNodesProvisioner::buildNodes() {

@@ -22,27 +22,27 @@ void appendBlock(std::ofstream& out, const std::vector<T>& data) {
     out.write(reinterpret_cast<const char*>(&bytes), sizeof(bytes));
     out.write(reinterpret_cast<const char*>(data.data()), static_cast<std::streamsize>(bytes));
 }
-} // namespace
 
-void VtkOutputter::writeTriangles(const std::string& fileName, const real_matrix_type& x, const real_matrix_type& y,
-                                  const real_matrix_type& field, const std::string& fieldName) {
-    const index_type nv = field.rows(), nc = field.cols();
-    if (nv != 3 || x.rows() != 3 || y.rows() != 3 || x.cols() != nc || y.cols() != nc)
-        throw std::runtime_error("VtkOutputter: expected (3, numTriangles) arrays");
-    const std::uint64_t numPoints = static_cast<std::uint64_t>(3) * nc, numCells = static_cast<std::uint64_t>(nc);
+// One cell per column of the (nv, numCells) arrays, every cell with its own nv points; the cell lists them in the order perm.
+void writeCells(const std::string& fileName, const real_matrix_type& x, const real_matrix_type& y, const real_matrix_type& field,
+                const std::string& fieldName, index_type nv, std::uint8_t cellType, const int* perm, const char* what) {
+    const index_type nc = field.cols();
+    if (field.rows() != nv || x.rows() != nv || y.rows() != nv || x.cols() != nc || y.cols() != nc)
+        throw std::runtime_error(std::string("VtkOutputter: expected ") + what + " arrays");
+    const std::uint64_t numPoints = static_cast<std::uint64_t>(nv) * nc, numCells = static_cast<std::uint64_t>(nc);
     std::vector<double> values(numPoints), points(3 * numPoints);
     std::vector<std::int64_t> conn(numPoints), offsets(numCells);
-    std::vector<std::uint8_t> types(numCells, 5); // VTK_TRIANGLE
+    std::vector<std::uint8_t> types(numCells, cellType);
     for (index_type k = 0; k < nc; ++k) {
-        for (index_type n = 0; n < 3; ++n) {
-            const std::uint64_t id = static_cast<std::uint64_t>(3) * k + n;
+        for (index_type n = 0; n < nv; ++n) {
+            const std::uint64_t id = static_cast<std::uint64_t>(nv) * k + n;
             values[id] = field(n, k);
             points[3 * id] = x(n, k);
             points[3 * id + 1] = y(n, k);
             points[3 * id + 2] = 0.0;
-            conn[id] = static_cast<std::int64_t>(id);
+            conn[id] = static_cast<std::int64_t>(static_cast<std::uint64_t>(nv) * k + perm[n]);
         }
-        offsets[k] = static_cast<std::int64_t>(3) * (k + 1);
+        offsets[k] = static_cast<std::int64_t>(nv) * (k + 1);
     }
     std::ofstream out(fileName, std::ios::binary);
     if (!out) throw std::runtime_error("VtkOutputter: cannot open " + fileName);
@@ -77,13 +77,39 @@ void VtkOutputter::writeTriangles(const std::string& fileName, const real_matrix
     if (!out) throw std::runtime_error("VtkOutputter: write failed for " + fileName);
 }
 
+} // namespace
+
+void VtkOutputter::writeTriangles(const std::string& fileName, const real_matrix_type& x, const real_matrix_type& y,
+                                  const real_matrix_type& field, const std::string& fieldName) {
+    static const int perm[3] = {0, 1, 2};
+    writeCells(fileName, x, y, field, fieldName, 3, 5, perm, "(3, numTriangles)"); // VTK_TRIANGLE
+}
+
+void VtkOutputter::writeQuads(const std::string& fileName, const real_matrix_type& x, const real_matrix_type& y,
+                              const real_matrix_type& field, const std::string& fieldName) {
+    static const int perm[4] = {0, 2, 3, 1}; // a closed loop around the quadrilateral
+    writeCells(fileName, x, y, field, fieldName, 4, 9, perm, "(4, numQuads)"); // VTK_QUAD
+}
+
 void VtkOutputter::writeFieldToFile(const std::string& fileName, const real_matrix_type& field,
                                     const std::string& fieldName) const {
-    const real_matrix_type& x = NodesProvisioner.get_xGrid();
-    const real_matrix_type& y = NodesProvisioner.get_yGrid();
-    if (NodesProvisioner.get_NOrder() > 1) { // higher order than linear: break up the triangles
+    if (QuadProvisioner) {
+        const real_matrix_type& x = QuadProvisioner->get_xGrid();
+        const real_matrix_type& y = QuadProvisioner->get_yGrid();
+        if (QuadProvisioner->get_NOrder() > 1) { // higher order than linear: break up the quadrilaterals
+            real_matrix_type xnew, ynew, fieldnew;
+            QuadProvisioner->splitElements(x, y, field, xnew, ynew, fieldnew);
+            writeQuads(fileName, xnew, ynew, fieldnew, fieldName);
+        } else {
+            writeQuads(fileName, x, y, field, fieldName);
+        }
+        return;
+    }
+    const real_matrix_type& x = NodesProvisioner->get_xGrid();
+    const real_matrix_type& y = NodesProvisioner->get_yGrid();
+    if (NodesProvisioner->get_NOrder() > 1) { // higher order than linear: break up the triangles
         real_matrix_type xnew, ynew, fieldnew;
-        NodesProvisioner.splitElements(x, y, field, xnew, ynew, fieldnew);
+        NodesProvisioner->splitElements(x, y, field, xnew, ynew, fieldnew);
         writeTriangles(fileName, xnew, ynew, fieldnew, fieldName);
     } else {
         writeTriangles(fileName, x, y, field, fieldName);

@@ -413,6 +413,26 @@ class QuadNodesProvisioner:
         check(lib.bdg_quadnodes_build_bchash(self._h, C.ptr(b), b.size))
         self._tables_version += 1
 
+    def splitElements(self, field):
+        """(xnew, ynew, fieldnew), each (4, N^2*K): the field on N^2 small quadrilaterals per element, corners
+        (n,m), (n,m+1), (n+1,m), (n+1,m+1) of the equispaced lattice (reference src/QuadNodesProvisioner.cpp:721-838)."""
+        _, Np, _, K = self._dims()
+        n = lib.bdg_quadnodes_split_count(self._h) * K
+        f = C.as_f64(field, (Np, K), "field")
+        out = [np.empty((4, n)) for _ in range(3)]
+        check(lib.bdg_quadnodes_split_elements(self._h, C.ptr(f), *[C.ptr(o) for o in out]))
+        return tuple(out)
+
+    def splitOperators(self):
+        """(IM, I1, quads): (Np, Np) interpolation to the equispaced lattice (point n (N+1) + m at r = -1 + 2m/N,
+        s = -1 + 2n/N); its 1-D factor (N+1, N+1), IM[n (N+1) + m, (N+1) j + i] = I1[m, j] I1[n, i]; and the (N^2, 4)
+        lattice-point indices of the small quadrilaterals."""
+        N, Np, _, _ = self._dims()
+        n = lib.bdg_quadnodes_split_count(self._h)
+        IM, I1, quads = np.empty((Np, Np)), np.empty((N + 1, N + 1)), np.empty((n, 4), dtype=np.int32)
+        check(lib.bdg_quadnodes_split_operators(self._h, C.ptr(IM), C.ptr(I1), C.ptr(quads)))
+        return IM, I1, quads
+
     def dgContext(self):
         return DGContext2D(self)
 
@@ -524,10 +544,12 @@ def burgers1dRun(N=6, K=40, xmin=-5.0, xmax=5.0, alpha=1.0, nu=0.1, c=0.5, CFL=0
 
 class VtkOutputter:
     """Writes nodal fields as *.vtu files for Paraview; names of the reference's binding
-    (src/pyblitzdg/pyblitzdg.cpp:189-192). No VTK library involved."""
+    (src/pyblitzdg/pyblitzdg.cpp:189-192). No VTK library involved. On a QuadNodesProvisioner the cells are
+    quadrilaterals (reference include/VtkOutputter.hpp:111-141)."""
 
     def __init__(self, TriangleNodesProvisioner):
         self._nodes = TriangleNodesProvisioner
+        self._quads = getattr(self._nodes, "_numFaces", 3) == 4
 
     @staticmethod
     def generateFileName(fieldName, fileNumber):
@@ -536,22 +558,58 @@ class VtkOutputter:
     def writeFieldToFile(self, fileName, field, fieldName):
         _, Np, _, K = self._nodes._dims()
         f = C.as_f64(field, (Np, K), "field")
-        check(lib.bdg_trinodes_write_vtu(self._nodes._h, str(fileName).encode(), C.ptr(f), str(fieldName).encode()))
+        write = lib.bdg_quadnodes_write_vtu if self._quads else lib.bdg_trinodes_write_vtu
+        check(write(self._nodes._h, str(fileName).encode(), C.ptr(f), str(fieldName).encode()))
 
     def writeFieldsToFiles(self, fields, tstep):
         for name, field in fields.items():
             self.writeFieldToFile(self.generateFileName(name, tstep), field, name)
 
     def splitNodes(self):
-        """Coordinates of the small triangles' corners, (3, K*N^2) each (third entry: zeros)."""
+        """Coordinates of the small cells' corners, (3, K*N^2) each on triangles, (4, K*N^2) on quadrilaterals (third entry:
+        zeros)."""
         _, Np, _, K = self._nodes._dims()
         return self._nodes.splitElements(np.zeros((Np, K)))
 
-    def writeSolverFields(self, solver, tstep, directory="."):
+    def _quadLattice(self):
+        """(I1 or None, cut, xq, yq): the device interpolates with I1, `cut` turns a (Np, K') lattice array into the (4, N^2 K')
+        corner array of the writer, xq, yq are the corners' coordinates. Order 1 is written unsplit."""
+        if not hasattr(self, "_lattice"):
+            order = self._nodes._dims()[0]
+            ctx = self._nodes.dgContext()
+            if order == 1:
+                self._lattice = (None, lambda a: a, ctx.x, ctx.y)
+            else:
+                _, I1, quads = self._nodes.splitOperators()
+                cut = lambda a: np.ascontiguousarray(a[quads.T, :].transpose(0, 2, 1).reshape(4, -1))  # noqa: E731
+                xq, yq, _ = self.splitNodes()                    # (4, K*N^2), element-major
+                self._lattice = (I1, cut, xq, yq)
+        return self._lattice
+
+    def _writeQuadSolverFields(self, solver, tstep, directory, H):
+        import os
+        I1, cut, xq, yq = self._quadLattice()
+        names = ("eta", "u", "v", "N")[:solver.fields]
+        paths = []
+        for name, lat in zip(names, solver.outputFields(H=H, lattice=I1 if I1 is not None else False)):
+            fq = cut(lat)
+            path = os.path.join(directory, self.generateFileName(name, tstep))
+            check(lib.bdg_write_vtu_quads(path.encode(), C.ptr(xq), C.ptr(yq), C.ptr(np.ascontiguousarray(fq)), fq.shape[1],
+                                          name.encode()))
+            paths.append(path)
+        return paths
+
+    def writeSolverFields(self, solver, tstep, directory=".", H=None):
         """eta, u, v of a device-resident ``sw2d.Sw2dSolver`` to ``<directory>/{eta,u,v}NNNNNNN.vtu``:
         primitive variables and lattice interpolation happen on the device, the host only cuts the
-        lattice into triangles and writes. Returns the file paths."""
+        lattice into triangles and writes. Returns the file paths. On a QuadNodesProvisioner ``solver`` is a
+        ``sw2dquads.Sw2dQuadSolver`` (one device launch for eta = h - H, u, v and, with four fields, N; the host cuts the
+        lattice into quadrilaterals); ``H`` is the still-water depth of that solver's eta (None: eta = h)."""
         import os
+        if self._quads:
+            return self._writeQuadSolverFields(solver, tstep, directory, H)
+        if H is not None:
+            raise ValueError("H: the triangle solver takes its bathymetry from setBathymetry")
         order, Np, _, K = self._nodes._dims()
         if not hasattr(self, "_lattice"):
             IM, tri = self._nodes.splitOperators()

@@ -70,6 +70,7 @@ class Sw2dQuadSolver:
         else:
             raise ValueError("Sw2dQuadSolver needs `nodes` or `tables`")
         self._h = h
+        self._nodes = nodes
         self.g = float(g)
         self._finalizer = weakref.finalize(self, lib.bdg_sw2dq_destroy, h)
         if sources is not None:
@@ -132,6 +133,38 @@ class Sw2dQuadSolver:
         out = [np.empty((self.Np, self.K)) for _ in range(4)]
         check(lib.bdg_sw2dq_rhs4(self._h, *[C.ptr(a) for a in f], *[C.ptr(o) for o in out], int(bool(filter))))
         return tuple(out)
+
+    def _lattice(self, lattice):
+        """None, or the (N+1, N+1) matrix I1 of QuadNodesProvisioner.splitOperators the device interpolates with."""
+        if lattice is None or lattice is False:
+            return None
+        if lattice is True:
+            if getattr(self, "_I1", None) is None:
+                if self._nodes is None:
+                    raise ValueError("lattice=True needs a solver created from `nodes`; pass I1 of splitOperators() instead")
+                self._I1 = self._nodes.splitOperators()[1]
+            return self._I1
+        return C.as_f64(lattice, (self.order + 1, self.order + 1), "lattice")
+
+    def outputFields(self, H=None, lattice=True):
+        """The drivers' output fields of the resident state, (eta, u, v) or with four fields (eta, u, v, N): eta = h - H
+        (h without ``H``), u = hu / h, v = hv / h, N = hN / h, each (Np, K), from one device launch. ``lattice=True``
+        interpolates them on the device to each element's equispaced lattice (what splitElements does before a *.vtu is
+        written; ``lattice`` may also be I1 of ``nodes.splitOperators()``), ``lattice=False`` returns nodal values. On a
+        partitioned solver only the owned elements' columns are computed; the others are zero."""
+        Hh = None if H is None else self._field(H, "H")
+        I1 = self._lattice(lattice)
+        out = [np.zeros((self.Np, self.K)) for _ in range(self.fields)]
+        ptrs = [C.ptr(o) for o in out] + [None] * (4 - self.fields)
+        check(lib.bdg_sw2dq_output_fields(self._h, C.ptr(Hh), C.ptr(I1), *ptrs))
+        return tuple(out)
+
+    def timeOutput(self, count, H=None, lattice=True):
+        """Average device milliseconds of the output launch (every field of the solver)."""
+        Hh = None if H is None else self._field(H, "H")
+        ms = c_float()
+        check(lib.bdg_sw2dq_time_output(self._h, C.ptr(Hh), C.ptr(self._lattice(lattice)), int(count), byref(ms)))
+        return ms.value
 
     def computeDt(self, CFL):
         """(dt, speed) from the resident state: dt = CFL / ((N+1)^2 * 0.5 * speed), speed the face-node maximum of
@@ -248,6 +281,44 @@ class NativeDistributedSw2dQuad:
         """(global ids, h, hu, hv) of the owned elements; with four fields (global ids, h, hu, hv, hN)."""
         n = self.plan.num_owned
         return (self.plan.own_global,) + tuple(a[:, :n] for a in self._state())
+
+    def output_fields(self, H=None, lattice=True):
+        """(global ids, eta, u, v) of the owned elements (four fields: (global ids, eta, u, v, N)), as
+        Sw2dQuadSolver.outputFields; ``H`` on the rank-local nodes. The ghosts are neither computed nor returned."""
+        n = self.plan.num_owned
+        return (self.plan.own_global,) + tuple(a[:, :n] for a in self.solver.outputFields(H=H, lattice=lattice))
+
+    def write_piece(self, tstep, directory=".", H=None):
+        """This rank's owned elements as ``<field><tstep, 7 digits>.<rank>.vtu`` for eta, u, v (and N); rank 0 also writes the
+        ``<field><tstep>.pvtu`` index that names every rank's piece. Returns the paths this rank wrote."""
+        import os
+        from . import pyblitzdg as dg
+        if getattr(self, "_outputter", None) is None:
+            self._outputter = dg.VtkOutputter(self.nodes)
+        I1, cut, xq, yq = self._outputter._quadLattice()
+        n, cells = self.plan.num_owned, (self.order * self.order if self.order > 1 else 1)
+        xq, yq = np.ascontiguousarray(xq[:, :n * cells]), np.ascontiguousarray(yq[:, :n * cells])
+        names = ("eta", "u", "v", "N")[:self.fields]
+        paths = []
+        for name, lat in zip(names, self.solver.outputFields(H=H, lattice=I1 if I1 is not None else False)):
+            fq = np.ascontiguousarray(cut(lat[:, :n]))
+            piece = f"{name}{int(tstep):07d}.{self.plan.rank}.vtu"
+            check(lib.bdg_write_vtu_quads(os.path.join(directory, piece).encode(), C.ptr(xq), C.ptr(yq), C.ptr(fq), fq.shape[1],
+                                          name.encode()))
+            paths.append(os.path.join(directory, piece))
+            if self.plan.rank == 0:
+                index = os.path.join(directory, f"{name}{int(tstep):07d}.pvtu")
+                with open(index, "w") as f:
+                    f.write('<?xml version="1.0"?>\n<VTKFile type="PUnstructuredGrid" version="1.0" byte_order="LittleEndian" '
+                            'header_type="UInt64">\n  <PUnstructuredGrid GhostLevel="0">\n'
+                            f'    <PPointData Scalars="{name}">\n      <PDataArray type="Float64" Name="{name}"/>\n'
+                            '    </PPointData>\n    <PPoints>\n      <PDataArray type="Float64" NumberOfComponents="3"/>\n'
+                            '    </PPoints>\n')
+                    for r in range(self.plan.world):
+                        f.write(f'    <Piece Source="{name}{int(tstep):07d}.{r}.vtu"/>\n')
+                    f.write('  </PUnstructuredGrid>\n</VTKFile>\n')
+                paths.append(index)
+        return paths
 
     def owned_mass(self, field=0):
         """Integral of h (field=3: of the tracer hN) over the owned elements: sum of w J h with w the tensor Gauss-Lobatto

@@ -2,7 +2,7 @@
 """The loop of examples/sw2d_quads.py on an element partition: one process per GPU, each owning a share of the mesh
 plus one layer of ghost elements, the ghosts refreshed by the library over RCCL before every evaluation.
 
-    RANK=r WORLD_SIZE=w python examples/sw2d_quads_partitioned.py [finalTime] [order] [box n]
+    RANK=r WORLD_SIZE=w python examples/sw2d_quads_partitioned.py [finalTime] [order] [box n] [outputDir]
 
 Rank and world come from RANK / WORLD_SIZE (LOCAL_RANK picks the GPU; default RANK), as bench.py --gpus passes them to
 its child processes; rank 0's RCCL id reaches the others through a private file (blitzdg_amd.halo.file_rendezvous), so
@@ -10,7 +10,9 @@ every rank must be a child of the same launcher. The script's set-up: coarse_box
 [-1, 1]^2 with a third argument), N = 4, the filter with Nc = 0.99 N and s = 4, a Gaussian hump of height 1 on still water
 of depth 10, dt = 0.45 * 0.000724295 (scaled with the element size on a box), g = 9.81; midpoint RK2 with the filter, 20
 steps per call, the blow-up check on every rank together. At the end rank 0 prints the global eta range and the relative
-mass drift (each rank leaves its four numbers in the rendezvous directory; rank 0 combines them).
+mass drift (each rank leaves its four numbers in the rendezvous directory; rank 0 combines them). With an output directory
+(box n = 0 keeps the Gmsh file) every rank writes its owned elements' eta, u, v as <field><step>.<rank>.vtu at step 0 and every
+20 steps, and rank 0 the <field><step>.pvtu index of the pieces.
 """
 import json
 import os
@@ -39,6 +41,7 @@ def main():
     finalTime = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     n = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    outdir = sys.argv[4] if len(sys.argv) > 4 else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = int(os.environ.get("LOCAL_RANK", rank))
     g, H = 9.81, 10.0
@@ -56,6 +59,11 @@ def main():
     d = NativeDistributedSw2dQuad(plan, N, g=g, filter_args=(0.99 * N, 4), device=device)
     d.set_initial_state(lambda x, y: (H + np.exp(-10 * x * x - 10 * y * y), np.zeros_like(x), np.zeros_like(x)))
     m0 = d.owned_mass()
+    Hloc = None
+    if outdir:
+        os.makedirs(outdir, exist_ok=True)
+        Hloc = H * np.ones_like(d.nodes.dgContext().x)
+        d.write_piece(0, outdir, H=Hloc)
     t, step, chunk = 0.0, 0, 20
     t0 = time.perf_counter()
     while t < finalTime:
@@ -63,6 +71,8 @@ def main():
         d.step_rk2(dt, k, filter=True)  # raises NumericalInstability on every rank together
         t += k * dt
         step += k
+        if outdir and step % 20 == 0:
+            d.write_piece(step, outdir, H=Hloc)
     d.barrier()
     wall = time.perf_counter() - t0
     _, h, _, _ = d.owned_state()

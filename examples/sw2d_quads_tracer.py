@@ -8,7 +8,8 @@ f-plane rotation and quadratic drag, on an n x m box of quadrangles with walls o
 Midpoint RK2 with the modal filter on every right-hand side; the time step is recomputed on the device every 10 steps
 (computeDt: dt = CFL / ((N+1)^2 / 2 * max |Fscale| (|u| + sqrt(g h)))) and shortened to end at finalTime. Water mass
 sum(w J h) and tracer mass sum(w J hN) are printed: the sources enter neither equation, so both hold to round-off. With an
-output directory the fields are written as .npy files (the .vtu writer is triangle-only).
+output directory the state is written as .npy files and h, u, v, N as *.vtu files (eta = h: no still-water depth is
+subtracted).
 """
 import os
 import sys
@@ -61,8 +62,10 @@ def main():
     solver = sw2dquads.Sw2dQuadSolver(nodes=nodes, g=g, fields=4, sources=sources)
     solver.setState4(*q)
     m0, n0 = (wJ * q[0]).sum(), (wJ * q[3]).sum()
+    outputter = None
     if outdir:
         os.makedirs(outdir, exist_ok=True)
+        outputter = dg.VtkOutputter(nodes)
     t, step, CFL = 0.0, 0, 0.5
     while t < finalTime:
         dt, speed = solver.computeDt(CFL)
@@ -77,6 +80,7 @@ def main():
               f"N in [{(hN / h).min():.4f}, {(hN / h).max():.4f}] water {abs(m1 - m0) / m0:.2e} tracer {abs(n1 - n0) / n0:.2e}")
         if outdir:
             np.save(os.path.join(outdir, f"state{step:07d}.npy"), np.stack([h, hu, hv, hN]))
+            outputter.writeSolverFields(solver, step, directory=outdir)
     assert abs(m1 - m0) <= 1e-12 * m0 and abs(n1 - n0) <= 1e-12 * n0, "mass is not conserved to round-off"
     return solver.getState4(), t
 

@@ -37,6 +37,16 @@ public:
                                       real_matrix_type& V2Dr, real_matrix_type& V2Ds) const;
     /// IM = V(rout, sout) Vinv: interpolation from the nodes to (rout, sout).
     void computeInterpMatrix(const real_vector_type& rout, const real_vector_type& sout, real_matrix_type& IM) const;
+    /// Output step (reference src/QuadNodesProvisioner.cpp:721-838): interpolate a nodal field to the equispaced
+    /// (N+1)^2 lattice of its element (point n (N+1) + m at r = -1 + 2m/N, s = -1 + 2n/N) and cut the element into N^2
+    /// small quadrilaterals with corners (n,m), (n,m+1), (n+1,m), (n+1,m+1); xnew, ynew, fieldnew become (4, N^2*K),
+    /// one column per small quadrilateral, element-major.
+    void splitElements(const real_matrix_type& x, const real_matrix_type& y, const real_matrix_type& field,
+                       real_matrix_type& xnew, real_matrix_type& ynew, real_matrix_type& fieldnew) const;
+    /// The pieces of splitElements: IM (Np, Np) from computeInterpMatrix; its 1-D factor I1 (N+1, N+1), the Lagrange
+    /// interpolation from the Gauss-Lobatto points to the equispaced ones (IM(n (N+1) + m, (N+1) j + i) = I1(m, j) I1(n, i));
+    /// and the local connectivity of the N^2 small quadrilaterals (lattice point indices, 4 per quadrilateral).
+    void splitOperators(real_matrix_type& IM, real_matrix_type& I1, std::vector<index_type>& localE2V) const;
 
     void buildNodes();
     void buildLift();

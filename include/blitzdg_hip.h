@@ -144,6 +144,21 @@ int bdg_trinodes_split_elements(const bdg_trinodes* nodes, const double* field, 
                                 double* fieldnew);
 int bdg_trinodes_write_vtu(const bdg_trinodes* nodes, const char* path, const double* field,
                            const char* field_name);
+/* The same on quadrilaterals (reference QuadNodesProvisioner::splitElements, src/QuadNodesProvisioner.cpp:721-838, and the
+ * VTK_QUAD branch of include/VtkOutputter.hpp:111-141). split_count = N^2 small quadrilaterals per element. split_operators: IM
+ * (Np, Np) interpolation to the equispaced lattice (point n (N+1) + m at r = -1 + 2m/N, s = -1 + 2n/N), its 1-D factor I1
+ * (N+1, N+1) (Gauss-Lobatto -> equispaced Lagrange interpolation; IM(n (N+1) + m, (N+1) j + i) = I1(m, j) I1(n, i)) and
+ * 4*N^2 lattice-point indices, corners (n,m), (n,m+1), (n+1,m), (n+1,m+1). split_elements: xnew, ynew, fieldnew as (4, N^2*K).
+ * write_vtu: one field to a *.vtu file of VTK_QUAD cells, each listing its four own points in the order 0, 2, 3, 1. */
+int bdg_quadnodes_split_count(const bdg_quadnodes* nodes);
+int bdg_quadnodes_split_operators(const bdg_quadnodes* nodes, double* IM, double* I1, int* local_quads);
+int bdg_quadnodes_split_elements(const bdg_quadnodes* nodes, const double* field, double* xnew, double* ynew,
+                                 double* fieldnew);
+int bdg_quadnodes_write_vtu(const bdg_quadnodes* nodes, const char* path, const double* field,
+                            const char* field_name);
+/* Writes small quadrilaterals ((4, num_quads) x, y, field; one column per quadrilateral, corners as split_elements) as a *.vtu. */
+int bdg_write_vtu_quads(const char* path, const double* x, const double* y, const double* field, int num_quads,
+                        const char* field_name);
 
 /* ---------------------------------------------------------------- GaussFaceContext2D / CubatureContext2D
  * reference: TriangleNodesProvisioner::buildGaussFaceNodes (src/TriangleNodesProvisioner.cpp:207-381,
@@ -410,6 +425,16 @@ int bdg_sw2dq_rhs4(bdg_sw2dq* s, const double* h, const double* hu, const double
  * |Fscale| (sqrt(u^2 + v^2) + sqrt(g h)) (a device reduction in IEEE-exact operations). Either kind of solver. After comm_init
  * the maximum covers the owned elements and is all-reduced, so every rank gets the same dt. BDG_ERR_UNSTABLE on NaN. */
 int bdg_sw2dq_compute_dt(bdg_sw2dq* s, double cfl, double* dt, double* speed);
+/* Output step: the drivers' primitive fields eta = h - H (h where H is NULL; H: host (Np, K)), u = hu / h, v = hv / h and, on a
+ * four-field solver, N = hN / h of the resident state as host (Np, K) arrays, all from ONE kernel launch that reads h once.
+ * With lattice != NULL (I1, (N+1, N+1), from bdg_quadnodes_split_operators) they are interpolated on the device to each
+ * element's equispaced lattice first (what splitElements does before a *.vtu is written), I1 applied along r and then along s,
+ * each sum in ascending order and without contraction. NULL outputs are skipped; N != NULL on a three-field solver is
+ * BDG_ERR_ARGUMENT. After set_partition only the owned elements are computed and only the columns [0, num_owned) of the
+ * outputs are written. The values pass through device memory that is free between steps; the state is not disturbed. */
+int bdg_sw2dq_output_fields(bdg_sw2dq* s, const double* H, const double* lattice, double* eta, double* u, double* v, double* N);
+/* HIP-event milliseconds of that launch alone (every field of the solver; H, lattice as above), averaged over count */
+int bdg_sw2dq_time_output(bdg_sw2dq* s, const double* H, const double* lattice, int count, float* ms);
 /* Element-partitioned runs, as bdg_sw2d_curved_set_partition and friends (same argument order, refusals and error codes):
  * the solver's mesh is ordered [elements without a ghost neighbour: num_interior | partition-boundary elements: up to
  * num_owned | ghosts: up to K]; set_partition refuses (BDG_ERR_ARGUMENT) a bad range, an element of [0, num_interior) whose
