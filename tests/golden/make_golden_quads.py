@@ -15,7 +15,9 @@ Writes
                           evaluated on those tables (rhs1, rhs2, rhs3)
 Cases: coarse_box_quads_fine at N = 1..8; a 5x4 box with randomly displaced interior vertices (convex, not
 parallelograms) at N = 2, 5, 8; a 6x5 box with shuffled elements and rotated local vertex order (parallelograms) at
-N = 4 and 7; a state whose depth jumps across every face on coarse_box_quads_fine at N = 3.
+N = 4 and 7; the same 6x5 box with every vertex mapped by x' = [[1, 0.35], [-0.2, 0.8]] x (oblique parallelograms: all of
+rx, sx, ry, sy non-zero, no axis-aligned normal) at N = 3 and 8; a state whose depth jumps across every face on
+coarse_box_quads_fine at N = 3.
 """
 import os
 import shutil
@@ -69,11 +71,16 @@ def mesh_tables(path=None, EToV=None, Vert=None):
     return m, m.elements.astype(np.int32), m.vertices[:, :2].copy()
 
 
-def box(nx, ny, jitter=0.0, shuffle=False, seed=0):
+SHEAR = np.array([[1.0, 0.35], [-0.2, 0.8]])
+
+
+def box(nx, ny, jitter=0.0, shuffle=False, seed=0, shear=None):
     rng = np.random.default_rng(seed)
     xs, ys = np.linspace(-1, 1, nx + 1), np.linspace(-1, 1, ny + 1)
     X, Y = np.meshgrid(xs, ys)
     V = np.stack([X.ravel(), Y.ravel()], axis=1)
+    if shear is not None:
+        V = V @ np.asarray(shear).T
     if jitter:
         inner = (np.abs(V[:, 0]) < 1) & (np.abs(V[:, 1]) < 1)
         V[inner] += jitter * rng.uniform(-1, 1, (inner.sum(), 2)) * np.array([2 / nx, 2 / ny])
@@ -126,6 +133,9 @@ def main():
     Es, Vs = box(6, 5, shuffle=True, seed=5)
     for N in (4, 7):
         case(f"box6x5_shuffled_N{N}", N, Es, Vs, seed=20 + N)
+    Eo, Vo = box(6, 5, shuffle=True, seed=5, shear=SHEAR)
+    for N in (3, 8):
+        case(f"shear_box6x5_N{N}", N, Eo, Vo, seed=50 + N)
     case("regime_coarse_box_quads_fine_N3", 3, E, V, regime=True, seed=33)
 
 

@@ -11,7 +11,7 @@ Writes
                           imported as it is (only the alias np.float = float, which NumPy removed, is set), evaluated on
                           those quadrilateral tables: the function takes numFaces and numFacePoints from the context.
 Cases (meshes as make_golden_quads.py): coarse_box_quads_fine at N = 1..8; the jittered 5x4 box (general geometry) at
-N = 2, 5, 8; the shuffled 6x5 box (parallelograms) at N = 4, 7, all with tracer, Coriolis array, drag and bed slope as
+N = 2, 5, 8; the shuffled 6x5 box (parallelograms) at N = 4, 7; the sheared 6x5 box (oblique parallelograms) at N = 6, all with tracer, Coriolis array, drag and bed slope as
 make_golden.py's sw2d_rhs4_* cases; scalarf_*: scalar f; nosrc_*: f = CD = 0, zx = zy = 0; regime_*: a state whose depth
 jumps across every face and whose flow is supercritical (|u| > sqrt(g h)), N = 3. h >= 1 everywhere.
 """
@@ -29,7 +29,7 @@ sys.path.insert(0, HERE)
 sys.dont_write_bytecode = True
 
 from make_golden import seeded_fields  # noqa: E402
-from make_golden_quads import box, mesh_tables  # noqa: E402
+from make_golden_quads import SHEAR, box, mesh_tables  # noqa: E402
 
 
 def case(name, order, EToV, Vert, kind="full", seed=1):
@@ -87,6 +87,8 @@ def main():
     Es, Vs = box(6, 5, shuffle=True, seed=5)
     for N in (4, 7):
         case(f"box6x5_shuffled_N{N}", N, Es, Vs, seed=20 + N)
+    Eo, Vo = box(6, 5, shuffle=True, seed=5, shear=SHEAR)
+    case("shear_box6x5_N6", 6, Eo, Vo, seed=56)
     case("scalarf_jitter_box5x4_N4", 4, Ej, Vj, kind="scalarf", seed=41)
     case("nosrc_box6x5_shuffled_N5", 5, Es, Vs, kind="nosrc", seed=42)
     case("regime_coarse_box_quads_fine_N3", 3, E, V, kind="regime", seed=33)

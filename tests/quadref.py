@@ -11,7 +11,8 @@ import blitzdg_amd.pyblitzdg as dg
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 FIXTURES = ([f"coarse_box_quads_fine_N{n}" for n in range(1, 9)] + [f"jitter_box5x4_N{n}" for n in (2, 5, 8)]
-            + ["box6x5_shuffled_N4", "box6x5_shuffled_N7", "regime_coarse_box_quads_fine_N3"])
+            + ["box6x5_shuffled_N4", "box6x5_shuffled_N7", "shear_box6x5_N3", "shear_box6x5_N8",
+               "regime_coarse_box_quads_fine_N3"])
 
 
 def load_fixture(name):

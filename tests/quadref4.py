@@ -11,9 +11,9 @@ import blitzdg_amd.pyblitzdg as dg
 from quadref import GOLDEN, tables  # noqa: F401
 
 FIXTURES4 = ([f"coarse_box_quads_fine_N{n}" for n in range(1, 9)] + [f"jitter_box5x4_N{n}" for n in (2, 5, 8)]
-             + ["box6x5_shuffled_N4", "box6x5_shuffled_N7", "scalarf_jitter_box5x4_N4", "nosrc_box6x5_shuffled_N5",
-                "regime_coarse_box_quads_fine_N3"])
-PARALLELOGRAM4 = {"box6x5_shuffled_N4", "box6x5_shuffled_N7", "nosrc_box6x5_shuffled_N5"}
+             + ["box6x5_shuffled_N4", "box6x5_shuffled_N7", "shear_box6x5_N6", "scalarf_jitter_box5x4_N4",
+                "nosrc_box6x5_shuffled_N5", "regime_coarse_box_quads_fine_N3"])
+PARALLELOGRAM4 = {"box6x5_shuffled_N4", "box6x5_shuffled_N7", "shear_box6x5_N6", "nosrc_box6x5_shuffled_N5"}
 
 
 def load_fixture4(name):

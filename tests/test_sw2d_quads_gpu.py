@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 RHS_TOL = 1e-12
 STATE_TOL = 1e-11
-PARALLELOGRAM = {"box6x5_shuffled_N4", "box6x5_shuffled_N7"}
+PARALLELOGRAM = {"box6x5_shuffled_N4", "box6x5_shuffled_N7", "shear_box6x5_N3", "shear_box6x5_N8"}
 
 
 @pytest.mark.parametrize("name", FIXTURES)
