@@ -89,8 +89,10 @@ __global__ __launch_bounds__(256) void sw2d_quad4_stage_kernel(const Quad4Params
 
     // Phase C visits the node items of phase A again. Where its item loop is unrolled, the sources are formed in phase A, from
     // the state and the velocities that are in registers there, and carried across (2 doubles per item); where it stays rolled
-    // (N > 6 unfiltered) they are formed in phase C from a second read of the node.
-    constexpr int kUnrollC = N <= 6 || FILT ? Q::NI : 1;
+    // (N = 7, 8 unfiltered) they are formed in phase C from a second read of the node. Above N = 8 the tile has 8 elements and
+    // a thread at most 6 items: with sources the loop is unrolled again and the sources come from phase A (rolled, with the
+    // sources formed in it, these instances took 256 VGPRs and 188-256 AGPRs, and scratch at N = 11, 12; unrolled 132-240, none).
+    constexpr int kUnrollC = N <= 6 || FILT || (SRC && N > 8) ? Q::NI : 1;
     constexpr bool kSrcEarly = SRC && kUnrollC == Q::NI;
     double src2[kSrcEarly ? Q::NI : 1], src3[kSrcEarly ? Q::NI : 1];
 
@@ -271,6 +273,24 @@ __global__ __launch_bounds__(256) void sw2d_quad4_stage_kernel(const Quad4Params
             }
         }
         __syncthreads();
+    }
+    // Above N = 8 a filtered row goes from the LDS planes straight into the stage update, as in the three-field kernel.
+    constexpr bool kFiltStream = FILT && N > 8;
+    if (kFiltStream) {
+#pragma unroll 1
+        for (int m = 0; m < Q::NI; ++m) {
+            const int idx = tid + T * m;
+            if (idx >= Np * E) break;
+            const int n = idx / E, e = idx % E, k = k0 + e;
+            double a[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < Np; ++q) {
+                const double w = p.filt[n * Np + q];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) a[c] += w * fl[(c * Np + q) * E + e];
+            }
+            if (k < p.kEnd) store4<MODE>(p, n * ld + k, plane, a);
+        }
+    } else if (FILT) {
 #pragma unroll
         for (int m = 0; m < Q::NI; ++m) {
             const int idx = tid + T * m;

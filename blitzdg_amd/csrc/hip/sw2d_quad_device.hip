@@ -38,6 +38,10 @@ hipError_t sw2d_quad_stage(int order, int mode, bool filter, bool general, const
     case 6: return sw2d_quad_launch<6>(mode, filter, general, p, stream);
     case 7: return sw2d_quad_launch<7>(mode, filter, general, p, stream);
     case 8: return sw2d_quad_launch<8>(mode, filter, general, p, stream);
+    case 9: return sw2d_quad_launch<9>(mode, filter, general, p, stream);
+    case 10: return sw2d_quad_launch<10>(mode, filter, general, p, stream);
+    case 11: return sw2d_quad_launch<11>(mode, filter, general, p, stream);
+    case 12: return sw2d_quad_launch<12>(mode, filter, general, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -53,6 +57,10 @@ hipError_t sw2d_quad4_stage(int order, int mode, bool filter, bool general, bool
     case 6: return sw2d_quad4_launch<6>(mode, filter, general, sources, p, stream);
     case 7: return sw2d_quad4_launch<7>(mode, filter, general, sources, p, stream);
     case 8: return sw2d_quad4_launch<8>(mode, filter, general, sources, p, stream);
+    case 9: return sw2d_quad4_launch<9>(mode, filter, general, sources, p, stream);
+    case 10: return sw2d_quad4_launch<10>(mode, filter, general, sources, p, stream);
+    case 11: return sw2d_quad4_launch<11>(mode, filter, general, sources, p, stream);
+    case 12: return sw2d_quad4_launch<12>(mode, filter, general, sources, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -67,6 +75,10 @@ hipError_t sw2d_quad_output(int order, int fields, const QuadOutParams& p, hipSt
     case 6: return sw2d_quad_output_launch<6>(fields, p, stream);
     case 7: return sw2d_quad_output_launch<7>(fields, p, stream);
     case 8: return sw2d_quad_output_launch<8>(fields, p, stream);
+    case 9: return sw2d_quad_output_launch<9>(fields, p, stream);
+    case 10: return sw2d_quad_output_launch<10>(fields, p, stream);
+    case 11: return sw2d_quad_output_launch<11>(fields, p, stream);
+    case 12: return sw2d_quad_output_launch<12>(fields, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -75,6 +87,7 @@ int sw2d_quad_tile(int order) {
     switch (order) {
     case 1: return QuadElem<1>::E;
     case 2: return QuadElem<2>::E;
+    case 9: case 10: case 11: case 12: return QuadElem<9>::E;
     default: return QuadElem<3>::E;
     }
 }
@@ -377,6 +390,10 @@ std::vector<double> tensorFactors(int N, const double* Dr, const double* Ds, con
     for (int j = 0; j < Nq; ++j) lN[j] = Lift[static_cast<size_t>(Nq * j) * NFN + Nq];    // face 1, q = i = 0
     const double tolD = 1e-13 * std::max(maxAbs(Dr, static_cast<size_t>(Np) * Np), maxAbs(Ds, static_cast<size_t>(Np) * Np));
     const double tolL = 1e-13 * maxAbs(Lift, static_cast<size_t>(Np) * NFN);
+    // (a zero table would pass a tolerance relative to its own largest entry)
+    if (!(tolD > 0.0) || !(tolL > 0.0))
+        throw arg_error("bdg_sw2dq_create: Dr / Ds or Lift is identically zero or not finite: these are not the operators of an "
+                        "element of order " + std::to_string(N));
     double errD = 0.0, errL = 0.0;
     for (int j = 0; j < Nq; ++j)
         for (int i = 0; i < Nq; ++i) {

@@ -10,7 +10,8 @@
 // Node (N+1) j + i sits at r = r1d[j], s = s1d[i]; faces are s=-1 (i = 0), r=+1 (j = N), s=+1 (i = N), r=-1 (j = 0).
 //
 // Mapping to the hardware: one 256-thread workgroup owns a tile of E consecutive elements (E = 64 / 32 / 16 for
-// N = 1 / 2 / >= 3, so every access to one nodal row of a tile is a contiguous run of E doubles, >= 128 bytes) of the
+// N = 1 / 2 / 3..8, so every access to one nodal row of a tile is a contiguous run of E doubles, >= 128 bytes; E = 8 for
+// N = 9..12, 64-byte runs, which keeps two or three workgroups on a CU where a tile of 16 leaves one: DESIGN section 3.8) of the
 // element range [kBegin, kEnd): tile kBegin + blockIdx.x * E, one workgroup per tile (a single domain evaluates [0, K); a
 // partitioned run its interior and partition-boundary ranges, never its ghosts). Three phases, separated by workgroup barriers:
 //   A  node items (n, e): load h, hu, hv, write hu, hv, F2, G2, G3 to LDS;
@@ -30,7 +31,7 @@ struct QuadElem {
     static constexpr int Nq = N + 1;
     static constexpr int Np = Nq * Nq;
     static constexpr int NFN = 4 * Nq;
-    static constexpr int E = N == 1 ? 64 : (N == 2 ? 32 : 16); // elements per workgroup tile
+    static constexpr int E = N == 1 ? 64 : (N == 2 ? 32 : (N <= 8 ? 16 : 8)); // elements per workgroup tile
     static constexpr int THREADS = 256;
     static constexpr int NI = (Np * E + THREADS - 1) / THREADS;  // node items per thread
     static constexpr int FI = (NFN * E + THREADS - 1) / THREADS; // face-node items per thread
@@ -259,6 +260,9 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
         }
     }
 
+    // Above N = 8 a filtered row goes from the LDS planes straight into the stage update, one item at a time, instead of
+    // waiting in registers until every row of the thread is filtered.
+    constexpr bool kFiltStream = FILT && N > 8;
     if (FILT) {
         __syncthreads(); // every derivative read of fl is done
 #pragma unroll
@@ -272,6 +276,23 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
             }
         }
         __syncthreads();
+    }
+    if (kFiltStream) {
+#pragma unroll 1
+        for (int m = 0; m < Q::NI; ++m) {
+            const int idx = tid + T * m;
+            if (idx >= Np * E) break;
+            const int n = idx / E, e = idx % E, k = k0 + e;
+            double a = 0.0, b = 0.0, c = 0.0;
+            for (int q = 0; q < Np; ++q) {
+                const double w = p.filt[n * Np + q];
+                a += w * fl[(0 * Np + q) * E + e];
+                b += w * fl[(1 * Np + q) * E + e];
+                c += w * fl[(2 * Np + q) * E + e];
+            }
+            if (k < p.kEnd) store<MODE>(p, n * ld + k, plane, a, b, c);
+        }
+    } else if (FILT) {
 #pragma unroll
         for (int m = 0; m < Q::NI; ++m) {
             const int idx = tid + T * m;
@@ -289,7 +310,7 @@ __global__ __launch_bounds__(256) void sw2d_quad_stage_kernel(const QuadParams p
         }
     }
 
-    if (FILT) {
+    if (FILT && !kFiltStream) {
 #pragma unroll
         for (int m = 0; m < Q::NI; ++m) {
             const int idx = tid + T * m;

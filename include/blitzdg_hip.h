@@ -380,7 +380,7 @@ typedef struct bdg_sw2dq_desc {
     int flags;          /* BDG_SW2DQ_*                                              */
 } bdg_sw2dq_desc;
 
-#define BDG_SW2DQ_MAX_ORDER 8
+#define BDG_SW2DQ_MAX_ORDER 12 /* 9..12: tiles of 8 elements; triangles and curved elements stop at 8 */
 #define BDG_SW2DQ_GENERAL_GEOMETRY 1u /* always read rx..sy per node and nx, ny, Fscale per face node. Default: if
                                every element is a parallelogram (metric terms constant per element, normals and
                                Fscale per face, to 1e-10 relative), 16 values per element are kept instead. */

@@ -6,7 +6,9 @@ per (round, order, geometry form, kind): kind "fields3" (LSERK4 stage and RK2 + 
 a build of the parent commit also runs, selected with BDG_HIP_LIBRARY and labelled with `label`), "fields4" (four fields, no
 sources) and "fields4_sources" (Coriolis array, drag, bed slope); the kinds a library lacks are skipped. Compulsory bytes of a
 parallelogram-form LSERK4 stage per element: state in, residual in and out, state out = 4 fields Np doubles, plus 2 Np (3 Np
-with an f array) for the sources, plus the gather index (4 bytes per face node) and 16 geometry values."""
+with an f array) for the sources, plus the gather index (4 bytes per face node) and 16 geometry values. Each line also
+carries the node count and the picoseconds per node of both timings, the figure that compares orders (9 to 12 beside 8:
+profiles/quads_high_order.jsonl)."""
 import json
 import os
 import sys
@@ -59,9 +61,12 @@ def main():
                     ms_stage = s.timeStages(dt, stages)
                     ms_rk2 = s.timeStages(dt, max(stages // 5, 2), rk2=True)
                     b = stage_bytes(N, K, general, fields, planes)
-                    print(json.dumps({"build": label, "round": rnd, "kind": kind, "order": N, "K": K,
+                    nodes_total = K * (N + 1) ** 2
+                    print(json.dumps({"build": label, "round": rnd, "kind": kind, "order": N, "K": K, "nodes": nodes_total,
                                       "geometry": "general" if general else "parallelogram",
                                       "ms_per_lserk4_stage": round(ms_stage, 4), "ms_per_rk2_filter_step": round(ms_rk2, 4),
+                                      "ps_per_node_lserk4_stage": round(ms_stage * 1e9 / nodes_total, 2),
+                                      "ps_per_node_rk2_filter_step": round(ms_rk2 * 1e9 / nodes_total, 2),
                                       "stage_bytes": b, "stage_TBps": round(b / ms_stage / 1e9, 3)}), flush=True)
                     s.close()
 
