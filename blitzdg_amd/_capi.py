@@ -228,6 +228,15 @@ _SIGNATURES = {
     "bdg_sw2dq_step_rk2_exchanged": (c_int, [_P, c_double, c_int, c_int]),
     "bdg_sw2dq_lserk4_stages_exchanged": (c_int, [_P, c_double, c_int]),
     "bdg_sw2dq_barrier": (c_int, [_P]),
+    "bdg_sw2dq_enable_variant_b": (c_int, [_P, POINTER(Sw2dVbDesc)]),  # bdg_sw2dq_vb_desc has bdg_sw2d_vb_desc's fields
+    "bdg_sw2dq_set_time": (c_int, [_P, c_double]),
+    "bdg_sw2dq_get_time": (c_int, [_P, POINTER(c_double)]),
+    "bdg_sw2dq_global_speed": (c_int, [_P, POINTER(c_double)]),
+    "bdg_sw2dq_step_ssprk2": (c_int, [_P, c_double, c_int, c_int, c_double]),
+    "bdg_sw2dq_step_ssprk2_exchanged": (c_int, [_P, c_double, c_int, c_int, c_double]),
+    "bdg_sw2dq_time_speed": (c_int, [_P, c_int, POINTER(c_float)]),
+    "bdg_quadnodes_bed_slopes": (c_int, [_P, _P, _P, _P]),
+    "bdg_quadnodes_sponge_coeff": (c_int, [_P, _P, c_int, c_double, c_double, _P]),
     "bdg_sw2d_step_lserk4": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_lserk4_stages": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_step_rk2": (c_int, [_P, c_double, c_int, c_int]),

@@ -6,10 +6,13 @@
 // partition_schedule.hpp on a second stream. A solver created with four fields (bdg_sw2dq_create_fields) launches
 // sw2d_quad4_stage_kernel (sw2d_quad4_kernel.hpp) instead, with the sources of bdg_sw2dq_set_sources if there are any.
 // The output step (bdg_sw2dq_output_fields) is one launch of sw2d_quad_output_kernel (sw2d_quad_output_kernel.hpp).
+// After bdg_sw2dq_enable_variant_b a three-field solver evaluates the tidal driver's right-hand side instead: the speed pass
+// sw2d_quadb_speed_kernel, then sw2d_quadb_stage_kernel (sw2d_quadb_kernel.hpp), which reads the speed from device memory.
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
+#include "sw2d_quadb_kernel.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "blitzdg/MeshManager.hpp"
 #include <algorithm>
@@ -81,6 +84,37 @@ hipError_t sw2d_quad_output(int order, int fields, const QuadOutParams& p, hipSt
     case 12: return sw2d_quad_output_launch<12>(fields, p, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t sw2d_quadb_stage(int order, int mode, bool filter, bool general, const QuadBParams& p, hipStream_t stream) {
+    switch (order) {
+    case 1: return sw2d_quadb_launch<1>(mode, filter, general, p, stream);
+    case 2: return sw2d_quadb_launch<2>(mode, filter, general, p, stream);
+    case 3: return sw2d_quadb_launch<3>(mode, filter, general, p, stream);
+    case 4: return sw2d_quadb_launch<4>(mode, filter, general, p, stream);
+    case 5: return sw2d_quadb_launch<5>(mode, filter, general, p, stream);
+    case 6: return sw2d_quadb_launch<6>(mode, filter, general, p, stream);
+    case 7: return sw2d_quadb_launch<7>(mode, filter, general, p, stream);
+    case 8: return sw2d_quadb_launch<8>(mode, filter, general, p, stream);
+    case 9: return sw2d_quadb_launch<9>(mode, filter, general, p, stream);
+    case 10: return sw2d_quadb_launch<10>(mode, filter, general, p, stream);
+    case 11: return sw2d_quadb_launch<11>(mode, filter, general, p, stream);
+    case 12: return sw2d_quadb_launch<12>(mode, filter, general, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t sw2d_quadb_speed(int order, bool general, const QuadBParams& p, double* out, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(double), stream);
+    if (e != hipSuccess || p.q.kEnd <= p.q.kBegin) return e;
+    const long long items = 4LL * (order + 1) * (p.q.kEnd - p.q.kBegin);
+    const dim3 grid(static_cast<unsigned>(std::min<long long>((items + 255) / 256, 2048))), block(256);
+    unsigned long long* bits = reinterpret_cast<unsigned long long*>(out);
+    if (general)
+        hipLaunchKernelGGL((sw2d_quadb_speed_kernel<true>), grid, block, 0, stream, p, order, bits);
+    else
+        hipLaunchKernelGGL((sw2d_quadb_speed_kernel<false>), grid, block, 0, stream, p, order, bits);
+    return hipGetLastError();
 }
 
 int sw2d_quad_tile(int order) {
@@ -169,6 +203,13 @@ struct bdg_sw2dq {
     bool evaluated = false;   // a stage kernel has been launched: the sources are fixed from then on
     double fconst = 0.0, CD = 0.0;
     DevBuf<double> zx, zy, fcor;
+    // variant B (bdg_sw2dq_enable_variant_b): sw2d_quadb_kernel.hpp
+    bool variantB = false;
+    DevBuf<double> vbH, vbHx, vbHy, vbSponge, lamBuf;
+    DevBuf<int> gidxB;        // gidx with the open-boundary nodes marked
+    double vbF = 0.0, vbCD = 0.0, tideAmp = 0.0, tidePeriod = 1.0, tideRamp = 0.0;
+    double timeNow = 0.0;     // model time of the resident state (tide phase); the steppers advance it
+    double spongeC = 0.0;     // scalar sponge coefficient of the Heun step in flight
     long long ld = 0;
     double g = 9.81;
     bool general = true, hasFilter = false;
@@ -204,9 +245,38 @@ struct bdg_sw2dq {
         p.ld = ld; p.kBegin = 0; p.kEnd = K; p.g = g;
         return p;
     }
-    void launch(int mode, bool filter, const QuadParams& p) { launchOn(mode, filter, p, stream); }
+    double tideAt(double t) const { // main.cpp:352
+        const double om = 2.0 * M_PI / tidePeriod;
+        return tideAmp * std::cos(om * t) * 0.5 * (std::tanh(tideRamp * (t - tidePeriod)) + 1);
+    }
+    QuadBParams paramsB(const QuadParams& p) const {
+        QuadBParams b{};
+        b.q = p; b.q.gidx = gidxB.p;
+        b.H = vbH.p; b.Hx = vbHx.p; b.Hy = vbHy.p; b.lam = lamBuf.p; b.sponge = vbSponge.p; b.spongeC = spongeC;
+        b.tide = tideAt(timeNow); b.fcor = vbF; b.cd = vbCD;
+        return b;
+    }
+    // variant B: the global speed of `state` over the columns [0, count) into lamBuf, on the solver's stream; with a
+    // communicator the maximum over every rank (one 8-byte all-reduce). Needs no current ghosts (sw2d_quadb_kernel.hpp).
+    void speedPass(const double* state, int count) {
+        QuadParams p = params();
+        p.qin = state; p.kEnd = count;
+        hipCheck(sw2d_quadb_speed(N, general, paramsB(p), lamBuf.p, stream), "sw2d_quadb_speed_kernel launch");
+        if (halo.comm)
+            bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, halo.comm, stream),
+                                "ncclAllReduce");
+    }
+    // one evaluation of every element on the solver's stream
+    void launch(int mode, bool filter, const QuadParams& p) {
+        if (variantB) speedPass(p.qin, K);
+        launchOn(mode, filter, p, stream);
+    }
     void launchOn(int mode, bool filter, const QuadParams& p, hipStream_t on) {
         evaluated = true;
+        if (variantB) {
+            hipCheck(sw2d_quadb_stage(N, mode, filter, general, paramsB(p), on), "sw2d_quadb_stage_kernel launch");
+            return;
+        }
         if (fields == 4) {
             const Quad4Params p4{p, zx.p, zy.p, fcor.p, fconst, CD};
             hipCheck(sw2d_quad4_stage(N, mode, filter, general, hasSources, p4, on), "sw2d_quad4_stage_kernel launch");
@@ -220,6 +290,24 @@ struct bdg_sw2dq {
         launch(QMODE_COMBINE, filter, p);
         p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;              // corrector: q += dt F R(q1)
         launch(QMODE_COMBINE, filter, p);
+        timeNow += dt; // (both evaluations at the old time level)
+    }
+    // SSP-RK2 (Heun) of the tidal driver (main.cpp:211-236), the sponge division in the stage store:
+    //   q1 = sp(q + dt R(q));  q = sp(1/2 (q + q1 + dt R(q1))), both evaluations at the old time level
+    void heunStep(double dt, bool filter, bool exchanged, bool two) {
+        QuadParams p = params();
+        p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.ca = 1.0; p.cb = 0.0; p.cc = dt;
+        if (exchanged) evaluateExchanged(two, QMODE_HEUN, filter, p);
+        else launch(QMODE_HEUN, filter, p);
+        p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.ca = 0.5; p.cb = 0.5; p.cc = 0.5 * dt;
+        if (exchanged) evaluateExchanged(two, QMODE_HEUN, filter, p);
+        else launch(QMODE_HEUN, filter, p);
+        timeNow += dt;
+    }
+    // the tide is frozen over the five stages of an LSERK4 step and the model time moves on after the last
+    void lserkAdvance(double dt) {
+        if (stageCount % blitzdg::LSERK4::numStages == blitzdg::LSERK4::numStages - 1) timeNow += dt;
+        ++stageCount;
     }
     void lserkStage(double dt) {
         const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
@@ -228,7 +316,7 @@ struct bdg_sw2dq {
         p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
         launch(QMODE_LSERK, false, p);
         std::swap(q.p, q1.p); // neighbours read the old traces during the launch: double-buffered
-        ++stageCount;
+        lserkAdvance(dt);
     }
     // the reference script's check after every step: max|h| > 1e8 or NaN, over the columns [0, count) of h. collective: the two
     // values are all-reduced (maximum) over every rank of the communicator first, so that all ranks raise together
@@ -300,13 +388,15 @@ struct bdg_sw2dq {
     }
     // The two-chain schedule of partition_schedule.hpp; without an interior element, or with BDG_SW2DQ_NO_OVERLAP:
     // exchange, then every owned element, in stream order.
+    // Variant B is never overlapped: the all-rank speed has to exist before any element of the evaluation starts.
     bool overlapped() const {
-        return part.numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
+        return !variantB && part.numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
     }
     // one evaluation: reads p.qin (ghost columns refreshed first), writes the owned columns of its outputs
     void evaluateExchanged(bool two, int mode, bool filter, const QuadParams& p) {
         double* in = const_cast<double*>(p.qin);
         if (!two) {
+            if (variantB) speedPass(in, part.numOwned);
             exchangeOn(in, stream);
             evaluateRange(mode, filter, p, 0, part.numOwned, stream);
             return;
@@ -330,6 +420,7 @@ struct bdg_sw2dq {
             evaluateExchanged(two, QMODE_COMBINE, filter, p);
             p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;
             evaluateExchanged(two, QMODE_COMBINE, filter, p);
+            timeNow += dt;
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -345,7 +436,7 @@ struct bdg_sw2dq {
             p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
             evaluateExchanged(two, QMODE_LSERK, false, p);
             std::swap(q.p, q1.p);
-            ++stageCount;
+            lserkAdvance(dt);
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -670,6 +761,115 @@ int bdg_sw2dq_set_sources(bdg_sw2dq* s, const double* zx, const double* zy, doub
     });
 }
 
+int bdg_sw2dq_enable_variant_b(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_enable_variant_b");
+        if (!d || !d->H || !d->Hx || !d->Hy) throw arg_error("bdg_sw2dq_enable_variant_b: H, Hx and Hy are required");
+        if (s->fields != 3)
+            throw arg_error("bdg_sw2dq_enable_variant_b: the solver was created with four fields; variant B has three (h, hu, hv)");
+        if (s->evaluated)
+            throw arg_error("bdg_sw2dq_enable_variant_b: the solver has evaluated a right-hand side already; variant B is enabled "
+                            "before the first evaluation");
+        if (d->num_out < 0 || (d->num_out > 0 && !d->mapO)) throw arg_error("bdg_sw2dq_enable_variant_b: bad open-boundary list");
+        if (!(d->tide_period > 0.0) && d->num_out > 0) throw arg_error("bdg_sw2dq_enable_variant_b: tide_period must be > 0");
+        const long long nFaceNodes = static_cast<long long>(s->NFN) * s->K;
+        for (int i = 0; i < d->num_out; ++i)
+            if (d->mapO[i] < 0 || d->mapO[i] >= nFaceNodes)
+                throw arg_error("bdg_sw2dq_enable_variant_b: open-boundary node index out of range");
+        s->use();
+        const long long plane = s->plane();
+        // the gather index again, open-boundary nodes as kQuadBOpen (they win over the wall flag where a node has both)
+        std::vector<int> gi(s->gidx.n);
+        hipCheck(hipMemcpyAsync(gi.data(), s->gidx.p, gi.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (gidx)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        for (int i = 0; i < d->num_out; ++i) {
+            const int k = d->mapO[i] / s->NFN, fn = d->mapO[i] % s->NFN;
+            gi[static_cast<size_t>(fn) * s->ld + k] = kQuadBOpen;
+        }
+        s->gidxB.alloc(gi.size(), s->bytes);
+        hipCheck(hipMemcpyAsync(s->gidxB.p, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "hipMemcpy (gidx)");
+        s->vbH.alloc(plane, s->bytes, s->stream);
+        s->vbHx.alloc(plane, s->bytes, s->stream);
+        s->vbHy.alloc(plane, s->bytes, s->stream);
+        s->upload(s->vbH.p, d->H, s->Np);
+        s->upload(s->vbHx.p, d->Hx, s->Np);
+        s->upload(s->vbHy.p, d->Hy, s->Np);
+        if (d->sponge) {
+            s->vbSponge.alloc(plane, s->bytes, s->stream);
+            s->upload(s->vbSponge.p, d->sponge, s->Np);
+        } else if (s->vbSponge.p) {
+            s->vbSponge.alloc(0, s->bytes);
+        }
+        s->lamBuf.alloc(1, s->bytes, s->stream);
+        s->vbF = d->coriolis;
+        s->vbCD = d->drag;
+        s->tideAmp = d->tide_amplitude;
+        s->tidePeriod = d->tide_period > 0.0 ? d->tide_period : 1.0;
+        s->tideRamp = d->tide_ramp;
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vector dies here
+        s->variantB = true;
+    });
+}
+
+int bdg_sw2dq_set_time(bdg_sw2dq* s, double t) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_set_time");
+        s->timeNow = t;
+    });
+}
+
+int bdg_sw2dq_get_time(const bdg_sw2dq* s, double* t) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_get_time");
+        if (!t) throw arg_error("bdg_sw2dq_get_time: NULL argument");
+        *t = s->timeNow;
+    });
+}
+
+int bdg_sw2dq_global_speed(bdg_sw2dq* s, double* lam) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_global_speed");
+        if (!s->variantB || !lam) throw arg_error("bdg_sw2dq_global_speed: variant B is not enabled");
+        s->use();
+        hipCheck(hipMemcpyAsync(lam, s->lamBuf.p, sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (speed)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_time_speed");
+        if (!ms || count < 1) throw arg_error("bdg_sw2dq_time_speed: bad argument");
+        if (!s->variantB) throw arg_error("bdg_sw2dq_time_speed: variant B is not enabled");
+        s->use();
+        hipEvent_t a, b;
+        hipCheck(hipEventCreate(&a), "hipEventCreate");
+        hipCheck(hipEventCreate(&b), "hipEventCreate");
+        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
+        for (int i = 0; i < count; ++i) s->speedPass(s->q.p, s->part.numOwned > 0 ? s->part.numOwned : s->K);
+        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
+        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
+        float t = 0.0f;
+        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        *ms = t / count;
+    });
+}
+
+int bdg_sw2dq_step_ssprk2(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_step_ssprk2");
+        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2: num_steps < 0");
+        if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2: variant B is not enabled (the Heun step is the tidal driver's)");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2: filter requested but the solver has no Filter");
+        s->use();
+        s->spongeC = sponge_coeff;
+        for (int i = 0; i < num_steps; ++i) s->heunStep(dt, filter != 0, false, false);
+        s->checkBlowUp();
+    });
+}
+
 int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_state4");
@@ -808,7 +1008,8 @@ int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages) {
 int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_time");
-        if (!ms || count < 1 || kind < 0 || kind > 1) throw arg_error("bdg_sw2dq_time: bad argument");
+        if (!ms || count < 1 || kind < 0 || kind > 2) throw arg_error("bdg_sw2dq_time: bad argument");
+        if (kind == 2 && !s->variantB) throw arg_error("bdg_sw2dq_time: the Heun step needs variant B");
         if (kind == 1 && !s->hasFilter) throw arg_error("bdg_sw2dq_time: RK2 + filter needs a Filter");
         s->use();
         hipEvent_t a, b;
@@ -817,7 +1018,8 @@ int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms) {
         hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
         for (int i = 0; i < count; ++i) {
             if (kind == 0) s->lserkStage(dt);
-            else s->rk2Step(dt, true);
+            else if (kind == 1) s->rk2Step(dt, true);
+            else s->heunStep(dt, false, false, false);
         }
         hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
         hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
@@ -879,6 +1081,19 @@ int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int fil
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2_exchanged: filter requested but the solver has no Filter");
         s->use();
         s->stepRk2Exchanged(dt, num_steps, filter != 0);
+        s->checkBlowUp(s->part.numOwned, true);
+    });
+}
+
+int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff) {
+    return guard([&] {
+        requireComm(s, "bdg_sw2dq_step_ssprk2_exchanged");
+        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: num_steps < 0");
+        if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: variant B is not enabled");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: filter requested but the solver has no Filter");
+        s->use();
+        s->spongeC = sponge_coeff;
+        for (int i = 0; i < num_steps; ++i) s->heunStep(dt, filter != 0, true, false);
         s->checkBlowUp(s->part.numOwned, true);
     });
 }

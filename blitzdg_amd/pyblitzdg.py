@@ -413,6 +413,24 @@ class QuadNodesProvisioner:
         check(lib.bdg_quadnodes_build_bchash(self._h, C.ptr(b), b.size))
         self._tables_version += 1
 
+    def bedSlopes(self, H):
+        """(Hx, Hy) as the tidal driver builds them (reference src/sw2d/main.cpp:128-133): Filter @ (rx Dr H + sx Ds H,
+        ry Dr H + sy Ds H); ``buildFilter`` first."""
+        _, Np, _, K = self._dims()
+        Hh = C.as_f64(H, (Np, K), "H")
+        Hx, Hy = np.empty((Np, K)), np.empty((Np, K))
+        check(lib.bdg_quadnodes_bed_slopes(self._h, C.ptr(Hh), C.ptr(Hx), C.ptr(Hy)))
+        return Hx, Hy
+
+    def buildSpongeCoeff(self, mapO, spongeStrength, radInfl):
+        """reference src/sw2d/main.cpp:517-553 (sw2d::buildSpongeCoeff); ``mapO``: BCmap[2] after ``buildBCHash``."""
+        _, Np, _, K = self._dims()
+        mo = C.as_i32(mapO).reshape(-1)
+        out = np.empty((Np, K))
+        check(lib.bdg_quadnodes_sponge_coeff(self._h, C.ptr(mo) if mo.size else None, mo.size, float(spongeStrength),
+                                             float(radInfl), C.ptr(out)))
+        return out
+
     def splitElements(self, field):
         """(xnew, ynew, fieldnew), each (4, N^2*K): the field on N^2 small quadrilaterals per element, corners
         (n,m), (n,m+1), (n+1,m), (n+1,m+1) of the equispaced lattice (reference src/QuadNodesProvisioner.cpp:721-838)."""

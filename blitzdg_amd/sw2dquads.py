@@ -97,6 +97,59 @@ class Sw2dQuadSolver:
         check(lib.bdg_sw2dq_set_sources(self._h, C.ptr(zx), C.ptr(zy), 0.0 if farr is not None else float(f), C.ptr(farr),
                                         float(CD)))
 
+    def enableVariantB(self, H, Hx, Hy, mapO=None, CD=0.0, f=0.0, tide=(3.0, 3600 * 12.42, 0.15 / 3600), sponge=None):
+        """Switches a three-field solver to the right-hand side of the reference's tidal driver (src/sw2d/main.cpp:279-484,
+        "variant B"): still-water depth ``H`` with star states at the faces, the open-boundary nodes ``mapO`` (flat face-node
+        indices, BCmap[2] of the provisioner) driven by ``tide = (amplitude, period, ramp)``, one global Lax-Friedrichs
+        speed, bed slope (``Hx, Hy``: ``QuadNodesProvisioner.bedSlopes(H)``), drag ``CD`` and Coriolis ``f`` (scalars).
+        ``sponge``: (Np, K) coefficient of ``stepSSPRK2`` (``buildSpongeCoeff``). Before the first evaluation only; computeRHS,
+        stepRK2, lserk4Stages and timeStages then evaluate variant B at the model time (``setTime``). Wrong shapes raise
+        ValueError; a four-field solver and a solver that has evaluated already are refused by the library."""
+        shape = (self.Np, self.K)
+        a = [C.as_f64(H, shape, "H"), C.as_f64(Hx, shape, "Hx"), C.as_f64(Hy, shape, "Hy")]
+        sp = None if sponge is None else C.as_f64(sponge, shape, "sponge")
+        mo = C.as_i32([] if mapO is None else mapO).reshape(-1)
+        if np.ndim(CD) != 0 or np.ndim(f) != 0:
+            raise ValueError("CD, f: expected scalars")
+        amp, period, ramp = (float(v) for v in tide)
+        d = C.Sw2dVbDesc(C.ptr(a[0]), C.ptr(a[1]), C.ptr(a[2]), C.ptr(mo) if mo.size else None, mo.size, float(CD), float(f),
+                         amp, period, ramp, C.ptr(sp))
+        check(lib.bdg_sw2dq_enable_variant_b(self._h, byref(d)))
+        self.variantB = True
+
+    def setTime(self, t):
+        """Model time of the resident state (the tide phase of variant B); the steppers advance it."""
+        check(lib.bdg_sw2dq_set_time(self._h, float(t)))
+
+    def getTime(self):
+        t = c_double()
+        check(lib.bdg_sw2dq_get_time(self._h, byref(t)))
+        return t.value
+
+    def globalSpeed(self):
+        """The global Lax-Friedrichs speed of the most recent variant-B evaluation."""
+        lam = c_double()
+        check(lib.bdg_sw2dq_global_speed(self._h, byref(lam)))
+        return lam.value
+
+    def stepSSPRK2(self, dt, nsteps=1, filter=False, sponge=0.0):
+        """``nsteps`` of the tidal driver's Heun step (main.cpp:211-236): q1 = sp(q + dt R(q)); q = sp((q + q1 + dt R(q1)) / 2),
+        sp(x) = x / (1 + c x^2) on hu and hv, c the sponge array of ``enableVariantB`` or else the scalar ``sponge``.
+        Variant B only. Same check as stepRK2."""
+        check(lib.bdg_sw2dq_step_ssprk2(self._h, float(dt), int(nsteps), int(bool(filter)), float(sponge)))
+
+    def timeSpeedPass(self, count):
+        """Average device milliseconds of variant B's speed pass alone."""
+        ms = c_float()
+        check(lib.bdg_sw2dq_time_speed(self._h, int(count), byref(ms)))
+        return ms.value
+
+    def timeHeun(self, dt, count):
+        """Average device milliseconds per unfiltered Heun step of variant B."""
+        ms = c_float()
+        check(lib.bdg_sw2dq_time(self._h, 2, float(dt), int(count), byref(ms)))
+        return ms.value
+
     def _field(self, a, name):
         return C.as_f64(a, (self.Np, self.K), name)
 
@@ -227,13 +280,16 @@ class NativeDistributedSw2dQuad:
     id reaches the others through ``halo.file_rendezvous`` (or pass ``unique_id``)."""
 
     def __init__(self, plan, order, g=9.81, filter_args=None, device=0, flags=0, unique_id=None, loopback=False, fields=3,
-                 sources=None):
+                 sources=None, variant_b=None):
         """filter_args: (Nc, s) of QuadNodesProvisioner.buildFilter (the script's filter: (0.99 N, 4)); flags as
         Sw2dQuadSolver. loopback=True: this one process computes plan.rank's share of a plan.world-way split and every
         neighbour exchange is a send-to-self of the same size through the real transport (the ghosts then hold this rank's
         own boundary elements: a rehearsal of the exchange on one GPU, not a partitioned result). fields, sources as
         Sw2dQuadSolver, the sources on the rank-local nodes (owned and ghost elements): a dict of arrays, or a function
-        (x, y) -> dict of the rank-local node coordinates."""
+        (x, y) -> dict of the rank-local node coordinates. variant_b: the keyword arguments of
+        Sw2dQuadSolver.enableVariantB, handled as sources is (a dict, or a function (x, y) -> dict; arrays on the rank-local
+        nodes); a missing ``mapO`` is BCmap[2] of the rank-local provisioner (owned elements keep the global mesh's BC tags:
+        tag the open side with MeshManager.setBCType before the plan is built)."""
         from . import pyblitzdg as dg
         from .halo import attach_native, build_local_mesh
 
@@ -248,6 +304,15 @@ class NativeDistributedSw2dQuad:
             ctx = self.nodes.dgContext()
             sources = sources(ctx.x, ctx.y)
         self.solver = Sw2dQuadSolver(nodes=self.nodes, g=g, device=device, flags=flags, fields=fields, sources=sources)
+        if variant_b is not None:
+            ctx = self.nodes.dgContext()
+            vb = dict(variant_b(ctx.x, ctx.y) if callable(variant_b) else variant_b)
+            vb.setdefault("mapO", ctx.BCmap.get(2, []))
+            try:
+                self.solver.enableVariantB(**vb)
+            except Exception:
+                self.solver.close()
+                raise
         self.peer_table = attach_native(self.solver._h, "bdg_sw2dq", plan, unique_id, loopback)
 
     def close(self):
@@ -272,6 +337,15 @@ class NativeDistributedSw2dQuad:
         """The script's predictor / corrector, ghosts refreshed before each evaluation; every rank raises
         NumericalInstability together when max|h| > 1e8 or h has a NaN on any rank's owned elements."""
         check(lib.bdg_sw2dq_step_rk2_exchanged(self.solver._h, float(dt), int(nsteps), int(bool(filter))))
+
+    def step_ssprk2(self, dt, nsteps=1, filter=False, sponge=0.0):
+        """Sw2dQuadSolver.stepSSPRK2 on the partition (variant B): before each evaluation the all-rank global speed and the
+        ghost refresh; same collective check."""
+        check(lib.bdg_sw2dq_step_ssprk2_exchanged(self.solver._h, float(dt), int(nsteps), int(bool(filter)), float(sponge)))
+
+    def global_speed(self):
+        """The global speed of the last evaluation: the same value on every rank."""
+        return self.solver.globalSpeed()
 
     def lserk4_stages(self, dt, nstages):
         """LSERK4 stages with an exchange in front of every stage (same collective check)."""

@@ -399,7 +399,8 @@ int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double*
 int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter);
 /* LSERK4 stages (stage i = count % 5, count reset by set_state), same blow-up check at the end */
 int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages);
-/* HIP-event milliseconds per LSERK4 stage (kind 0) or per RK2 + filter step (kind 1), averaged over count */
+/* HIP-event milliseconds per LSERK4 stage (kind 0) or per RK2 + filter step (kind 1), averaged over count
+ * (kind 2: see bdg_sw2dq_time_speed) */
 int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms);
 int bdg_sw2dq_synchronize(bdg_sw2dq* s);
 size_t bdg_sw2dq_device_bytes(const bdg_sw2dq* s);
@@ -458,6 +459,51 @@ int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int fil
 int bdg_sw2dq_lserk4_stages_exchanged(bdg_sw2dq* s, double dt, int num_stages);
 /* drains both streams, meets every rank (an 8-byte all-reduce), drains again */
 int bdg_sw2dq_barrier(bdg_sw2dq* s);
+/* ---- "variant B" on quadrilaterals: the tidal driver's right-hand side (src/sw2d/main.cpp:279-484; the text above
+ * bdg_sw2d_vb_desc) on a three-field quadrilateral solver, orders 1 to 12, both geometry forms. The descriptor has the
+ * triangle one's fields: H, Hx, Hy, sponge are host (Np, K); mapO holds flat face-node indices k * 4 Nfp + face node, as mapW
+ * (QuadNodesProvisioner's BCmap[2] after buildBCHash); an open-boundary node wins over a wall node where a node is both.
+ * Once, before the solver's first evaluation (afterwards BDG_ERR_ARGUMENT, as set_sources); a four-field solver refuses it
+ * with BDG_ERR_ARGUMENT and stays usable. From then on bdg_sw2dq_rhs, step_rk2, lserk4_stages, time and their _exchanged
+ * forms evaluate variant B at the solver's model time: every evaluation is the speed pass (global Lax-Friedrichs speed,
+ * main.cpp:400-414, left on the device) and the stage launch that reads it. RK2 and Heun steps evaluate twice at the old
+ * time level and advance the time by dt; LSERK4 freezes the tide over its five stages and advances after the last.
+ * Quirks kept as on triangles: the momentum rescale hMstar (huM / hMstar) is NaN for a dry star state, and the
+ * hydrostatic correction of main.cpp:420-421 is identically zero. bdg_sw2dq_compute_dt is unchanged. */
+typedef struct bdg_sw2dq_vb_desc {
+    const double* H;       /* (Np, K)                                    */
+    const double* Hx;      /* (Np, K)                                    */
+    const double* Hy;      /* (Np, K)                                    */
+    const int* mapO;       /* flat face-node indices of open-boundary nodes, or NULL */
+    int num_out;
+    double drag;           /* physParams.CD                              */
+    double coriolis;       /* physParams.f                               */
+    double tide_amplitude; /* reference: 3.0                             */
+    double tide_period;    /* reference: 3600*12.42                      */
+    double tide_ramp;      /* reference: 0.15/3600                       */
+    const double* sponge;  /* (Np, K) or NULL                            */
+} bdg_sw2dq_vb_desc;
+int bdg_sw2dq_enable_variant_b(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* desc);
+int bdg_sw2dq_set_time(bdg_sw2dq* s, double t);
+int bdg_sw2dq_get_time(const bdg_sw2dq* s, double* t);
+/* The global Lax-Friedrichs speed of the most recent variant-B evaluation (on a partition: the all-rank maximum). */
+int bdg_sw2dq_global_speed(bdg_sw2dq* s, double* lam);
+/* Heun / SSP-RK2 of the tidal driver (main.cpp:211-236), variant B only (BDG_ERR_ARGUMENT without):
+ * q1 = sp(q + dt R(q)); q = sp((q + q1 + dt R(q1))/2), sp(x) = x/(1 + c x^2) on hu, hv, the division fused into the stage
+ * store; c is the descriptor's sponge array where it has one, else sponge_coeff (0: plain Heun). Blow-up check as step_rk2. */
+int bdg_sw2dq_step_ssprk2(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff);
+/* On a partition every variant-B evaluation is: the speed pass over the owned elements (it needs no current ghosts), one
+ * 8-byte all-reduce (maximum) on the solver's stream, the exchange, then every owned element, in stream order. These
+ * evaluations are not overlapped: the all-rank speed has to exist before any element starts (as the triangle solver's). */
+int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff);
+/* HIP-event milliseconds of the speed pass alone on the resident state, averaged over count; bdg_sw2dq_time takes kind 2
+ * (one unfiltered Heun step with the sponge of the last bdg_sw2dq_step_ssprk2) on a variant-B solver. */
+int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms);
+/* Host helpers of the tidal set-up, argument lists as the bdg_trinodes_* ones: Hx, Hy = Filter (rx Dr H + sx Ds H,
+ * ry Dr H + sy Ds H) (main.cpp:128-133; bdg_quadnodes_build_filter first), and buildSpongeCoeff (main.cpp:517-553). */
+int bdg_quadnodes_bed_slopes(const bdg_quadnodes* nodes, const double* H, double* Hx, double* Hy);
+int bdg_quadnodes_sponge_coeff(const bdg_quadnodes* nodes, const int* mapO, int num_out, double strength, double radius,
+                               double* coeff);
 
 /* Resident time stepping (state stays in HBM). */
 int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps);          /* 5 fused stages per step */
