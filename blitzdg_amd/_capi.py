@@ -79,6 +79,11 @@ class Sw2dVbDesc(Structure):
                 ("tide_period", c_double), ("tide_ramp", c_double), ("sponge", c_void_p)]
 
 
+class Sw2dqMonitorDesc(Structure):
+    _fields_ = [("weights", c_void_p), ("H", c_void_p), ("num_gauges", c_int), ("gauge_element", c_void_p),
+                ("gauge_r", c_void_p), ("gauge_s", c_void_p), ("stride", c_int), ("capacity", c_int)]
+
+
 class Sw2dCurvedDesc(Structure):
     _fields_ = [("order", c_int), ("num_elements", c_int), ("num_cub", c_int), ("num_gauss", c_int),
                 ("V", c_void_p), ("Filter", c_void_p), ("J", c_void_p),
@@ -237,6 +242,16 @@ _SIGNATURES = {
     "bdg_sw2dq_time_speed": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_quadnodes_bed_slopes": (c_int, [_P, _P, _P, _P]),
     "bdg_quadnodes_sponge_coeff": (c_int, [_P, _P, c_int, c_double, c_double, _P]),
+    "bdg_quadnodes_quadrature_weights": (c_int, [_P, _P]),
+    "bdg_quadnodes_locate_points": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),
+    "bdg_quadnodes_lagrange_basis": (c_int, [_P, _P, c_int, _P]),
+    "bdg_sw2dq_enable_monitor": (c_int, [_P, POINTER(Sw2dqMonitorDesc)]),
+    "bdg_sw2dq_monitor_sample": (c_int, [_P]),
+    "bdg_sw2dq_monitor_count": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2dq_monitor_read": (c_int, [_P, c_int, c_int, _P]),
+    "bdg_sw2dq_monitor_width": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2dq_monitor_reset": (c_int, [_P]),
+    "bdg_sw2dq_monitor_reduce": (c_int, [_P]),
     "bdg_sw2d_step_lserk4": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_lserk4_stages": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_step_rk2": (c_int, [_P, c_double, c_int, c_int]),

@@ -8,11 +8,14 @@
 // The output step (bdg_sw2dq_output_fields) is one launch of sw2d_quad_output_kernel (sw2d_quad_output_kernel.hpp).
 // After bdg_sw2dq_enable_variant_b a three-field solver evaluates the tidal driver's right-hand side instead: the speed pass
 // sw2d_quadb_speed_kernel, then sw2d_quadb_stage_kernel (sw2d_quadb_kernel.hpp), which reads the speed from device memory.
+// After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_quad_monitor_kernel.hpp).
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 #include "sw2d_quadb_kernel.hpp"
+#include "blitzdg/JacobiBuilders.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "blitzdg/MeshManager.hpp"
 #include <algorithm>
@@ -225,6 +228,16 @@ struct bdg_sw2dq {
     bdg_halo::Partition part;
     bdg_halo::Transport halo;
     bdg_halo::TwoChains chains;
+    // run monitor (bdg_sw2dq_enable_monitor): sw2d_quad_monitor_kernel.hpp
+    struct Monitor {
+        bool on = false;
+        int stride = 1, capacity = 0, numGauges = 0, width = 0;
+        int count = 0;        // records taken
+        int reduced = 0;      // records [0, reduced) have been all-reduced
+        long long steps = 0;  // completed steps since set_state / monitor_reset
+        DevBuf<double> w, H, lr, ls, partials, rec, stage;
+        DevBuf<int> element;
+    } mon;
 
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
     long long plane() const { return static_cast<long long>(Np) * ld; }
@@ -379,6 +392,41 @@ struct bdg_sw2dq {
         return count;
     }
 
+    // ---- run monitor
+    // records a stepping call of `steps` further completed steps would take; refused before anything is launched
+    void monitorReserve(long long steps, const char* fn) const {
+        if (!mon.on) return;
+        const long long take = (mon.steps + steps) / mon.stride - mon.steps / mon.stride;
+        if (take > mon.capacity - mon.count)
+            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " monitor records and " +
+                            std::to_string(mon.capacity - mon.count) + " are free (bdg_sw2dq_monitor_read, then bdg_sw2dq_monitor_reset)");
+    }
+    // completed LSERK4 steps among the next `stages` stages
+    long long lserkSteps(long long stages) const {
+        return (stageCount + stages) / blitzdg::LSERK4::numStages - stageCount / blitzdg::LSERK4::numStages;
+    }
+    // one record of the resident state, two launches on the solver's stream
+    void monitorSample() {
+        const int count = part.numOwned > 0 ? part.numOwned : K;
+        const double* Hm = mon.H.p ? mon.H.p : (variantB ? vbH.p : nullptr);
+        const QuadMonParams rp{q.p, mon.w.p, Hm, ld, N, fields, count, quadMonChunk(count), g};
+        hipLaunchKernelGGL(sw2d_quad_monitor_reduce_kernel, dim3(kQuadMonBlocks), dim3(kQuadMonThreads), 0, stream, rp, mon.partials.p);
+        hipCheck(hipGetLastError(), "sw2d_quad_monitor_reduce_kernel launch");
+        const QuadMonFinish fp{mon.partials.p, q.p, Hm, mon.element.p, mon.lr.p, mon.ls.p, mon.rec.p, ld, N, fields, count,
+                               mon.numGauges, mon.capacity, mon.count, timeNow};
+        hipLaunchKernelGGL(sw2d_quad_monitor_finish_kernel, dim3(1), dim3(kQuadMonThreads), 0, stream, fp);
+        hipCheck(hipGetLastError(), "sw2d_quad_monitor_finish_kernel launch");
+        ++mon.count;
+    }
+    // after every completed step of a stepping call. two: the call runs the two-chain schedule, whose chains are joined
+    // in front of the sample and started again behind it (the sample reads columns the exchange stream wrote)
+    void stepDone(bool two = false) {
+        if (!mon.on || ++mon.steps % mon.stride != 0) return;
+        if (two) chains.end(stream, halo.stream);
+        monitorSample();
+        if (two) chains.begin(stream, halo.stream);
+    }
+
     // ---- partitioned runs
     void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, fields * Np, K, on); }
     // one evaluation of the elements [kBegin, kEnd) on `on`
@@ -421,6 +469,7 @@ struct bdg_sw2dq {
             p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;
             evaluateExchanged(two, QMODE_COMBINE, filter, p);
             timeNow += dt;
+            stepDone(two);
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -437,6 +486,7 @@ struct bdg_sw2dq {
             evaluateExchanged(two, QMODE_LSERK, false, p);
             std::swap(q.p, q1.p);
             lserkAdvance(dt);
+            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone(two);
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -689,6 +739,7 @@ int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const d
         s->upload(s->q.p + 2 * plane, hv, s->Np);
         s->res.zero(s->stream);
         s->stageCount = 0;
+        s->mon.steps = 0;
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
@@ -863,9 +914,13 @@ int bdg_sw2dq_step_ssprk2(bdg_sw2dq* s, double dt, int num_steps, int filter, do
         if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2: num_steps < 0");
         if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2: variant B is not enabled (the Heun step is the tidal driver's)");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2: filter requested but the solver has no Filter");
+        s->monitorReserve(num_steps, "bdg_sw2dq_step_ssprk2");
         s->use();
         s->spongeC = sponge_coeff;
-        for (int i = 0; i < num_steps; ++i) s->heunStep(dt, filter != 0, false, false);
+        for (int i = 0; i < num_steps; ++i) {
+            s->heunStep(dt, filter != 0, false, false);
+            s->stepDone();
+        }
         s->checkBlowUp();
     });
 }
@@ -881,6 +936,7 @@ int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const 
         for (int c = 0; c < 4; ++c) s->upload(s->q.p + c * plane, in[c], s->Np);
         s->res.zero(s->stream);
         s->stageCount = 0;
+        s->mon.steps = 0;
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
@@ -989,8 +1045,12 @@ int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter) {
         requireSolver(s, "bdg_sw2dq_step_rk2");
         if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2: num_steps < 0");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2: filter requested but the solver has no Filter");
+        s->monitorReserve(num_steps, "bdg_sw2dq_step_rk2");
         s->use();
-        for (int i = 0; i < num_steps; ++i) s->rk2Step(dt, filter != 0);
+        for (int i = 0; i < num_steps; ++i) {
+            s->rk2Step(dt, filter != 0);
+            s->stepDone();
+        }
         s->checkBlowUp();
     });
 }
@@ -999,8 +1059,12 @@ int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_lserk4_stages");
         if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages: num_stages < 0");
+        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages");
         s->use();
-        for (int i = 0; i < num_stages; ++i) s->lserkStage(dt);
+        for (int i = 0; i < num_stages; ++i) {
+            s->lserkStage(dt);
+            if (s->stageCount % blitzdg::LSERK4::numStages == 0) s->stepDone();
+        }
         s->checkBlowUp();
     });
 }
@@ -1079,6 +1143,7 @@ int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int fil
         requireComm(s, "bdg_sw2dq_step_rk2_exchanged");
         if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2_exchanged: num_steps < 0");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2_exchanged: filter requested but the solver has no Filter");
+        s->monitorReserve(num_steps, "bdg_sw2dq_step_rk2_exchanged");
         s->use();
         s->stepRk2Exchanged(dt, num_steps, filter != 0);
         s->checkBlowUp(s->part.numOwned, true);
@@ -1091,9 +1156,13 @@ int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int 
         if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: num_steps < 0");
         if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: variant B is not enabled");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: filter requested but the solver has no Filter");
+        s->monitorReserve(num_steps, "bdg_sw2dq_step_ssprk2_exchanged");
         s->use();
         s->spongeC = sponge_coeff;
-        for (int i = 0; i < num_steps; ++i) s->heunStep(dt, filter != 0, true, false);
+        for (int i = 0; i < num_steps; ++i) {
+            s->heunStep(dt, filter != 0, true, false);
+            s->stepDone();
+        }
         s->checkBlowUp(s->part.numOwned, true);
     });
 }
@@ -1102,6 +1171,7 @@ int bdg_sw2dq_lserk4_stages_exchanged(bdg_sw2dq* s, double dt, int num_stages) {
     return guard([&] {
         requireComm(s, "bdg_sw2dq_lserk4_stages_exchanged");
         if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages_exchanged: num_stages < 0");
+        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages_exchanged");
         s->use();
         s->lserkStagesExchanged(dt, num_stages);
         s->checkBlowUp(s->part.numOwned, true);
@@ -1113,6 +1183,152 @@ int bdg_sw2dq_barrier(bdg_sw2dq* s) {
         requireComm(s, "bdg_sw2dq_barrier");
         s->use();
         bdg_halo::barrier(s->halo, s->stream);
+    });
+}
+
+// ---- run monitor
+int bdg_sw2dq_enable_monitor(bdg_sw2dq* s, const bdg_sw2dq_monitor_desc* d) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_enable_monitor");
+        if (!d || !d->weights) throw arg_error("bdg_sw2dq_enable_monitor: the descriptor and its weights are required");
+        if (s->mon.on) throw arg_error("bdg_sw2dq_enable_monitor: the monitor is already enabled");
+        if (d->stride < 1 || d->capacity < 1) throw arg_error("bdg_sw2dq_enable_monitor: stride and capacity must be >= 1");
+        const int ng = d->num_gauges, Nq = s->N + 1;
+        if (ng < 0 || (ng > 0 && (!d->gauge_element || !d->gauge_r || !d->gauge_s)))
+            throw arg_error("bdg_sw2dq_enable_monitor: bad gauge list");
+        for (int i = 0; i < ng; ++i) {
+            if (d->gauge_element[i] < 0 || d->gauge_element[i] >= s->K)
+                throw arg_error("bdg_sw2dq_enable_monitor: gauge " + std::to_string(i) + " names an element outside [0, K)");
+            if (!(std::fabs(d->gauge_r[i]) <= 1.0 + 1e-10) || !(std::fabs(d->gauge_s[i]) <= 1.0 + 1e-10))
+                throw arg_error("bdg_sw2dq_enable_monitor: gauge " + std::to_string(i) + " lies outside its element (|r|, |s| <= 1)");
+        }
+        const int width = 7 + s->fields + ng * s->fields;
+        // the 1-D basis at every gauge, on the solver's Gauss-Lobatto points
+        blitzdg::real_vector_type r1d(Nq);
+        blitzdg::JacobiBuilders().computeGaussLobottoPoints(0.0, 0.0, s->N, r1d);
+        std::vector<double> lr(static_cast<size_t>(std::max(1, ng)) * Nq, 0.0), ls(lr.size(), 0.0);
+        for (int i = 0; i < ng; ++i) {
+            blitzdg::QuadNodesProvisioner::lagrangeBasis1D(r1d.data(), Nq, d->gauge_r[i], lr.data() + static_cast<size_t>(i) * Nq);
+            blitzdg::QuadNodesProvisioner::lagrangeBasis1D(r1d.data(), Nq, d->gauge_s[i], ls.data() + static_cast<size_t>(i) * Nq);
+        }
+        s->use();
+        bdg_sw2dq::Monitor& m = s->mon;
+        const size_t bytesBefore = s->bytes;
+        try {
+            const long long plane = s->plane();
+            m.w.alloc(plane, s->bytes, s->stream);
+            s->upload(m.w.p, d->weights, s->Np);
+            if (d->H) {
+                m.H.alloc(plane, s->bytes, s->stream);
+                s->upload(m.H.p, d->H, s->Np);
+            }
+            m.lr.alloc(lr.size(), s->bytes);
+            m.ls.alloc(ls.size(), s->bytes);
+            m.element.alloc(static_cast<size_t>(std::max(1, ng)), s->bytes, s->stream);
+            hipCheck(hipMemcpyAsync(m.lr.p, lr.data(), lr.size() * sizeof(double), hipMemcpyHostToDevice, s->stream), "hipMemcpy (basis)");
+            hipCheck(hipMemcpyAsync(m.ls.p, ls.data(), ls.size() * sizeof(double), hipMemcpyHostToDevice, s->stream), "hipMemcpy (basis)");
+            if (ng > 0)
+                hipCheck(hipMemcpyAsync(m.element.p, d->gauge_element, static_cast<size_t>(ng) * sizeof(int), hipMemcpyHostToDevice,
+                                        s->stream), "hipMemcpy (gauges)");
+            m.partials.alloc(static_cast<size_t>(kQuadMonBlocks) * kQuadMonPartial, s->bytes, s->stream);
+            m.rec.alloc(static_cast<size_t>(width) * d->capacity, s->bytes, s->stream);
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
+        } catch (...) { // nothing changes: the solver stays without a monitor
+            (void)hipStreamSynchronize(s->stream);
+            for (DevBuf<double>* b : {&m.w, &m.H, &m.lr, &m.ls, &m.partials, &m.rec}) b->release();
+            m.element.release();
+            s->bytes = bytesBefore;
+            throw;
+        }
+        m.on = true;
+        m.stride = d->stride; m.capacity = d->capacity; m.numGauges = ng; m.width = width;
+    });
+}
+
+namespace {
+void requireMonitor(const bdg_sw2dq* s, const char* fn) {
+    requireSolver(s, fn);
+    if (!s->mon.on) throw arg_error(std::string(fn) + ": the monitor is not enabled (bdg_sw2dq_enable_monitor)");
+}
+} // namespace
+
+int bdg_sw2dq_monitor_sample(bdg_sw2dq* s) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_sample");
+        if (s->mon.count >= s->mon.capacity) throw arg_error("bdg_sw2dq_monitor_sample: no free record (bdg_sw2dq_monitor_reset)");
+        s->use();
+        s->monitorSample();
+    });
+}
+
+int bdg_sw2dq_monitor_count(const bdg_sw2dq* s, int* n) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_count");
+        if (!n) throw arg_error("bdg_sw2dq_monitor_count: NULL argument");
+        *n = s->mon.count;
+    });
+}
+
+int bdg_sw2dq_monitor_width(const bdg_sw2dq* s, int* width) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_width");
+        if (!width) throw arg_error("bdg_sw2dq_monitor_width: NULL argument");
+        *width = s->mon.width;
+    });
+}
+
+int bdg_sw2dq_monitor_read(bdg_sw2dq* s, int first, int count, double* records) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_read");
+        if (first < 0 || count < 0 || first > s->mon.count - count || (count > 0 && !records))
+            throw arg_error("bdg_sw2dq_monitor_read: bad record range");
+        if (count == 0) return;
+        s->use();
+        const int width = s->mon.width;
+        std::vector<double> cols(static_cast<size_t>(width) * count); // by column, as on the device
+        hipCheck(hipMemcpy2DAsync(cols.data(), count * sizeof(double), s->mon.rec.p + first, s->mon.capacity * sizeof(double),
+                                  count * sizeof(double), width, hipMemcpyDeviceToHost, s->stream), "hipMemcpy2D (records)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        for (int n = 0; n < count; ++n)
+            for (int c = 0; c < width; ++c) records[static_cast<size_t>(n) * width + c] = cols[static_cast<size_t>(c) * count + n];
+    });
+}
+
+int bdg_sw2dq_monitor_reset(bdg_sw2dq* s) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_reset");
+        s->mon.count = 0;
+        s->mon.reduced = 0;
+        s->mon.steps = 0;
+    });
+}
+
+int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s) {
+    return guard([&] {
+        requireMonitor(s, "bdg_sw2dq_monitor_reduce");
+        bdg_halo::requireComm(s->halo, "bdg_sw2dq", "bdg_sw2dq_monitor_reduce");
+        bdg_sw2dq::Monitor& m = s->mon;
+        const int n = m.count - m.reduced;
+        if (n <= 0) return;
+        s->use();
+        // the new records of every column but t, packed by column; the columns that share an operator are contiguous
+        const int cols = m.width - 1, nf = s->fields;
+        if (!m.stage.p) m.stage.alloc(static_cast<size_t>(cols) * m.capacity, s->bytes);
+        hipCheck(hipMemcpy2DAsync(m.stage.p, n * sizeof(double), m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double),
+                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
+        auto reduce = [&](int firstCol, int numCols, ncclRedOp_t op) {
+            if (numCols <= 0) return;
+            double* at = m.stage.p + static_cast<size_t>(firstCol) * n;
+            bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(at, at, static_cast<size_t>(numCols) * n, ncclDouble, op, s->halo.comm, s->stream),
+                                "ncclAllReduce");
+        };
+        reduce(0, nf + 1, ncclSum);                 // integrals and E
+        reduce(nf + 1, 1, ncclMin);                 // min h
+        reduce(nf + 2, 3, ncclMax);                 // max h, max|hu|, max|hv|
+        reduce(nf + 5, cols - (nf + 5), ncclSum);   // NaN count and gauges
+        hipCheck(hipMemcpy2DAsync(m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double), m.stage.p, n * sizeof(double),
+                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
+        m.reduced = m.count;
     });
 }
 

@@ -360,6 +360,33 @@ int bdg_quadnodes_split_elements(const bdg_quadnodes* nodes, const double* field
     });
 }
 
+// ---- set-up of the run monitor (bdg_sw2dq_enable_monitor): weights, point location, 1-D basis values
+int bdg_quadnodes_quadrature_weights(const bdg_quadnodes* nodes, double* w) {
+    return guard([&] {
+        if (!nodes || !w) throw bdg_detail::arg_error("bdg_quadnodes_quadrature_weights: NULL argument");
+        real_matrix_type m;
+        nodes->prov.quadratureWeights(m);
+        std::copy(m.data(), m.data() + static_cast<size_t>(m.rows()) * m.cols(), w);
+    });
+}
+
+int bdg_quadnodes_locate_points(const bdg_quadnodes* nodes, const double* x, const double* y, int n, int* element, double* r,
+                                double* s) {
+    return guard([&] {
+        if (!nodes || n < 0 || (n > 0 && (!x || !y || !element || !r || !s)))
+            throw bdg_detail::arg_error("bdg_quadnodes_locate_points: bad argument");
+        nodes->prov.locatePoints(x, y, n, element, r, s);
+    });
+}
+
+int bdg_quadnodes_lagrange_basis(const bdg_quadnodes* nodes, const double* r, int n, double* basis) {
+    return guard([&] {
+        if (!nodes || n < 0 || (n > 0 && (!r || !basis))) throw bdg_detail::arg_error("bdg_quadnodes_lagrange_basis: bad argument");
+        const int Nq = nodes->prov.get_NOrder() + 1;
+        for (int p = 0; p < n; ++p) nodes->prov.lagrangeBasis1D(r[p], basis + static_cast<size_t>(p) * Nq);
+    });
+}
+
 int bdg_quadnodes_write_vtu(const bdg_quadnodes* nodes, const char* path, const double* field, const char* field_name) {
     return guard([&] {
         if (!nodes || !path || !field || !field_name) throw bdg_detail::arg_error("bdg_quadnodes_write_vtu: NULL argument");

@@ -139,6 +139,117 @@ void QuadNodesProvisioner::splitElements(const real_matrix_type& x, const real_m
             }
 }
 
+std::vector<real_type> QuadNodesProvisioner::gaussLobattoWeights() const {
+    // w_a = 2 / (N (N+1) P_N(r_a)^2) with the orthonormal P~_N = sqrt((2N+1)/2) P_N of V1's last column
+    const index_type N = NOrder, Nq = N + 1;
+    std::vector<real_type> w1(Nq);
+    for (index_type a = 0; a < Nq; ++a)
+        w1[a] = static_cast<real_type>(2 * N + 1) / (static_cast<real_type>(N) * static_cast<real_type>(N + 1) * V1(a, N) * V1(a, N));
+    return w1;
+}
+
+void QuadNodesProvisioner::quadratureWeights(real_matrix_type& w) const {
+    const index_type Nq = NOrder + 1, Np = NumLocalPoints, K = NumElements;
+    const std::vector<real_type> w1 = gaussLobattoWeights();
+    w.resizeUninitialized(Np, K);
+    for (index_type j = 0; j < Nq; ++j)
+        for (index_type i = 0; i < Nq; ++i) {
+            const index_type n = Nq * j + i;
+            const real_type ww = w1[j] * w1[i];
+            for (index_type k = 0; k < K; ++k) w(n, k) = ww * J(n, k);
+        }
+}
+
+void QuadNodesProvisioner::lagrangeBasis1D(const real_type* nodes, index_type n, real_type r, real_type* basis) {
+    for (index_type a = 0; a < n; ++a)
+        if (r == nodes[a]) { // on a node: the unit vector, exactly
+            for (index_type b = 0; b < n; ++b) basis[b] = b == a ? 1.0 : 0.0;
+            return;
+        }
+    // second barycentric form: l_a(r) = (c_a / (r - x_a)) / sum_b c_b / (r - x_b), c_a = 1 / prod_{b != a} (x_a - x_b)
+    real_type sum = 0;
+    for (index_type a = 0; a < n; ++a) {
+        real_type c = 1;
+        for (index_type b = 0; b < n; ++b)
+            if (b != a) c *= nodes[a] - nodes[b];
+        basis[a] = 1 / (c * (r - nodes[a]));
+        sum += basis[a];
+    }
+    for (index_type a = 0; a < n; ++a) basis[a] /= sum;
+}
+
+void QuadNodesProvisioner::locatePoints(const real_type* px, const real_type* py, index_type n, index_type* element,
+                                        real_type* rOut, real_type* sOut) const {
+    const index_type Nq = NOrder + 1, Np = NumLocalPoints, K = NumElements;
+    constexpr real_type inside = 1.0 + 1e-10;
+    // bounding boxes of the elements' nodes, widened by 1e-9 of their size
+    std::vector<real_type> box(static_cast<std::size_t>(4) * K);
+    for (index_type k = 0; k < K; ++k) {
+        real_type x0 = xGrid(0, k), x1 = x0, y0 = yGrid(0, k), y1 = y0;
+        for (index_type m = 1; m < Np; ++m) {
+            x0 = std::min(x0, xGrid(m, k)); x1 = std::max(x1, xGrid(m, k));
+            y0 = std::min(y0, yGrid(m, k)); y1 = std::max(y1, yGrid(m, k));
+        }
+        const real_type pad = 1e-9 * std::max(x1 - x0, y1 - y0);
+        box[4 * k] = x0 - pad; box[4 * k + 1] = x1 + pad; box[4 * k + 2] = y0 - pad; box[4 * k + 3] = y1 + pad;
+    }
+    detail::parallelFor(n, [&](index_type p) {
+        std::vector<real_type> X(Np), Y(Np), Xr(Np), Xs(Np), Yr(Np), Ys(Np), lr(Nq), ls(Nq);
+        element[p] = -1;
+        rOut[p] = 0;
+        sOut[p] = 0;
+        for (index_type k = 0; k < K; ++k) {
+            if (px[p] < box[4 * k] || px[p] > box[4 * k + 1] || py[p] < box[4 * k + 2] || py[p] > box[4 * k + 3]) continue;
+            // the element's nodal map and its derivatives at the nodes (the derivative of the interpolant is the
+            // interpolant of D1 applied to the nodal values)
+            // coordinates relative to the element's first node: the rounding of the map is then that of the element's
+            // size, not of its distance from the origin (a mesh in UTM coordinates has 1e6 m offsets and 1e2 m cells)
+            const real_type x0 = xGrid(0, k), y0 = yGrid(0, k);
+            for (index_type m = 0; m < Np; ++m) { X[m] = xGrid(m, k) - x0; Y[m] = yGrid(m, k) - y0; }
+            const real_type qx = px[p] - x0, qy = py[p] - y0;
+            for (index_type j = 0; j < Nq; ++j)
+                for (index_type i = 0; i < Nq; ++i) {
+                    real_type a = 0, b = 0, c = 0, d = 0;
+                    for (index_type m = 0; m < Nq; ++m) {
+                        a += D1(j, m) * X[Nq * m + i]; b += D1(j, m) * Y[Nq * m + i];
+                        c += D1(i, m) * X[Nq * j + m]; d += D1(i, m) * Y[Nq * j + m];
+                    }
+                    Xr[Nq * j + i] = a; Yr[Nq * j + i] = b; Xs[Nq * j + i] = c; Ys[Nq * j + i] = d;
+                }
+            real_type r = 0, s = 0;
+            bool converged = false;
+            for (int it = 0; it < 50 && !converged; ++it) {
+                lagrangeBasis1D(r, lr.data());
+                lagrangeBasis1D(s, ls.data());
+                real_type x = 0, y = 0, xr = 0, xs = 0, yr = 0, ys = 0;
+                for (index_type j = 0; j < Nq; ++j)
+                    for (index_type i = 0; i < Nq; ++i) {
+                        const real_type l = lr[j] * ls[i];
+                        const index_type m = Nq * j + i;
+                        x += l * X[m]; y += l * Y[m];
+                        xr += l * Xr[m]; xs += l * Xs[m]; yr += l * Yr[m]; ys += l * Ys[m];
+                    }
+                const real_type det = xr * ys - xs * yr;
+                if (!(std::fabs(det) > 0)) break;
+                const real_type fx = qx - x, fy = qy - y;
+                const real_type dr = (ys * fx - xs * fy) / det, ds = (xr * fy - yr * fx) / det;
+                r += dr;
+                s += ds;
+                if (!(std::fabs(r) < 10 && std::fabs(s) < 10)) break; // the point is far outside this element
+                // Newton converges quadratically: a step of 1e-12 leaves an error at the rounding of the map, far below
+                // the 1e-10 of the inside test. (A smaller figure is below that rounding and may never be met.)
+                converged = std::max(std::fabs(dr), std::fabs(ds)) <= 1e-12;
+            }
+            if (converged && std::fabs(r) <= inside && std::fabs(s) <= inside) {
+                element[p] = k;
+                rOut[p] = r;
+                sOut[p] = s;
+                break; // ascending k: the lowest element index wins
+            }
+        }
+    }, 8);
+}
+
 void QuadNodesProvisioner::buildNodes() {
     const index_type N = NOrder, Nq = N + 1, Np = NumLocalPoints;
     r1d.resize(Nq);

@@ -451,6 +451,33 @@ class QuadNodesProvisioner:
         check(lib.bdg_quadnodes_split_operators(self._h, C.ptr(IM), C.ptr(I1), C.ptr(quads)))
         return IM, I1, quads
 
+    def quadratureWeights(self):
+        """(Np, K) collocated quadrature weights w1[j] w1[i] J at node (N+1) j + i, w1 the 1-D Gauss-Lobatto weights: the sum
+        of ``w * f`` is the integral of the nodal field f (what ``Sw2dQuadSolver.enableMonitor`` integrates with)."""
+        _, Np, _, K = self._dims()
+        w = np.empty((Np, K))
+        check(lib.bdg_quadnodes_quadrature_weights(self._h, C.ptr(w)))
+        return w
+
+    def locatePoints(self, x, y):
+        """(element, r, s) of the points (x[p], y[p]): the element that contains each and its reference coordinates, by
+        Newton iteration on the element's nodal map. A point on a shared edge or vertex goes to the lowest element index; a
+        point in no element gets element -1."""
+        x, y = C.as_f64(x).reshape(-1), C.as_f64(y).reshape(-1)
+        if x.size != y.size:
+            raise ValueError("locatePoints: x and y must have the same length")
+        el, r, s = np.empty(x.size, dtype=np.int32), np.empty(x.size), np.empty(x.size)
+        check(lib.bdg_quadnodes_locate_points(self._h, C.ptr(x), C.ptr(y), x.size, C.ptr(el), C.ptr(r), C.ptr(s)))
+        return el, r, s
+
+    def lagrangeBasis(self, r):
+        """(n, N+1): the 1-D Lagrange basis of the Gauss-Lobatto points at the abscissae ``r`` (barycentric formula; an
+        abscissa that equals a node bit for bit gives the exact unit vector)."""
+        r = C.as_f64(r).reshape(-1)
+        out = np.empty((r.size, self._dims()[0] + 1))
+        check(lib.bdg_quadnodes_lagrange_basis(self._h, C.ptr(r), r.size, C.ptr(out)))
+        return out
+
     def dgContext(self):
         return DGContext2D(self)
 

@@ -219,6 +219,62 @@ class Sw2dQuadSolver:
         check(lib.bdg_sw2dq_time_output(self._h, C.ptr(Hh), C.ptr(self._lattice(lattice)), int(count), byref(ms)))
         return ms.value
 
+    def enableMonitor(self, nodes, H=None, gauges=None, stride=1, capacity=4096):
+        """Switches on the run monitor: from now on stepRK2, stepSSPRK2 and lserk4Stages (a step is the fifth stage) record the
+        mass, momentum, tracer and energy integrals, min / max h, max|hu|, max|hv|, a NaN count and the primitive fields at the
+        ``gauges`` after every ``stride``-th completed step, on the device and without waiting for it; ``capacity`` records
+        are held there. ``nodes``: the QuadNodesProvisioner of the solver's mesh (weights and point location). ``H``: (Np, K)
+        still-water depth of eta = h - H and of the potential energy (a variant-B solver uses its own without one).
+        ``gauges``: (n, 2) array of x, y, located with ``nodes.locatePoints`` (a gauge in no element raises ValueError), or a
+        tuple (element, r, s) of reference coordinates. Once per solver."""
+        shape = (self.Np, self.K)
+        w = C.as_f64(nodes.quadratureWeights(), shape, "weights")
+        Hh = None if H is None else C.as_f64(H, shape, "H")
+        if gauges is None:
+            el, r, s = np.empty(0, np.int32), np.empty(0), np.empty(0)
+        elif isinstance(gauges, tuple):
+            el, r, s = C.as_i32(gauges[0]).reshape(-1), C.as_f64(gauges[1]).reshape(-1), C.as_f64(gauges[2]).reshape(-1)
+            if not (el.size == r.size == s.size):
+                raise ValueError("gauges: element, r and s must have the same length")
+        else:
+            xy = C.as_f64(gauges)
+            if xy.ndim != 2 or xy.shape[1] != 2:
+                raise ValueError("gauges: expected an (n, 2) array of x, y")
+            el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
+            if (el < 0).any():
+                raise ValueError(f"gauges {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+        d = C.Sw2dqMonitorDesc(C.ptr(w), C.ptr(Hh), el.size, C.ptr(el) if el.size else None, C.ptr(r) if el.size else None,
+                               C.ptr(s) if el.size else None, int(stride), int(capacity))
+        check(lib.bdg_sw2dq_enable_monitor(self._h, byref(d)))
+        self.numGauges = int(el.size)
+
+    def sampleMonitor(self):
+        """One record of the resident state now (at the model time ``getTime()``)."""
+        check(lib.bdg_sw2dq_monitor_sample(self._h))
+
+    def resetMonitor(self):
+        """Drops the records held on the device and restarts the step count."""
+        check(lib.bdg_sw2dq_monitor_reset(self._h))
+
+    def monitorRecordArray(self):
+        """The records as a (records, width) array in the layout of include/blitzdg_hip.h; waits for the solver's stream."""
+        n, width = C.c_int(), C.c_int()
+        check(lib.bdg_sw2dq_monitor_count(self._h, byref(n)))
+        check(lib.bdg_sw2dq_monitor_width(self._h, byref(width)))
+        out = np.empty((n.value, width.value))
+        check(lib.bdg_sw2dq_monitor_read(self._h, 0, n.value, C.ptr(out)))
+        return out
+
+    def monitorRecords(self):
+        """The records taken so far as a dict of arrays, one entry per record: ``t``, ``mass``, ``momentum`` (records, 2),
+        ``tracer`` (zeros on three fields), ``energy``, ``hmin``, ``hmax``, ``humax``, ``hvmax``, ``nan`` and ``gauges``
+        (records, n, fields) holding eta, u, v (, N)."""
+        a, nf = self.monitorRecordArray(), self.fields
+        rec = {"t": a[:, 0], "mass": a[:, 1], "momentum": a[:, 2:4], "tracer": a[:, 4] if nf == 4 else np.zeros(len(a)),
+               "energy": a[:, nf + 1], "hmin": a[:, nf + 2], "hmax": a[:, nf + 3], "humax": a[:, nf + 4], "hvmax": a[:, nf + 5],
+               "nan": a[:, nf + 6], "gauges": a[:, nf + 7:].reshape(len(a), -1, nf)}
+        return {k: np.ascontiguousarray(v) for k, v in rec.items()}
+
     def computeDt(self, CFL):
         """(dt, speed) from the resident state: dt = CFL / ((N+1)^2 * 0.5 * speed), speed the face-node maximum of
         |Fscale| (|u| + sqrt(g h)); on a partition the maximum over every rank. Raises NumericalInstability on NaN."""
@@ -393,6 +449,42 @@ class NativeDistributedSw2dQuad:
                     f.write('  </PUnstructuredGrid>\n</VTKFile>\n')
                 paths.append(index)
         return paths
+
+    def enable_monitor(self, H=None, gauges=None, stride=1, capacity=4096, global_nodes=None):
+        """Sw2dQuadSolver.enableMonitor on the partition: the integrals and extrema cover this rank's owned elements, and each
+        gauge is evaluated by the rank that owns its element while the other ranks' entries stay 0 until ``monitor_records``
+        adds them up. ``gauges`` is the same list on every rank, in the numbering of the global mesh: a tuple
+        (global element, r, s), or an (n, 2) array of x, y that is located on ``global_nodes``, a QuadNodesProvisioner of the
+        global mesh (``locatePoints``: a point on a shared edge goes to the lowest global element, so exactly one rank owns
+        it). ``H`` on the rank-local nodes. A gauge in no element raises ValueError on every rank."""
+        n_own = self.plan.num_owned
+        loc = None
+        if gauges is not None:
+            if isinstance(gauges, tuple):
+                gel, r, s = (np.asarray(a).reshape(-1) for a in gauges)
+            else:
+                xy = C.as_f64(gauges)
+                if xy.ndim != 2 or xy.shape[1] != 2:
+                    raise ValueError("gauges: expected an (n, 2) array of x, y")
+                if global_nodes is None:
+                    raise ValueError("gauges given as x, y need `global_nodes`, a QuadNodesProvisioner of the global mesh")
+                gel, r, s = global_nodes.locatePoints(xy[:, 0], xy[:, 1])
+            if (np.asarray(gel) < 0).any():
+                raise ValueError(f"gauges {np.nonzero(np.asarray(gel) < 0)[0].tolist()} lie in no element of the mesh")
+            local = {int(g): i for i, g in enumerate(np.asarray(self.plan.own_global))}
+            # a gauge of another rank names a ghost column, which the device leaves at 0
+            el = np.array([local.get(int(g), n_own) for g in gel], dtype=np.int32)
+            mine = el < n_own
+            if (~mine).any() and self.solver.K <= n_own:
+                raise ValueError("a gauge belongs to another rank, but this rank has no ghost element to name for it")
+            loc = (el, np.where(mine, r, 0.0), np.where(mine, s, 0.0))
+        self.solver.enableMonitor(self.nodes, H=H, gauges=loc, stride=stride, capacity=capacity)
+
+    def monitor_records(self):
+        """Sw2dQuadSolver.monitorRecords of the whole mesh (collective): the records not yet reduced are all-reduced on the
+        device (sums for the integrals, the NaN count and the gauges, min / max for the extrema), then read."""
+        check(lib.bdg_sw2dq_monitor_reduce(self.solver._h))
+        return self.solver.monitorRecords()
 
     def owned_mass(self, field=0):
         """Integral of h (field=3: of the tracer hN) over the owned elements: sum of w J h with w the tensor Gauss-Lobatto

@@ -48,6 +48,22 @@ public:
     /// and the local connectivity of the N^2 small quadrilaterals (lattice point indices, 4 per quadrilateral).
     void splitOperators(real_matrix_type& IM, real_matrix_type& I1, std::vector<index_type>& localE2V) const;
 
+    /// The N+1 Gauss-Lobatto quadrature weights, w1[a] = (2N+1) / (N (N+1) V1(a, N)^2): the row sums of the 1-D mass matrix
+    /// (V1 V1^T)^-1.
+    std::vector<real_type> gaussLobattoWeights() const;
+    /// Collocated quadrature weights (Np, K): w((N+1) j + i, k) = w1[j] w1[i] J((N+1) j + i, k).
+    void quadratureWeights(real_matrix_type& w) const;
+    /// The N+1 Lagrange basis values of the nodes `nodes` at abscissa r (barycentric formula); an abscissa that equals a
+    /// node bit for bit gives the exact unit vector.
+    static void lagrangeBasis1D(const real_type* nodes, index_type n, real_type r, real_type* basis);
+    /// ... of this provisioner's Gauss-Lobatto points.
+    void lagrangeBasis1D(real_type r, real_type* basis) const { lagrangeBasis1D(r1d.data(), NOrder + 1, r, basis); }
+    /// For each point (x[p], y[p]) the element that contains it and its reference coordinates: Newton iteration on the
+    /// element's nodal map x(r, s), y(r, s), candidates by element bounding boxes. |r|, |s| <= 1 + 1e-10 is inside; a point
+    /// on a shared edge or vertex goes to the lowest element index; a point in no element gets element -1 (r = s = 0).
+    void locatePoints(const real_type* x, const real_type* y, index_type n, index_type* element, real_type* r,
+                      real_type* s) const;
+
     void buildNodes();
     void buildLift();
     void buildPhysicalGrid();
@@ -64,6 +80,7 @@ public:
     const real_matrix_type& get_yGrid() const { return yGrid; }
     const real_vector_type& get_rGrid() const { return rGrid; }
     const real_vector_type& get_sGrid() const { return sGrid; }
+    const real_vector_type& get_r1d() const { return r1d; }
     const real_matrix_type& get_V() const { return V; }
     const real_matrix_type& get_Vinv() const { return Vinv; }
     const real_matrix_type& get_Dr() const { return Dr; }

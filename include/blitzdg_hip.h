@@ -504,6 +504,57 @@ int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms);
 int bdg_quadnodes_bed_slopes(const bdg_quadnodes* nodes, const double* H, double* Hx, double* Hy);
 int bdg_quadnodes_sponge_coeff(const bdg_quadnodes* nodes, const int* mapO, int num_out, double strength, double radius,
                                double* coeff);
+/* ---- run monitor: conservation diagnostics and gauges recorded on the device during the stepping calls, with no host round
+ * trip and no state download (csrc/hip/sw2d_quad_monitor_kernel.hpp). Host set-up, from a quadrilateral provisioner:
+ * quadrature_weights: w (Np, K), w[(N+1) j + i, k] = w1[j] w1[i] J[(N+1) j + i, k], w1 the 1-D Gauss-Lobatto weights (the row
+ * sums of the 1-D mass matrix). locate_points: for each (x[p], y[p]) the element that contains it and its reference
+ * coordinates, by Newton iteration on the element's own nodal map (either geometry form); |r|, |s| <= 1 + 1e-10 counts as
+ * inside, a point on a shared edge or vertex goes to the lowest element index, a point in no element gets element -1.
+ * lagrange_basis: basis (n, N+1), the 1-D Lagrange basis of the Gauss-Lobatto points at r[p] (barycentric formula; an
+ * abscissa that equals a node bit for bit gives the exact unit vector): what the gauges interpolate with. */
+int bdg_quadnodes_quadrature_weights(const bdg_quadnodes* nodes, double* w);
+int bdg_quadnodes_locate_points(const bdg_quadnodes* nodes, const double* x, const double* y, int n, int* element, double* r,
+                                double* s);
+int bdg_quadnodes_lagrange_basis(const bdg_quadnodes* nodes, const double* r, int n, double* basis);
+/* One record is `width` doubles, width = 10 + 3 num_gauges (four fields: 11 + 4 num_gauges):
+ *   [t, int h, int hu, int hv, (int hN,) E, min h, max h, max|hu|, max|hv|, NaN count, then per gauge eta, u, v (, N)]
+ * t: the model time of the sample (bdg_sw2dq_get_time). Integrals: sum of w f over the nodes of the elements [0, K) (after
+ * set_partition: the owned ones). E = int (hu^2 + hv^2) / (2 h) + g (h - H)^2 / 2, H = 0 without one. Extrema skip NaNs; the NaN
+ * count covers every field of the state. Gauges: eta = h - H, u = hu / h, v = hv / h (N = hN / h) formed at the nodes of the
+ * gauge's element and interpolated along r and then along s, each sum in ascending order and without contraction (the rule
+ * of bdg_sw2dq_output_fields), so a gauge on a node is that node's output value bit for bit. The summation order of the
+ * integrals is fixed (a fixed grid, a fixed element range per workgroup, an LDS tree, partials added in ascending order; no
+ * floating-point atomics): equal states give equal records bit for bit. */
+typedef struct bdg_sw2dq_monitor_desc {
+    const double* weights;      /* (Np, K), bdg_quadnodes_quadrature_weights */
+    const double* H;            /* (Np, K) or NULL (a variant-B solver then uses its descriptor's H) */
+    int num_gauges;             /* may be 0 */
+    const int* gauge_element;   /* caller's numbering, each in [0, K) */
+    const double* gauge_r;      /* reference coordinates, |r|, |s| <= 1 + 1e-10 (bdg_quadnodes_locate_points) */
+    const double* gauge_s;
+    int stride;                 /* sample after every stride-th completed step, >= 1 */
+    int capacity;               /* records held on the device, >= 1 */
+} bdg_sw2dq_monitor_desc;
+/* Once per solver. BDG_ERR_ARGUMENT, changing nothing, for a NULL handle or descriptor or weights, a gauge element outside
+ * [0, K), |r| or |s| above 1 + 1e-10, stride < 1, capacity < 1, and a second call. From then on step_rk2, step_ssprk2,
+ * lserk4_stages (a step is the fifth stage) and their _exchanged forms take a record after every stride-th completed step
+ * (counted over calls; set_state, set_state4 and monitor_reset restart the count), two launches on the solver's stream
+ * behind the step and no host wait. A stepping call that would take more records than the capacity has left returns
+ * BDG_ERR_ARGUMENT before it launches anything. bdg_sw2dq_time* take no samples. Without this call no stepping call
+ * launches anything it did not launch before. */
+int bdg_sw2dq_enable_monitor(bdg_sw2dq* s, const bdg_sw2dq_monitor_desc* desc);
+int bdg_sw2dq_monitor_sample(bdg_sw2dq* s);            /* one record of the resident state now */
+int bdg_sw2dq_monitor_count(const bdg_sw2dq* s, int* n);
+/* records [first, first + count) as count x width doubles; synchronises the solver's stream */
+int bdg_sw2dq_monitor_read(bdg_sw2dq* s, int first, int count, double* records);
+int bdg_sw2dq_monitor_width(const bdg_sw2dq* s, int* width);
+int bdg_sw2dq_monitor_reset(bdg_sw2dq* s);             /* count = 0, step counter = 0 */
+/* Partitioned runs: the reduction covers the owned elements, and a gauge whose element is a ghost (>= num_owned) is not
+ * evaluated, its entries stay 0: pass each gauge to the rank that owns its element and any ghost element to the others.
+ * monitor_reduce is the one collective (after comm_init): it all-reduces the stored records that no earlier call has
+ * reduced, in place on the solver's stream: sum for the integrals, E, the gauges and the NaN count, minimum / maximum for
+ * the extrema, t left alone. Call it once before reading, not per sample. */
+int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s);
 
 /* Resident time stepping (state stays in HBM). */
 int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps);          /* 5 fused stages per step */
