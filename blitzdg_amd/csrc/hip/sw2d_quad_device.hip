@@ -8,12 +8,15 @@
 // The output step (bdg_sw2dq_output_fields) is one launch of sw2d_quad_output_kernel (sw2d_quad_output_kernel.hpp).
 // After bdg_sw2dq_enable_variant_b a three-field solver evaluates the tidal driver's right-hand side instead: the speed pass
 // sw2d_quadb_speed_kernel, then sw2d_quadb_stage_kernel (sw2d_quadb_kernel.hpp), which reads the speed from device memory.
+// After bdg_sw2dq_enable_variant_b4 a four-field solver does the same with the tracer as a fourth equation
+// (sw2d_quadb4_stage_kernel, sw2d_quadb4_kernel.hpp; the speed pass is the three-field one).
 // After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_quad_monitor_kernel.hpp).
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
 #include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
+#include "sw2d_quadb4_kernel.hpp"
 #include "sw2d_quadb_kernel.hpp"
 #include "blitzdg/JacobiBuilders.hpp"
 #include "blitzdg/LSERK4.hpp"
@@ -103,6 +106,24 @@ hipError_t sw2d_quadb_stage(int order, int mode, bool filter, bool general, cons
     case 10: return sw2d_quadb_launch<10>(mode, filter, general, p, stream);
     case 11: return sw2d_quadb_launch<11>(mode, filter, general, p, stream);
     case 12: return sw2d_quadb_launch<12>(mode, filter, general, p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t sw2d_quadb4_stage(int order, int mode, bool filter, bool general, const QuadB4Params& p, hipStream_t stream) {
+    switch (order) {
+    case 1: return sw2d_quadb4_launch<1>(mode, filter, general, p, stream);
+    case 2: return sw2d_quadb4_launch<2>(mode, filter, general, p, stream);
+    case 3: return sw2d_quadb4_launch<3>(mode, filter, general, p, stream);
+    case 4: return sw2d_quadb4_launch<4>(mode, filter, general, p, stream);
+    case 5: return sw2d_quadb4_launch<5>(mode, filter, general, p, stream);
+    case 6: return sw2d_quadb4_launch<6>(mode, filter, general, p, stream);
+    case 7: return sw2d_quadb4_launch<7>(mode, filter, general, p, stream);
+    case 8: return sw2d_quadb4_launch<8>(mode, filter, general, p, stream);
+    case 9: return sw2d_quadb4_launch<9>(mode, filter, general, p, stream);
+    case 10: return sw2d_quadb4_launch<10>(mode, filter, general, p, stream);
+    case 11: return sw2d_quadb4_launch<11>(mode, filter, general, p, stream);
+    case 12: return sw2d_quadb4_launch<12>(mode, filter, general, p, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -210,6 +231,11 @@ struct bdg_sw2dq {
     bool variantB = false;
     DevBuf<double> vbH, vbHx, vbHy, vbSponge, lamBuf;
     DevBuf<int> gidxB;        // gidx with the open-boundary nodes marked
+    // four fields (bdg_sw2dq_enable_variant_b4): the open-boundary concentration, sw2d_quadb4_kernel.hpp
+    DevBuf<long long> openKey;
+    DevBuf<double> openN;
+    int numOpenN = 0;
+    double nOpenC = 0.0;
     double vbF = 0.0, vbCD = 0.0, tideAmp = 0.0, tidePeriod = 1.0, tideRamp = 0.0;
     double timeNow = 0.0;     // model time of the resident state (tide phase); the steppers advance it
     double spongeC = 0.0;     // scalar sponge coefficient of the Heun step in flight
@@ -286,6 +312,11 @@ struct bdg_sw2dq {
     }
     void launchOn(int mode, bool filter, const QuadParams& p, hipStream_t on) {
         evaluated = true;
+        if (variantB && fields == 4) {
+            const QuadB4Params p4{paramsB(p), openKey.p, openN.p, numOpenN, nOpenC};
+            hipCheck(sw2d_quadb4_stage(N, mode, filter, general, p4, on), "sw2d_quadb4_stage_kernel launch");
+            return;
+        }
         if (variantB) {
             hipCheck(sw2d_quadb_stage(N, mode, filter, general, paramsB(p), on), "sw2d_quadb_stage_kernel launch");
             return;
@@ -789,6 +820,7 @@ int bdg_sw2dq_set_sources(bdg_sw2dq* s, const double* zx, const double* zy, doub
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_sources");
         requireFields(s, 4, "bdg_sw2dq_set_sources");
+        if (s->variantB) throw arg_error("bdg_sw2dq_set_sources: variant B is enabled and brings its own sources");
         if (s->evaluated)
             throw arg_error("bdg_sw2dq_set_sources: the solver has evaluated a right-hand side already; sources are set before the "
                             "first evaluation");
@@ -812,53 +844,114 @@ int bdg_sw2dq_set_sources(bdg_sw2dq* s, const double* zx, const double* zy, doub
     });
 }
 
+namespace {
+
+// what bdg_sw2dq_enable_variant_b and _b4 share: the checks on the descriptor (`fn` names the caller in the messages), the
+// gather index with the open-boundary nodes marked, the bed, the sponge and the tide
+void checkVariantB(const bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d, const std::string& fn) {
+    if (s->evaluated)
+        throw arg_error(fn + ": the solver has evaluated a right-hand side already; variant B is enabled "
+                        "before the first evaluation");
+    if (d->num_out < 0 || (d->num_out > 0 && !d->mapO)) throw arg_error(fn + ": bad open-boundary list");
+    if (!(d->tide_period > 0.0) && d->num_out > 0) throw arg_error(fn + ": tide_period must be > 0");
+    const long long nFaceNodes = static_cast<long long>(s->NFN) * s->K;
+    for (int i = 0; i < d->num_out; ++i)
+        if (d->mapO[i] < 0 || d->mapO[i] >= nFaceNodes)
+            throw arg_error(fn + ": open-boundary node index out of range");
+}
+
+void enableVariantB(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d) {
+    const long long plane = s->plane();
+    // the gather index again, open-boundary nodes as kQuadBOpen (they win over the wall flag where a node has both)
+    std::vector<int> gi(s->gidx.n);
+    hipCheck(hipMemcpyAsync(gi.data(), s->gidx.p, gi.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (gidx)");
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    for (int i = 0; i < d->num_out; ++i) {
+        const int k = d->mapO[i] / s->NFN, fn = d->mapO[i] % s->NFN;
+        gi[static_cast<size_t>(fn) * s->ld + k] = kQuadBOpen;
+    }
+    s->gidxB.alloc(gi.size(), s->bytes);
+    hipCheck(hipMemcpyAsync(s->gidxB.p, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "hipMemcpy (gidx)");
+    s->vbH.alloc(plane, s->bytes, s->stream);
+    s->vbHx.alloc(plane, s->bytes, s->stream);
+    s->vbHy.alloc(plane, s->bytes, s->stream);
+    s->upload(s->vbH.p, d->H, s->Np);
+    s->upload(s->vbHx.p, d->Hx, s->Np);
+    s->upload(s->vbHy.p, d->Hy, s->Np);
+    if (d->sponge) {
+        s->vbSponge.alloc(plane, s->bytes, s->stream);
+        s->upload(s->vbSponge.p, d->sponge, s->Np);
+    } else if (s->vbSponge.p) {
+        s->vbSponge.alloc(0, s->bytes);
+    }
+    s->lamBuf.alloc(1, s->bytes, s->stream);
+    s->vbF = d->coriolis;
+    s->vbCD = d->drag;
+    s->tideAmp = d->tide_amplitude;
+    s->tidePeriod = d->tide_period > 0.0 ? d->tide_period : 1.0;
+    s->tideRamp = d->tide_ramp;
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vector dies here
+    s->variantB = true;
+}
+
+} // namespace
+
 int bdg_sw2dq_enable_variant_b(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_enable_variant_b");
         if (!d || !d->H || !d->Hx || !d->Hy) throw arg_error("bdg_sw2dq_enable_variant_b: H, Hx and Hy are required");
         if (s->fields != 3)
             throw arg_error("bdg_sw2dq_enable_variant_b: the solver was created with four fields; variant B has three (h, hu, hv)");
-        if (s->evaluated)
-            throw arg_error("bdg_sw2dq_enable_variant_b: the solver has evaluated a right-hand side already; variant B is enabled "
-                            "before the first evaluation");
-        if (d->num_out < 0 || (d->num_out > 0 && !d->mapO)) throw arg_error("bdg_sw2dq_enable_variant_b: bad open-boundary list");
-        if (!(d->tide_period > 0.0) && d->num_out > 0) throw arg_error("bdg_sw2dq_enable_variant_b: tide_period must be > 0");
-        const long long nFaceNodes = static_cast<long long>(s->NFN) * s->K;
-        for (int i = 0; i < d->num_out; ++i)
-            if (d->mapO[i] < 0 || d->mapO[i] >= nFaceNodes)
-                throw arg_error("bdg_sw2dq_enable_variant_b: open-boundary node index out of range");
+        checkVariantB(s, d, "bdg_sw2dq_enable_variant_b");
         s->use();
-        const long long plane = s->plane();
-        // the gather index again, open-boundary nodes as kQuadBOpen (they win over the wall flag where a node has both)
-        std::vector<int> gi(s->gidx.n);
-        hipCheck(hipMemcpyAsync(gi.data(), s->gidx.p, gi.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (gidx)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        for (int i = 0; i < d->num_out; ++i) {
-            const int k = d->mapO[i] / s->NFN, fn = d->mapO[i] % s->NFN;
-            gi[static_cast<size_t>(fn) * s->ld + k] = kQuadBOpen;
+        enableVariantB(s, d);
+    });
+}
+
+int bdg_sw2dq_enable_variant_b4(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d, const double* n_open, int n_open_count) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2dq_enable_variant_b4";
+        requireSolver(s, fn.c_str());
+        if (!d || !d->H || !d->Hx || !d->Hy) throw arg_error(fn + ": H, Hx and Hy are required");
+        if (s->fields != 4)
+            throw arg_error(fn + ": the solver was created with three fields; the tracer needs four (bdg_sw2dq_create_fields)");
+        if (s->hasSources)
+            throw arg_error(fn + ": the solver has sources of bdg_sw2dq_set_sources; variant B brings its own");
+        if (s->variantB) throw arg_error(fn + ": variant B is already enabled on this solver; the call is made once");
+        checkVariantB(s, d, fn);
+        // (without an open-boundary node no concentration is read: a count of 0 is then num_out, and n_open may be NULL)
+        const bool none = d->num_out == 0 && n_open_count == 0;
+        if (!none && (!n_open || (n_open_count != 1 && n_open_count != d->num_out)))
+            throw arg_error(fn + ": n_open must hold 1 value or one per open-boundary node (num_out)");
+        s->use();
+        if (none || n_open_count == 1) { // (also a single open node given per node)
+            s->nOpenC = none ? 0.0 : n_open[0];
+            s->numOpenN = 0;
+            s->openKey.alloc(0, s->bytes);
+            s->openN.alloc(0, s->bytes);
+        } else {
+            // positions fn * ld + k in the gather index, sorted; the last entry of a node listed twice wins, as an assignment
+            // through mapO does
+            std::vector<std::pair<long long, int>> slots(static_cast<size_t>(d->num_out));
+            for (int i = 0; i < d->num_out; ++i)
+                slots[static_cast<size_t>(i)] = {static_cast<long long>(d->mapO[i] % s->NFN) * s->ld + d->mapO[i] / s->NFN, i};
+            std::sort(slots.begin(), slots.end());
+            std::vector<long long> keys;
+            std::vector<double> vals;
+            for (const auto& kv : slots) {
+                if (!keys.empty() && keys.back() == kv.first) vals.back() = n_open[kv.second];
+                else { keys.push_back(kv.first); vals.push_back(n_open[kv.second]); }
+            }
+            s->openKey.alloc(keys.size(), s->bytes);
+            s->openN.alloc(vals.size(), s->bytes);
+            hipCheck(hipMemcpyAsync(s->openKey.p, keys.data(), keys.size() * sizeof(long long), hipMemcpyHostToDevice, s->stream),
+                     "hipMemcpy (open-boundary slots)");
+            hipCheck(hipMemcpyAsync(s->openN.p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice, s->stream),
+                     "hipMemcpy (open-boundary tracer)");
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
+            s->numOpenN = static_cast<int>(keys.size());
         }
-        s->gidxB.alloc(gi.size(), s->bytes);
-        hipCheck(hipMemcpyAsync(s->gidxB.p, gi.data(), gi.size() * sizeof(int), hipMemcpyHostToDevice, s->stream), "hipMemcpy (gidx)");
-        s->vbH.alloc(plane, s->bytes, s->stream);
-        s->vbHx.alloc(plane, s->bytes, s->stream);
-        s->vbHy.alloc(plane, s->bytes, s->stream);
-        s->upload(s->vbH.p, d->H, s->Np);
-        s->upload(s->vbHx.p, d->Hx, s->Np);
-        s->upload(s->vbHy.p, d->Hy, s->Np);
-        if (d->sponge) {
-            s->vbSponge.alloc(plane, s->bytes, s->stream);
-            s->upload(s->vbSponge.p, d->sponge, s->Np);
-        } else if (s->vbSponge.p) {
-            s->vbSponge.alloc(0, s->bytes);
-        }
-        s->lamBuf.alloc(1, s->bytes, s->stream);
-        s->vbF = d->coriolis;
-        s->vbCD = d->drag;
-        s->tideAmp = d->tide_amplitude;
-        s->tidePeriod = d->tide_period > 0.0 ? d->tide_period : 1.0;
-        s->tideRamp = d->tide_ramp;
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vector dies here
-        s->variantB = true;
+        enableVariantB(s, d);
     });
 }
 

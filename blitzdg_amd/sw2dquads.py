@@ -97,14 +97,19 @@ class Sw2dQuadSolver:
         check(lib.bdg_sw2dq_set_sources(self._h, C.ptr(zx), C.ptr(zy), 0.0 if farr is not None else float(f), C.ptr(farr),
                                         float(CD)))
 
-    def enableVariantB(self, H, Hx, Hy, mapO=None, CD=0.0, f=0.0, tide=(3.0, 3600 * 12.42, 0.15 / 3600), sponge=None):
+    def enableVariantB(self, H, Hx, Hy, mapO=None, CD=0.0, f=0.0, tide=(3.0, 3600 * 12.42, 0.15 / 3600), sponge=None, tracer=None):
         """Switches a three-field solver to the right-hand side of the reference's tidal driver (src/sw2d/main.cpp:279-484,
         "variant B"): still-water depth ``H`` with star states at the faces, the open-boundary nodes ``mapO`` (flat face-node
         indices, BCmap[2] of the provisioner) driven by ``tide = (amplitude, period, ramp)``, one global Lax-Friedrichs
         speed, bed slope (``Hx, Hy``: ``QuadNodesProvisioner.bedSlopes(H)``), drag ``CD`` and Coriolis ``f`` (scalars).
         ``sponge``: (Np, K) coefficient of ``stepSSPRK2`` (``buildSpongeCoeff``). Before the first evaluation only; computeRHS,
         stepRK2, lserk4Stages and timeStages then evaluate variant B at the model time (``setTime``). Wrong shapes raise
-        ValueError; a four-field solver and a solver that has evaluated already are refused by the library."""
+        ValueError; a four-field solver and a solver that has evaluated already are refused by the library.
+
+        ``tracer``: on a four-field solver (without ``sources``: variant B brings its own), the concentration N = hN / h the
+        open-boundary nodes take on their outer side, a scalar or one value per entry of ``mapO``; variant B then carries the
+        passive tracer hN as a fourth equation (computeRHS4, setState4, the steppers). A wrong length and a three-field
+        solver raise ValueError. Without ``tracer`` a four-field solver is refused as before."""
         shape = (self.Np, self.K)
         a = [C.as_f64(H, shape, "H"), C.as_f64(Hx, shape, "Hx"), C.as_f64(Hy, shape, "Hy")]
         sp = None if sponge is None else C.as_f64(sponge, shape, "sponge")
@@ -114,7 +119,21 @@ class Sw2dQuadSolver:
         amp, period, ramp = (float(v) for v in tide)
         d = C.Sw2dVbDesc(C.ptr(a[0]), C.ptr(a[1]), C.ptr(a[2]), C.ptr(mo) if mo.size else None, mo.size, float(CD), float(f),
                          amp, period, ramp, C.ptr(sp))
-        check(lib.bdg_sw2dq_enable_variant_b(self._h, byref(d)))
+        if tracer is None:
+            check(lib.bdg_sw2dq_enable_variant_b(self._h, byref(d)))
+        else:
+            if self.fields != 4:
+                raise ValueError("tracer needs a solver with fields=4")
+            scalar = np.ndim(tracer) == 0
+            if scalar:
+                tr = np.array([float(tracer)])
+            else:
+                tr = C.as_f64(tracer).reshape(-1)
+                if np.ndim(tracer) != 1 or tr.size != mo.size:
+                    raise ValueError(f"tracer: expected a scalar or {mo.size} values, one per entry of mapO")
+            if tr.size == 0:                         # no open-boundary node (a rank away from the open side): nothing to feed
+                tr, scalar = np.zeros(1), True
+            check(lib.bdg_sw2dq_enable_variant_b4(self._h, byref(d), C.ptr(tr), 1 if scalar else tr.size))
         self.variantB = True
 
     def setTime(self, t):
@@ -345,7 +364,9 @@ class NativeDistributedSw2dQuad:
         (x, y) -> dict of the rank-local node coordinates. variant_b: the keyword arguments of
         Sw2dQuadSolver.enableVariantB, handled as sources is (a dict, or a function (x, y) -> dict; arrays on the rank-local
         nodes); a missing ``mapO`` is BCmap[2] of the rank-local provisioner (owned elements keep the global mesh's BC tags:
-        tag the open side with MeshManager.setBCType before the plan is built)."""
+        tag the open side with MeshManager.setBCType before the plan is built). With fields=4 its ``tracer`` entry (a scalar, an
+        array with one value per rank-local open-boundary node, or a function (x, y) -> array of those nodes' coordinates, in
+        the order of ``mapO``) makes it variant B with the passive tracer."""
         from . import pyblitzdg as dg
         from .halo import attach_native, build_local_mesh
 
@@ -364,6 +385,10 @@ class NativeDistributedSw2dQuad:
             ctx = self.nodes.dgContext()
             vb = dict(variant_b(ctx.x, ctx.y) if callable(variant_b) else variant_b)
             vb.setdefault("mapO", ctx.BCmap.get(2, []))
+            if callable(vb.get("tracer")):
+                vm = np.asarray(ctx.vmapM).reshape(-1)[np.asarray(vb["mapO"], dtype=np.int64)]
+                xf, yf = np.asarray(ctx.x).ravel("F"), np.asarray(ctx.y).ravel("F")
+                vb["tracer"] = np.asarray(vb["tracer"](xf[vm], yf[vm]), dtype=np.float64) + np.zeros(vm.size)
             try:
                 self.solver.enableVariantB(**vb)
             except Exception:

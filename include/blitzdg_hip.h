@@ -499,6 +499,20 @@ int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int 
 /* HIP-event milliseconds of the speed pass alone on the resident state, averaged over count; bdg_sw2dq_time takes kind 2
  * (one unfiltered Heun step with the sponge of the last bdg_sw2dq_step_ssprk2) on a variant-B solver. */
 int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms);
+/* Variant B with a passive tracer: the same physics on a FOUR-field solver (bdg_sw2dq_create_fields), hN as a fourth equation
+ * (csrc/hip/sw2d_quadb4_kernel.hpp; the reference's tidal driver has none, the definition is tests/quadrefB4.py). The face
+ * concentrations are formed from the depths before the star states, NM = hNM / hM, NP = hNP / hP; a wall node takes NP = NM and an
+ * open-boundary node NP = n_open (it wins where a node is both); the star tracer is hM* NM, hP* NP, so a uniform concentration
+ * stays uniform over a discontinuous bed; fluxes (hN* hu) / h*, (hN* hv) / h* with the same global speed, which the tracer does
+ * not enter; no source term. n_open_count is 1 (one concentration for every open-boundary node) or desc->num_out (n_open[i]
+ * belongs to mapO[i]; with num_out = 0 a count of 0 is accepted and n_open is not read); anything else, a NULL handle,
+ * descriptor or n_open is BDG_ERR_ARGUMENT, and so is a second call. Once, on a four-field solver
+ * before its first evaluation and without a bdg_sw2dq_set_sources call (variant B brings its own sources; set_sources is
+ * refused afterwards); a refusal changes nothing. From then on bdg_sw2dq_rhs4, step_rk2, step_ssprk2 (hN is stepped as h is:
+ * the sponge division touches hu and hv only), lserk4_stages, time and the _exchanged forms (one record is 4 Np doubles)
+ * evaluate it, the speed pass in front as on three fields; set_time, get_time, global_speed, time_speed, the monitor (int hN,
+ * gauge N, the descriptor's H by default) and output_fields work as there. bdg_sw2dq_enable_variant_b still refuses four fields. */
+int bdg_sw2dq_enable_variant_b4(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* desc, const double* n_open, int n_open_count);
 /* Host helpers of the tidal set-up, argument lists as the bdg_trinodes_* ones: Hx, Hy = Filter (rx Dr H + sx Ds H,
  * ry Dr H + sy Ds H) (main.cpp:128-133; bdg_quadnodes_build_filter first), and buildSpongeCoeff (main.cpp:517-553). */
 int bdg_quadnodes_bed_slopes(const bdg_quadnodes* nodes, const double* H, double* Hx, double* Hy);
