@@ -84,6 +84,11 @@ class Sw2dqMonitorDesc(Structure):
                 ("gauge_r", c_void_p), ("gauge_s", c_void_p), ("stride", c_int), ("capacity", c_int)]
 
 
+class Sw2dqDrifterDesc(Structure):
+    _fields_ = [("count", c_int), ("element", c_void_p), ("r", c_void_p), ("s", c_void_p), ("bilinear", c_void_p),
+                ("neighbours", c_void_p), ("bary", c_void_p), ("stride", c_int), ("capacity", c_int)]
+
+
 class Sw2dCurvedDesc(Structure):
     _fields_ = [("order", c_int), ("num_elements", c_int), ("num_cub", c_int), ("num_gauss", c_int),
                 ("V", c_void_p), ("Filter", c_void_p), ("J", c_void_p),
@@ -253,6 +258,14 @@ _SIGNATURES = {
     "bdg_sw2dq_monitor_width": (c_int, [_P, POINTER(c_int)]),
     "bdg_sw2dq_monitor_reset": (c_int, [_P]),
     "bdg_sw2dq_monitor_reduce": (c_int, [_P]),
+    "bdg_quadnodes_drifter_tables": (c_int, [_P, _P, c_int, _P, _P, _P]),
+    "bdg_sw2dq_enable_drifters": (c_int, [_P, POINTER(Sw2dqDrifterDesc)]),
+    "bdg_sw2dq_drifters_advance": (c_int, [_P, c_double, c_int]),
+    "bdg_sw2dq_drifters_time": (c_int, [_P, c_double, c_int, POINTER(c_float)]),
+    "bdg_sw2dq_drifters_state": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2dq_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "bdg_sw2dq_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "bdg_sw2dq_drifters_reset": (c_int, [_P]),
     "bdg_sw2d_step_lserk4": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_lserk4_stages": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_step_rk2": (c_int, [_P, c_double, c_int, c_int]),

@@ -11,9 +11,11 @@
 // After bdg_sw2dq_enable_variant_b4 a four-field solver does the same with the tracer as a fourth equation
 // (sw2d_quadb4_stage_kernel, sw2d_quadb4_kernel.hpp; the speed pass is the three-field one).
 // After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_quad_monitor_kernel.hpp).
+// After bdg_sw2dq_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_quad_drifter_kernel.hpp).
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_drifter_kernel.hpp"
 #include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 #include "sw2d_quadb4_kernel.hpp"
@@ -264,6 +266,16 @@ struct bdg_sw2dq {
         DevBuf<double> w, H, lr, ls, partials, rec, stage;
         DevBuf<int> element;
     } mon;
+    // drifters (bdg_sw2dq_enable_drifters): sw2d_quad_drifter_kernel.hpp
+    struct Drifters {
+        bool on = false;
+        int n = 0, stride = 1, capacity = 0;
+        int count = 0;        // records taken
+        long long steps = 0;  // advances made
+        double t = 0.0;       // time of the next record: the model time in the stepping calls, + dt per bdg_sw2dq_drifters_advance
+        DevBuf<double> bil, r1d, bary, x, y, r, s, u0, v0, recT, recX, recY;
+        DevBuf<int> neigh, k, status, recStatus;
+    } drf;
 
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
     long long plane() const { return static_cast<long long>(Np) * ld; }
@@ -449,13 +461,47 @@ struct bdg_sw2dq {
         hipCheck(hipGetLastError(), "sw2d_quad_monitor_finish_kernel launch");
         ++mon.count;
     }
-    // after every completed step of a stepping call. two: the call runs the two-chain schedule, whose chains are joined
-    // in front of the sample and started again behind it (the sample reads columns the exchange stream wrote)
-    void stepDone(bool two = false) {
-        if (!mon.on || ++mon.steps % mon.stride != 0) return;
-        if (two) chains.end(stream, halo.stream);
-        monitorSample();
-        if (two) chains.begin(stream, halo.stream);
+    // ---- drifters
+    // as monitorReserve: records `steps` further advances would take
+    void drifterReserve(long long steps, const char* fn) const {
+        if (!drf.on) return;
+        const long long take = (drf.steps + steps) / drf.stride - drf.steps / drf.stride;
+        if (take > drf.capacity - drf.count)
+            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " drifter records and " +
+                            std::to_string(drf.capacity - drf.count) + " are free (bdg_sw2dq_drifters_read, then bdg_sw2dq_drifters_reset)");
+    }
+    // one launch of the drifter kernel on the solver's stream; slot < 0: no record
+    void drifterLaunch(int mode, double dt, int slot) {
+        const QuadDriftParams p{q.p, drf.bil.p, drf.neigh.p, drf.r1d.p, drf.bary.p, drf.x.p, drf.y.p, drf.r.p, drf.s.p, drf.u0.p,
+                                drf.v0.p, drf.k.p, drf.status.p, drf.recT.p, drf.recX.p, drf.recY.p, drf.recStatus.p, ld, N, drf.n,
+                                mode, slot, dt, drf.t};
+        hipLaunchKernelGGL(sw2d_quad_drifter_kernel, dim3((drf.n + kQuadDriftThreads - 1) / kQuadDriftThreads), dim3(kQuadDriftThreads),
+                           0, stream, p);
+        hipCheck(hipGetLastError(), "sw2d_quad_drifter_kernel launch");
+    }
+    // one advance in the resident state, with the record of time drf.t if one is due (room was reserved by the caller)
+    void drifterAdvance(double dt, bool record = true) {
+        const bool due = record && ++drf.steps % drf.stride == 0;
+        drifterLaunch(kQuadDriftAdvance, dt, due ? drf.count : -1);
+        if (due) ++drf.count;
+    }
+    // (u0, v0) again after the state under the drifters has been replaced
+    void drifterResample() {
+        if (drf.on) drifterLaunch(kQuadDriftSample, 0.0, -1);
+    }
+    // after every completed step (of size dt) of a stepping call: the monitor's sample, then the drifters' advance. two: the call
+    // runs the two-chain schedule, whose chains are joined in front of the sample and started again behind it (the sample reads
+    // columns the exchange stream wrote); drifters exist on unpartitioned solvers only
+    void stepDone(double dt, bool two = false) {
+        if (mon.on && ++mon.steps % mon.stride == 0) {
+            if (two) chains.end(stream, halo.stream);
+            monitorSample();
+            if (two) chains.begin(stream, halo.stream);
+        }
+        if (drf.on) {
+            drf.t = timeNow;
+            drifterAdvance(dt);
+        }
     }
 
     // ---- partitioned runs
@@ -500,7 +546,7 @@ struct bdg_sw2dq {
             p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;
             evaluateExchanged(two, QMODE_COMBINE, filter, p);
             timeNow += dt;
-            stepDone(two);
+            stepDone(dt, two);
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -517,7 +563,7 @@ struct bdg_sw2dq {
             evaluateExchanged(two, QMODE_LSERK, false, p);
             std::swap(q.p, q1.p);
             lserkAdvance(dt);
-            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone(two);
+            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone(dt, two);
         }
         if (two) chains.end(stream, halo.stream);
     }
@@ -771,6 +817,7 @@ int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const d
         s->res.zero(s->stream);
         s->stageCount = 0;
         s->mon.steps = 0;
+        s->drifterResample();
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
@@ -1008,11 +1055,12 @@ int bdg_sw2dq_step_ssprk2(bdg_sw2dq* s, double dt, int num_steps, int filter, do
         if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2: variant B is not enabled (the Heun step is the tidal driver's)");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2: filter requested but the solver has no Filter");
         s->monitorReserve(num_steps, "bdg_sw2dq_step_ssprk2");
+        s->drifterReserve(num_steps, "bdg_sw2dq_step_ssprk2");
         s->use();
         s->spongeC = sponge_coeff;
         for (int i = 0; i < num_steps; ++i) {
             s->heunStep(dt, filter != 0, false, false);
-            s->stepDone();
+            s->stepDone(dt);
         }
         s->checkBlowUp();
     });
@@ -1030,6 +1078,7 @@ int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const 
         s->res.zero(s->stream);
         s->stageCount = 0;
         s->mon.steps = 0;
+        s->drifterResample();
         hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     });
 }
@@ -1139,10 +1188,11 @@ int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter) {
         if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2: num_steps < 0");
         if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2: filter requested but the solver has no Filter");
         s->monitorReserve(num_steps, "bdg_sw2dq_step_rk2");
+        s->drifterReserve(num_steps, "bdg_sw2dq_step_rk2");
         s->use();
         for (int i = 0; i < num_steps; ++i) {
             s->rk2Step(dt, filter != 0);
-            s->stepDone();
+            s->stepDone(dt);
         }
         s->checkBlowUp();
     });
@@ -1153,10 +1203,11 @@ int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages) {
         requireSolver(s, "bdg_sw2dq_lserk4_stages");
         if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages: num_stages < 0");
         s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages");
+        s->drifterReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages");
         s->use();
         for (int i = 0; i < num_stages; ++i) {
             s->lserkStage(dt);
-            if (s->stageCount % blitzdg::LSERK4::numStages == 0) s->stepDone();
+            if (s->stageCount % blitzdg::LSERK4::numStages == 0) s->stepDone(dt);
         }
         s->checkBlowUp();
     });
@@ -1200,6 +1251,8 @@ int bdg_sw2dq_synchronize(bdg_sw2dq* s) {
 int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_partition");
+        if (s->drf.on)
+            throw arg_error("bdg_sw2dq_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
         s->use();
         s->part.set("bdg_sw2dq", s->K, s->maxNeighbourHost, num_interior, num_owned, send_elements, num_send, s->halo.comm != nullptr,
                     s->bytes, s->stream);
@@ -1254,7 +1307,7 @@ int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int 
         s->spongeC = sponge_coeff;
         for (int i = 0; i < num_steps; ++i) {
             s->heunStep(dt, filter != 0, true, false);
-            s->stepDone();
+            s->stepDone(dt);
         }
         s->checkBlowUp(s->part.numOwned, true);
     });
@@ -1422,6 +1475,159 @@ int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s) {
         hipCheck(hipMemcpy2DAsync(m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double), m.stage.p, n * sizeof(double),
                                   n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
         m.reduced = m.count;
+    });
+}
+
+// ---- drifters
+int bdg_sw2dq_enable_drifters(bdg_sw2dq* s, const bdg_sw2dq_drifter_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2dq_enable_drifters";
+        requireSolver(s, fn.c_str());
+        if (!d || d->count < 1 || !d->element || !d->r || !d->s || !d->bilinear || !d->neighbours || !d->bary)
+            throw arg_error(fn + ": the descriptor, at least one drifter and the tables of bdg_quadnodes_drifter_tables are required");
+        if (d->stride < 1 || d->capacity < 1) throw arg_error(fn + ": stride and capacity must be >= 1");
+        if (s->drf.on) throw arg_error(fn + ": drifters are already enabled on this solver; the call is made once");
+        if (s->part.numOwned > 0 || s->halo.comm)
+            throw arg_error(fn + ": the solver has a partition set; drifters do not migrate between ranks (single domain only)");
+        const int n = d->count, K = s->K, Nq = s->N + 1;
+        if (static_cast<long long>(n) * d->capacity >= (1LL << 31)) throw arg_error(fn + ": count * capacity must stay below 2^31");
+        for (int i = 0; i < n; ++i) {
+            if (d->element[i] < 0 || d->element[i] >= K)
+                throw arg_error(fn + ": drifter " + std::to_string(i) + " names an element outside [0, K)");
+            if (!(std::fabs(d->r[i]) <= 1.0 + 1e-10) || !(std::fabs(d->s[i]) <= 1.0 + 1e-10))
+                throw arg_error(fn + ": drifter " + std::to_string(i) + " lies outside its element (|r|, |s| <= 1)");
+        }
+        // the kernel follows these entries without a further check
+        std::vector<int> nb(static_cast<size_t>(4) * K);
+        for (int f = 0; f < 4; ++f)
+            for (int k = 0; k < K; ++k) {
+                const int v = d->neighbours[static_cast<size_t>(f) * K + k];
+                if (v < kQuadDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
+                nb[static_cast<size_t>(4) * k + f] = v;
+            }
+        blitzdg::real_vector_type r1d(Nq);
+        blitzdg::JacobiBuilders().computeGaussLobottoPoints(0.0, 0.0, s->N, r1d);
+        s->use();
+        bdg_sw2dq::Drifters& m = s->drf;
+        const size_t bytesBefore = s->bytes, cells = static_cast<size_t>(n) * d->capacity;
+        try {
+            auto put = [&](auto& buf, const auto* src, size_t count) {
+                buf.alloc(count, s->bytes);
+                hipCheck(hipMemcpyAsync(buf.p, src, count * sizeof(*src), hipMemcpyHostToDevice, s->stream), "hipMemcpy (drifters)");
+            };
+            put(m.bil, d->bilinear, static_cast<size_t>(8) * K);
+            put(m.neigh, nb.data(), nb.size());
+            put(m.r1d, r1d.data(), static_cast<size_t>(Nq));
+            put(m.bary, d->bary, static_cast<size_t>(Nq));
+            put(m.k, d->element, static_cast<size_t>(n));
+            put(m.r, d->r, static_cast<size_t>(n));
+            put(m.s, d->s, static_cast<size_t>(n));
+            for (DevBuf<double>* b : {&m.x, &m.y, &m.u0, &m.v0}) b->alloc(static_cast<size_t>(n), s->bytes, s->stream);
+            m.status.alloc(static_cast<size_t>(n), s->bytes, s->stream);
+            m.recT.alloc(static_cast<size_t>(d->capacity), s->bytes, s->stream);
+            m.recX.alloc(cells, s->bytes, s->stream);
+            m.recY.alloc(cells, s->bytes, s->stream);
+            m.recStatus.alloc(cells, s->bytes, s->stream);
+            m.n = n;
+            s->drifterLaunch(kQuadDriftInit, 0.0, -1); // x, y from the map, (u0, v0) from the resident state
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
+        } catch (...) { // nothing changes: the solver stays without drifters
+            (void)hipStreamSynchronize(s->stream);
+            for (DevBuf<double>* b : {&m.bil, &m.r1d, &m.bary, &m.x, &m.y, &m.r, &m.s, &m.u0, &m.v0, &m.recT, &m.recX, &m.recY}) b->release();
+            for (DevBuf<int>* b : {&m.neigh, &m.k, &m.status, &m.recStatus}) b->release();
+            m.n = 0;
+            s->bytes = bytesBefore;
+            throw;
+        }
+        m.on = true;
+        m.stride = d->stride; m.capacity = d->capacity; m.count = 0; m.steps = 0; m.t = s->timeNow;
+    });
+}
+
+namespace {
+void requireDrifters(const bdg_sw2dq* s, const char* fn) {
+    requireSolver(s, fn);
+    if (!s->drf.on) throw arg_error(std::string(fn) + ": drifters are not enabled (bdg_sw2dq_enable_drifters)");
+}
+} // namespace
+
+int bdg_sw2dq_drifters_advance(bdg_sw2dq* s, double dt, int num_steps) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_advance");
+        if (num_steps < 0) throw arg_error("bdg_sw2dq_drifters_advance: num_steps < 0");
+        s->drifterReserve(num_steps, "bdg_sw2dq_drifters_advance");
+        s->use();
+        for (int i = 0; i < num_steps; ++i) {
+            s->drf.t += dt;
+            s->drifterAdvance(dt);
+        }
+    });
+}
+
+int bdg_sw2dq_drifters_time(bdg_sw2dq* s, double dt, int count, float* ms) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_time");
+        if (!ms || count < 1) throw arg_error("bdg_sw2dq_drifters_time: bad argument");
+        s->use();
+        hipEvent_t a, b;
+        hipCheck(hipEventCreate(&a), "hipEventCreate");
+        hipCheck(hipEventCreate(&b), "hipEventCreate");
+        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
+        for (int i = 0; i < count; ++i) s->drifterAdvance(dt, false);
+        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
+        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
+        float t = 0.0f;
+        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        *ms = t / count;
+    });
+}
+
+int bdg_sw2dq_drifters_state(bdg_sw2dq* s, double* x, double* y, int* element, double* r, double* sref, int* status) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_state");
+        s->use();
+        const bdg_sw2dq::Drifters& m = s->drf;
+        const size_t n = static_cast<size_t>(m.n);
+        const std::pair<double*, const double*> dbl[] = {{x, m.x.p}, {y, m.y.p}, {r, m.r.p}, {sref, m.s.p}};
+        for (const auto& c : dbl)
+            if (c.first) hipCheck(hipMemcpyAsync(c.first, c.second, n * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        if (element) hipCheck(hipMemcpyAsync(element, m.k.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        if (status) hipCheck(hipMemcpyAsync(status, m.status.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_drifters_count(const bdg_sw2dq* s, int* num_records, int* num_drifters) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_count");
+        if (num_records) *num_records = s->drf.count;
+        if (num_drifters) *num_drifters = s->drf.n;
+    });
+}
+
+int bdg_sw2dq_drifters_read(bdg_sw2dq* s, int first, int count, double* t, double* x, double* y, int* status) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_read");
+        const bdg_sw2dq::Drifters& m = s->drf;
+        if (first < 0 || count < 0 || first > m.count - count) throw arg_error("bdg_sw2dq_drifters_read: bad record range");
+        if (count == 0) return;
+        s->use();
+        const size_t at = static_cast<size_t>(first) * m.n, cells = static_cast<size_t>(count) * m.n;
+        if (t) hipCheck(hipMemcpyAsync(t, m.recT.p + first, count * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (x) hipCheck(hipMemcpyAsync(x, m.recX.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (y) hipCheck(hipMemcpyAsync(y, m.recY.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (status)
+            hipCheck(hipMemcpyAsync(status, m.recStatus.p + at, cells * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_drifters_reset(bdg_sw2dq* s) {
+    return guard([&] {
+        requireDrifters(s, "bdg_sw2dq_drifters_reset");
+        s->drf.count = 0;
     });
 }
 

@@ -387,6 +387,65 @@ int bdg_quadnodes_lagrange_basis(const bdg_quadnodes* nodes, const double* r, in
     });
 }
 
+// ---- set-up of the drifters (bdg_sw2dq_enable_drifters): bilinear map, neighbour table, barycentric weights
+int bdg_quadnodes_drifter_tables(const bdg_quadnodes* nodes, const int* mapO, int num_out, double* bilinear, int* neighbours,
+                                 double* bary) {
+    return guard([&] {
+        const std::string fn = "bdg_quadnodes_drifter_tables";
+        if (!nodes || !bilinear || !neighbours || !bary || num_out < 0 || (num_out > 0 && !mapO))
+            throw bdg_detail::arg_error(fn + ": bad argument");
+        const auto& p = nodes->prov;
+        const int N = p.get_NOrder(), Nq = N + 1, Np = p.get_NumLocalPoints(), K = p.get_NumElements(), NFN = 4 * Nq;
+        const real_matrix_type& x = p.get_xGrid(), &y = p.get_yGrid();
+        const real_vector_type& r1d = p.get_r1d();
+        const int c00 = 0, c10 = Nq * N, c01 = N, c11 = Np - 1;
+        for (int k = 0; k < K; ++k) {
+            double* b = bilinear + static_cast<size_t>(8) * k;
+            const real_matrix_type* g[2] = {&x, &y};
+            for (int c = 0; c < 2; ++c) {
+                const double v00 = (*g[c])(c00, k), v10 = (*g[c])(c10, k), v01 = (*g[c])(c01, k), v11 = (*g[c])(c11, k);
+                b[4 * c + 0] = (v00 + v10 + v01 + v11) / 4;
+                b[4 * c + 1] = (v10 - v00 + v11 - v01) / 4;
+                b[4 * c + 2] = (v01 - v00 + v11 - v10) / 4;
+                b[4 * c + 3] = (v00 - v10 - v01 + v11) / 4;
+            }
+            // a mesh whose nodes have left this map (deformed coordinates) is not bilinear: the drifters cannot follow it
+            const double size = std::max(std::hypot(b[1], b[5]), std::hypot(b[2], b[6]));
+            for (int j = 0; j < Nq; ++j)
+                for (int i = 0; i < Nq; ++i) {
+                    const double r = r1d(j), s = r1d(i);
+                    const double ex = b[0] + b[1] * r + b[2] * s + b[3] * r * s - x(Nq * j + i, k);
+                    const double ey = b[4] + b[5] * r + b[6] * s + b[7] * r * s - y(Nq * j + i, k);
+                    if (!(std::hypot(ex, ey) <= 1e-10 * size))
+                        throw bdg_detail::arg_error(fn + ": the nodes of element " + std::to_string(k) + " differ from the bilinear map of "
+                                                    "its corners; drifters need bilinear elements");
+                }
+        }
+        // faces in Fmask order (s = -1, r = +1, s = +1, r = -1), which is the mesh's face order
+        const index_vector_type& E2E = p.get_MeshManager().get_EToE();
+        std::vector<char> open(static_cast<size_t>(4) * K, 0);
+        for (int i = 0; i < num_out; ++i) {
+            if (mapO[i] < 0 || mapO[i] >= NFN * K) throw bdg_detail::arg_error(fn + ": open-boundary node index out of range");
+            open[static_cast<size_t>(mapO[i] / NFN) * 4 + mapO[i] % NFN / Nq] = 1;
+        }
+        const index_vector_type& vmapM = p.get_vmapM(), &vmapP = p.get_vmapP();
+        for (int k = 0; k < K; ++k)
+            for (int f = 0; f < 4; ++f) {
+                const int k2 = E2E(4 * k + f);
+                // (a boundary face is its own neighbour in EToE and maps its nodes onto themselves)
+                const size_t g = (static_cast<size_t>(k) * 4 + f) * Nq;
+                const bool boundary = k2 == k && vmapP(g) == vmapM(g);
+                neighbours[static_cast<size_t>(f) * K + k] = boundary ? (open[static_cast<size_t>(k) * 4 + f] ? -2 : -1) : k2;
+            }
+        for (int a = 0; a < Nq; ++a) {
+            double c = 1;
+            for (int b = 0; b < Nq; ++b)
+                if (b != a) c *= r1d(a) - r1d(b);
+            bary[a] = 1 / c;
+        }
+    });
+}
+
 int bdg_quadnodes_write_vtu(const bdg_quadnodes* nodes, const char* path, const double* field, const char* field_name) {
     return guard([&] {
         if (!nodes || !path || !field || !field_name) throw bdg_detail::arg_error("bdg_quadnodes_write_vtu: NULL argument");

@@ -478,6 +478,18 @@ class QuadNodesProvisioner:
         check(lib.bdg_quadnodes_lagrange_basis(self._h, C.ptr(r), r.size, C.ptr(out)))
         return out
 
+    def drifterTables(self, mapO=None):
+        """(bilinear, neighbours, bary) of ``Sw2dQuadSolver.enableDrifters``: (K, 8) coefficients xc, ax, bx, cx, yc, ay, by, cy
+        of each element's bilinear map x(r, s) = xc + ax r + bx s + cx r s; (4, K) the element across each face (Fmask order),
+        -1 for a wall, -2 for a boundary face with a node in ``mapO``; (N+1,) the barycentric weights of the Gauss-Lobatto
+        points. A mesh whose nodes have left the bilinear map raises BdgError."""
+        N, _, _, K = self._dims()
+        mo = C.as_i32([] if mapO is None else mapO).reshape(-1)
+        bil, neigh, bary = np.empty((K, 8)), np.empty((4, K), dtype=np.int32), np.empty(N + 1)
+        check(lib.bdg_quadnodes_drifter_tables(self._h, C.ptr(mo) if mo.size else None, mo.size, C.ptr(bil), C.ptr(neigh),
+                                               C.ptr(bary)))
+        return bil, neigh, bary
+
     def dgContext(self):
         return DGContext2D(self)
 

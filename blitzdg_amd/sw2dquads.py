@@ -294,6 +294,65 @@ class Sw2dQuadSolver:
                "nan": a[:, nf + 6], "gauges": a[:, nf + 7:].reshape(len(a), -1, nf)}
         return {k: np.ascontiguousarray(v) for k, v in rec.items()}
 
+    def enableDrifters(self, nodes, points, mapO=None, stride=1, capacity=1024):
+        """Switches on Lagrangian drifters: points that move with the velocity (hu / h, hv / h) of the resident state. From now
+        on stepRK2, stepSSPRK2 and lserk4Stages (a step is the fifth stage) advance them on the device by that step's dt after
+        every completed step (Heun; one launch, no state download) and keep their positions after every ``stride``-th
+        advance, ``capacity`` records at most. ``nodes``: the QuadNodesProvisioner of the solver's mesh, whose elements must be
+        bilinear. ``points``: (n, 2) array of x, y, located with ``nodes.locatePoints`` (a point in no element raises
+        ValueError), or a tuple (element, r, s) of reference coordinates. ``mapO``: the open-boundary face nodes of
+        ``enableVariantB``; a drifter that crosses one of their faces has exited (status 1), at every other boundary face it
+        slides along the wall (status bit 4). Set the state first; once per solver; not on a partitioned solver."""
+        if isinstance(points, tuple):
+            el, r, s = C.as_i32(points[0]).reshape(-1), C.as_f64(points[1]).reshape(-1), C.as_f64(points[2]).reshape(-1)
+            if not (el.size == r.size == s.size):
+                raise ValueError("points: element, r and s must have the same length")
+        else:
+            xy = C.as_f64(points)
+            if xy.ndim != 2 or xy.shape[1] != 2:
+                raise ValueError("points: expected an (n, 2) array of x, y")
+            el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
+            if (el < 0).any():
+                raise ValueError(f"points {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+        bil, neigh, bary = nodes.drifterTables(mapO)
+        d = C.Sw2dqDrifterDesc(el.size, C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(bil), C.ptr(neigh), C.ptr(bary), int(stride),
+                               int(capacity))
+        check(lib.bdg_sw2dq_enable_drifters(self._h, byref(d)))
+        self.numDrifters = int(el.size)
+
+    def advanceDrifters(self, dt, nsteps=1):
+        """``nsteps`` advances by ``dt`` in the resident state as it is (a steady flow); the records' time moves on, the model
+        time does not."""
+        check(lib.bdg_sw2dq_drifters_advance(self._h, float(dt), int(nsteps)))
+
+    def timeDrifters(self, dt, count):
+        """Average device milliseconds per advance (no records taken; the drifters move)."""
+        ms = c_float()
+        check(lib.bdg_sw2dq_drifters_time(self._h, float(dt), int(count), byref(ms)))
+        return ms.value
+
+    def drifterState(self):
+        """dict of the drifters now: ``xy`` (n, 2), ``element``, ``r``, ``s``, ``status`` (0 moving, 1 exited, 2 lost, + 4 once it
+        has touched a wall); waits for the solver's stream."""
+        n = self.numDrifters
+        x, y, r, s = (np.empty(n) for _ in range(4))
+        el, st = np.empty(n, np.int32), np.empty(n, np.int32)
+        check(lib.bdg_sw2dq_drifters_state(self._h, C.ptr(x), C.ptr(y), C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(st)))
+        return {"xy": np.stack([x, y], axis=1), "element": el, "r": r, "s": s, "status": st}
+
+    def drifterTracks(self):
+        """(t, xy, status) of the records taken so far: (m,), (m, n, 2), (m, n); waits for the solver's stream."""
+        m, n = C.c_int(), C.c_int()
+        check(lib.bdg_sw2dq_drifters_count(self._h, byref(m), byref(n)))
+        m, n = m.value, n.value
+        t, x, y, st = np.empty(m), np.empty((m, n)), np.empty((m, n)), np.empty((m, n), np.int32)
+        check(lib.bdg_sw2dq_drifters_read(self._h, 0, m, C.ptr(t), C.ptr(x), C.ptr(y), C.ptr(st)))
+        return t, np.stack([x, y], axis=2), st
+
+    def resetDrifterTracks(self):
+        """Drops the records held on the device (the drifters stay where they are)."""
+        check(lib.bdg_sw2dq_drifters_reset(self._h))
+
     def computeDt(self, CFL):
         """(dt, speed) from the resident state: dt = CFL / ((N+1)^2 * 0.5 * speed), speed the face-node maximum of
         |Fscale| (|u| + sqrt(g h)); on a partition the maximum over every rank. Raises NumericalInstability on NaN."""

@@ -569,6 +569,50 @@ int bdg_sw2dq_monitor_reset(bdg_sw2dq* s);             /* count = 0, step counte
  * reduced, in place on the solver's stream: sum for the integrals, E, the gauges and the NaN count, minimum / maximum for
  * the extrema, t left alone. Call it once before reading, not per sample. */
 int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s);
+/* ---- drifters: points that move with the velocity (hu / h, hv / h) of the resident state, followed from element to element
+ * and recorded on the device, one launch per advance on the solver's stream and no host wait
+ * (csrc/hip/sw2d_quad_drifter_kernel.hpp, which states the algorithm). Single domain and bilinear elements only.
+ * Host set-up, from a quadrilateral provisioner: bilinear (K, 8), per element xc, ax, bx, cx, yc, ay, by, cy of the map
+ * x(r, s) = xc + ax r + bx s + cx r s of its four corner nodes; neighbours (4, K), the element across each face (faces in
+ * Fmask order: s = -1, r = +1, s = +1, r = -1), -1 for a wall, -2 for an open boundary face: a boundary face with a node in
+ * mapO (the list of bdg_sw2dq_enable_variant_b; may be empty); bary (N+1), the barycentric weights of the Gauss-Lobatto
+ * points. BDG_ERR_ARGUMENT for a mesh whose nodes differ from the bilinear map of their element's corners by more than 1e-10
+ * of the element's size. */
+int bdg_quadnodes_drifter_tables(const bdg_quadnodes* nodes, const int* mapO, int num_out, double* bilinear, int* neighbours,
+                                 double* bary);
+typedef struct bdg_sw2dq_drifter_desc {
+    int count;                  /* number of drifters, >= 1 */
+    const int* element;         /* initial positions: element in [0, K) and reference coordinates, |r|, |s| <= 1 + 1e-10 */
+    const double* r;            /* (bdg_quadnodes_locate_points) */
+    const double* s;
+    const double* bilinear;     /* (K, 8), (4, K), (N+1): bdg_quadnodes_drifter_tables */
+    const int* neighbours;
+    const double* bary;
+    int stride;                 /* record after every stride-th advance, >= 1 */
+    int capacity;               /* records held on the device, >= 1 */
+} bdg_sw2dq_drifter_desc;
+/* Status of a drifter: 0 moving, 1 exited through an open face (frozen there), 2 lost (frozen where it was: the search ran
+ * out of hops, its Newton iteration failed or the velocity was not finite), + 4 once it has touched a wall (it slides along it).
+ * enable_drifters: once per solver; computes x, y from the map and samples the velocity of the resident state (set_state
+ * first). BDG_ERR_ARGUMENT, changing nothing, for a NULL or incomplete descriptor, count, stride or capacity < 1, an element
+ * outside [0, K), a point outside its element, a neighbour entry outside [-2, K), a second call, and a solver with a partition
+ * set; bdg_sw2dq_set_partition in turn refuses a solver that has drifters. From then on step_rk2, step_ssprk2 and
+ * lserk4_stages (a step is the fifth stage) advance the drifters by that step's dt after every completed step (Heun: the
+ * velocity sampled before the step and the one of the new state), behind the monitor's sample if there is one, and store a
+ * record with t = the model time after every stride-th advance; a call that would take more records than the capacity has left
+ * returns BDG_ERR_ARGUMENT before it launches anything. set_state and set_state4 sample the velocity again.
+ * drifters_advance: num_steps advances by dt in the resident state as it is (steady flows); the records' time moves on by dt per
+ * advance, the model time does not. drifters_time: average device milliseconds of `count` such advances, no records taken.
+ * drifters_state: the current x, y, element, r, s, status (count entries each; any may be NULL). drifters_count: records
+ * taken and drifters. drifters_read: records [first, first + num): t (num), x, y, status (num x count each, record-major; any
+ * may be NULL); synchronises the solver's stream. drifters_reset drops the records only. */
+int bdg_sw2dq_enable_drifters(bdg_sw2dq* s, const bdg_sw2dq_drifter_desc* desc);
+int bdg_sw2dq_drifters_advance(bdg_sw2dq* s, double dt, int num_steps);
+int bdg_sw2dq_drifters_time(bdg_sw2dq* s, double dt, int count, float* ms);
+int bdg_sw2dq_drifters_state(bdg_sw2dq* s, double* x, double* y, int* element, double* r, double* sref, int* status);
+int bdg_sw2dq_drifters_count(const bdg_sw2dq* s, int* num_records, int* num_drifters);
+int bdg_sw2dq_drifters_read(bdg_sw2dq* s, int first, int num, double* t, double* x, double* y, int* status);
+int bdg_sw2dq_drifters_reset(bdg_sw2dq* s);
 
 /* Resident time stepping (state stays in HBM). */
 int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps);          /* 5 fused stages per step */
