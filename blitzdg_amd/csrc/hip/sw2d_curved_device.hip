@@ -6,6 +6,7 @@
 #include "blitzdg/LSERK4.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_curved_kernel.hpp"
+#include "sw2d_curved_kernel_info.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -35,6 +36,31 @@ const CurvedKernelTable* curved_kernel_table(int order) {
     case 6: return curved_kernel_table_order6();
     case 7: return curved_kernel_table_order7();
     case 8: return curved_kernel_table_order8();
+    default: return nullptr;
+    }
+}
+
+// Which instance an order's launch path picks (sw2d_curved_order.hip: kernelInfo, built on the launches' own helpers).
+static_assert(kCurvedKernelInfoFields == BDG_SW2D_CURVED_KERNEL_INFO_FIELDS, "the C ABI and the order objects disagree on the fields");
+CurvedKernelInfoFn curved_kernel_info_order1();
+CurvedKernelInfoFn curved_kernel_info_order2();
+CurvedKernelInfoFn curved_kernel_info_order3();
+CurvedKernelInfoFn curved_kernel_info_order4();
+CurvedKernelInfoFn curved_kernel_info_order5();
+CurvedKernelInfoFn curved_kernel_info_order6();
+CurvedKernelInfoFn curved_kernel_info_order7();
+CurvedKernelInfoFn curved_kernel_info_order8();
+
+CurvedKernelInfoFn curved_kernel_info(int order) {
+    switch (order) {
+    case 1: return curved_kernel_info_order1();
+    case 2: return curved_kernel_info_order2();
+    case 3: return curved_kernel_info_order3();
+    case 4: return curved_kernel_info_order4();
+    case 5: return curved_kernel_info_order5();
+    case 6: return curved_kernel_info_order6();
+    case 7: return curved_kernel_info_order7();
+    case 8: return curved_kernel_info_order8();
     default: return nullptr;
     }
 }
@@ -1045,5 +1071,18 @@ int bdg_sw2d_curved_synchronize(bdg_sw2d_curved* s) {
 size_t bdg_sw2d_curved_device_bytes(const bdg_sw2d_curved* s) { return s ? s->bytes : 0; }
 double bdg_sw2d_curved_bytes_per_element(const bdg_sw2d_curved* s) { return s ? s->bytesPerElement : 0.0; }
 int bdg_sw2d_curved_form(const bdg_sw2d_curved* s) { return s ? (s->useNT ? 1 : 0) : -1; }
+
+int bdg_sw2d_curved_kernel_info(const bdg_sw2d_curved* s, int filter, int* out, int n) {
+    return guard([&] {
+        requireCurved(s, "bdg_sw2d_curved_kernel_info");
+        if (!out || n < 0) throw arg_error("bdg_sw2d_curved_kernel_info: bad output buffer");
+        if (filter && !s->hasFilter) throw arg_error("bdg_sw2d_curved: filter requested but the solver was created without a Filter matrix");
+        int v[BDG_SW2D_CURVED_KERNEL_INFO_FIELDS];
+        const bdg_dev::CurvedKernelInfoFn info = bdg_dev::curved_kernel_info(s->N);
+        if (!info || !info(s->useNT, s->ncb, s->ng, s->fb, !s->identityM, filter != 0, v))
+            throw arg_error("bdg_sw2d_curved_kernel_info: no compiled kernel serves this solver");
+        std::copy(v, v + std::min(n, BDG_SW2D_CURVED_KERNEL_INFO_FIELDS), out);
+    });
+}
 
 } // extern "C"

@@ -1,5 +1,6 @@
 // Instantiates the curved / over-integrated sw2d kernels for one polynomial order (-DBDG_ORDER=N).
 #include "sw2d_curved_kernel.hpp"
+#include "sw2d_curved_kernel_info.hpp"
 #include "sw2d_curved_nt_kernel.hpp"
 #include <algorithm>
 #include <cstdio>
@@ -53,10 +54,18 @@ int curvedWaves() {
     return w;
 }
 
+// What a launch of the general stage kernel decides on the host (also what kernelInfo reports): the register budget (a rewired
+// interior map is rare and has one budget only), and whether the operator image is staged in LDS or read from global memory.
+bool stageMapM(const CurvedParams& p) { return p.gmapM != nullptr; }
+int stageWaves(bool mapm) { return mapm ? 1 : curvedWaves(); }
+size_t stageWrefBytes(int ncb) { return static_cast<size_t>(16 * ncb) * sizeof(double); } // reference weights of straight elements, behind the image
+size_t stageImageBytes(int ncb, int fb) { return static_cast<size_t>(O::tiles(ncb, fb)) * 64 * sizeof(double) + stageWrefBytes(ncb); }
+bool stageImageInLds(int ncb, int fb) { return stageImageBytes(ncb, fb) <= static_cast<size_t>(kLdsBudgetBytes); }
+
 template <int MODE, bool FILTER>
 hipError_t launchStage(const CurvedParams& p, hipStream_t stream) {
-    const bool two = curvedWaves() == 2;
-    if (p.gmapM) { // rewired interior map (rare): one register budget only
+    const bool mapm = stageMapM(p), two = stageWaves(mapm) == 2;
+    if (mapm) {
         if (p.fb == 1) return launchStageFb<MODE, FILTER, 1, 1, true>(p, stream);
         if (p.fb == 2) return launchStageFb<MODE, FILTER, 2, 1, true>(p, stream);
         return hipErrorInvalidValue;
@@ -69,9 +78,8 @@ hipError_t launchStage(const CurvedParams& p, hipStream_t stream) {
 template <int MODE, bool FILTER, int FB, int WAVES, bool MAPM>
 hipError_t launchStageFb(const CurvedParams& p, hipStream_t stream) {
     if (p.K < 1) return hipSuccess;
-    const size_t wref = static_cast<size_t>(16 * p.ncb) * sizeof(double); // reference weights of straight elements, behind the image
-    const size_t lds = static_cast<size_t>(O::tiles(p.ncb, p.fb)) * 64 * sizeof(double) + wref;
-    if (lds <= static_cast<size_t>(kLdsBudgetBytes)) {
+    if (stageImageInLds(p.ncb, p.fb)) {
+        const size_t lds = stageImageBytes(p.ncb, p.fb);
         auto kern = sw2d_curved_stage_kernel<kN, MODE, FILTER, true, FB, WAVES, MAPM>;
         if (lds > 64 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -81,7 +89,8 @@ hipError_t launchStageFb(const CurvedParams& p, hipStream_t stream) {
         const int wgPerCu = std::max(1, static_cast<int>(160 * 1024 / std::max<size_t>(lds, 1)));
         hipLaunchKernelGGL(kern, dim3(gridFor(p.K, std::min(wgPerCu, 2))), dim3(256), lds, stream, p);
     } else {
-        hipLaunchKernelGGL((sw2d_curved_stage_kernel<kN, MODE, FILTER, false, FB, WAVES, MAPM>), dim3(gridFor(p.K, 2)), dim3(256), wref, stream, p);
+        hipLaunchKernelGGL((sw2d_curved_stage_kernel<kN, MODE, FILTER, false, FB, WAVES, MAPM>), dim3(gridFor(p.K, 2)), dim3(256),
+                           stageWrefBytes(p.ncb), stream, p);
     }
     return hipGetLastError();
 }
@@ -139,9 +148,11 @@ bool ntFits(int ncb, int fb, bool filter) {
                                : ntLdsResident(ncb, fb) <= static_cast<size_t>(kLdsBudgetBytes);
 }
 
+constexpr int kNtWaves = kDefaultWaves; // the nodal-trace kernels have one register budget per order
+
 template <int MODE, bool FILTER, int STREAM, int FB, int RL>
 hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
-    constexpr int WAVES = kDefaultWaves;
+    constexpr int WAVES = kNtWaves;
     auto kern = sw2d_curved_nt_kernel<kN, MODE, FILTER, STREAM, FB, WAVES, RL>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -191,25 +202,40 @@ hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
 // steps in the last one -- and the two general shapes (every step of one / two blocks) for any other rule.
 constexpr int kNgDef = 2 * (BDG_ORDER + 1), kFbDef = (kNgDef + 15) / 16, kRlDef = (kNgDef - 16 * (kFbDef - 1) + 3) / 4;
 
+struct FaceShape { int fb, rl; };
+FaceShape ntShape(int ng, int fb) {
+    const int rl = (ng - 16 * (fb - 1) + 3) / 4;
+    if (fb == kFbDef && rl == kRlDef) return {kFbDef, kRlDef};
+    return {fb == 1 ? 1 : 2, 4};
+}
+
 template <int MODE, bool FILTER, int STREAM>
 hipError_t launchShape(const CurvedParams& p, hipStream_t stream, size_t lds) {
-    const int rl = (p.ng - 16 * (p.fb - 1) + 3) / 4;
-    if (p.fb == kFbDef && rl == kRlDef) return launchNT<MODE, FILTER, STREAM, kFbDef, kRlDef>(p, stream, lds);
-    if (p.fb == 1) return launchNT<MODE, FILTER, STREAM, 1, 4>(p, stream, lds);
+    const FaceShape sh = ntShape(p.ng, p.fb);
+    if (sh.fb == kFbDef && sh.rl == kRlDef) return launchNT<MODE, FILTER, STREAM, kFbDef, kRlDef>(p, stream, lds);
+    if (sh.fb == 1) return launchNT<MODE, FILTER, STREAM, 1, 4>(p, stream, lds);
     return launchNT<MODE, FILTER, STREAM, 2, 4>(p, stream, lds);
+}
+
+// The nodal-trace launch's plan: streamed or resident image and its LDS bytes; false when no compiled kernel serves it.
+struct NtPlan { bool streamed; size_t lds; };
+bool ntPlan(int ncb, int fb, bool filter, NtPlan& plan) {
+    plan.streamed = ntStreamed(ncb, fb);
+    plan.lds = plan.streamed ? ntLdsStreamed(ncb, fb, filter) : ntLdsResident(ncb, fb);
+    return plan.lds <= kLdsLimitBytes && fb >= 1 && fb <= 2; // (ntFits was asked at creation)
 }
 
 template <int MODE, bool FILTER>
 hipError_t launchStageNT(const CurvedParams& p, hipStream_t stream) {
     if (p.K <= p.kbegin) return hipSuccess;
-    const bool streamed = ntStreamed(p.ncb, p.fb);
-    const size_t lds = streamed ? ntLdsStreamed(p.ncb, p.fb, FILTER) : ntLdsResident(p.ncb, p.fb);
-    if (lds > kLdsLimitBytes || p.fb < 1 || p.fb > 2) return hipErrorInvalidValue; // (ntFits was asked at creation)
-    if (streamed) {
-        if constexpr (kNtStream) return launchShape<MODE, FILTER, 1>(p, stream, lds);
-        return hipErrorInvalidValue;
+    NtPlan plan;
+    if (!ntPlan(p.ncb, p.fb, FILTER, plan)) return hipErrorInvalidValue;
+    // ntStreamed answers with a form this order has; the guards only keep kernels that do not exist from being instantiated
+    if (plan.streamed) {
+        if constexpr (kNtStream) return launchShape<MODE, FILTER, 1>(p, stream, plan.lds);
+    } else {
+        if constexpr (kNtResident) return launchShape<MODE, FILTER, 0>(p, stream, plan.lds);
     }
-    if constexpr (kNtResident) return launchShape<MODE, FILTER, 0>(p, stream, lds);
     return hipErrorInvalidValue;
 }
 
@@ -222,6 +248,25 @@ hipError_t stageNT(int mode, bool filter, const CurvedParams& p, hipStream_t str
     }
 }
 
+// Which instance a solver with these sizes launches, from the helpers the launches use: form, streamed, image_in_lds, fb,
+// live_steps, waves, mapm, lds_bytes (-1: does not apply to the form). Launches nothing. False: no kernel serves the sizes.
+bool kernelInfo(bool nodalTrace, int ncb, int ng, int fb, bool mapm, bool filter, int out[kCurvedKernelInfoFields]) {
+    if (fb < 1 || fb > 2) return false;
+    if (nodalTrace) {
+        NtPlan plan;
+        if (!ntPlan(ncb, fb, filter, plan)) return false;
+        const FaceShape sh = ntShape(ng, fb);
+        const int v[kCurvedKernelInfoFields] = {1, plan.streamed ? 1 : 0, -1, sh.fb, sh.rl, kNtWaves, 0, static_cast<int>(plan.lds)};
+        std::copy(v, v + kCurvedKernelInfoFields, out);
+    } else {
+        const bool inLds = stageImageInLds(ncb, fb);
+        const int v[kCurvedKernelInfoFields] = {0, -1, inLds ? 1 : 0, fb, -1, stageWaves(mapm), mapm ? 1 : 0,
+                          static_cast<int>(inLds ? stageImageBytes(ncb, fb) : stageWrefBytes(ncb))};
+        std::copy(v, v + kCurvedKernelInfoFields, out);
+    }
+    return true;
+}
+
 const CurvedKernelTable kTable = {kN, O::Np, O::KV, O::MT, opsTiles, stageTiles, opsOffsets, gauss, stage, fixup,
                                   ntTiles, ntOffsets, ntFits, stageNT};
 
@@ -230,5 +275,7 @@ const CurvedKernelTable kTable = {kN, O::Np, O::KV, O::MT, opsTiles, stageTiles,
 #define BDG_CAT2(a, b) a##b
 #define BDG_CAT(a, b) BDG_CAT2(a, b)
 const CurvedKernelTable* BDG_CAT(curved_kernel_table_order, BDG_ORDER)() { return &kTable; }
+// (beside the table, whose declaration is shared with the device code in sw2d_curved_kernel.hpp)
+CurvedKernelInfoFn BDG_CAT(curved_kernel_info_order, BDG_ORDER)() { return &kernelInfo; }
 
 } // namespace bdg_dev

@@ -143,6 +143,16 @@ class Sw2dCurvedSolver:
         """phase 0: intermediate = state + dt/2 RHS(state); phase 1: state += dt RHS(intermediate)."""
         check(lib.bdg_sw2d_curved_rk2_phase(self._h, float(dt), int(phase), int(bool(filter))))
 
+    KERNEL_INFO_FIELDS = ("form", "streamed", "image_in_lds", "fb", "live_steps", "waves", "mapm", "lds_bytes")
+
+    def kernelInfo(self, filter=False):
+        """Which kernel instance an evaluation of this solver launches, as the launch path decides it (bdg_sw2d_curved_kernel_info;
+        nothing runs on the GPU): form 0 general / 1 nodal-trace; streamed (nodal-trace) and image_in_lds (general), None on the
+        other form; fb and live_steps, the compiled face-block shape (live_steps None on the general form); waves; mapm; lds_bytes."""
+        out = (C.c_int * len(self.KERNEL_INFO_FIELDS))()
+        check(lib.bdg_sw2d_curved_kernel_info(self._h, int(bool(filter)), out, len(out)))
+        return {k: (None if v < 0 else int(v)) for k, v in zip(self.KERNEL_INFO_FIELDS, out)}
+
     deviceBytes = property(lambda self: lib.bdg_sw2d_curved_device_bytes(self._h))
     bytesPerElement = property(lambda self: lib.bdg_sw2d_curved_bytes_per_element(self._h))
     usesNodalTraces = property(lambda self: lib.bdg_sw2d_curved_form(self._h) == 1)

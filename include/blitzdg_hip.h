@@ -803,6 +803,21 @@ double bdg_sw2d_curved_bytes_per_element(const bdg_sw2d_curved* s);
  * rows vanish off the face nodes -- what buildGaussFaceNodes produces, periodic rewiring included), 0 = the general form
  * (Gauss-trace planes; any map). Decided at creation; BDG_SW2D_CURVED_GENERAL=1 forces 0. -1: NULL handle. */
 int bdg_sw2d_curved_form(const bdg_sw2d_curved* s);
+/* Which kernel instance this solver's evaluations launch (with the filter fused or not), as the launch path itself decides it:
+ * the first min(n, 8) of
+ *   out[0] form          0 general, 1 nodal-trace (bdg_sw2d_curved_form)
+ *   out[1] streamed      nodal-trace: 1 when the operator image is streamed through LDS, 0 when it is resident (-1: general)
+ *   out[2] image_in_lds  general: 1 when the stage kernel holds the operator image in LDS, 0 when it reads it from global
+ *                        memory (-1: nodal-trace)
+ *   out[3] fb            16-row blocks per face
+ *   out[4] live_steps    nodal-trace: live 4-row steps of a face's last block in the compiled shape (4: every step) (-1: general)
+ *   out[5] waves         register budget: waves per SIMD the instance is compiled for
+ *   out[6] mapm          general: 1 when the interior traces are gathered through a rewired gmapM
+ *   out[7] lds_bytes     dynamic LDS of the stage launch
+ * No GPU work, nothing is launched. BDG_SW2D_CURVED_STREAM and BDG_SW2D_CURVED_WAVES are read once per process, by the first
+ * launch or by this call, whichever comes first. */
+#define BDG_SW2D_CURVED_KERNEL_INFO_FIELDS 8
+int bdg_sw2d_curved_kernel_info(const bdg_sw2d_curved* s, int filter, int* out, int n);
 
 #ifdef __cplusplus
 }

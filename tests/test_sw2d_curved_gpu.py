@@ -123,33 +123,11 @@ def test_drop_in_signature_of_the_reference_function():
 
 
 def big_problem(order, nx, ny, seed=7):
-    """A deformed box with many elements, contexts from this repo's builders, and the oracle's tables."""
-    mesh = dg.MeshManager()
-    mesh.buildBoxMesh(nx, ny)
-    nodes = dg.TriangleNodesProvisioner(order, mesh)
-    nodes.buildFilter(0.9 * order, order)
-    ctx = nodes.dgContext()
-    x0, y0 = ctx.x, ctx.y
-    rho2 = ((x0 - 0.4) ** 2 + (y0 + 1.0) ** 2) / 0.8 ** 2
-    b = np.where(rho2 < 1.0, (1.0 - rho2) ** 3, 0.0)
-    x, y = x0 + 0.02 * b * np.cos(1.3 * y0), y0 + 0.05 * b * np.sin(1.7 * x0 + 0.4)
-    curvedEls = np.where((np.abs(x - x0) + np.abs(y - y0)).max(axis=0) > 0)[0].astype(np.int32)
-    nodes.setCoordinates(x, y)
-    J = (ctx.Dr @ x) * (ctx.Ds @ y) - (ctx.Ds @ x) * (ctx.Dr @ y)
-    gauss = nodes.buildGaussFaceNodes(2 * (order + 1))
-    cub = nodes.buildCubatureVolumeMesh(3 * (order + 1))
-    rng = np.random.default_rng(seed)
-    h = 1.0 + 0.3 * np.exp(-8 * x * x - 8 * y * y)
-    hu, hv = 0.05 * rng.standard_normal(x.shape), 0.05 * rng.standard_normal(x.shape)
-    hN = h * (0.5 + 0.3 * np.sin(2 * x) * np.cos(3 * y))
-    zx, zy = 0.05 + 0 * x, -0.04 * y
-    CD = 2.5e-3 * (1.0 + 0.5 * np.cos(x))
-    t = dict(cubV=cub.V, cubDr=cub.Dr, cubDs=cub.Ds, cubW=cub.W, cubrx=cub.rx, cubry=cub.ry, cubsx=cub.sx, cubsy=cub.sy,
-             gInterp=gauss.Interp, gW=gauss.W, gnx=gauss.nx, gny=gauss.ny, gmapM=gauss.mapM, gmapP=gauss.mapP,
-             gmapW=np.array(gauss.BCmap[3], dtype=np.int32), V=ctx.V, J=J, MMChol=cub.MMChol, curvedEls=curvedEls,
-             Filter=ctx.filter)
-    solver = Sw2dCurvedSolver(ctx, cub, gauss, curvedEls, J, gauss.mapM, gauss.mapP, g=0.0245, zx=zx, zy=zy, f=0.0788, CD=CD)
-    return solver, t, (h, hu, hv, hN), dict(zx=zx, zy=zy, g=0.0245, f=0.0788, CD=CD)
+    """A deformed box with many elements, contexts from this repo's builders, and the oracle's tables (tests/curved_cases.py:
+    curvedEls = the deformed elements, as they are)."""
+    import curved_cases
+    c = curved_cases.problem(order, nx, ny, seed=seed, odd_curved=False)
+    return curved_cases.solver(c), c.t, c.q, c.ph
 
 
 @pytest.mark.parametrize("order,nx,ny", [(1, 23, 17), (4, 40, 33), (5, 21, 16), (7, 9, 8)])
