@@ -770,31 +770,10 @@ def test_non_affine_tables_on_the_matrix_core_kernel(order, nx, ny, vector, monk
         if order > 6:
             pytest.skip("the vector kernel exists up to N = 6")
         monkeypatch.setenv("BDG_SW2D_NODAL_VECTOR", "1")
-    mesh = dg.MeshManager()
-    mesh.buildBoxMesh(nx, ny, shuffleSeed=77)
-    nodes = dg.TriangleNodesProvisioner(order, mesh)
-    nodes.buildFilter(0.9 * order, max(order, 2))
-    ctx = nodes.dgContext()
-    x0, y0 = ctx.x, ctx.y
-    x = x0 + 0.06 * np.sin(2.1 * y0) * (1 - x0 * x0)
-    y = y0 + 0.05 * np.sin(2.7 * x0 + 0.3) * (1 - y0 * y0)
-    # per-node metric terms and face geometry of the deformed elements, as the reference's formulas give them
-    # (src/TriangleNodesProvisioner.cpp:810-892), from this repository's Dr / Ds
-    Dr, Ds = ctx.Dr, ctx.Ds
-    xr, xs, yr, ys = Dr @ x, Ds @ x, Dr @ y, Ds @ y
-    J = xr * ys - xs * yr
-    assert J.min() > 0
-    t = tables_from_nodes(nodes)
-    t.update(rx=ys / J, sx=-yr / J, ry=-xs / J, sy=xr / J, x=x, y=y)
-    Fm = ctx.Fmask.T.reshape(-1) if ctx.Fmask.shape[0] == order + 1 else ctx.Fmask.reshape(-1)
-    Nfp = order + 1
-    fxr, fxs, fyr, fys = xr[Fm], xs[Fm], yr[Fm], ys[Fm]
-    nxf, nyf = np.empty_like(fxr), np.empty_like(fxr)
-    nxf[:Nfp], nyf[:Nfp] = fyr[:Nfp], -fxr[:Nfp]
-    nxf[Nfp:2 * Nfp], nyf[Nfp:2 * Nfp] = fys[Nfp:2 * Nfp] - fyr[Nfp:2 * Nfp], -fxs[Nfp:2 * Nfp] + fxr[Nfp:2 * Nfp]
-    nxf[2 * Nfp:], nyf[2 * Nfp:] = -fys[2 * Nfp:], fxs[2 * Nfp:]
-    sJ = np.hypot(nxf, nyf)
-    t.update(nx=nxf / sJ, ny=nyf / sJ, Fscale=sJ / J[Fm])
+    # per-node metric terms and face geometry of the deformed elements (tests/nonaffine_cases.py)
+    from nonaffine_cases import deformed_box_tables
+    t = deformed_box_tables(order, nx, ny)
+    x, y = t["x"], t["y"]
     # (three-node elements stay straight whatever the map: at N = 1 the per-node path is asked for explicitly)
     s = sw2d.Sw2dSolver(tables=t, g=9.81, flags=sw2d.KEEP_ORDER | (sw2d.NODAL_GEOMETRY if order == 1 else 0))
     assert not s.usesAffineGeometry
