@@ -1,5 +1,5 @@
-// device_buffer.hpp -- the HIP error check and the owning device buffer of the two sw2d solvers (sw2d_device.hip,
-// sw2d_curved_device.hip).
+// device_buffer.hpp -- the HIP error check, the owning device buffer and the event timer of the sw2d solvers
+// (sw2d_device.hip, sw2d_curved_device.hip, sw2d_quad_device.hip).
 #pragma once
 #include "../host/capi_internal.hpp"
 #include <hip/hip_runtime.h>
@@ -41,5 +41,27 @@ struct DevBuf {
     }
     ~DevBuf() { release(); }
 };
+
+// an owned event: destroyed on every way out, a throwing hipCheck included
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() { hipCheck(hipEventCreate(&e), "hipEventCreate"); }
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { (void)hipEventDestroy(e); }
+};
+
+// `body()` run `count` times between two events on `stream`, waited for: device milliseconds per run
+template <class Body>
+float timePerRun(hipStream_t stream, int count, Body&& body) {
+    DevEvent a, b;
+    hipCheck(hipEventRecord(a.e, stream), "hipEventRecord");
+    for (int i = 0; i < count; ++i) body();
+    hipCheck(hipEventRecord(b.e, stream), "hipEventRecord");
+    hipCheck(hipEventSynchronize(b.e), "hipEventSynchronize");
+    float ms = 0.0f;
+    hipCheck(hipEventElapsedTime(&ms, a.e, b.e), "hipEventElapsedTime");
+    return ms / count;
+}
 
 } // namespace bdg_dev

@@ -2118,23 +2118,13 @@ int bdg_probe_stream_triad(int device, size_t bytes_per_array, int repeats, doub
         hipCheck(hipMemset(a.p, 0, 2 * n2 * sizeof(double)), "hipMemset");
         hipCheck(hipMemset(b.p, 0, 2 * n2 * sizeof(double)), "hipMemset");
         hipCheck(hipMemset(c.p, 0, 2 * n2 * sizeof(double)), "hipMemset");
-        hipEvent_t e0, e1;
-        hipCheck(hipEventCreate(&e0), "hipEventCreate");
-        hipCheck(hipEventCreate(&e1), "hipEventCreate");
         auto launch = [&] {
             hipLaunchKernelGGL(bdg_dev::triad_kernel, dim3(256 * 8), dim3(256), 0, nullptr, reinterpret_cast<double2*>(a.p),
                                reinterpret_cast<const double2*>(b.p), reinterpret_cast<const double2*>(c.p), 0.5, n2);
         };
         launch();
-        hipCheck(hipEventRecord(e0, nullptr), "hipEventRecord");
-        for (int i = 0; i < repeats; ++i) launch();
-        hipCheck(hipEventRecord(e1, nullptr), "hipEventRecord");
-        hipCheck(hipEventSynchronize(e1), "hipEventSynchronize");
-        float ms = 0.f;
-        hipCheck(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        *gbps = 3.0 * static_cast<double>(n2) * sizeof(double2) * repeats / (ms * 1e-3) / 1e9;
+        const float ms = bdg_dev::timePerRun(nullptr, repeats, launch);
+        *gbps = 3.0 * static_cast<double>(n2) * sizeof(double2) / (ms * 1e-3) / 1e9;
     });
 }
 

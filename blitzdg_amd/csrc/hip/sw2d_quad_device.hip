@@ -15,6 +15,7 @@
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_dispatch.hpp"
 #include "sw2d_quad_drifter_kernel.hpp"
 #include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
@@ -39,95 +40,31 @@ using namespace bdg_dev;
 
 namespace bdg_dev {
 
+namespace {
+// the per-order launchers exist for 1..BDG_SW2DQ_MAX_ORDER (the Makefile's QUAD_ORDERS)
+template <class F>
+hipError_t forOrder(int order, F&& f) { return quadForOrder<BDG_SW2DQ_MAX_ORDER>(order, std::forward<F>(f)); }
+} // namespace
+
 hipError_t sw2d_quad_stage(int order, int mode, bool filter, bool general, const QuadParams& p, hipStream_t stream) {
-    switch (order) {
-    case 1: return sw2d_quad_launch<1>(mode, filter, general, p, stream);
-    case 2: return sw2d_quad_launch<2>(mode, filter, general, p, stream);
-    case 3: return sw2d_quad_launch<3>(mode, filter, general, p, stream);
-    case 4: return sw2d_quad_launch<4>(mode, filter, general, p, stream);
-    case 5: return sw2d_quad_launch<5>(mode, filter, general, p, stream);
-    case 6: return sw2d_quad_launch<6>(mode, filter, general, p, stream);
-    case 7: return sw2d_quad_launch<7>(mode, filter, general, p, stream);
-    case 8: return sw2d_quad_launch<8>(mode, filter, general, p, stream);
-    case 9: return sw2d_quad_launch<9>(mode, filter, general, p, stream);
-    case 10: return sw2d_quad_launch<10>(mode, filter, general, p, stream);
-    case 11: return sw2d_quad_launch<11>(mode, filter, general, p, stream);
-    case 12: return sw2d_quad_launch<12>(mode, filter, general, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return forOrder(order, [&](auto n) { return sw2d_quad_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quad4_stage(int order, int mode, bool filter, bool general, bool sources, const Quad4Params& p,
                             hipStream_t stream) {
-    switch (order) {
-    case 1: return sw2d_quad4_launch<1>(mode, filter, general, sources, p, stream);
-    case 2: return sw2d_quad4_launch<2>(mode, filter, general, sources, p, stream);
-    case 3: return sw2d_quad4_launch<3>(mode, filter, general, sources, p, stream);
-    case 4: return sw2d_quad4_launch<4>(mode, filter, general, sources, p, stream);
-    case 5: return sw2d_quad4_launch<5>(mode, filter, general, sources, p, stream);
-    case 6: return sw2d_quad4_launch<6>(mode, filter, general, sources, p, stream);
-    case 7: return sw2d_quad4_launch<7>(mode, filter, general, sources, p, stream);
-    case 8: return sw2d_quad4_launch<8>(mode, filter, general, sources, p, stream);
-    case 9: return sw2d_quad4_launch<9>(mode, filter, general, sources, p, stream);
-    case 10: return sw2d_quad4_launch<10>(mode, filter, general, sources, p, stream);
-    case 11: return sw2d_quad4_launch<11>(mode, filter, general, sources, p, stream);
-    case 12: return sw2d_quad4_launch<12>(mode, filter, general, sources, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return forOrder(order, [&](auto n) { return sw2d_quad4_launch<decltype(n)::value>(mode, filter, general, sources, p, stream); });
 }
 
 hipError_t sw2d_quad_output(int order, int fields, const QuadOutParams& p, hipStream_t stream) {
-    switch (order) {
-    case 1: return sw2d_quad_output_launch<1>(fields, p, stream);
-    case 2: return sw2d_quad_output_launch<2>(fields, p, stream);
-    case 3: return sw2d_quad_output_launch<3>(fields, p, stream);
-    case 4: return sw2d_quad_output_launch<4>(fields, p, stream);
-    case 5: return sw2d_quad_output_launch<5>(fields, p, stream);
-    case 6: return sw2d_quad_output_launch<6>(fields, p, stream);
-    case 7: return sw2d_quad_output_launch<7>(fields, p, stream);
-    case 8: return sw2d_quad_output_launch<8>(fields, p, stream);
-    case 9: return sw2d_quad_output_launch<9>(fields, p, stream);
-    case 10: return sw2d_quad_output_launch<10>(fields, p, stream);
-    case 11: return sw2d_quad_output_launch<11>(fields, p, stream);
-    case 12: return sw2d_quad_output_launch<12>(fields, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return forOrder(order, [&](auto n) { return sw2d_quad_output_launch<decltype(n)::value>(fields, p, stream); });
 }
 
 hipError_t sw2d_quadb_stage(int order, int mode, bool filter, bool general, const QuadBParams& p, hipStream_t stream) {
-    switch (order) {
-    case 1: return sw2d_quadb_launch<1>(mode, filter, general, p, stream);
-    case 2: return sw2d_quadb_launch<2>(mode, filter, general, p, stream);
-    case 3: return sw2d_quadb_launch<3>(mode, filter, general, p, stream);
-    case 4: return sw2d_quadb_launch<4>(mode, filter, general, p, stream);
-    case 5: return sw2d_quadb_launch<5>(mode, filter, general, p, stream);
-    case 6: return sw2d_quadb_launch<6>(mode, filter, general, p, stream);
-    case 7: return sw2d_quadb_launch<7>(mode, filter, general, p, stream);
-    case 8: return sw2d_quadb_launch<8>(mode, filter, general, p, stream);
-    case 9: return sw2d_quadb_launch<9>(mode, filter, general, p, stream);
-    case 10: return sw2d_quadb_launch<10>(mode, filter, general, p, stream);
-    case 11: return sw2d_quadb_launch<11>(mode, filter, general, p, stream);
-    case 12: return sw2d_quadb_launch<12>(mode, filter, general, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return forOrder(order, [&](auto n) { return sw2d_quadb_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quadb4_stage(int order, int mode, bool filter, bool general, const QuadB4Params& p, hipStream_t stream) {
-    switch (order) {
-    case 1: return sw2d_quadb4_launch<1>(mode, filter, general, p, stream);
-    case 2: return sw2d_quadb4_launch<2>(mode, filter, general, p, stream);
-    case 3: return sw2d_quadb4_launch<3>(mode, filter, general, p, stream);
-    case 4: return sw2d_quadb4_launch<4>(mode, filter, general, p, stream);
-    case 5: return sw2d_quadb4_launch<5>(mode, filter, general, p, stream);
-    case 6: return sw2d_quadb4_launch<6>(mode, filter, general, p, stream);
-    case 7: return sw2d_quadb4_launch<7>(mode, filter, general, p, stream);
-    case 8: return sw2d_quadb4_launch<8>(mode, filter, general, p, stream);
-    case 9: return sw2d_quadb4_launch<9>(mode, filter, general, p, stream);
-    case 10: return sw2d_quadb4_launch<10>(mode, filter, general, p, stream);
-    case 11: return sw2d_quadb4_launch<11>(mode, filter, general, p, stream);
-    case 12: return sw2d_quadb4_launch<12>(mode, filter, general, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return forOrder(order, [&](auto n) { return sw2d_quadb4_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quadb_speed(int order, bool general, const QuadBParams& p, double* out, hipStream_t stream) {
@@ -317,11 +254,6 @@ struct bdg_sw2dq {
             bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, halo.comm, stream),
                                 "ncclAllReduce");
     }
-    // one evaluation of every element on the solver's stream
-    void launch(int mode, bool filter, const QuadParams& p) {
-        if (variantB) speedPass(p.qin, K);
-        launchOn(mode, filter, p, stream);
-    }
     void launchOn(int mode, bool filter, const QuadParams& p, hipStream_t on) {
         evaluated = true;
         if (variantB && fields == 4) {
@@ -340,39 +272,90 @@ struct bdg_sw2dq {
         }
         hipCheck(sw2d_quad_stage(N, mode, filter, general, p, on), "sw2d_quad_stage_kernel launch");
     }
-    void rk2Step(double dt, bool filter) {
+    // ---- how one evaluation (reads p.qin, writes its outputs) is carried out
+    enum class Eval {
+        Whole,     // every element on the solver's stream
+        Exchanged, // a partition: the ghost columns of p.qin refreshed, then every owned element, in stream order
+        TwoChains  // a partition: the two-chain schedule of partition_schedule.hpp, interior elements beside the exchange
+    };
+    // Eval of the *_exchanged calls: the two chains unless there is no interior element or BDG_SW2DQ_NO_OVERLAP is set.
+    // Variant B is never overlapped: the all-rank speed has to exist before any element of the evaluation starts.
+    Eval exchangedEval() const {
+        const bool two = !variantB && part.numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
+        return two ? Eval::TwoChains : Eval::Exchanged;
+    }
+    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, fields * Np, K, on); }
+    // one evaluation of the elements [kBegin, kEnd) on `on`
+    void evaluateRange(int mode, bool filter, QuadParams p, int kBegin, int kEnd, hipStream_t on) {
+        p.kBegin = kBegin; p.kEnd = kEnd;
+        launchOn(mode, filter, p, on);
+    }
+    void evaluate(Eval how, int mode, bool filter, const QuadParams& p) {
+        double* in = const_cast<double*>(p.qin);
+        switch (how) {
+        case Eval::Whole:
+            if (variantB) speedPass(in, K);
+            launchOn(mode, filter, p, stream);
+            return;
+        case Eval::Exchanged:
+            if (variantB) speedPass(in, part.numOwned);
+            exchangeOn(in, stream);
+            evaluateRange(mode, filter, p, 0, part.numOwned, stream);
+            return;
+        case Eval::TwoChains:
+            // (the interior launch is the plain grid of one workgroup per tile: a capped grid of workgroups looping over tiles,
+            // which leaves room for the boundary launch, measured slower at every split and order: DESIGN section 3.8)
+            chains.eval(stream, halo.stream,
+                        [&](hipStream_t a) { evaluateRange(mode, filter, p, 0, part.numInterior, a); },
+                        [&](hipStream_t b) {
+                            exchangeOn(in, b);
+                            evaluateRange(mode, filter, p, part.numInterior, part.numOwned, b);
+                        });
+            return;
+        }
+    }
+
+    // ---- the steppers: one RK2 or Heun step, or one LSERK4 stage, of the resident state
+    enum class Stepper { Lserk, Rk2, Heun }; // (in the order of bdg_sw2dq_time's `kind`)
+    // the script's midpoint RK2, both evaluations at the old time level
+    void rk2Step(double dt, bool filter, Eval how) {
         QuadParams p = params();
         p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.cc = 0.5 * dt;        // predictor: q1 = q + dt/2 F R(q)
-        launch(QMODE_COMBINE, filter, p);
+        evaluate(how, QMODE_COMBINE, filter, p);
         p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;              // corrector: q += dt F R(q1)
-        launch(QMODE_COMBINE, filter, p);
-        timeNow += dt; // (both evaluations at the old time level)
+        evaluate(how, QMODE_COMBINE, filter, p);
+        timeNow += dt;
     }
     // SSP-RK2 (Heun) of the tidal driver (main.cpp:211-236), the sponge division in the stage store:
     //   q1 = sp(q + dt R(q));  q = sp(1/2 (q + q1 + dt R(q1))), both evaluations at the old time level
-    void heunStep(double dt, bool filter, bool exchanged, bool two) {
+    void heunStep(double dt, bool filter, Eval how) {
         QuadParams p = params();
         p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.ca = 1.0; p.cb = 0.0; p.cc = dt;
-        if (exchanged) evaluateExchanged(two, QMODE_HEUN, filter, p);
-        else launch(QMODE_HEUN, filter, p);
+        evaluate(how, QMODE_HEUN, filter, p);
         p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.ca = 0.5; p.cb = 0.5; p.cc = 0.5 * dt;
-        if (exchanged) evaluateExchanged(two, QMODE_HEUN, filter, p);
-        else launch(QMODE_HEUN, filter, p);
+        evaluate(how, QMODE_HEUN, filter, p);
         timeNow += dt;
     }
-    // the tide is frozen over the five stages of an LSERK4 step and the model time moves on after the last
-    void lserkAdvance(double dt) {
-        if (stageCount % blitzdg::LSERK4::numStages == blitzdg::LSERK4::numStages - 1) timeNow += dt;
-        ++stageCount;
-    }
-    void lserkStage(double dt) {
+    // q and q1 swap roles after every stage (neighbours read the old traces during the launch: double-buffered; on a partition
+    // the next stage's exchange refreshes the ghosts of the new q). The tide is frozen over the five stages of an LSERK4 step and
+    // the model time moves on after the last
+    void lserkStage(double dt, Eval how) {
         const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
         QuadParams p = params();
         p.qin = q.p; p.qout = q1.p; p.res = res.p;
         p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
-        launch(QMODE_LSERK, false, p);
-        std::swap(q.p, q1.p); // neighbours read the old traces during the launch: double-buffered
-        lserkAdvance(dt);
+        evaluate(how, QMODE_LSERK, false, p);
+        std::swap(q.p, q1.p);
+        if (st == blitzdg::LSERK4::numStages - 1) timeNow += dt;
+        ++stageCount;
+    }
+    // true when a step of size dt is complete (an LSERK4 stage: after the fifth)
+    bool advance(Stepper kind, double dt, bool filter, Eval how) {
+        switch (kind) {
+        case Stepper::Rk2: rk2Step(dt, filter, how); return true;
+        case Stepper::Heun: heunStep(dt, filter, how); return true;
+        default: lserkStage(dt, how); return stageCount % blitzdg::LSERK4::numStages == 0;
+        }
     }
     // the reference script's check after every step: max|h| > 1e8 or NaN, over the columns [0, count) of h. collective: the two
     // values are all-reduced (maximum) over every rank of the communicator first, so that all ranks raise together
@@ -504,69 +487,6 @@ struct bdg_sw2dq {
         }
     }
 
-    // ---- partitioned runs
-    void exchangeOn(double* state, hipStream_t on) { bdg_halo::exchange(halo, part, state, ld, fields * Np, K, on); }
-    // one evaluation of the elements [kBegin, kEnd) on `on`
-    void evaluateRange(int mode, bool filter, QuadParams p, int kBegin, int kEnd, hipStream_t on) {
-        p.kBegin = kBegin; p.kEnd = kEnd;
-        launchOn(mode, filter, p, on);
-    }
-    // The two-chain schedule of partition_schedule.hpp; without an interior element, or with BDG_SW2DQ_NO_OVERLAP:
-    // exchange, then every owned element, in stream order.
-    // Variant B is never overlapped: the all-rank speed has to exist before any element of the evaluation starts.
-    bool overlapped() const {
-        return !variantB && part.numInterior >= 1 && std::getenv("BDG_SW2DQ_NO_OVERLAP") == nullptr; // (A/B switch, read per call)
-    }
-    // one evaluation: reads p.qin (ghost columns refreshed first), writes the owned columns of its outputs
-    void evaluateExchanged(bool two, int mode, bool filter, const QuadParams& p) {
-        double* in = const_cast<double*>(p.qin);
-        if (!two) {
-            if (variantB) speedPass(in, part.numOwned);
-            exchangeOn(in, stream);
-            evaluateRange(mode, filter, p, 0, part.numOwned, stream);
-            return;
-        }
-        // (the interior launch is the plain grid of one workgroup per tile: a capped grid of workgroups looping over tiles,
-        // which leaves room for the boundary launch, measured slower at every split and order: DESIGN section 3.8)
-        chains.eval(stream, halo.stream,
-                    [&](hipStream_t a) { evaluateRange(mode, filter, p, 0, part.numInterior, a); },
-                    [&](hipStream_t b) {
-                        exchangeOn(in, b);
-                        evaluateRange(mode, filter, p, part.numInterior, part.numOwned, b);
-                    });
-    }
-    // the script's RK2 step with an exchange of q before the predictor and of q1 before the corrector
-    void stepRk2Exchanged(double dt, int steps, bool filter) {
-        const bool two = overlapped();
-        if (two) chains.begin(stream, halo.stream);
-        for (int i = 0; i < steps; ++i) {
-            QuadParams p = params();
-            p.qin = q.p; p.qbase = q.p; p.qout = q1.p; p.cc = 0.5 * dt;
-            evaluateExchanged(two, QMODE_COMBINE, filter, p);
-            p.qin = q1.p; p.qbase = q.p; p.qout = q.p; p.cc = dt;
-            evaluateExchanged(two, QMODE_COMBINE, filter, p);
-            timeNow += dt;
-            stepDone(dt, two);
-        }
-        if (two) chains.end(stream, halo.stream);
-    }
-    // LSERK4 stages with an exchange of the state each stage reads; q and q1 swap roles after every stage, and the next stage's
-    // exchange refreshes the ghosts of the new q
-    void lserkStagesExchanged(double dt, int stages) {
-        const bool two = overlapped();
-        if (two) chains.begin(stream, halo.stream);
-        for (int i = 0; i < stages; ++i) {
-            const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
-            QuadParams p = params();
-            p.qin = q.p; p.qout = q1.p; p.res = res.p;
-            p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dt;
-            evaluateExchanged(two, QMODE_LSERK, false, p);
-            std::swap(q.p, q1.p);
-            lserkAdvance(dt);
-            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone(dt, two);
-        }
-        if (two) chains.end(stream, halo.stream);
-    }
     ~bdg_sw2dq() { // both streams drained before the members destroy the events, the communicator and the exchange stream
         if (!stream) return;
         (void)hipSetDevice(device);
@@ -578,6 +498,9 @@ struct bdg_sw2dq {
 
 namespace {
 
+using Eval = bdg_sw2dq::Eval;
+using Stepper = bdg_sw2dq::Stepper;
+
 void requireSolver(const bdg_sw2dq* s, const char* fn) {
     if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
 }
@@ -587,6 +510,11 @@ void requireFields(const bdg_sw2dq* s, int fields, const char* fn) {
     if (s->fields != fields)
         throw arg_error(std::string(fn) + ": the solver was created with " + std::to_string(s->fields) + " fields; use " +
                         (s->fields == 4 ? "the *4 calls (h, hu, hv, hN)" : "the three-field calls (h, hu, hv)"));
+}
+
+void requireComm(const bdg_sw2dq* s, const char* fn) {
+    requireSolver(s, fn);
+    bdg_halo::requireComm(s->halo, "bdg_sw2dq", fn);
 }
 
 double maxAbs(const double* a, size_t n) {
@@ -759,6 +687,74 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
     return s.release();
 }
 
+// ---- what the three-field calls and their *4 twins share: `nf` fields, `fn` names the caller in the messages
+void setState(bdg_sw2dq* s, int nf, const double* const* in, const std::string& fn) {
+    requireSolver(s, fn.c_str());
+    requireFields(s, nf, fn.c_str());
+    if (std::find(in, in + nf, nullptr) != in + nf) throw arg_error(fn + ": NULL field");
+    s->use();
+    for (int c = 0; c < nf; ++c) s->upload(s->q.p + c * s->plane(), in[c], s->Np);
+    s->res.zero(s->stream);
+    s->stageCount = 0;
+    s->mon.steps = 0;
+    s->drifterResample();
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+}
+
+void getState(bdg_sw2dq* s, int nf, double* const* out, const char* fn) {
+    requireSolver(s, fn);
+    requireFields(s, nf, fn);
+    s->use();
+    for (int c = 0; c < nf; ++c)
+        if (out[c]) s->download(out[c], s->q.p + c * s->plane(), s->Np);
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+}
+
+void computeRhs(bdg_sw2dq* s, int nf, const double* const* in, double* const* out, int filter, const std::string& fn) {
+    requireSolver(s, fn.c_str());
+    requireFields(s, nf, fn.c_str());
+    if (std::find(in, in + nf, nullptr) != in + nf || std::find(out, out + nf, nullptr) != out + nf)
+        throw arg_error(fn + ": NULL argument");
+    if (filter && !s->hasFilter) throw arg_error(fn + ": filter requested but the solver has no Filter");
+    s->use();
+    const long long plane = s->plane();
+    if (!s->io.p) {
+        s->io.alloc(nf * plane, s->bytes, s->stream);
+        s->ioOut.alloc(nf * plane, s->bytes, s->stream);
+    }
+    for (int c = 0; c < nf; ++c) s->upload(s->io.p + c * plane, in[c], s->Np);
+    QuadParams p = s->params();
+    p.qin = s->io.p; p.rhs = s->ioOut.p;
+    s->evaluate(Eval::Whole, QMODE_RHS, filter != 0, p);
+    for (int c = 0; c < nf; ++c) s->download(out[c], s->ioOut.p + c * plane, s->Np);
+    hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+}
+
+// ---- what the stepping calls share: `count` steps (Stepper::Lserk: stages) of size dt, on a partition (`exchanged`) with the
+// ghost exchange in front of every evaluation. The schedule is chosen once per call and the two chains bracket the whole call.
+void stepping(bdg_sw2dq* s, const std::string& fn, Stepper kind, bool exchanged, double dt, int count, int filter,
+              double spongeCoeff = 0.0) {
+    if (exchanged) requireComm(s, fn.c_str());
+    else requireSolver(s, fn.c_str());
+    if (count < 0) throw arg_error(fn + (kind == Stepper::Lserk ? ": num_stages < 0" : ": num_steps < 0"));
+    if (kind == Stepper::Heun && !s->variantB)
+        throw arg_error(fn + ": variant B is not enabled" + (exchanged ? "" : " (the Heun step is the tidal driver's)"));
+    if (filter && !s->hasFilter) throw arg_error(fn + ": filter requested but the solver has no Filter");
+    const long long steps = kind == Stepper::Lserk ? s->lserkSteps(count) : count;
+    s->monitorReserve(steps, fn.c_str());
+    if (!exchanged) s->drifterReserve(steps, fn.c_str()); // (drifters exist on unpartitioned solvers only)
+    s->use();
+    if (kind == Stepper::Heun) s->spongeC = spongeCoeff;
+    const Eval how = exchanged ? s->exchangedEval() : Eval::Whole;
+    const bool two = how == Eval::TwoChains;
+    if (two) s->chains.begin(s->stream, s->halo.stream);
+    for (int i = 0; i < count; ++i)
+        if (s->advance(kind, dt, filter != 0, how)) s->stepDone(dt, two);
+    if (two) s->chains.end(s->stream, s->halo.stream);
+    if (exchanged) s->checkBlowUp(s->part.numOwned, true);
+    else s->checkBlowUp();
+}
+
 } // namespace
 
 extern "C" {
@@ -806,58 +802,24 @@ void bdg_sw2dq_destroy(bdg_sw2dq* s) { delete s; }
 
 int bdg_sw2dq_set_state(bdg_sw2dq* s, const double* h, const double* hu, const double* hv) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_set_state");
-        requireFields(s, 3, "bdg_sw2dq_set_state");
-        if (!h || !hu || !hv) throw arg_error("bdg_sw2dq_set_state: NULL field");
-        s->use();
-        const long long plane = s->plane();
-        s->upload(s->q.p, h, s->Np);
-        s->upload(s->q.p + plane, hu, s->Np);
-        s->upload(s->q.p + 2 * plane, hv, s->Np);
-        s->res.zero(s->stream);
-        s->stageCount = 0;
-        s->mon.steps = 0;
-        s->drifterResample();
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        const double* in[] = {h, hu, hv};
+        setState(s, 3, in, "bdg_sw2dq_set_state");
     });
 }
 
 int bdg_sw2dq_get_state(bdg_sw2dq* s, double* h, double* hu, double* hv) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_get_state");
-        requireFields(s, 3, "bdg_sw2dq_get_state");
-        s->use();
-        const long long plane = s->plane();
-        if (h) s->download(h, s->q.p, s->Np);
-        if (hu) s->download(hu, s->q.p + plane, s->Np);
-        if (hv) s->download(hv, s->q.p + 2 * plane, s->Np);
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        double* out[] = {h, hu, hv};
+        getState(s, 3, out, "bdg_sw2dq_get_state");
     });
 }
 
 int bdg_sw2dq_rhs(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, double* rhs1, double* rhs2,
                   double* rhs3, int filter) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_rhs");
-        requireFields(s, 3, "bdg_sw2dq_rhs");
-        if (!h || !hu || !hv || !rhs1 || !rhs2 || !rhs3) throw arg_error("bdg_sw2dq_rhs: NULL argument");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_rhs: filter requested but the solver has no Filter");
-        s->use();
-        const long long plane = s->plane();
-        if (!s->io.p) {
-            s->io.alloc(3 * plane, s->bytes, s->stream);
-            s->ioOut.alloc(3 * plane, s->bytes, s->stream);
-        }
-        s->upload(s->io.p, h, s->Np);
-        s->upload(s->io.p + plane, hu, s->Np);
-        s->upload(s->io.p + 2 * plane, hv, s->Np);
-        QuadParams p = s->params();
-        p.qin = s->io.p; p.rhs = s->ioOut.p;
-        s->launch(QMODE_RHS, filter != 0, p);
-        s->download(rhs1, s->ioOut.p, s->Np);
-        s->download(rhs2, s->ioOut.p + plane, s->Np);
-        s->download(rhs3, s->ioOut.p + 2 * plane, s->Np);
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        const double* in[] = {h, hu, hv};
+        double* out[] = {rhs1, rhs2, rhs3};
+        computeRhs(s, 3, in, out, filter, "bdg_sw2dq_rhs");
     });
 }
 
@@ -1033,90 +995,35 @@ int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms) {
         if (!ms || count < 1) throw arg_error("bdg_sw2dq_time_speed: bad argument");
         if (!s->variantB) throw arg_error("bdg_sw2dq_time_speed: variant B is not enabled");
         s->use();
-        hipEvent_t a, b;
-        hipCheck(hipEventCreate(&a), "hipEventCreate");
-        hipCheck(hipEventCreate(&b), "hipEventCreate");
-        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
-        for (int i = 0; i < count; ++i) s->speedPass(s->q.p, s->part.numOwned > 0 ? s->part.numOwned : s->K);
-        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
-        float t = 0.0f;
-        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        *ms = t / count;
+        const int owned = s->part.numOwned > 0 ? s->part.numOwned : s->K;
+        *ms = timePerRun(s->stream, count, [&] { s->speedPass(s->q.p, owned); });
     });
 }
 
 int bdg_sw2dq_step_ssprk2(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2dq_step_ssprk2");
-        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2: num_steps < 0");
-        if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2: variant B is not enabled (the Heun step is the tidal driver's)");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2: filter requested but the solver has no Filter");
-        s->monitorReserve(num_steps, "bdg_sw2dq_step_ssprk2");
-        s->drifterReserve(num_steps, "bdg_sw2dq_step_ssprk2");
-        s->use();
-        s->spongeC = sponge_coeff;
-        for (int i = 0; i < num_steps; ++i) {
-            s->heunStep(dt, filter != 0, false, false);
-            s->stepDone(dt);
-        }
-        s->checkBlowUp();
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_step_ssprk2", Stepper::Heun, false, dt, num_steps, filter, sponge_coeff); });
 }
 
 int bdg_sw2dq_set_state4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_set_state4");
-        requireFields(s, 4, "bdg_sw2dq_set_state4");
-        if (!h || !hu || !hv || !hN) throw arg_error("bdg_sw2dq_set_state4: NULL field");
-        s->use();
-        const long long plane = s->plane();
-        const double* in[4] = {h, hu, hv, hN};
-        for (int c = 0; c < 4; ++c) s->upload(s->q.p + c * plane, in[c], s->Np);
-        s->res.zero(s->stream);
-        s->stageCount = 0;
-        s->mon.steps = 0;
-        s->drifterResample();
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        const double* in[] = {h, hu, hv, hN};
+        setState(s, 4, in, "bdg_sw2dq_set_state4");
     });
 }
 
 int bdg_sw2dq_get_state4(bdg_sw2dq* s, double* h, double* hu, double* hv, double* hN) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_get_state4");
-        requireFields(s, 4, "bdg_sw2dq_get_state4");
-        s->use();
-        const long long plane = s->plane();
-        double* out[4] = {h, hu, hv, hN};
-        for (int c = 0; c < 4; ++c)
-            if (out[c]) s->download(out[c], s->q.p + c * plane, s->Np);
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        double* out[] = {h, hu, hv, hN};
+        getState(s, 4, out, "bdg_sw2dq_get_state4");
     });
 }
 
 int bdg_sw2dq_rhs4(bdg_sw2dq* s, const double* h, const double* hu, const double* hv, const double* hN, double* rhs1, double* rhs2,
                    double* rhs3, double* rhs4, int filter) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_rhs4");
-        requireFields(s, 4, "bdg_sw2dq_rhs4");
-        if (!h || !hu || !hv || !hN || !rhs1 || !rhs2 || !rhs3 || !rhs4) throw arg_error("bdg_sw2dq_rhs4: NULL argument");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_rhs4: filter requested but the solver has no Filter");
-        s->use();
-        const long long plane = s->plane();
-        if (!s->io.p) {
-            s->io.alloc(4 * plane, s->bytes, s->stream);
-            s->ioOut.alloc(4 * plane, s->bytes, s->stream);
-        }
-        const double* in[4] = {h, hu, hv, hN};
-        double* out[4] = {rhs1, rhs2, rhs3, rhs4};
-        for (int c = 0; c < 4; ++c) s->upload(s->io.p + c * plane, in[c], s->Np);
-        QuadParams p = s->params();
-        p.qin = s->io.p; p.rhs = s->ioOut.p;
-        s->launch(QMODE_RHS, filter != 0, p);
-        for (int c = 0; c < 4; ++c) s->download(out[c], s->ioOut.p + c * plane, s->Np);
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        const double* in[] = {h, hu, hv, hN};
+        double* out[] = {rhs1, rhs2, rhs3, rhs4};
+        computeRhs(s, 4, in, out, filter, "bdg_sw2dq_rhs4");
     });
 }
 
@@ -1167,50 +1074,16 @@ int bdg_sw2dq_time_output(bdg_sw2dq* s, const double* H, const double* lattice, 
         s->use();
         const int mask = (1 << s->fields) - 1;
         s->outputLaunch(H, lattice, mask); // uploads H and I1; not timed
-        hipEvent_t a, b;
-        hipCheck(hipEventCreate(&a), "hipEventCreate");
-        hipCheck(hipEventCreate(&b), "hipEventCreate");
-        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
-        for (int i = 0; i < count; ++i) s->outputLaunch(H, lattice, mask, false);
-        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
-        float t = 0.0f;
-        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        *ms = t / count;
+        *ms = timePerRun(s->stream, count, [&] { s->outputLaunch(H, lattice, mask, false); });
     });
 }
 
 int bdg_sw2dq_step_rk2(bdg_sw2dq* s, double dt, int num_steps, int filter) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2dq_step_rk2");
-        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2: num_steps < 0");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2: filter requested but the solver has no Filter");
-        s->monitorReserve(num_steps, "bdg_sw2dq_step_rk2");
-        s->drifterReserve(num_steps, "bdg_sw2dq_step_rk2");
-        s->use();
-        for (int i = 0; i < num_steps; ++i) {
-            s->rk2Step(dt, filter != 0);
-            s->stepDone(dt);
-        }
-        s->checkBlowUp();
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_step_rk2", Stepper::Rk2, false, dt, num_steps, filter); });
 }
 
 int bdg_sw2dq_lserk4_stages(bdg_sw2dq* s, double dt, int num_stages) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2dq_lserk4_stages");
-        if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages: num_stages < 0");
-        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages");
-        s->drifterReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages");
-        s->use();
-        for (int i = 0; i < num_stages; ++i) {
-            s->lserkStage(dt);
-            if (s->stageCount % blitzdg::LSERK4::numStages == 0) s->stepDone(dt);
-        }
-        s->checkBlowUp();
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_lserk4_stages", Stepper::Lserk, false, dt, num_stages, 0); });
 }
 
 int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms) {
@@ -1220,22 +1093,8 @@ int bdg_sw2dq_time(bdg_sw2dq* s, int kind, double dt, int count, float* ms) {
         if (kind == 2 && !s->variantB) throw arg_error("bdg_sw2dq_time: the Heun step needs variant B");
         if (kind == 1 && !s->hasFilter) throw arg_error("bdg_sw2dq_time: RK2 + filter needs a Filter");
         s->use();
-        hipEvent_t a, b;
-        hipCheck(hipEventCreate(&a), "hipEventCreate");
-        hipCheck(hipEventCreate(&b), "hipEventCreate");
-        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
-        for (int i = 0; i < count; ++i) {
-            if (kind == 0) s->lserkStage(dt);
-            else if (kind == 1) s->rk2Step(dt, true);
-            else s->heunStep(dt, false, false, false);
-        }
-        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
-        float t = 0.0f;
-        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        *ms = t / count;
+        // (steps without stepDone: nothing is recorded and no drifter moves; one check at the end)
+        *ms = timePerRun(s->stream, count, [&] { s->advance(static_cast<Stepper>(kind), dt, kind == 1, Eval::Whole); });
         s->checkBlowUp();
     });
 }
@@ -1269,13 +1128,6 @@ int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id
     });
 }
 
-namespace {
-void requireComm(const bdg_sw2dq* s, const char* fn) {
-    requireSolver(s, fn);
-    bdg_halo::requireComm(s->halo, "bdg_sw2dq", fn);
-}
-} // namespace
-
 int bdg_sw2dq_exchange(bdg_sw2dq* s, int intermediate) {
     return guard([&] {
         requireComm(s, "bdg_sw2dq_exchange");
@@ -1285,43 +1137,15 @@ int bdg_sw2dq_exchange(bdg_sw2dq* s, int intermediate) {
 }
 
 int bdg_sw2dq_step_rk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int filter) {
-    return guard([&] {
-        requireComm(s, "bdg_sw2dq_step_rk2_exchanged");
-        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_rk2_exchanged: num_steps < 0");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_rk2_exchanged: filter requested but the solver has no Filter");
-        s->monitorReserve(num_steps, "bdg_sw2dq_step_rk2_exchanged");
-        s->use();
-        s->stepRk2Exchanged(dt, num_steps, filter != 0);
-        s->checkBlowUp(s->part.numOwned, true);
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_step_rk2_exchanged", Stepper::Rk2, true, dt, num_steps, filter); });
 }
 
 int bdg_sw2dq_step_ssprk2_exchanged(bdg_sw2dq* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return guard([&] {
-        requireComm(s, "bdg_sw2dq_step_ssprk2_exchanged");
-        if (num_steps < 0) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: num_steps < 0");
-        if (!s->variantB) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: variant B is not enabled");
-        if (filter && !s->hasFilter) throw arg_error("bdg_sw2dq_step_ssprk2_exchanged: filter requested but the solver has no Filter");
-        s->monitorReserve(num_steps, "bdg_sw2dq_step_ssprk2_exchanged");
-        s->use();
-        s->spongeC = sponge_coeff;
-        for (int i = 0; i < num_steps; ++i) {
-            s->heunStep(dt, filter != 0, true, false);
-            s->stepDone(dt);
-        }
-        s->checkBlowUp(s->part.numOwned, true);
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_step_ssprk2_exchanged", Stepper::Heun, true, dt, num_steps, filter, sponge_coeff); });
 }
 
 int bdg_sw2dq_lserk4_stages_exchanged(bdg_sw2dq* s, double dt, int num_stages) {
-    return guard([&] {
-        requireComm(s, "bdg_sw2dq_lserk4_stages_exchanged");
-        if (num_stages < 0) throw arg_error("bdg_sw2dq_lserk4_stages_exchanged: num_stages < 0");
-        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2dq_lserk4_stages_exchanged");
-        s->use();
-        s->lserkStagesExchanged(dt, num_stages);
-        s->checkBlowUp(s->part.numOwned, true);
-    });
+    return guard([&] { stepping(s, "bdg_sw2dq_lserk4_stages_exchanged", Stepper::Lserk, true, dt, num_stages, 0); });
 }
 
 int bdg_sw2dq_barrier(bdg_sw2dq* s) {
@@ -1569,18 +1393,7 @@ int bdg_sw2dq_drifters_time(bdg_sw2dq* s, double dt, int count, float* ms) {
         requireDrifters(s, "bdg_sw2dq_drifters_time");
         if (!ms || count < 1) throw arg_error("bdg_sw2dq_drifters_time: bad argument");
         s->use();
-        hipEvent_t a, b;
-        hipCheck(hipEventCreate(&a), "hipEventCreate");
-        hipCheck(hipEventCreate(&b), "hipEventCreate");
-        hipCheck(hipEventRecord(a, s->stream), "hipEventRecord");
-        for (int i = 0; i < count; ++i) s->drifterAdvance(dt, false);
-        hipCheck(hipEventRecord(b, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(b), "hipEventSynchronize");
-        float t = 0.0f;
-        hipCheck(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime");
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        *ms = t / count;
+        *ms = timePerRun(s->stream, count, [&] { s->drifterAdvance(dt, false); });
     });
 }
 

@@ -50,7 +50,8 @@ struct QuadElem {
 enum QuadMode {
     QMODE_RHS = 0,     // rhs = [Filter] R(qin)
     QMODE_COMBINE = 1, // qout = qbase + cc [Filter] R(qin)            (midpoint RK2 predictor / corrector)
-    QMODE_LSERK = 2    // res = ca res + cc R(qin); qout = qin + cb res
+    QMODE_LSERK = 2,   // res = ca res + cc R(qin); qout = qin + cb res
+    QMODE_HEUN = 3     // variant B only (sw2d_quadb_kernel.hpp): qout = sp(ca qbase + cb qin + cc [Filter] R(qin))
 };
 
 struct QuadParams {

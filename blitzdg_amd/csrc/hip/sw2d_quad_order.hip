@@ -3,6 +3,7 @@
 // (mode, filter, geometry form, sources) instance of the four-field sw2d_quad4_stage_kernel<N>; and the output step
 // sw2d_quad_output_kernel<N> for three and four fields, with and without the lattice interpolation.
 #include "sw2d_quad4_kernel.hpp"
+#include "sw2d_quad_dispatch.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 
 #ifndef BDG_ORDER
@@ -27,19 +28,9 @@ hipError_t launchForm(bool general, const QuadParams& p, hipStream_t stream) {
 
 template <>
 hipError_t sw2d_quad_launch<BDG_ORDER>(int mode, bool filter, bool general, const QuadParams& p, hipStream_t stream) {
-    constexpr int N = BDG_ORDER;
-    switch (mode) {
-    case QMODE_RHS:
-        return filter ? launchForm<N, QMODE_RHS, true>(general, p, stream) : launchForm<N, QMODE_RHS, false>(general, p, stream);
-    case QMODE_COMBINE:
-        return filter ? launchForm<N, QMODE_COMBINE, true>(general, p, stream)
-                      : launchForm<N, QMODE_COMBINE, false>(general, p, stream);
-    case QMODE_LSERK:
-        if (filter) return hipErrorInvalidValue; // LSERK4 stages are unfiltered
-        return launchForm<N, QMODE_LSERK, false>(general, p, stream);
-    default:
-        return hipErrorInvalidValue;
-    }
+    return quadForMode<false>(mode, filter, [&](auto m, auto f) {
+        return launchForm<BDG_ORDER, decltype(m)::value, decltype(f)::value>(general, p, stream);
+    });
 }
 
 namespace {
@@ -63,20 +54,9 @@ hipError_t launchForm4(bool general, bool sources, const Quad4Params& p, hipStre
 template <>
 hipError_t sw2d_quad4_launch<BDG_ORDER>(int mode, bool filter, bool general, bool sources, const Quad4Params& p,
                                         hipStream_t stream) {
-    constexpr int N = BDG_ORDER;
-    switch (mode) {
-    case QMODE_RHS:
-        return filter ? launchForm4<N, QMODE_RHS, true>(general, sources, p, stream)
-                      : launchForm4<N, QMODE_RHS, false>(general, sources, p, stream);
-    case QMODE_COMBINE:
-        return filter ? launchForm4<N, QMODE_COMBINE, true>(general, sources, p, stream)
-                      : launchForm4<N, QMODE_COMBINE, false>(general, sources, p, stream);
-    case QMODE_LSERK:
-        if (filter) return hipErrorInvalidValue; // LSERK4 stages are unfiltered
-        return launchForm4<N, QMODE_LSERK, false>(general, sources, p, stream);
-    default:
-        return hipErrorInvalidValue;
-    }
+    return quadForMode<false>(mode, filter, [&](auto m, auto f) {
+        return launchForm4<BDG_ORDER, decltype(m)::value, decltype(f)::value>(general, sources, p, stream);
+    });
 }
 
 namespace {

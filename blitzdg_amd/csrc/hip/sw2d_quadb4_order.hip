@@ -2,6 +2,7 @@
 // sw2d_quadb_order.hip): every (mode, filter, geometry form) instance of sw2d_quadb4_stage_kernel<N>: RHS, COMBINE and
 // HEUN plain and filtered, LSERK plain.
 #include "sw2d_quadb4_kernel.hpp"
+#include "sw2d_quad_dispatch.hpp"
 
 #ifndef BDG_ORDER
 #error "compile with -DBDG_ORDER=N"
@@ -26,21 +27,9 @@ hipError_t launchFormB4(bool general, const QuadB4Params& p, hipStream_t stream)
 
 template <>
 hipError_t sw2d_quadb4_launch<BDG_ORDER>(int mode, bool filter, bool general, const QuadB4Params& p, hipStream_t stream) {
-    constexpr int N = BDG_ORDER;
-    switch (mode) {
-    case QMODE_RHS:
-        return filter ? launchFormB4<N, QMODE_RHS, true>(general, p, stream) : launchFormB4<N, QMODE_RHS, false>(general, p, stream);
-    case QMODE_COMBINE:
-        return filter ? launchFormB4<N, QMODE_COMBINE, true>(general, p, stream)
-                      : launchFormB4<N, QMODE_COMBINE, false>(general, p, stream);
-    case QMODE_LSERK:
-        if (filter) return hipErrorInvalidValue; // LSERK4 stages are unfiltered
-        return launchFormB4<N, QMODE_LSERK, false>(general, p, stream);
-    case QMODE_HEUN:
-        return filter ? launchFormB4<N, QMODE_HEUN, true>(general, p, stream) : launchFormB4<N, QMODE_HEUN, false>(general, p, stream);
-    default:
-        return hipErrorInvalidValue;
-    }
+    return quadForMode<true>(mode, filter, [&](auto m, auto f) {
+        return launchFormB4<BDG_ORDER, decltype(m)::value, decltype(f)::value>(general, p, stream);
+    });
 }
 
 } // namespace bdg_dev

@@ -23,8 +23,6 @@
 
 namespace bdg_dev {
 
-enum QuadBMode { QMODE_HEUN = 3 }; // qout = sp(ca qbase + cb qin + cc [Filter] R(qin)), beside QuadMode
-
 constexpr int kQuadBOpen = INT_MIN; // gather-index value of an open-boundary node
 
 template <int N>

@@ -16,6 +16,37 @@ from . import _capi as C
 from ._capi import byref, c_double, c_float, c_void_p, check, lib
 
 GENERAL_GEOMETRY = C.BDG_SW2DQ_GENERAL_GEOMETRY
+_FIELD_NAMES = ("h", "hu", "hv", "hN")
+
+
+def _locate(points, nodes, noun):
+    """(element, r, s) of ``points``: a tuple of reference coordinates as it is, or an (n, 2) array of x, y located on the
+    QuadNodesProvisioner ``nodes``. ``noun`` names them in the messages."""
+    if isinstance(points, tuple):
+        el, r, s = C.as_i32(points[0]).reshape(-1), C.as_f64(points[1]).reshape(-1), C.as_f64(points[2]).reshape(-1)
+        if not (el.size == r.size == s.size):
+            raise ValueError(f"{noun}: element, r and s must have the same length")
+        return el, r, s
+    xy = C.as_f64(points)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError(f"{noun}: expected an (n, 2) array of x, y")
+    if nodes is None:
+        raise ValueError(f"{noun} given as x, y need `global_nodes`, a QuadNodesProvisioner of the global mesh")
+    el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
+    if (el < 0).any():
+        raise ValueError(f"{noun} {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+    return el, r, s
+
+
+def _by_fields(name, nf):
+    return getattr(lib, f"bdg_sw2dq_{name}4" if nf == 4 else f"bdg_sw2dq_{name}")
+
+
+def _timed(fn, *args):
+    """Average device milliseconds from one of the library's timing calls, whose last argument is the float it writes."""
+    ms = c_float()
+    check(fn(*args, byref(ms)))
+    return ms.value
 
 
 class Sw2dQuadSolver:
@@ -159,52 +190,53 @@ class Sw2dQuadSolver:
 
     def timeSpeedPass(self, count):
         """Average device milliseconds of variant B's speed pass alone."""
-        ms = c_float()
-        check(lib.bdg_sw2dq_time_speed(self._h, int(count), byref(ms)))
-        return ms.value
+        return _timed(lib.bdg_sw2dq_time_speed, self._h, int(count))
 
     def timeHeun(self, dt, count):
         """Average device milliseconds per unfiltered Heun step of variant B."""
-        ms = c_float()
-        check(lib.bdg_sw2dq_time(self._h, 2, float(dt), int(count), byref(ms)))
-        return ms.value
+        return _timed(lib.bdg_sw2dq_time, self._h, 2, float(dt), int(count))
 
     def _field(self, a, name):
         return C.as_f64(a, (self.Np, self.K), name)
 
+    # set-state, get-state and RHS for `nf` fields: the library's three-field calls or their *4 twins
+    def _setState(self, *q):
+        f = [self._field(a, n) for a, n in zip(q, _FIELD_NAMES)]
+        check(_by_fields("set_state", len(q))(self._h, *[C.ptr(a) for a in f]))
+
+    def _getState(self, nf=None):
+        nf = self.fields if nf is None else nf
+        out = [np.empty((self.Np, self.K)) for _ in range(nf)]
+        check(_by_fields("get_state", nf)(self._h, *[C.ptr(o) for o in out]))
+        return tuple(out)
+
+    def _computeRHS(self, *q, filter=False):
+        f = [self._field(a, n) for a, n in zip(q, _FIELD_NAMES)]
+        out = [np.empty((self.Np, self.K)) for _ in q]
+        check(_by_fields("rhs", len(q))(self._h, *[C.ptr(a) for a in f], *[C.ptr(o) for o in out], int(bool(filter))))
+        return tuple(out)
+
     def setState(self, h, hu, hv):
         """Uploads the state (and zeroes the LSERK4 residual, restarting the stage count)."""
-        h, hu, hv = self._field(h, "h"), self._field(hu, "hu"), self._field(hv, "hv")
-        check(lib.bdg_sw2dq_set_state(self._h, C.ptr(h), C.ptr(hu), C.ptr(hv)))
+        self._setState(h, hu, hv)
 
     def getState(self):
-        out = [np.empty((self.Np, self.K)) for _ in range(3)]
-        check(lib.bdg_sw2dq_get_state(self._h, *[C.ptr(o) for o in out]))
-        return tuple(out)
+        return self._getState(3)
 
     def computeRHS(self, h, hu, hv, filter=False):
         """(RHS1, RHS2, RHS3) of the script's sw2dComputeRHS; ``filter=True`` returns Filter @ RHS."""
-        h, hu, hv = self._field(h, "h"), self._field(hu, "hu"), self._field(hv, "hv")
-        out = [np.empty((self.Np, self.K)) for _ in range(3)]
-        check(lib.bdg_sw2dq_rhs(self._h, C.ptr(h), C.ptr(hu), C.ptr(hv), *[C.ptr(o) for o in out], int(bool(filter))))
-        return tuple(out)
+        return self._computeRHS(h, hu, hv, filter=filter)
 
     def setState4(self, h, hu, hv, hN):
-        f = [self._field(a, n) for a, n in zip((h, hu, hv, hN), ("h", "hu", "hv", "hN"))]
-        check(lib.bdg_sw2dq_set_state4(self._h, *[C.ptr(a) for a in f]))
+        self._setState(h, hu, hv, hN)
 
     def getState4(self):
-        out = [np.empty((self.Np, self.K)) for _ in range(4)]
-        check(lib.bdg_sw2dq_get_state4(self._h, *[C.ptr(o) for o in out]))
-        return tuple(out)
+        return self._getState(4)
 
     def computeRHS4(self, h, hu, hv, hN, filter=False):
         """(RHS1, RHS2, RHS3, RHS4) of the reference's swhelpers.rhs.sw2dComputeRHS with this solver's sources;
         ``filter=True`` returns Filter @ RHS."""
-        f = [self._field(a, n) for a, n in zip((h, hu, hv, hN), ("h", "hu", "hv", "hN"))]
-        out = [np.empty((self.Np, self.K)) for _ in range(4)]
-        check(lib.bdg_sw2dq_rhs4(self._h, *[C.ptr(a) for a in f], *[C.ptr(o) for o in out], int(bool(filter))))
-        return tuple(out)
+        return self._computeRHS(h, hu, hv, hN, filter=filter)
 
     def _lattice(self, lattice):
         """None, or the (N+1, N+1) matrix I1 of QuadNodesProvisioner.splitOperators the device interpolates with."""
@@ -234,9 +266,7 @@ class Sw2dQuadSolver:
     def timeOutput(self, count, H=None, lattice=True):
         """Average device milliseconds of the output launch (every field of the solver)."""
         Hh = None if H is None else self._field(H, "H")
-        ms = c_float()
-        check(lib.bdg_sw2dq_time_output(self._h, C.ptr(Hh), C.ptr(self._lattice(lattice)), int(count), byref(ms)))
-        return ms.value
+        return _timed(lib.bdg_sw2dq_time_output, self._h, C.ptr(Hh), C.ptr(self._lattice(lattice)), int(count))
 
     def enableMonitor(self, nodes, H=None, gauges=None, stride=1, capacity=4096):
         """Switches on the run monitor: from now on stepRK2, stepSSPRK2 and lserk4Stages (a step is the fifth stage) record the
@@ -251,17 +281,8 @@ class Sw2dQuadSolver:
         Hh = None if H is None else C.as_f64(H, shape, "H")
         if gauges is None:
             el, r, s = np.empty(0, np.int32), np.empty(0), np.empty(0)
-        elif isinstance(gauges, tuple):
-            el, r, s = C.as_i32(gauges[0]).reshape(-1), C.as_f64(gauges[1]).reshape(-1), C.as_f64(gauges[2]).reshape(-1)
-            if not (el.size == r.size == s.size):
-                raise ValueError("gauges: element, r and s must have the same length")
         else:
-            xy = C.as_f64(gauges)
-            if xy.ndim != 2 or xy.shape[1] != 2:
-                raise ValueError("gauges: expected an (n, 2) array of x, y")
-            el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
-            if (el < 0).any():
-                raise ValueError(f"gauges {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+            el, r, s = _locate(gauges, nodes, "gauges")
         d = C.Sw2dqMonitorDesc(C.ptr(w), C.ptr(Hh), el.size, C.ptr(el) if el.size else None, C.ptr(r) if el.size else None,
                                C.ptr(s) if el.size else None, int(stride), int(capacity))
         check(lib.bdg_sw2dq_enable_monitor(self._h, byref(d)))
@@ -303,17 +324,7 @@ class Sw2dQuadSolver:
         ValueError), or a tuple (element, r, s) of reference coordinates. ``mapO``: the open-boundary face nodes of
         ``enableVariantB``; a drifter that crosses one of their faces has exited (status 1), at every other boundary face it
         slides along the wall (status bit 4). Set the state first; once per solver; not on a partitioned solver."""
-        if isinstance(points, tuple):
-            el, r, s = C.as_i32(points[0]).reshape(-1), C.as_f64(points[1]).reshape(-1), C.as_f64(points[2]).reshape(-1)
-            if not (el.size == r.size == s.size):
-                raise ValueError("points: element, r and s must have the same length")
-        else:
-            xy = C.as_f64(points)
-            if xy.ndim != 2 or xy.shape[1] != 2:
-                raise ValueError("points: expected an (n, 2) array of x, y")
-            el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
-            if (el < 0).any():
-                raise ValueError(f"points {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+        el, r, s = _locate(points, nodes, "points")
         bil, neigh, bary = nodes.drifterTables(mapO)
         d = C.Sw2dqDrifterDesc(el.size, C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(bil), C.ptr(neigh), C.ptr(bary), int(stride),
                                int(capacity))
@@ -327,9 +338,7 @@ class Sw2dQuadSolver:
 
     def timeDrifters(self, dt, count):
         """Average device milliseconds per advance (no records taken; the drifters move)."""
-        ms = c_float()
-        check(lib.bdg_sw2dq_drifters_time(self._h, float(dt), int(count), byref(ms)))
-        return ms.value
+        return _timed(lib.bdg_sw2dq_drifters_time, self._h, float(dt), int(count))
 
     def drifterState(self):
         """dict of the drifters now: ``xy`` (n, 2), ``element``, ``r``, ``s``, ``status`` (0 moving, 1 exited, 2 lost, + 4 once it
@@ -370,9 +379,7 @@ class Sw2dQuadSolver:
 
     def timeStages(self, dt, count, rk2=False):
         """Average device milliseconds per LSERK4 stage (or per RK2 + filter step with ``rk2=True``)."""
-        ms = c_float()
-        check(lib.bdg_sw2dq_time(self._h, 1 if rk2 else 0, float(dt), int(count), byref(ms)))
-        return ms.value
+        return _timed(lib.bdg_sw2dq_time, self._h, 1 if rk2 else 0, float(dt), int(count))
 
     def synchronize(self):
         check(lib.bdg_sw2dq_synchronize(self._h))
@@ -464,10 +471,10 @@ class NativeDistributedSw2dQuad:
         """fn(x, y) -> (h, hu, hv) (four fields: (h, hu, hv, hN)) on the rank-local nodes (owned and ghost elements: the
         ghosts start current)."""
         ctx = self.nodes.dgContext()
-        (self.solver.setState4 if self.fields == 4 else self.solver.setState)(*fn(ctx.x, ctx.y))
+        self.solver._setState(*fn(ctx.x, ctx.y))
 
     def _state(self):
-        return self.solver.getState4() if self.fields == 4 else self.solver.getState()
+        return self.solver._getState()
 
     def compute_dt(self, CFL):
         """(dt, speed) over every rank's owned elements (collective): the same values on every rank."""
@@ -544,17 +551,12 @@ class NativeDistributedSw2dQuad:
         n_own = self.plan.num_owned
         loc = None
         if gauges is not None:
-            if isinstance(gauges, tuple):
+            if isinstance(gauges, tuple):                    # global element numbers, which may be of another rank
                 gel, r, s = (np.asarray(a).reshape(-1) for a in gauges)
+                if (gel < 0).any():
+                    raise ValueError(f"gauges {np.nonzero(gel < 0)[0].tolist()} lie in no element of the mesh")
             else:
-                xy = C.as_f64(gauges)
-                if xy.ndim != 2 or xy.shape[1] != 2:
-                    raise ValueError("gauges: expected an (n, 2) array of x, y")
-                if global_nodes is None:
-                    raise ValueError("gauges given as x, y need `global_nodes`, a QuadNodesProvisioner of the global mesh")
-                gel, r, s = global_nodes.locatePoints(xy[:, 0], xy[:, 1])
-            if (np.asarray(gel) < 0).any():
-                raise ValueError(f"gauges {np.nonzero(np.asarray(gel) < 0)[0].tolist()} lie in no element of the mesh")
+                gel, r, s = _locate(gauges, global_nodes, "gauges")
             local = {int(g): i for i, g in enumerate(np.asarray(self.plan.own_global))}
             # a gauge of another rank names a ghost column, which the device leaves at 0
             el = np.array([local.get(int(g), n_own) for g in gel], dtype=np.int32)
