@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <string>
+#include <vector>
 
 namespace bdg_dev {
 
@@ -30,6 +31,11 @@ struct DevBuf {
     void alloc(size_t count, size_t& total, hipStream_t zeroOn) {
         alloc(count, total);
         zero(zeroOn);
+    }
+    // allocated to the size of `host` and filled from it by a blocking copy; `what` names the copy in an error
+    void upload(const std::vector<T>& host, size_t& total, const char* what) {
+        alloc(host.size(), total);
+        if (p) hipCheck(hipMemcpy(p, host.data(), n * sizeof(T), hipMemcpyHostToDevice), what);
     }
     void zero(hipStream_t on) {
         if (p) hipCheck(hipMemsetAsync(p, 0, n * sizeof(T), on), "hipMemset");

@@ -79,7 +79,6 @@ struct bdg_sw2d_curved {
     long long ld = 0, sideLd = 0;
     bool hasFilter = false, identityM = true;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t bytes = 0;
     DevBuf<double> qA, qB, res, rhs, gq, cubG, gaussG, coef, mmSide, minvSide, ops, filt;
     // nodal coefficient planes inside coef (one allocation: the stage kernel reaches all of them through one buffer
@@ -112,8 +111,6 @@ struct bdg_sw2d_curved {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (halo.stream) (void)hipStreamSynchronize(halo.stream);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
     }
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
@@ -617,8 +614,6 @@ bdg_sw2d_curved* createCurved(const bdg_sw2d_curved_desc& d) {
 
     s->use();
     hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
-    hipCheck(hipEventCreate(&s->ev0), "hipEventCreate");
-    hipCheck(hipEventCreate(&s->ev1), "hipEventCreate");
     hipStream_t st = s->stream;
 
     // ---- state and work planes
@@ -938,12 +933,8 @@ int bdg_sw2d_curved_time_rk2(bdg_sw2d_curved* s, double dt, int num_steps, int f
         requireCurved(s, "bdg_sw2d_curved_time_rk2");
         if (num_steps < 1 || !ms_per_rhs) throw arg_error("bdg_sw2d_curved_time_rk2: bad argument");
         s->use();
-        hipCheck(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
-        s->stepRk2(dt, num_steps, filter != 0);
-        hipCheck(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(s->ev1), "hipEventSynchronize");
-        float ms = 0.f;
-        hipCheck(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
+        // (one run: all the steps, two evaluations each)
+        const float ms = bdg_dev::timePerRun(s->stream, 1, [&] { s->stepRk2(dt, num_steps, filter != 0); });
         *ms_per_rhs = ms / (2.0f * static_cast<float>(num_steps));
     });
 }

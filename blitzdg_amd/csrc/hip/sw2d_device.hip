@@ -152,7 +152,62 @@ using bdg_rccl::rccl;
 
 namespace {
 std::vector<double> matmulHost(const double* A, const double* B, int n, int c);
+
+// ---- run-time switches (A/B measurements and cross-checks; DESIGN.md section 3 lists them). Every name is read here and nowhere
+// else, and WHEN it is read is part of its meaning: once per process (the first call fixes the value: set it before the process
+// starts), when a solver is set up (the caller keeps the answer), or per call (the tests flip these within one process).
+namespace env {
+// -- once per process
+// =n pins the crossover to the one-tile-per-wave kernel of whole-mesh and interior launches (default: kSmallLaunch[N])
+int smallLaunchPinned() {
+    static const int v = [] { const char* e = std::getenv("BDG_SW2D_SMALL_LAUNCH"); return e ? std::atoi(e) : -1; }();
+    return v;
 }
+// =n pins the workgroup cap of the interior launch of a partitioned run (default: interiorGridCap)
+int interiorCapPinned() {
+    static const int v = [] { const char* e = std::getenv("BDG_SW2D_INTERIOR_CAP"); return e ? std::atoi(e) : 0; }();
+    return v;
+}
+// =0: a stage's `done` event is recorded by a packet behind the launch instead of by the launch itself
+bool extLaunch() {
+    static const bool v = [] { const char* e = std::getenv("BDG_SW2D_EXT_LAUNCH"); return !e || e[0] != '0'; }();
+    return v;
+}
+// -- when a solver is created (bdg_sw2d_create*)
+const char* affineVariantPin() { return std::getenv("BDG_SW2D_AFFINE_VARIANT"); } // =0..9: one kernel family, no small-launch crossover
+bool nodalVector() { return std::getenv("BDG_SW2D_NODAL_VECTOR") != nullptr; }      // per-node geometry on the vector kernel (N <= 6)
+bool fullStageTraffic() {                                                            // no face links, residual read and written at every stage
+    const char* e = std::getenv("BDG_SW2D_FULL_STAGE_TRAFFIC");
+    return e && e[0] != '0';
+}
+// ... and again when variant B is enabled: variants B/C/D on the rolled kernels
+bool rolledSources() { return std::getenv("BDG_SW2D_ROLLED_SOURCES") != nullptr; }
+// -- when the communicator is set up (bdg_sw2d_comm_init)
+bool eventFence() { // =1 (older spelling: NOFENCE=0): the stage events keep their system-scope fence
+    const char* on = std::getenv("BDG_SW2D_EVENT_FENCE");
+    const char* off = std::getenv("BDG_SW2D_EVENT_NOFENCE");
+    return (on && on[0] == '1') || (off && off[0] == '0');
+}
+bool noCommWarmup() { return std::getenv("BDG_SW2D_NO_COMM_WARMUP") != nullptr; }
+// -- per call
+bool eventSync() { // =1: the two chains of an exchanged stage meet through events, not inside the kernels
+    const char* e = std::getenv("BDG_SW2D_EVENT_SYNC");
+    return e && e[0] != '0';
+}
+bool sourcesProduct() { // =1: unfiltered evaluations with sources keep the products with the identity tiles (bit-identical)
+    const char* e = std::getenv("BDG_SW2D_SOURCES_PRODUCT");
+    return e && e[0] != '0';
+}
+bool speedPass() { return std::getenv("BDG_SW2D_SPEED_PASS") != nullptr; }             // variant B always runs its separate speed pass
+bool tracerPass() { return std::getenv("BDG_SW2D_TRACER_PASS") != nullptr; }           // the tracer in a pass of its own
+bool sourcesTwoWave() { return std::getenv("BDG_SW2D_SOURCES_TWO_WAVE") != nullptr; }  // variants B/C/D off the state-once schedule
+bool haloKernels() { return std::getenv("BDG_SW2D_HALO_KERNELS") != nullptr; }         // separate pack / unpack kernels
+bool stripThroughput() { return std::getenv("BDG_SW2D_STRIP_THROUGHPUT") != nullptr; } // (its boundary strips have no SYNC instance)
+// ="6": the boundary strip of N >= 5 on the two-waves schedule. Two read times, both kept: flagSyncUsable asks per call,
+// launchBoundaryStageFolded keeps the answer of its first launch for the rest of the process
+const char* haloVariant() { return std::getenv("BDG_SW2D_HALO_VARIANT"); }
+} // namespace env
+} // namespace
 
 struct bdg_sw2d {
     const bdg_dev::KernelTable* kt = nullptr;
@@ -161,15 +216,20 @@ struct bdg_sw2d {
     double g = 9.81;
     bool hasFilter = false, hasH = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t bytes = 0;
     DevBuf<double> qA, qB, res, aux, geo, fgeo, ops, Hbuf, stage, partials, red2;
     DevBuf<double> ageo, opsAffine, opsAffineFiltered; // affine-geometry fast path
     DevBuf<double> opsMfma, opsMfmaFiltered;           // same operators in MFMA A-operand layout
     DevBuf<double> opsMfma2, opsMfma2Filtered;         // ... with the lift tiles padded per face
     DevBuf<double> opsMfma2Src, opsMfma2SrcFiltered;   // ... followed by the source-term tiles F' (variants C/D, N >= 6)
+    DevBuf<double> opsMfma2NodalFilter; // plain MfmaOps2 image + MT*KV Filter tiles
     bool mfmaSources = false;
     bool affine = false;
+    bool nodalMfma = false;   // non-affine tables: matrix-core kernel (default) instead of the N <= 6 vector kernel
+    bool fastSources = false; // variants B/C/D on the unrolled kernels instead of the rolled ones
+    // up to this order the unrolled source-term kernels are used, above it the matrix-core ones
+    static constexpr int kUnrolledSourcesMaxOrder = 4;
+    DevBuf<double> filterT;   // [m][i] = Filter[i][m], for filtered source terms
     // variant D (reference swhelpers/rhs.py:178-311): optional tracer field and source terms
     int nf = 3;
     bool variantD = false;
@@ -184,10 +244,29 @@ struct bdg_sw2d {
     DevBuf<int> obcBuf;
     double tideAmp = 0.0, tidePeriod = 1.0, tideRamp = 0.0;
     double timeNow = 0.0;  // model time of the resident state (tide phase)
-    std::vector<double> hostDr, hostDs, hostLift, hostFilter; // kept for operator images built after creation
+    bool lamExternal = false; // variant B, partitioned: lamBuf holds the all-rank speed of the state about to be evaluated
+    DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
+    int lamSlot = 0;
+    const double* lamStateFor = nullptr; // state buffer the accumulated speed belongs to (nullptr: none)
+    double lamTideFor = 0.0;
+    double nextEvalTime = 0.0;         // model time of the evaluation that will follow the current launch
+    // kept for operator images built after creation; the last three are Filter * (Dr, Ds, Lift): the filtered RHS of an affine
+    // element is linear in these (empty without a Filter)
+    std::vector<double> hostDr, hostDs, hostLift, hostFilter, hostFDr, hostFDs, hostFLift;
     int affineVariant = 0; // 0: unrolled, register-resident state; 2/3: unrolled, streamed state at 2/3 waves
                            // per SIMD; 1: rolled, one field per wave; 4: rolled, three fields per lane; 5: matrix cores (MFMA f64),
                            // whole tile unrolled; 6: matrix cores, face-by-face / chunked schedule at 2 waves per SIMD
+    bool variantForced = false;                 // BDG_SW2D_AFFINE_VARIANT given
+    // elements below which the matrix-core kernel is the faster one, per order (measured crossovers:
+    // N=2 near 10 k, N=3 near 125 k, N=4 between 125 k and 250 k; N=1 never ahead; N=5 runs on
+    // the matrix cores at every size)
+    // (round 4, after the matrix-core kernel of N <= 4 got all its requests ahead of its first product -- kernel ms, unrolled / matrix cores,
+    // profiles/r04_rehearsal_experiments.txt: N=4 125 k elements 0.0543 / 0.0452, 250 k 0.1009 / 0.1142; N=3 125 k 0.0365 / 0.0313, 250 k 0.0612 /
+    // 0.0704; N=2 125 k 0.0189 / 0.0283: N=3's crossover moves up to where N=4's is)
+    static constexpr int kSmallLaunch[6] = {0, 4000, 10000, 160000, 160000, 0};
+    // resident-workgroup kernels, interior launch of a partitioned run: CUs left to the boundary kernel (a strip of a few
+    // hundred elements = 4..8 four-wave workgroups); N=8, 8-way rehearsal: 0.087 -> see profiles/r02_rehearsal.txt
+    static constexpr int kInteriorGridCap = 244;
     DevBuf<int> vmapP, perm, istage, sendSlots, haloSendOf;
     // (3, ld) face links (bdg_dev::FaceLink) of the LSERK stages on the unrolled kernel; empty when the switch
     // BDG_SW2D_FULL_STAGE_TRAFFIC is set, when that kernel does not serve the solver, or when a face's vmapP rows are not
@@ -211,13 +290,12 @@ struct bdg_sw2d {
     double* qcur = nullptr;  // current state
     double* qalt = nullptr;  // the other buffer
     long long stageCount = 0; // LSERK stage counter (stage index = count % 5)
+    double dtStage = 0.0;
     std::vector<int> permHost; // caller element -> device slot (empty = identity)
 
     ~bdg_sw2d() {
         for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evPacked[0], evPacked[1], evCopied[0], evCopied[1]})
             if (e) (void)hipEventDestroy(e);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -244,6 +322,45 @@ struct bdg_sw2d {
         hipCheck(hipMemcpyAsync(host, stage.p, n * sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
         hipCheck(hipStreamSynchronize(stream), "download sync");
     }
+    // one (Np, K) host array per field, to / from the nf consecutive device planes at `dev`
+    void uploadFields(const double* const* host, double* dev) {
+        for (int c = 0; c < nf; ++c) uploadRows(host[c], dev + c * planeSize(), Np);
+    }
+    void downloadFields(const double* dev, double* const* host) {
+        for (int c = 0; c < nf; ++c) downloadRows(dev + c * planeSize(), host[c], Np);
+    }
+    const double* uploadPlane(const double* host, DevBuf<double>& buf) {
+        if (!host) return nullptr;
+        if (!buf.p) buf.alloc(planeSize(), bytes);
+        hipCheck(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), stream), "hipMemset");
+        uploadRows(host, buf.p, Np);
+        return buf.p;
+    }
+
+    // ---- the field calls (bdg_sw2d_set_state / _get_state / _rhs and their four-field twins), nf fields each
+    void setFields(const double* const* f) {
+        uploadFields(f, qcur);
+        hipCheck(hipMemsetAsync(res.p, 0, res.n * sizeof(double), stream), "hipMemset");
+        stageCount = 0;
+        lamStateFor = nullptr; // a speed accumulated for the previous contents of this buffer is void
+        hipCheck(hipStreamSynchronize(stream), "set_state sync");
+    }
+    void getFields(double* const* f) {
+        downloadFields(qcur, f);
+        checkSyncError();
+    }
+    void rhsFields(const double* const* in, double* const* out, bool filter) {
+        uploadFields(in, qalt); // the inactive state buffer is scratch between steps
+        launchRhs(qalt, aux.p, filter);
+        downloadFields(aux.p, out);
+    }
+    // the (Np, Np) lattice interpolation of an output call, staged for the launches that follow on the stream (nullptr: none)
+    const double* stageOutputMatrix(const double* IM) {
+        if (!IM) return nullptr;
+        if (!outM.p) outM.alloc(static_cast<size_t>(Np) * Np, bytes);
+        hipCheck(hipMemcpyAsync(outM.p, IM, outM.n * sizeof(double), hipMemcpyHostToDevice, stream), "H2D copy");
+        return outM.p;
+    }
 
     bdg_dev::StageParams baseParams() const {
         bdg_dev::StageParams p{};
@@ -261,6 +378,52 @@ struct bdg_sw2d {
         return p;
     }
 
+    // :352  hP = HM + amp cos(om t) 1/2 (tanh(ramp (t - T)) + 1)
+    double tideAt(double t) const {
+        const double om = 2.0 * M_PI / tidePeriod;
+        return tideAmp * std::cos(om * t) * 0.5 * (std::tanh(tideRamp * (t - tidePeriod)) + 1);
+    }
+    // variant B's surface term and sources for the matrix-core source kernels (src/sw2d/main.cpp:461-478), at the tide in vb.tide
+    bdg_dev::PhysParams physB() const {
+        bdg_dev::PhysParams ph{};
+        ph.sx = vb.Hx; ph.sy = vb.Hy; ph.fconst = vb.fcor; ph.cd = vb.cd;
+        ph.slope = 1.0; ph.dragSign = -1.0;
+        ph.H = vb.H; ph.obc = vb.obc; ph.lam = lamBuf.p; ph.spongeField = vb.sponge; ph.tide = vb.tide;
+        return ph;
+    }
+    // variants C / D: the sources of swhelpers/rhs.py:300-309, if the solver has any
+    bdg_dev::PhysParams physD() const {
+        bdg_dev::PhysParams ph{};
+        if (vd.sources) {
+            ph.sx = vd.zx; ph.sy = vd.zy; ph.fcor = vd.fcor;
+            ph.fconst = vd.fconst; ph.cd = vd.cd;
+            ph.slope = -1.0; ph.dragSign = 1.0;
+        }
+        return ph;
+    }
+    // variant B's stage kernel on the state-once schedule where it exists (sw2d_mfma3src_kernel.hpp, PHYS = 2);
+    // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernel
+    bool variantBStateOnce() const {
+        return kt->mfma3SrcFields >= 3 && !env::sourcesTwoWave() && static_cast<long long>(3) * Np * ld * 8 <= 4294967295LL;
+    }
+    // unfiltered evaluation on a state-once kernel with sources: F' is the identity, the sources are added pointwise (IDF instance;
+    // BDG_SW2D_SOURCES_PRODUCT=1 keeps the products with the identity tiles for A/B runs and cross-checks -- bit-identical)
+    static int srcIdentity(bool filter) { return (!filter && !env::sourcesProduct()) ? bdg_dev::kSrcIdentity : 0; }
+    // ... and at N >= 5 the strip kernel's workgroups (one 16-element tile each, three waves; two fit a CU, none fits beside an
+    // interior workgroup's 120 KB of LDS) need free CUs, or the strip -- which sits on the exchange chain -- runs in many rounds.
+    // Round 3 left one CU per strip tile (cap 218-232). Round 4, with the chains meeting inside the kernels, swept the cap in
+    // the 8-way rehearsal (profiles/r04_rehearsal_experiments.txt; ms per stage): N=5 244: 0.0580, 250: 0.0521; N=6 244: 0.0486,
+    // 248: 0.0464, 252: 0.0584 (four free CUs: the strip's 32 tiles take four rounds); N=7 240: 0.0473, 246: 0.0401, 250: 0.0400;
+    // N=8 238: 0.0606 (1930 tiles are three rounds of a tile per wave on 952 waves, two on 968 and more), 242: 0.0546,
+    // 244: 0.0540, 246: 0.0542. The interior wants every CU it can get; the strip needs about a round's worth of slots for its
+    // tiles and RCCL's kernel a CU: eight free CUs, twelve at N = 8 (its strip tiles carry three row blocks).
+    // BDG_SW2D_INTERIOR_CAP=n pins the cap.
+    int interiorGridCap() const {
+        if (env::interiorCapPinned() > 0) return env::interiorCapPinned();
+        if (N < 5) return kInteriorGridCap;
+        return N >= 8 ? 244 : 248;
+    }
+
     // One fused pass. The affine path takes the filter through pre-multiplied operators.
     // `on`: stream to launch on (default: the compute stream).
     void launchStage(int mode, bool filter, bdg_dev::StageParams& p, const char* what, hipStream_t on = nullptr) {
@@ -272,7 +435,7 @@ struct bdg_sw2d {
         // 250 k elements 136 us vs 109 us -- DESIGN.md section 4).
         int variant = affineVariant;
         // BDG_SW2D_SMALL_LAUNCH=n pins the crossover (A/B runs; the partition-boundary strip keeps the table's value: halosFold)
-        static const int smallPinned = [] { const char* e = std::getenv("BDG_SW2D_SMALL_LAUNCH"); return e ? std::atoi(e) : -1; }();
+        const int smallPinned = env::smallLaunchPinned();
         const int smallLaunch = (smallPinned >= 0 && p.kbegin == 0) ? smallPinned : kSmallLaunch[N];
         if (!variantForced && affine && N <= 5 && p.kend - p.kbegin < smallLaunch) variant = 5;
         if (p.syncSignal && !(affine && !variantB && !variantD && (variant == 5 || variant == 7)))
@@ -304,12 +467,8 @@ struct bdg_sw2d {
                     p.opsAffine = opsAffine.p;
                     hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 2, filter ? filterT.p : nullptr, st), what);
                 } else if (mfmaSources) {
-                    bdg_dev::PhysParams ph{};
-                    ph.sx = vb.Hx; ph.sy = vb.Hy; ph.fconst = vb.fcor; ph.cd = vb.cd;
-                    ph.slope = 1.0; ph.dragSign = -1.0;
-                    ph.H = vb.H; ph.obc = vb.obc; ph.lam = lamBuf.p; ph.spongeField = vb.sponge; ph.tide = vb.tide;
                     p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
-                    hipCheck(kt->stageMfma2Src(mode, p, ph, variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
+                    hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
                 } else {
                     p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
                     hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 6, nullptr, st), what);
@@ -320,7 +479,7 @@ struct bdg_sw2d {
                 // that tide over the whole mesh, the separate speed pass is skipped.
                 p.opsAffine = opsAffine.p;
                 const bool whole = p.kbegin == 0 && p.kend == numOwned;
-                const bool reuse = whole && lamStateFor == p.qin && lamTideFor == vb.tide && !std::getenv("BDG_SW2D_SPEED_PASS");
+                const bool reuse = whole && lamStateFor == p.qin && lamTideFor == vb.tide && !env::speedPass();
                 const int cur = lamSlot, nxt = lamSlot ^ 1;
                 vb.lam = reuse ? lamPair.p + cur : lamBuf.p;
                 vb.lamNext = nullptr;
@@ -338,12 +497,8 @@ struct bdg_sw2d {
                 // N >= 6: speed pass, then the matrix-core kernel with variant B's surface term and sources
                 vb.lam = lamBuf.p;
                 hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 4, nullptr, st), what);
-                bdg_dev::PhysParams ph{};
-                ph.sx = vb.Hx; ph.sy = vb.Hy; ph.fconst = vb.fcor; ph.cd = vb.cd;
-                ph.slope = 1.0; ph.dragSign = -1.0;             // src/sw2d/main.cpp:461-478
-                ph.H = vb.H; ph.obc = vb.obc; ph.lam = lamBuf.p; ph.spongeField = vb.sponge; ph.tide = vb.tide;
                 p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
-                hipCheck(kt->stageMfma2Src(mode, p, ph, variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
+                hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
             } else {
                 p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
                 hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 0, nullptr, st), what);
@@ -351,16 +506,11 @@ struct bdg_sw2d {
         } else if (variantD && fastSources) {
             // three conserved fields on the unrolled kernel with the sources folded in, the tracer (if
             // any) by its own one-field-per-wave launch reading the same input state
-            bdg_dev::PhysParams ph{};
-            if (vd.sources) {
-                ph.sx = vd.zx; ph.sy = vd.zy; ph.fcor = vd.fcor;
-                ph.fconst = vd.fconst; ph.cd = vd.cd;
-                ph.slope = -1.0; ph.dragSign = 1.0;   // swhelpers/rhs.py:300-309
-            }
+            bdg_dev::PhysParams ph = physD();
             // filtered RHS: plain operators, Filter applied to flux terms + sources at the end
             ph.fmat = filter ? filterT.p : nullptr;
             p.opsAffine = opsAffine.p;
-            if (nf == 4 && !std::getenv("BDG_SW2D_TRACER_PASS")) {
+            if (nf == 4 && !env::tracerPass()) {
                 hipCheck(kt->stageAffineSrc(mode, p, ph, 1, st), what);    // the tracer rides in the same pass
             } else {
                 hipCheck(kt->stageAffineSrc(mode, p, ph, 0, st), what);
@@ -371,20 +521,15 @@ struct bdg_sw2d {
             }
         } else if (variantD && mfmaSources) {
             // N >= 6: three conserved fields with sources on the matrix cores, then the tracer pass
-            bdg_dev::PhysParams ph{};
-            if (vd.sources) {
-                ph.sx = vd.zx; ph.sy = vd.zy; ph.fcor = vd.fcor;
-                ph.fconst = vd.fconst; ph.cd = vd.cd;
-                ph.slope = -1.0; ph.dragSign = 1.0;   // swhelpers/rhs.py:300-309
-            }
+            const bdg_dev::PhysParams ph = physD();
             p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
             // state-once schedule where it exists (sw2d_mfma3src_kernel.hpp: N = 5, 6, 7 with and without the tracer, N = 8 three fields;
             // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernels below for A/B runs and cross-checks)
-            const bool stateOnceSrc = !std::getenv("BDG_SW2D_SOURCES_TWO_WAVE");
-            if (stateOnceSrc && kt->mfma3SrcFields >= nf && !std::getenv("BDG_SW2D_TRACER_PASS") &&
+            const bool stateOnceSrc = !env::sourcesTwoWave();
+            if (stateOnceSrc && kt->mfma3SrcFields >= nf && !env::tracerPass() &&
                 static_cast<long long>(nf) * Np * ld * 8 <= 4294967295LL) {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, (nf == 4 ? 5 : 4) | srcIdentity(filter), st), what);
-            } else if (stateOnceSrc && kt->mfma3TracerPhase && nf == 4 && !std::getenv("BDG_SW2D_TRACER_PASS") &&
+            } else if (stateOnceSrc && kt->mfma3TracerPhase && nf == 4 && !env::tracerPass() &&
                        static_cast<long long>(4) * Np * ld * 8 <= 4294967295LL) {
                 // N = 8: the tracer equation as a second phase of every tile, from the state tile still in LDS (one launch, state read once)
                 hipCheck(kt->stageMfma2Src(mode, p, ph, 7 | srcIdentity(filter), st), what);
@@ -393,7 +538,7 @@ struct bdg_sw2d {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, 4 | srcIdentity(filter), st), what);
                 p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
                 hipCheck(kt->stageMfma2Src(mode, p, ph, 1, st), what);
-            } else if (nf == 4 && kt->mfmaMT <= 2 && !std::getenv("BDG_SW2D_TRACER_PASS")) {
+            } else if (nf == 4 && kt->mfmaMT <= 2 && !env::tracerPass()) {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, 3, st), what);     // N <= 6: the tracer rides in the same pass
             } else {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, 0, st), what);
@@ -425,70 +570,39 @@ struct bdg_sw2d {
             hipCheck(kt->stage(mode, filter, p, st), what);
         }
     }
-    // variant B's stage kernel on the state-once schedule where it exists (sw2d_mfma3src_kernel.hpp, PHYS = 2);
-    // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernel
-    bool variantBStateOnce() const {
-        return kt->mfma3SrcFields >= 3 && !std::getenv("BDG_SW2D_SOURCES_TWO_WAVE") &&
-               static_cast<long long>(3) * Np * ld * 8 <= 4294967295LL;
-    }
-    DevBuf<double> opsMfma2NodalFilter; // plain MfmaOps2 image + MT*KV Filter tiles
-    bool nodalMfma = false;   // non-affine tables: matrix-core kernel (default) instead of the N <= 6 vector kernel
-    bool fastSources = false; // variants B/C/D on the unrolled kernels instead of the rolled ones
-    bool lamExternal = false; // variant B, partitioned: lamBuf holds the all-rank speed of the state about to be evaluated
-    // up to this order the unrolled source-term kernels are used, above it the matrix-core ones
-    static constexpr int kUnrolledSourcesMaxOrder = 4;
-    DevBuf<double> filterT;   // [m][i] = Filter[i][m], for filtered source terms
-    // :352  hP = HM + amp cos(om t) 1/2 (tanh(ramp (t - T)) + 1)
-    double tideAt(double t) const {
-        const double om = 2.0 * M_PI / tidePeriod;
-        return tideAmp * std::cos(om * t) * 0.5 * (std::tanh(tideRamp * (t - tidePeriod)) + 1);
-    }
-    DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
-    int lamSlot = 0;
-    const double* lamStateFor = nullptr; // state buffer the accumulated speed belongs to (nullptr: none)
-    double lamTideFor = 0.0;
-    double nextEvalTime = 0.0;         // model time of the evaluation that will follow the current launch
-    // elements below which the matrix-core kernel is the faster one, per order (measured crossovers:
-    // N=2 near 10 k, N=3 near 125 k, N=4 between 125 k and 250 k; N=1 never ahead; N=5 runs on
-    // the matrix cores at every size)
-    // (round 4, after the matrix-core kernel of N <= 4 got all its requests ahead of its first product -- kernel ms, unrolled / matrix cores,
-    // profiles/r04_rehearsal_experiments.txt: N=4 125 k elements 0.0543 / 0.0452, 250 k 0.1009 / 0.1142; N=3 125 k 0.0365 / 0.0313, 250 k 0.0612 /
-    // 0.0704; N=2 125 k 0.0189 / 0.0283: N=3's crossover moves up to where N=4's is)
-    static constexpr int kSmallLaunch[6] = {0, 4000, 10000, 160000, 160000, 0};
-    bool variantForced = false;                 // BDG_SW2D_AFFINE_VARIANT given
-    // resident-workgroup kernels, interior launch of a partitioned run: CUs left to the boundary kernel (a strip of a few
-    // hundred elements = 4..8 four-wave workgroups); N=8, 8-way rehearsal: 0.087 -> see profiles/r02_rehearsal.txt
-    static constexpr int kInteriorGridCap = 244;
-    // ... and at N >= 5 the strip kernel's workgroups (one 16-element tile each, three waves; two fit a CU, none fits beside an
-    // interior workgroup's 120 KB of LDS) need free CUs, or the strip -- which sits on the exchange chain -- runs in many rounds.
-    // Round 3 left one CU per strip tile (cap 218-232). Round 4, with the chains meeting inside the kernels, swept the cap in
-    // the 8-way rehearsal (profiles/r04_rehearsal_experiments.txt; ms per stage): N=5 244: 0.0580, 250: 0.0521; N=6 244: 0.0486,
-    // 248: 0.0464, 252: 0.0584 (four free CUs: the strip's 32 tiles take four rounds); N=7 240: 0.0473, 246: 0.0401, 250: 0.0400;
-    // N=8 238: 0.0606 (1930 tiles are three rounds of a tile per wave on 952 waves, two on 968 and more), 242: 0.0546,
-    // 244: 0.0540, 246: 0.0542. The interior wants every CU it can get; the strip needs about a round's worth of slots for its
-    // tiles and RCCL's kernel a CU: eight free CUs, twelve at N = 8 (its strip tiles carry three row blocks).
-    // BDG_SW2D_INTERIOR_CAP=n pins the cap.
-    int interiorGridCap() const {
-        static const int pinned = [] { const char* e = std::getenv("BDG_SW2D_INTERIOR_CAP"); return e ? std::atoi(e) : 0; }();
-        if (pinned > 0) return pinned;
-        if (N < 5) return kInteriorGridCap;
-        return N >= 8 ? 244 : 248;
-    }
 
     void launchRhs(const double* qin, double* out, bool filter) {
-        if (filter && !hasFilter) throw arg_error("filter requested but the solver was created without a Filter matrix");
         bdg_dev::StageParams p = baseParams();
         p.qin = qin;
         p.rhs = out;
         launchStage(bdg_dev::MODE_RHS, filter, p, "sw2d stage kernel <RHS>");
     }
 
+    // ---- one LSERK4 stage. What its two launches (launchLserkStage, launchBoundaryStageFolded) share: the stage index (returned),
+    // buffers and coefficients of the stage, and `done` -- an event to record when the launch has finished -- through the launch
+    // itself where its helper can (one packet on the queue instead of two; *recorded says whether it did)
+    int lserkStageParams(bdg_dev::StageParams& p, hipEvent_t done, bool* recorded) const {
+        const int s = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
+        const bool extLaunch = env::extLaunch();
+        if (done && extLaunch) { p.stopEvent = done; p.stopEventUsed = recorded; }
+        p.qin = qcur;
+        p.qout = qalt;
+        p.res = res.p;
+        p.ca = blitzdg::LSERK4::rk4a[s];
+        p.cb = blitzdg::LSERK4::rk4b[s];
+        p.cc = dtStage;
+        return s;
+    }
+    // ... and what follows them: the buffers swap roles; model time (the tide phase of variant B) is frozen over the five
+    // stages and moves on after the last
+    void lserkStageAdvance(int s) {
+        std::swap(qcur, qalt);
+        ++stageCount;
+        if (s == blitzdg::LSERK4::numStages - 1) timeNow += dtStage;
+    }
     // part: 0 = interior elements only (no ghost dependency; state not advanced),
     //       1 = partition-boundary elements, then advance; 2 = all owned elements, then advance.
-    // done: an event to record when this launch has finished -- through the launch itself where its helper can (one packet
-    // on the queue instead of two), by a record behind it otherwise
     void launchLserkStage(int part = 2, hipStream_t on = nullptr, bool advance = true, hipEvent_t done = nullptr, bool flagSync = false) {
-        const int s = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
         bdg_dev::StageParams p = baseParams();
         bool recorded = false;
         unsigned signals = 0;
@@ -498,20 +612,12 @@ struct bdg_sw2d {
             p.syncFirstTile = ringBegin / 16;
             p.syncSignalsOut = &signals;
         }
-        static const bool extLaunch = [] { const char* e = std::getenv("BDG_SW2D_EXT_LAUNCH"); return !e || e[0] != '0'; }();
-        if (done && extLaunch) { p.stopEvent = done; p.stopEventUsed = &recorded; }
+        const int s = lserkStageParams(p, done, &recorded);
         if (part == 0) {
             p.kend = numInterior;
             p.gridCap = interiorGridCap(); // the boundary kernel runs beside this launch (exchange stream)
         }
         if (part == 1) p.kbegin = numInterior;
-        p.qin = qcur;
-        p.qout = qalt;
-        p.res = res.p;
-        p.ca = blitzdg::LSERK4::rk4a[s];
-        p.cb = blitzdg::LSERK4::rk4b[s];
-        p.cc = dtStage;
-        // model time (the tide phase of variant B) is frozen over the five stages and moves on after the last
         const bool lastOfStep = s == blitzdg::LSERK4::numStages - 1;
         // the unrolled kernel's face-link instances (launchAffine, sw2d_order.hip); every other kernel ignores both
         p.faceLink = faceLink.p;
@@ -520,12 +626,8 @@ struct bdg_sw2d {
         launchStage(bdg_dev::MODE_LSERK, false, p, "sw2d stage kernel <LSERK>", on);
         expectRing += signals;
         if (done && !recorded) hipCheck(hipEventRecord(done, on ? on : stream), "hipEventRecord");
-        if (part == 0 || !advance) return;
-        std::swap(qcur, qalt);
-        ++stageCount;
-        if (lastOfStep) timeNow += dtStage;
+        if (part != 0 && advance) lserkStageAdvance(s);
     }
-    double dtStage = 0.0;
 
     // `state`: the planes whose boundary elements are packed / whose ghost columns are filled (default: the current state)
     void launchPack(double* buf, hipStream_t on = nullptr, const double* state = nullptr) {
@@ -575,31 +677,24 @@ struct bdg_sw2d {
     // True when the partition-boundary launch of an exchanged stage can do the halo staging itself (three-field
     // straight-sided solver whose boundary strip runs on a matrix-core kernel).
     bool halosFold() const {
-        if (!haloFusable || !affine || variantB || variantD || variantForced || std::getenv("BDG_SW2D_HALO_KERNELS")) return false;
+        if (!haloFusable || !affine || variantB || variantD || variantForced || env::haloKernels()) return false;
         return N >= 5 || numOwned - numInterior < kSmallLaunch[N]; // the strip runs on a matrix-core kernel
     }
     // True when the two chains of an exchanged stage can meet through device counters polled inside the kernels instead of
     // through events on the queues (BDG_SW2D_EVENT_SYNC=1 keeps the events): folded halo staging, and both launches of a stage
     // on kernels that have a SYNC instance -- the interior on the matrix-core kernel of its order, the strip on the latency form.
     bool flagSyncUsable() const {
-        const char* eventsPinned = std::getenv("BDG_SW2D_EVENT_SYNC"); // (read per call: the tests switch it within one process)
-        if ((eventsPinned && eventsPinned[0] != '0') || !syncBuf.p || !halosFold()) return false;
-        if (std::getenv("BDG_SW2D_STRIP_THROUGHPUT") || std::getenv("BDG_SW2D_HALO_VARIANT")) return false;
+        if (env::eventSync() || !syncBuf.p || !halosFold()) return false;
+        if (env::stripThroughput() || env::haloVariant()) return false;
         if (N >= 5) return affineVariant == 7 && (numOwned - numInterior + 15) / 16 <= 1024;
         // N <= 4: only while the interior share is small enough for the matrix-core kernel (8-way split of C3). A SYNC instance of
         // the unrolled kernel (the wait in front of its one big basic block, ring waves storing write-through) was built and
         // measured in the 2- and 4-way rehearsal: 0.332 / 0.164 ms per stage against 0.220 / 0.121 with the events -- the branch
         // at the top costs that kernel its load batching (profiles/r04_rehearsal_experiments.txt); larger shares keep the events.
-        static const int smallPinned = [] { const char* e = std::getenv("BDG_SW2D_SMALL_LAUNCH"); return e ? std::atoi(e) : -1; }();
+        const int smallPinned = env::smallLaunchPinned();
         return numInterior > 0 && affineVariant == 0 && numInterior < (smallPinned >= 0 ? smallPinned : kSmallLaunch[N]);
     }
     // a bounded in-kernel wait that gave up (sync_wait) left a mark: report it the next time the host looks at the device
-    // unfiltered evaluation on a state-once kernel with sources: F' is the identity, the sources are added pointwise (IDF instance;
-    // BDG_SW2D_SOURCES_PRODUCT=1 keeps the products with the identity tiles for A/B runs and cross-checks -- bit-identical)
-    static int srcIdentity(bool filter) {
-        const char* product = std::getenv("BDG_SW2D_SOURCES_PRODUCT"); // (read per call: the cross-check switches it within one process)
-        return (!filter && !(product && product[0] != '0')) ? bdg_dev::kSrcIdentity : 0;
-    }
     bool takeSyncMark() { // true (and the mark cleared) if a wait of this device gave up since the last look
         if (!syncBuf.p) return false;
         unsigned long long mark = 0;
@@ -618,7 +713,6 @@ struct bdg_sw2d {
     // ringExpected (flagSync): the ring-tile count the interior launch of the PREVIOUS stage brings the counter to
     void launchBoundaryStageFolded(hipStream_t on, const double* recv, double* send, hipEvent_t done = nullptr, bool flagSync = false,
                                    unsigned long long ringExpected = 0) {
-        const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
         bdg_dev::StageParams p = baseParams();
         bool recorded = false;
         unsigned signals = 0;
@@ -628,16 +722,13 @@ struct bdg_sw2d {
             p.syncFirstTile = 0;
             p.syncSignalsOut = &signals;
         }
-        static const bool extLaunch = [] { const char* e = std::getenv("BDG_SW2D_EXT_LAUNCH"); return !e || e[0] != '0'; }();
-        if (done && extLaunch) { p.stopEvent = done; p.stopEventUsed = &recorded; }
+        const int s = lserkStageParams(p, done, &recorded);
         p.kbegin = numInterior;
-        p.qin = qcur; p.qout = qalt; p.res = res.p;
-        p.ca = blitzdg::LSERK4::rk4a[st]; p.cb = blitzdg::LSERK4::rk4b[st]; p.cc = dtStage;
         p.haloRecv = recv; p.haloSend = send; p.haloSendOf = haloSendOf.p;
         p.haloOwned = numOwned; p.haloRows = nf * Np;
         if (N >= 5) { // the kernel family the interior (and a single-domain run) uses: bit-identical arithmetic
             p.opsAffine = opsMfma2.p;
-            static const char* haloVariant = std::getenv("BDG_SW2D_HALO_VARIANT"); // A/B switch: "6" = two-waves schedule
+            static const char* haloVariant = env::haloVariant(); // A/B switch: "6" = two-waves schedule
             const bool two = affineVariant == 6 || (haloVariant && haloVariant[0] == '6');
             hipCheck(two ? kt->stageMfma2Halo(p, on) : kt->stageMfma3Halo(p, on), "sw2d boundary stage kernel <LSERK, halo>");
         } else {
@@ -646,9 +737,7 @@ struct bdg_sw2d {
         }
         expectStrip += signals;
         if (done && !recorded) hipCheck(hipEventRecord(done, on), "hipEventRecord");
-        std::swap(qcur, qalt);
-        ++stageCount;
-        if (st == blitzdg::LSERK4::numStages - 1) timeNow += dtStage;
+        lserkStageAdvance(s);
     }
 
     // LSERK4 stages of a partitioned run, all on the device, as two concurrent chains:
@@ -722,70 +811,41 @@ struct bdg_sw2d {
         return out;
     }
 
+    // ---- the two-evaluation steppers. How an evaluation is issued: over the whole mesh, or -- a partitioned run -- exchanged:
+    // the ghost columns of the state it reads refreshed first and, variant B, the Lax-Friedrichs speed reduced over all ranks
+    enum class Eval { Whole, Exchanged };
+    // out = ca base + cb in + cc R(in), base = the current state; `next`: model time of the evaluation that will follow this one
+    void combine(Eval how, bool filter, bdg_dev::StageParams& p, double* in, double* out, double ca, double cb, double cc, double next) {
+        p.qin = in; p.qbase = qcur; p.qout = out;
+        p.ca = ca; p.cb = cb; p.cc = cc;
+        nextEvalTime = next;
+        auto launch = [&] { launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>"); };
+        if (how == Eval::Exchanged) evaluateExchanged(in, launch);
+        else launch();
+    }
     // q1 = q + dt/2 R(q);  q = q + dt R(q1)   (reference src/sw2d-simple/main.cpp:132-151)
-    void launchRk2Step(double dt, bool filter) {
+    void rk2Step(double dt, bool filter, Eval how) {
+        // (ahead of the first exchange of a partitioned run. The Heun step below leaves the check to launchStage, which in a
+        // partitioned run comes after that exchange and its communicator check: what a caller sees first differs, and stays)
         if (filter && !hasFilter) throw arg_error("filter requested but the solver was created without a Filter matrix");
         bdg_dev::StageParams p = baseParams();
-        p.qin = qcur; p.qbase = qcur; p.qout = aux.p;
-        p.ca = 1.0; p.cb = 0.0; p.cc = 0.5 * dt;
-        nextEvalTime = timeNow;
-        launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>");
-        p.qin = aux.p; p.qbase = qcur; p.qout = qalt;
-        p.ca = 1.0; p.cb = 0.0; p.cc = dt;
-        nextEvalTime = timeNow + dt;
-        launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>");
+        combine(how, filter, p, qcur, aux.p, 1.0, 0.0, 0.5 * dt, timeNow);
+        combine(how, filter, p, aux.p, qalt, 1.0, 0.0, dt, timeNow + dt);
         std::swap(qcur, qalt);
         timeNow += dt;
     }
-
-    // The same two schemes in a partitioned run: each evaluation first refreshes the ghost columns of the state it reads
-    // (and, variant B, reduces the Lax-Friedrichs speed over all ranks).
-    void launchRk2StepExchanged(double dt, bool filter) {
-        if (filter && !hasFilter) throw arg_error("filter requested but the solver was created without a Filter matrix");
-        bdg_dev::StageParams p = baseParams();
-        p.qin = qcur; p.qbase = qcur; p.qout = aux.p;
-        p.ca = 1.0; p.cb = 0.0; p.cc = 0.5 * dt;
-        nextEvalTime = timeNow;
-        evaluateExchanged(qcur, [&] { launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>"); });
-        p.qin = aux.p; p.qbase = qcur; p.qout = qalt;
-        p.ca = 1.0; p.cb = 0.0; p.cc = dt;
-        nextEvalTime = timeNow + dt;
-        evaluateExchanged(aux.p, [&] { launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>"); });
-        std::swap(qcur, qalt);
-        timeNow += dt;
-    }
-    void launchSspRk2StepExchanged(double dt, bool filter, double spongeCoeff) {
-        bdg_dev::StageParams p = baseParams();
-        p.sponge = spongeCoeff;
-        p.qin = qcur; p.qbase = qcur; p.qout = aux.p;
-        p.ca = 1.0; p.cb = 0.0; p.cc = dt;
-        nextEvalTime = timeNow;
-        evaluateExchanged(qcur, [&] { launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>"); });
-        p.qin = aux.p; p.qbase = qcur; p.qout = qalt;
-        p.ca = 0.5; p.cb = 0.5; p.cc = 0.5 * dt;
-        nextEvalTime = timeNow + dt;
-        evaluateExchanged(aux.p, [&] { launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>"); });
-        std::swap(qcur, qalt);
-        timeNow += dt;
-    }
-
     // SSP-RK2 (Heun) of the reference's variant-B driver (src/sw2d/main.cpp:211-235), sponge optional:
     //   q1 = sponge(q + dt R(q));   q = sponge(1/2 (q + q1 + dt R(q1)))
-    void launchSspRk2Step(double dt, bool filter, double spongeCoeff) {
+    void sspRk2Step(double dt, bool filter, double spongeCoeff, Eval how) {
         bdg_dev::StageParams p = baseParams();
         p.sponge = spongeCoeff;
-        p.qin = qcur; p.qbase = qcur; p.qout = aux.p;
-        p.ca = 1.0; p.cb = 0.0; p.cc = dt;
-        nextEvalTime = timeNow;                               // second evaluation: same time level (:225)
-        launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>");
-        p.qin = aux.p; p.qbase = qcur; p.qout = qalt;
-        p.ca = 0.5; p.cb = 0.5; p.cc = 0.5 * dt;
-        nextEvalTime = timeNow + dt;                          // first evaluation of the next step
-        launchStage(bdg_dev::MODE_COMBINE, filter, p, "sw2d stage kernel <COMBINE>");
+        combine(how, filter, p, qcur, aux.p, 1.0, 0.0, dt, timeNow);                  // second evaluation: same time level (:225)
+        combine(how, filter, p, aux.p, qalt, 0.5, 0.5, 0.5 * dt, timeNow + dt);       // then the first evaluation of the next step
         std::swap(qcur, qalt);
         timeNow += dt;
     }
 
+    // ---- operator images built when a variant first needs them
     // Row-wise operator image of the per-node-geometry form of variants B / C / D (VnOps: row i = Dr[i][.], Ds[i][.] interleaved,
     // then Lift[i][.]), the Filter rows of its second pass and the scratch planes of the unfiltered rows
     void buildNodalVariantOps() {
@@ -799,11 +859,9 @@ struct bdg_sw2d {
             }
             for (int j = 0; j < NFN; ++j) img[static_cast<size_t>(i) * row + 2 * Np + j] = hostLift[static_cast<size_t>(i) * NFN + j];
         }
-        opsVn.alloc(img.size(), bytes);
-        hipCheck(hipMemcpy(opsVn.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice), "nodal variant ops upload");
+        opsVn.upload(img, bytes, "nodal variant ops upload");
         if (!hostFilter.empty()) {
-            filterRows.alloc(hostFilter.size(), bytes);
-            hipCheck(hipMemcpy(filterRows.p, hostFilter.data(), hostFilter.size() * sizeof(double), hipMemcpyHostToDevice), "filter upload");
+            filterRows.upload(hostFilter, bytes, "filter upload");
             vnRaw.alloc(static_cast<size_t>(nf) * planeSize(), bytes);
         }
     }
@@ -826,18 +884,10 @@ struct bdg_sw2d {
                     img[static_cast<size_t>(3) * Np * Np + static_cast<size_t>(j) * Np + i] = Lift[i * NFN + j];
             return img;
         };
-        const std::vector<double> plain = image(hostDr.data(), hostDs.data(), nullptr, hostLift.data());
-        opsVd.alloc(plain.size(), bytes);
-        hipCheck(hipMemcpy(opsVd.p, plain.data(), plain.size() * sizeof(double), hipMemcpyHostToDevice), "source ops upload");
-        if (!hostFilter.empty()) {
-            const std::vector<double> FDr = matmulHost(hostFilter.data(), hostDr.data(), Np, Np),
-                                      FDs = matmulHost(hostFilter.data(), hostDs.data(), Np, Np),
-                                      FL = matmulHost(hostFilter.data(), hostLift.data(), Np, NFN);
-            const std::vector<double> filt = image(FDr.data(), FDs.data(), hostFilter.data(), FL.data());
-            opsVdFiltered.alloc(filt.size(), bytes);
-            hipCheck(hipMemcpy(opsVdFiltered.p, filt.data(), filt.size() * sizeof(double), hipMemcpyHostToDevice),
-                     "filtered source ops upload");
-        }
+        opsVd.upload(image(hostDr.data(), hostDs.data(), nullptr, hostLift.data()), bytes, "source ops upload");
+        if (!hostFilter.empty())
+            opsVdFiltered.upload(image(hostFDr.data(), hostFDs.data(), hostFilter.data(), hostFLift.data()), bytes,
+                                 "filtered source ops upload");
     }
 
     // Operator image of the matrix-core kernel with source terms (variants B/C/D at N >= 6): MfmaOps2 layout --
@@ -870,27 +920,18 @@ struct bdg_sw2d {
                 }
             return img;
         };
-        const std::vector<double> plain = image(hostDr.data(), hostDs.data(), hostLift.data(), nullptr);
-        opsMfma2Src.alloc(plain.size(), bytes);
-        hipCheck(hipMemcpy(opsMfma2Src.p, plain.data(), plain.size() * sizeof(double), hipMemcpyHostToDevice),
-                 "mfma2 source ops upload");
-        if (!hostFilter.empty()) {
-            const std::vector<double> FDr = matmulHost(hostFilter.data(), hostDr.data(), Np, Np),
-                                      FDs = matmulHost(hostFilter.data(), hostDs.data(), Np, Np),
-                                      FL = matmulHost(hostFilter.data(), hostLift.data(), Np, NFN);
-            const std::vector<double> filt = image(FDr.data(), FDs.data(), FL.data(), hostFilter.data());
-            opsMfma2SrcFiltered.alloc(filt.size(), bytes);
-            hipCheck(hipMemcpy(opsMfma2SrcFiltered.p, filt.data(), filt.size() * sizeof(double), hipMemcpyHostToDevice),
-                     "filtered mfma2 source ops upload");
-        }
+        opsMfma2Src.upload(image(hostDr.data(), hostDs.data(), hostLift.data(), nullptr), bytes, "mfma2 source ops upload");
+        if (!hostFilter.empty())
+            opsMfma2SrcFiltered.upload(image(hostFDr.data(), hostFDs.data(), hostFLift.data(), hostFilter.data()), bytes,
+                                       "filtered mfma2 source ops upload");
     }
-
-    const double* uploadPlane(const double* host, DevBuf<double>& buf) {
-        if (!host) return nullptr;
-        if (!buf.p) buf.alloc(planeSize(), bytes);
-        hipCheck(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), stream), "hipMemset");
-        uploadRows(host, buf.p, Np);
-        return buf.p;
+    // the transposed Filter of the unrolled source kernels' filtered evaluations
+    void buildFilterT() {
+        if (filterT.p || hostFilter.empty()) return;
+        std::vector<double> ft(static_cast<size_t>(Np) * Np);
+        for (int m = 0; m < Np; ++m)
+            for (int i = 0; i < Np; ++i) ft[static_cast<size_t>(m) * Np + i] = hostFilter[static_cast<size_t>(i) * Np + m];
+        filterT.upload(ft, bytes, "filter upload");
     }
 
     // Returns {max |Fscale|*spd, max |eta|}; NaN if any entry is NaN.
@@ -1060,12 +1101,10 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     s->affine = !(d.flags & BDG_SW2D_NODAL_GEOMETRY) && geometryIsAffine(d, Np, Nfp, K);
     // Non-affine tables: the matrix-core kernel with per-node geometry (every order). BDG_SW2D_NODAL_VECTOR=1 keeps the
     // round-1 vector kernel (one lane per element, N <= 6) for A/B measurements and cross-checks.
-    s->nodalMfma = !s->affine && !(std::getenv("BDG_SW2D_NODAL_VECTOR") && kt->ldsDoubles != 0);
+    s->nodalMfma = !s->affine && !(env::nodalVector() && kt->ldsDoubles != 0);
 
     s->use();
     hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
-    hipCheck(hipEventCreate(&s->ev0), "hipEventCreate");
-    hipCheck(hipEventCreate(&s->ev1), "hipEventCreate");
 
     const size_t plane3 = static_cast<size_t>(s->nf) * s->planeSize();
     s->qA.alloc(plane3, s->bytes);
@@ -1089,10 +1128,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     s->istage.alloc(static_cast<size_t>(NFN) * K, s->bytes);
     s->partials.alloc(2 * static_cast<size_t>((K + 255) / 256), s->bytes);
     s->red2.alloc(2, s->bytes);
-    if (!s->permHost.empty()) {
-        s->perm.alloc(K, s->bytes);
-        hipCheck(hipMemcpy(s->perm.p, s->permHost.data(), sizeof(int) * K, hipMemcpyHostToDevice), "perm upload");
-    }
+    if (!s->permHost.empty()) s->perm.upload(s->permHost, s->bytes, "perm upload");
     for (auto* b : {&s->qA, &s->qB, &s->res, &s->aux, &s->geo, &s->fgeo})
         if (b->p) hipCheck(hipMemsetAsync(b->p, 0, b->n * sizeof(double), s->stream), "hipMemset");
     hipCheck(hipMemsetAsync(s->vmapP.p, 0, s->vmapP.n * sizeof(int), s->stream), "hipMemset");
@@ -1133,12 +1169,22 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     // From N = 5 the default is the state-once matrix-core schedule (variant 7; measured against variant 6 at
     // 640 k / 500 k / 250 k / 250 k elements: N=5 0.36 vs 0.42 ms, N=6 0.33 vs 0.40, N=7 0.24 vs 0.28, N=8 0.30 vs 0.39).
     s->affineVariant = s->N <= 4 ? 0 : 7;
-    if (const char* e = std::getenv("BDG_SW2D_AFFINE_VARIANT")) {
+    if (const char* e = env::affineVariantPin()) {
         const int v = std::atoi(e);
         if (v >= 0 && v <= 9) {
             s->affineVariant = v;
             s->variantForced = true;
         }
+    }
+    // host copies for the operator images built after creation; Filter * (Dr, Ds, Lift) for every pre-filtered image
+    s->hostDr.assign(d.Dr, d.Dr + static_cast<size_t>(Np) * Np);
+    s->hostDs.assign(d.Ds, d.Ds + static_cast<size_t>(Np) * Np);
+    s->hostLift.assign(d.Lift, d.Lift + static_cast<size_t>(Np) * NFN);
+    if (d.Filter) {
+        s->hostFilter.assign(d.Filter, d.Filter + static_cast<size_t>(Np) * Np);
+        s->hostFDr = matmulHost(d.Filter, d.Dr, Np, Np);
+        s->hostFDs = matmulHost(d.Filter, d.Ds, Np, Np);
+        s->hostFLift = matmulHost(d.Filter, d.Lift, Np, NFN);
     }
     // the same operators as zero-padded 16x4 MFMA A tiles: lane l of tile (r, t) holds A[16r + (l&15)][4t + (l>>4)]
     auto mfmaImage = [&](const double* Dr, const double* Ds, const double* Lift) {
@@ -1176,8 +1222,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     };
     if (s->nodalMfma) { // per-node geometry on the matrix cores: the MfmaOps2 image, plain and pre-filtered
         const std::vector<double> img2 = mfma2Image(d.Dr, d.Ds, d.Lift);
-        s->opsMfma2.alloc(img2.size(), s->bytes);
-        hipCheck(hipMemcpy(s->opsMfma2.p, img2.data(), img2.size() * sizeof(double), hipMemcpyHostToDevice), "mfma2 ops upload");
+        s->opsMfma2.upload(img2, s->bytes, "mfma2 ops upload");
         if (d.Filter) { // the filter follows the metric terms: plain operators, then the Filter's own tiles (r, t)
             std::vector<double> imgF = img2;
             const int MT = kt->mfmaMT, KV = kt->mfmaKV;
@@ -1188,9 +1233,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
                         const int i = 16 * r + (l & 15), k = 4 * t + (l >> 4);
                         if (i < Np && k < Np) imgF[img2.size() + (static_cast<size_t>(r) * KV + t) * 64 + l] = d.Filter[i * Np + k];
                     }
-            s->opsMfma2NodalFilter.alloc(imgF.size(), s->bytes);
-            hipCheck(hipMemcpy(s->opsMfma2NodalFilter.p, imgF.data(), imgF.size() * sizeof(double), hipMemcpyHostToDevice),
-                     "nodal filter ops upload");
+            s->opsMfma2NodalFilter.upload(imgF, s->bytes, "nodal filter ops upload");
         }
     }
     if (s->affine) {
@@ -1206,80 +1249,37 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
             s->uploadRows(d.ny + row, s->ageo.p + (7 + f) * ld, 1);
             s->uploadRows(d.Fscale + row, s->ageo.p + (10 + f) * ld, 1);
         }
-        const std::vector<double> plain = affineOpsImage(d.Dr, d.Ds, d.Lift, Np, NFN);
-        s->opsAffine.alloc(plain.size(), s->bytes);
-        hipCheck(hipMemcpy(s->opsAffine.p, plain.data(), plain.size() * sizeof(double), hipMemcpyHostToDevice),
-                 "affine ops upload");
-        {
-            const std::vector<double> img2 = mfma2Image(d.Dr, d.Ds, d.Lift);
-            s->opsMfma2.alloc(img2.size(), s->bytes);
-            hipCheck(hipMemcpy(s->opsMfma2.p, img2.data(), img2.size() * sizeof(double), hipMemcpyHostToDevice), "mfma2 ops upload");
-        }
-        {
-            const std::vector<double> img = mfmaImage(d.Dr, d.Ds, d.Lift);
-            s->opsMfma.alloc(img.size(), s->bytes);
-            hipCheck(hipMemcpy(s->opsMfma.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice), "mfma ops upload");
-        }
+        s->opsAffine.upload(affineOpsImage(d.Dr, d.Ds, d.Lift, Np, NFN), s->bytes, "affine ops upload");
+        s->opsMfma2.upload(mfma2Image(d.Dr, d.Ds, d.Lift), s->bytes, "mfma2 ops upload");
+        s->opsMfma.upload(mfmaImage(d.Dr, d.Ds, d.Lift), s->bytes, "mfma ops upload");
         if (d.Filter) {
-            // Filter * (Dr, Ds, Lift): the filtered RHS of an affine element is linear in these.
-            const std::vector<double> FDr = matmulHost(d.Filter, d.Dr, Np, Np), FDs = matmulHost(d.Filter, d.Ds, Np, Np),
-                                      FL = matmulHost(d.Filter, d.Lift, Np, NFN);
-            {
-                const std::vector<double> img2 = mfma2Image(FDr.data(), FDs.data(), FL.data());
-                s->opsMfma2Filtered.alloc(img2.size(), s->bytes);
-                hipCheck(hipMemcpy(s->opsMfma2Filtered.p, img2.data(), img2.size() * sizeof(double), hipMemcpyHostToDevice),
-                         "filtered mfma2 ops upload");
-            }
-            {
-                const std::vector<double> img = mfmaImage(FDr.data(), FDs.data(), FL.data());
-                s->opsMfmaFiltered.alloc(img.size(), s->bytes);
-                hipCheck(hipMemcpy(s->opsMfmaFiltered.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice),
-                         "filtered mfma ops upload");
-            }
-            const std::vector<double> filt = affineOpsImage(FDr.data(), FDs.data(), FL.data(), Np, NFN);
-            s->opsAffineFiltered.alloc(filt.size(), s->bytes);
-            hipCheck(hipMemcpy(s->opsAffineFiltered.p, filt.data(), filt.size() * sizeof(double),
-                               hipMemcpyHostToDevice), "filtered affine ops upload");
+            const double *FDr = s->hostFDr.data(), *FDs = s->hostFDs.data(), *FL = s->hostFLift.data();
+            s->opsMfma2Filtered.upload(mfma2Image(FDr, FDs, FL), s->bytes, "filtered mfma2 ops upload");
+            s->opsMfmaFiltered.upload(mfmaImage(FDr, FDs, FL), s->bytes, "filtered mfma ops upload");
+            s->opsAffineFiltered.upload(affineOpsImage(FDr, FDs, FL, Np, NFN), s->bytes, "filtered affine ops upload");
         }
     }
 
     // ---- variant D: operator image with a third row per (m, i) (identity or Filter) + source tables
-    s->hostDr.assign(d.Dr, d.Dr + static_cast<size_t>(Np) * Np);
-    s->hostDs.assign(d.Ds, d.Ds + static_cast<size_t>(Np) * Np);
-    s->hostLift.assign(d.Lift, d.Lift + static_cast<size_t>(Np) * NFN);
-    if (d.Filter) s->hostFilter.assign(d.Filter, d.Filter + static_cast<size_t>(Np) * Np);
     if (s->variantD) {
         s->buildSourceOps();
         if (s->N > bdg_sw2d::kUnrolledSourcesMaxOrder) {
             s->buildMfma2SourceOps();
-            s->mfmaSources = !std::getenv("BDG_SW2D_ROLLED_SOURCES");
+            s->mfmaSources = !env::rolledSources();
         }
         s->vd.nf = s->nf;
         s->vd.sources = d.sources ? 1 : 0;
         s->vd.fconst = d.coriolis_const;
         s->vd.cd = d.drag;
-        auto plane = [&](const double* host, DevBuf<double>& buf) -> const double* {
-            if (!host) return nullptr;
-            buf.alloc(s->planeSize(), s->bytes);
-            hipCheck(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), s->stream), "hipMemset");
-            s->uploadRows(host, buf.p, Np);
-            return buf.p;
-        };
         if (d.sources) {
-            s->vd.zx = plane(d.zx, s->zxBuf);
-            s->vd.zy = plane(d.zy, s->zyBuf);
-            s->vd.fcor = plane(d.coriolis, s->fcorBuf);
+            s->vd.zx = s->uploadPlane(d.zx, s->zxBuf);
+            s->vd.zy = s->uploadPlane(d.zy, s->zyBuf);
+            s->vd.fcor = s->uploadPlane(d.coriolis, s->fcorBuf);
         }
         // Measured at C3 (10^6 triangles, N=4): rolled kernel 0.87 ms (3 fields) / 1.16 ms (4 fields) per
         // stage; unrolled kernel + tracer launch: see DESIGN.md section 3.
-        s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !std::getenv("BDG_SW2D_ROLLED_SOURCES");
-        if (s->fastSources && d.Filter) {
-            std::vector<double> ft(static_cast<size_t>(Np) * Np);
-            for (int m = 0; m < Np; ++m)
-                for (int i = 0; i < Np; ++i) ft[static_cast<size_t>(m) * Np + i] = d.Filter[i * Np + m];
-            s->filterT.alloc(ft.size(), s->bytes);
-            hipCheck(hipMemcpy(s->filterT.p, ft.data(), ft.size() * sizeof(double), hipMemcpyHostToDevice), "filter upload");
-        }
+        s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources();
+        if (s->fastSources) s->buildFilterT();
     }
 
     // ---- gather offsets: reference numbering (n' + Np*k') -> n'*ld + slot(k'), as (NFN, K) rows;
@@ -1309,8 +1309,8 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
         // ---- face links: every face of every element must reproduce its Nfp rows above exactly (address and wall
         //      flag); one face that does not (periodic maps, non-conforming meshes, hand-made tables) keeps the whole
         //      solver on the vmapP gather
-        const char* full = std::getenv("BDG_SW2D_FULL_STAGE_TRAFFIC");
-        if (s->affine && s->N <= 4 && !s->variantD && !(full && full[0] != '0')) {
+        const bool full = env::fullStageTraffic();
+        if (s->affine && s->N <= 4 && !s->variantD && !full) {
             int fm[3][5]; // (N <= 4)
             for (int f = 0; f < 3; ++f)
                 for (int n = 0; n < Nfp; ++n) fm[f][n] = kt->fmask(f, n);
@@ -1361,6 +1361,26 @@ void requireSolver(const bdg_sw2d* s, const char* fn) {
     if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
 }
 
+// prologue of the six field calls: a solver of `count` fields (`other`: what the refusal says otherwise) and no NULL field
+void requireFields(const bdg_sw2d* s, const char* fn, int count, const char* other, std::initializer_list<const void*> fields) {
+    requireSolver(s, fn);
+    if (s->nf != count) throw arg_error(std::string(fn) + ": " + other);
+    for (const void* f : fields)
+        if (!f) throw arg_error(std::string(fn) + ": NULL field");
+    s->use();
+}
+
+// the four bdg_sw2d_step_*rk2* calls: their prologue, then `step()` num_steps times
+template <class Step>
+int stepCall(bdg_sw2d* s, const char* fn, int num_steps, Step&& step) {
+    return guard([&] {
+        requireSolver(s, fn);
+        if (num_steps < 0) throw arg_error(std::string(fn) + ": num_steps < 0");
+        s->use();
+        for (int i = 0; i < num_steps; ++i) step();
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1406,32 +1426,17 @@ void bdg_sw2d_destroy(bdg_sw2d* s) {
 
 int bdg_sw2d_set_state(bdg_sw2d* s, const double* h, const double* hu, const double* hv) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_set_state");
-        if (s->nf != 3) throw arg_error("bdg_sw2d_set_state: this solver has 4 fields, use bdg_sw2d_set_state4");
-        if (!h || !hu || !hv) throw arg_error("bdg_sw2d_set_state: NULL field");
-        s->use();
-        const size_t pl = s->planeSize();
-        s->uploadRows(h, s->qcur, s->Np);
-        s->uploadRows(hu, s->qcur + pl, s->Np);
-        s->uploadRows(hv, s->qcur + 2 * pl, s->Np);
-        hipCheck(hipMemsetAsync(s->res.p, 0, s->res.n * sizeof(double), s->stream), "hipMemset");
-        s->stageCount = 0;
-        s->lamStateFor = nullptr; // a speed accumulated for the previous contents of this buffer is void
-        hipCheck(hipStreamSynchronize(s->stream), "set_state sync");
+        requireFields(s, "bdg_sw2d_set_state", 3, "this solver has 4 fields, use bdg_sw2d_set_state4", {h, hu, hv});
+        const double* f[] = {h, hu, hv};
+        s->setFields(f);
     });
 }
 
 int bdg_sw2d_get_state(bdg_sw2d* s, double* h, double* hu, double* hv) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_get_state");
-        if (s->nf != 3) throw arg_error("bdg_sw2d_get_state: this solver has 4 fields, use bdg_sw2d_get_state4");
-        if (!h || !hu || !hv) throw arg_error("bdg_sw2d_get_state: NULL field");
-        s->use();
-        const size_t pl = s->planeSize();
-        s->downloadRows(s->qcur, h, s->Np);
-        s->downloadRows(s->qcur + pl, hu, s->Np);
-        s->downloadRows(s->qcur + 2 * pl, hv, s->Np);
-        s->checkSyncError();
+        requireFields(s, "bdg_sw2d_get_state", 3, "this solver has 4 fields, use bdg_sw2d_get_state4", {h, hu, hv});
+        double* f[] = {h, hu, hv};
+        s->getFields(f);
     });
 }
 
@@ -1439,16 +1444,13 @@ int bdg_sw2d_output_fields(bdg_sw2d* s, const double* IM, double* eta, double* u
     return guard([&] {
         requireSolver(s, "bdg_sw2d_output_fields");
         s->use();
-        if (IM) {
-            if (!s->outM.p) s->outM.alloc(static_cast<size_t>(s->Np) * s->Np, s->bytes);
-            hipCheck(hipMemcpyAsync(s->outM.p, IM, s->outM.n * sizeof(double), hipMemcpyHostToDevice, s->stream), "H2D copy");
-        }
+        const double* M = s->stageOutputMatrix(IM);
         double* targets[3] = {eta, u, v};
         for (int which = 0; which < 3; ++which) {
             if (!targets[which]) continue;
             // aux is scratch between steps (RHS output / RK2 intermediate)
-            hipCheck(s->kt->output(s->qcur, s->hasH ? s->Hbuf.p : nullptr, IM ? s->outM.p : nullptr, s->aux.p, s->ld,
-                                   s->numOwned, which, s->stream), "sw2d_output_kernel");
+            hipCheck(s->kt->output(s->qcur, s->hasH ? s->Hbuf.p : nullptr, M, s->aux.p, s->ld, s->numOwned, which, s->stream),
+                     "sw2d_output_kernel");
             s->downloadRows(s->aux.p, targets[which], s->Np);
         }
     });
@@ -1460,12 +1462,8 @@ int bdg_sw2d_output_tracer(bdg_sw2d* s, const double* IM, double* tracer) {
         if (s->nf != 4) throw arg_error("bdg_sw2d_output_tracer: the solver has no tracer field");
         if (!tracer) throw arg_error("bdg_sw2d_output_tracer: NULL output");
         s->use();
-        if (IM) {
-            if (!s->outM.p) s->outM.alloc(static_cast<size_t>(s->Np) * s->Np, s->bytes);
-            hipCheck(hipMemcpyAsync(s->outM.p, IM, s->outM.n * sizeof(double), hipMemcpyHostToDevice, s->stream), "H2D copy");
-        }
         // which = 3: field 3 divided by h, i.e. the concentration N = hN / h the reference script writes out
-        hipCheck(s->kt->output(s->qcur, nullptr, IM ? s->outM.p : nullptr, s->aux.p, s->ld, s->numOwned, 3, s->stream),
+        hipCheck(s->kt->output(s->qcur, nullptr, s->stageOutputMatrix(IM), s->aux.p, s->ld, s->numOwned, 3, s->stream),
                  "sw2d_output_kernel");
         s->downloadRows(s->aux.p, tracer, s->Np);
     });
@@ -1500,19 +1498,12 @@ int bdg_sw2d_enable_variant_b(bdg_sw2d* s, const bdg_sw2d_vb_desc* d) {
                 throw arg_error("bdg_sw2d_enable_variant_b: open-boundary node index out of range");
         s->use();
         s->buildSourceOps();
-        s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !std::getenv("BDG_SW2D_ROLLED_SOURCES");
-        if (s->N > bdg_sw2d::kUnrolledSourcesMaxOrder && !std::getenv("BDG_SW2D_ROLLED_SOURCES")) {
+        s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources();
+        if (s->N > bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources()) {
             s->buildMfma2SourceOps();
             s->mfmaSources = true;
         }
-        if (s->fastSources && !s->hostFilter.empty() && !s->filterT.p) {
-            const int Np = s->Np;
-            std::vector<double> ft(static_cast<size_t>(Np) * Np);
-            for (int m = 0; m < Np; ++m)
-                for (int i = 0; i < Np; ++i) ft[static_cast<size_t>(m) * Np + i] = s->hostFilter[static_cast<size_t>(i) * Np + m];
-            s->filterT.alloc(ft.size(), s->bytes);
-            hipCheck(hipMemcpy(s->filterT.p, ft.data(), ft.size() * sizeof(double), hipMemcpyHostToDevice), "filter upload");
-        }
+        if (s->fastSources) s->buildFilterT();
         if (!s->Hbuf.p) s->Hbuf.alloc(s->planeSize(), s->bytes);
         hipCheck(hipMemsetAsync(s->Hbuf.p, 0, s->Hbuf.n * sizeof(double), s->stream), "hipMemset");
         // padding lanes are never computed, but give them a positive depth anyway
@@ -1574,19 +1565,10 @@ int bdg_sw2d_global_speed(bdg_sw2d* s, double* lam) {
 int bdg_sw2d_rhs(bdg_sw2d* s, const double* h, const double* hu, const double* hv, double* r1, double* r2,
                  double* r3, int filter) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_rhs");
-        if (s->nf != 3) throw arg_error("bdg_sw2d_rhs: this solver has 4 fields, use bdg_sw2d_rhs4");
-        if (!h || !hu || !hv || !r1 || !r2 || !r3) throw arg_error("bdg_sw2d_rhs: NULL field");
-        s->use();
-        const size_t pl = s->planeSize();
-        // the inactive state buffer is scratch between steps
-        s->uploadRows(h, s->qalt, s->Np);
-        s->uploadRows(hu, s->qalt + pl, s->Np);
-        s->uploadRows(hv, s->qalt + 2 * pl, s->Np);
-        s->launchRhs(s->qalt, s->aux.p, filter != 0);
-        s->downloadRows(s->aux.p, r1, s->Np);
-        s->downloadRows(s->aux.p + pl, r2, s->Np);
-        s->downloadRows(s->aux.p + 2 * pl, r3, s->Np);
+        requireFields(s, "bdg_sw2d_rhs", 3, "this solver has 4 fields, use bdg_sw2d_rhs4", {h, hu, hv, r1, r2, r3});
+        const double* in[] = {h, hu, hv};
+        double* out[] = {r1, r2, r3};
+        s->rhsFields(in, out, filter != 0);
     });
 }
 
@@ -1594,47 +1576,27 @@ int bdg_sw2d_num_fields(const bdg_sw2d* s) { return s ? s->nf : -1; }
 
 int bdg_sw2d_set_state4(bdg_sw2d* s, const double* h, const double* hu, const double* hv, const double* hN) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_set_state4");
-        if (s->nf != 4) throw arg_error("bdg_sw2d_set_state4: the solver was created with 3 fields");
-        const double* f[4] = {h, hu, hv, hN};
-        s->use();
-        for (int c = 0; c < 4; ++c) {
-            if (!f[c]) throw arg_error("bdg_sw2d_set_state4: NULL field");
-            s->uploadRows(f[c], s->qcur + c * s->planeSize(), s->Np);
-        }
-        hipCheck(hipMemsetAsync(s->res.p, 0, s->res.n * sizeof(double), s->stream), "hipMemset");
-        s->stageCount = 0;
-        hipCheck(hipStreamSynchronize(s->stream), "set_state sync");
+        requireFields(s, "bdg_sw2d_set_state4", 4, "the solver was created with 3 fields", {h, hu, hv, hN});
+        const double* f[] = {h, hu, hv, hN};
+        s->setFields(f);
     });
 }
 
 int bdg_sw2d_get_state4(bdg_sw2d* s, double* h, double* hu, double* hv, double* hN) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_get_state4");
-        if (s->nf != 4) throw arg_error("bdg_sw2d_get_state4: the solver was created with 3 fields");
-        double* f[4] = {h, hu, hv, hN};
-        s->use();
-        for (int c = 0; c < 4; ++c) {
-            if (!f[c]) throw arg_error("bdg_sw2d_get_state4: NULL field");
-            s->downloadRows(s->qcur + c * s->planeSize(), f[c], s->Np);
-        }
+        requireFields(s, "bdg_sw2d_get_state4", 4, "the solver was created with 3 fields", {h, hu, hv, hN});
+        double* f[] = {h, hu, hv, hN};
+        s->getFields(f);
     });
 }
 
 int bdg_sw2d_rhs4(bdg_sw2d* s, const double* h, const double* hu, const double* hv, const double* hN, double* r1,
                   double* r2, double* r3, double* r4, int filter) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_rhs4");
-        if (s->nf != 4) throw arg_error("bdg_sw2d_rhs4: the solver was created with 3 fields");
-        const double* in[4] = {h, hu, hv, hN};
-        double* out[4] = {r1, r2, r3, r4};
-        s->use();
-        for (int c = 0; c < 4; ++c) {
-            if (!in[c] || !out[c]) throw arg_error("bdg_sw2d_rhs4: NULL field");
-            s->uploadRows(in[c], s->qalt + c * s->planeSize(), s->Np);
-        }
-        s->launchRhs(s->qalt, s->aux.p, filter != 0);
-        for (int c = 0; c < 4; ++c) s->downloadRows(s->aux.p + c * s->planeSize(), out[c], s->Np);
+        requireFields(s, "bdg_sw2d_rhs4", 4, "the solver was created with 3 fields", {h, hu, hv, hN, r1, r2, r3, r4});
+        const double* in[] = {h, hu, hv, hN};
+        double* out[] = {r1, r2, r3, r4};
+        s->rhsFields(in, out, filter != 0);
     });
 }
 
@@ -1661,39 +1623,22 @@ int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps) {
 }
 
 int bdg_sw2d_step_rk2(bdg_sw2d* s, double dt, int num_steps, int filter) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2d_step_rk2");
-        if (num_steps < 0) throw arg_error("bdg_sw2d_step_rk2: num_steps < 0");
-        s->use();
-        for (int i = 0; i < num_steps; ++i) s->launchRk2Step(dt, filter != 0);
-    });
+    return stepCall(s, "bdg_sw2d_step_rk2", num_steps, [&] { s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole); });
 }
 
 int bdg_sw2d_step_ssprk2(bdg_sw2d* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2d_step_ssprk2");
-        if (num_steps < 0) throw arg_error("bdg_sw2d_step_ssprk2: num_steps < 0");
-        s->use();
-        for (int i = 0; i < num_steps; ++i) s->launchSspRk2Step(dt, filter != 0, sponge_coeff);
-    });
+    return stepCall(s, "bdg_sw2d_step_ssprk2", num_steps,
+                    [&] { s->sspRk2Step(dt, filter != 0, sponge_coeff, bdg_sw2d::Eval::Whole); });
 }
 
 int bdg_sw2d_step_rk2_exchanged(bdg_sw2d* s, double dt, int num_steps, int filter) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2d_step_rk2_exchanged");
-        if (num_steps < 0) throw arg_error("bdg_sw2d_step_rk2_exchanged: num_steps < 0");
-        s->use();
-        for (int i = 0; i < num_steps; ++i) s->launchRk2StepExchanged(dt, filter != 0);
-    });
+    return stepCall(s, "bdg_sw2d_step_rk2_exchanged", num_steps,
+                    [&] { s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Exchanged); });
 }
 
 int bdg_sw2d_step_ssprk2_exchanged(bdg_sw2d* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return guard([&] {
-        requireSolver(s, "bdg_sw2d_step_ssprk2_exchanged");
-        if (num_steps < 0) throw arg_error("bdg_sw2d_step_ssprk2_exchanged: num_steps < 0");
-        s->use();
-        for (int i = 0; i < num_steps; ++i) s->launchSspRk2StepExchanged(dt, filter != 0, sponge_coeff);
-    });
+    return stepCall(s, "bdg_sw2d_step_ssprk2_exchanged", num_steps,
+                    [&] { s->sspRk2Step(dt, filter != 0, sponge_coeff, bdg_sw2d::Eval::Exchanged); });
 }
 
 int bdg_sw2d_compute_dt(bdg_sw2d* s, double cfl, double* dt, double* eta_max) {
@@ -1718,7 +1663,7 @@ int bdg_sw2d_run_adaptive(bdg_sw2d* s, double cfl, double final_time, int max_st
         s->use();
         double t = *t_inout, dt = *dt_inout;
         while (t < final_time && (max_steps <= 0 || done < max_steps)) {
-            s->launchRk2Step(dt, filter != 0);
+            s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole);
             double r[2];
             s->reduceDt(r);
             if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
@@ -1749,13 +1694,7 @@ int bdg_sw2d_time_lserk4_stages(bdg_sw2d* s, double dt, int num_stages, float* m
         if (num_stages < 1 || !ms_per_launch) throw arg_error("bdg_sw2d_time_lserk4_stages: bad argument");
         s->use();
         s->dtStage = dt;
-        hipCheck(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
-        for (int i = 0; i < num_stages; ++i) s->launchLserkStage();
-        hipCheck(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(s->ev1), "hipEventSynchronize");
-        float ms = 0.f;
-        hipCheck(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
-        *ms_per_launch = ms / num_stages;
+        *ms_per_launch = bdg_dev::timePerRun(s->stream, num_stages, [&] { s->launchLserkStage(); });
     });
 }
 
@@ -1812,10 +1751,7 @@ int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const i
         }
         s->haloSendOf.release();
         s->haloFusable = ok && nB > 0;
-        if (s->haloFusable) {
-            s->haloSendOf.alloc(of.size(), s->bytes);
-            hipCheck(hipMemcpy(s->haloSendOf.p, of.data(), of.size() * sizeof(int), hipMemcpyHostToDevice), "send table upload");
-        }
+        if (s->haloFusable) s->haloSendOf.upload(of, s->bytes, "send table upload");
     });
 }
 
@@ -1857,11 +1793,9 @@ int bdg_sw2d_rhs_resident(bdg_sw2d* s, double* r1, double* r2, double* r3) {
         if (s->nf != 3) throw arg_error("bdg_sw2d_rhs_resident: three-field solvers only");
         if (!r1 || !r2 || !r3) throw arg_error("bdg_sw2d_rhs_resident: NULL output");
         s->use();
-        const size_t pl = s->planeSize();
+        double* out[] = {r1, r2, r3};
         s->launchRhs(s->qcur, s->aux.p, false);
-        s->downloadRows(s->aux.p, r1, s->Np);
-        s->downloadRows(s->aux.p + pl, r2, s->Np);
-        s->downloadRows(s->aux.p + 2 * pl, r3, s->Np);
+        s->downloadFields(s->aux.p, out);
     });
 }
 
@@ -1899,10 +1833,7 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
         // needed and costs 2-3 us per stage (8-way rehearsal, N=4: 0.056 ms per stage without, 0.058-0.059 with).
         // tests/test_dist_gpu.py::test_loopback_rccl_result_is_independent_of_event_flags_and_halo_staging compares both
         // settings bit for bit through real RCCL; BDG_SW2D_EVENT_FENCE=1 (or BDG_SW2D_EVENT_NOFENCE=0) restores the fence.
-        const char* fenceOn = std::getenv("BDG_SW2D_EVENT_FENCE");
-        const char* fenceOff = std::getenv("BDG_SW2D_EVENT_NOFENCE");
-        const bool fence = (fenceOn && fenceOn[0] == '1') || (fenceOff && fenceOff[0] == '0');
-        const unsigned evFlags = hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence);
+        const unsigned evFlags = hipEventDisableTiming | (env::eventFence() ? 0u : hipEventDisableSystemFence);
         for (hipEvent_t* e : {&s->evA[0], &s->evA[1], &s->evB[0], &s->evB[1]})
             hipCheck(hipEventCreateWithFlags(e, evFlags), "hipEventCreate");
         s->syncBuf.alloc(8, s->bytes);
@@ -1912,7 +1843,7 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
         // slower of the two gets there). Do that HERE, where every rank is anyway and nothing is in flight: one double each way with
         // every neighbour, in the buffers and with the pairing of the stage exchange. Otherwise it would happen in the first exchanged
         // stage, behind interior launches whose ring tiles wait -- with a bound -- for the launches queued behind that exchange.
-        if (!s->halo.peers.empty() && !std::getenv("BDG_SW2D_NO_COMM_WARMUP")) {
+        if (!s->halo.peers.empty() && !env::noCommWarmup()) {
             s->halo.sendRecv(s->halo.stream, rows, 1);
             hipCheck(hipStreamSynchronize(s->halo.stream), "hipStreamSynchronize");
         }
@@ -2145,13 +2076,8 @@ int bdg_sw2d_probe_stage_traffic(bdg_sw2d* s, int repeats, float* ms_per_launch)
                                s->K, !links || stage != 0 ? 1 : 0, !links || stage != last ? 1 : 0);
         };
         launch(1);
-        hipCheck(hipEventRecord(s->ev0, s->stream), "hipEventRecord");
-        for (int i = 0; i < repeats; ++i) launch(i % blitzdg::LSERK4::numStages);
-        hipCheck(hipEventRecord(s->ev1, s->stream), "hipEventRecord");
-        hipCheck(hipEventSynchronize(s->ev1), "hipEventSynchronize");
-        float ms = 0.f;
-        hipCheck(hipEventElapsedTime(&ms, s->ev0, s->ev1), "hipEventElapsedTime");
-        *ms_per_launch = ms / repeats;
+        int i = 0;
+        *ms_per_launch = bdg_dev::timePerRun(s->stream, repeats, [&] { launch(i++ % blitzdg::LSERK4::numStages); });
     });
 }
 
