@@ -296,6 +296,8 @@ _SIGNATURES = {
     "bdg_sw2d_probe_stage_traffic": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_sw2d_uses_affine_geometry": (c_int, [_P]),
     "bdg_sw2d_is_renumbered": (c_int, [_P]),
+    "bdg_element_order": (c_int, [_P, c_int, c_int, _P]),
+    "bdg_element_order_wanted": (c_int, [_P, c_int, c_int]),
     "bdg_sw2d_device_bytes": (c_size_t, [_P]),
     "bdg_sw2d_stream": (c_void_p, [_P]),
     "bdg_sw2d_curved_create": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(_P)]),

@@ -13,6 +13,7 @@
 // Elements may be renumbered internally (BDG_SW2D_REORDER); all I/O is in the
 // caller's numbering.
 #include "../host/capi_internal.hpp"
+#include "../host/element_order.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "halo_transport.hpp"
@@ -948,33 +949,6 @@ struct bdg_sw2d {
 
 namespace {
 
-// Breadth-first (Cuthill-McKee style) renumbering from the face-neighbour graph:
-// neighbours end up within O(sqrt(K)) slots of each other, so the trace gather of
-// a wave hits lines its own or nearby waves stream. perm[k] = device slot.
-std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp) {
-    std::vector<int> perm(K, -1);
-    int next = 0;
-    std::vector<int> frontier, nextFrontier;
-    for (int seed = 0; seed < K; ++seed) {
-        if (perm[seed] >= 0) continue;
-        perm[seed] = next++;
-        frontier.assign(1, seed);
-        while (!frontier.empty()) {
-            nextFrontier.clear();
-            for (int k : frontier)
-                for (int f = 0; f < 3; ++f) {
-                    const int k2 = vmapP[(static_cast<size_t>(k) * 3 + f) * Nfp] / Np;
-                    if (k2 >= 0 && k2 < K && perm[k2] < 0) {
-                        perm[k2] = next++;
-                        nextFrontier.push_back(k2);
-                    }
-                }
-            frontier.swap(nextFrontier);
-        }
-    }
-    return perm;
-}
-
 // True when the metric terms are constant per element and the face terms constant per
 // face (straight-sided elements), to round-off: then one value per element/face suffices.
 // The tables themselves carry round-off from Dr*x on small elements (relative ~1e-16 * |Dr| / h:
@@ -1081,23 +1055,16 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
             throw arg_error("bdg_sw2d_create: wall-node index out of range");
 
     // Element numbering: the trace gather is cheap only when face neighbours sit within an L2-sized
-    // window of slots. Forced by BDG_SW2D_REORDER, suppressed by BDG_SW2D_KEEP_ORDER, otherwise
-    // decided from the mean neighbour distance (shuffled 10^6-triangle box: 1.11 ms as given,
-    // 0.37 ms renumbered; natural order: 0.38 ms either way).
-    bool reorder = (d.flags & BDG_SW2D_REORDER) != 0;
-    if (!reorder && !(d.flags & BDG_SW2D_KEEP_ORDER)) {
-        std::atomic<long long> total{0};        // integers: the same sum whatever the number of workers
-        blitzdg::detail::parallelChunks(K, [&](int kBegin, int kEnd) {
-            long long mine = 0;
-            for (int k = kBegin; k < kEnd; ++k)
-                for (int f = 0; f < 3; ++f)
-                    mine += std::llabs(static_cast<long long>(d.vmapP[(static_cast<size_t>(k) * 3 + f) * Nfp] / Np) - k);
-            total += mine;
-        });
-        const double sum = static_cast<double>(total.load());
-        reorder = sum / (3.0 * K) > 4.0 * std::sqrt(static_cast<double>(K));
-    }
-    if (reorder) s->permHost = bfsOrder(d.vmapP, K, Np, Nfp);
+    // window of slots. Forced by BDG_SW2D_REORDER, suppressed by BDG_SW2D_KEEP_ORDER, otherwise decided
+    // from the neighbour distances (element_order.hpp): mean above 4 sqrt(K), as on a shuffled mesh
+    // (10^6-triangle box: 1.06 ms as given, 0.32 ms renumbered), or, at N <= 4, over a tenth of the faces
+    // beyond 1 MiB of stage traffic on a mesh larger than one XCD's L2, as in the row-by-row order of a
+    // wide box (0.306 ms as given, 0.300 renumbered). The numbering is breadth-first;
+    // BDG_SW2D_ORDER_PATCH=n makes it compact patches of n elements instead (measured, not kept).
+    namespace eo = blitzdg::element_order;
+    const bool reorder = (d.flags & BDG_SW2D_REORDER) != 0 ||
+                         (!(d.flags & BDG_SW2D_KEEP_ORDER) && eo::renumberingWanted(d.vmapP, K, Np, Nfp, d.order));
+    if (reorder) s->permHost = eo::renumbering(d.vmapP, K, Np, Nfp, eo::patchSetting());
     s->affine = !(d.flags & BDG_SW2D_NODAL_GEOMETRY) && geometryIsAffine(d, Np, Nfp, K);
     // Non-affine tables: the matrix-core kernel with per-node geometry (every order). BDG_SW2D_NODAL_VECTOR=1 keeps the
     // round-1 vector kernel (one lane per element, N <= 6) for A/B measurements and cross-checks.

@@ -3,6 +3,7 @@
 // (blitzdg_amd/pyblitzdg.py) can mirror the reference's boost::python module
 // (src/pyblitzdg/pyblitzdg.cpp:59-201) without copying on this side.
 #include "capi_internal.hpp"
+#include "element_order.hpp"
 #include "parallel_for.hpp"
 #include "blitzdg/Advec1d.hpp"
 #include "blitzdg/Burgers1d.hpp"
@@ -890,6 +891,24 @@ int bdg_burgers1d_run(int order, int K, double xmin, double xmax, double alpha, 
         *max_error = burgers1d::run(order, K, xmin, xmax, alpha, nu, c, cfl, final_time, &steps);
         if (num_steps) *num_steps = steps;
     });
+}
+
+// The numbering and the renumbering rule of the sw2d solvers (element_order.hpp) for callers without a GPU.
+int bdg_element_order(const int* EToE, int num_elements, int patch, int* perm) {
+    return guard([&] {
+        if (!EToE || !perm || num_elements < 1) throw bdg_detail::arg_error("bdg_element_order: bad argument");
+        const std::vector<int> p = blitzdg::element_order::renumbering(EToE, num_elements, 1, 1, patch);
+        std::copy(p.begin(), p.end(), perm);
+    });
+}
+
+int bdg_element_order_wanted(const int* EToE, int num_elements, int order) {
+    int wanted = -1;
+    guard([&] {
+        if (!EToE || num_elements < 1 || order < 1) throw bdg_detail::arg_error("bdg_element_order_wanted: bad argument");
+        wanted = blitzdg::element_order::renumberingWanted(EToE, num_elements, 1, 1, order) ? 1 : 0;
+    });
+    return wanted;
 }
 
 } // extern "C"

@@ -273,7 +273,9 @@ typedef struct bdg_sw2d_desc {
 #define BDG_SW2D_REORDER 1u /* renumber elements internally for gather locality (results are
                                returned in the caller's numbering either way)         */
 #define BDG_SW2D_KEEP_ORDER 4u /* never renumber (default: renumber when the mean face-neighbour
-                               distance exceeds 4*sqrt(K) slots, e.g. a shuffled mesh). Required
+                               distance exceeds 4*sqrt(K) slots, e.g. a shuffled mesh, or, at N <= 4,
+                               when over a tenth of the faces have their neighbour more than 1 MiB of
+                               stage traffic away, e.g. a wide box row by row). Required
                                for bdg_sw2d_set_partition, whose element ranges are in caller order */
 #define BDG_SW2D_NODAL_GEOMETRY 2u /* always read rx..sy, nx, ny, Fscale per node (general path).
                                Default: if they are constant per element / per face to round-off
@@ -705,6 +707,14 @@ int bdg_sw2d_probe_stage_traffic(bdg_sw2d* s, int repeats, float* ms_per_launch)
 int bdg_sw2d_uses_affine_geometry(const bdg_sw2d* s);
 /* 1 if the solver renumbered the elements internally (I/O stays in the caller's numbering). */
 int bdg_sw2d_is_renumbered(const bdg_sw2d* s);
+/* The numbering a renumbering solver gives a triangle mesh, from its face-neighbour table alone (no GPU):
+ * EToE is (num_elements, 3) row-major, a boundary face naming its own element; perm[caller element] = slot.
+ * patch <= 0: breadth-first from element 0 (the solvers' numbering); patch > 0: compact patches of that many
+ * elements grown over the face graph, slots by caller index inside a patch (a solver's with BDG_SW2D_ORDER_PATCH=patch). */
+int bdg_element_order(const int* EToE, int num_elements, int patch, int* perm);
+/* 1 if a solver of this order created without BDG_SW2D_REORDER / BDG_SW2D_KEEP_ORDER renumbers this mesh,
+ * 0 if it keeps the caller's order, -1 on a bad argument. */
+int bdg_element_order_wanted(const int* EToE, int num_elements, int order);
 size_t bdg_sw2d_device_bytes(const bdg_sw2d* s);
 /* The raw stream (hipStream_t) launches are issued on, for callers that interleave their own work. */
 void* bdg_sw2d_stream(bdg_sw2d* s);
