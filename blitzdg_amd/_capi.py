@@ -301,6 +301,7 @@ _SIGNATURES = {
     "bdg_sw2d_device_bytes": (c_size_t, [_P]),
     "bdg_sw2d_stream": (c_void_p, [_P]),
     "bdg_sw2d_curved_create": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(_P)]),
+    "bdg_sw2d_curved_plan": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(c_int), c_int]),
     "bdg_sw2d_curved_destroy": (None, [_P]),
     "bdg_sw2d_curved_rhs": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2d_curved_set_state": (c_int, [_P, _P, _P, _P, _P]),

@@ -23,6 +23,31 @@ constexpr int kLdsBudgetBytes = 150 * 1024;
 // 0.70, N=5 0.84 / 0.74, N=6 0.88 / 0.73, N=8 1.86 / 1.76
 constexpr int kDefaultWaves = BDG_ORDER <= 4 ? 2 : 1;
 
+// ---- switches, each read once per process by the first launch or kernelInfo call that needs it:
+// register budget of the general stage kernel, 1 | 2 waves per SIMD (A/B switch)
+int curvedWaves() {
+    static const int w = [] {
+        const char* e = std::getenv("BDG_SW2D_CURVED_WAVES");
+        return (e && e[0] == '2') ? 2 : ((e && e[0] == '1') ? 1 : kDefaultWaves);
+    }();
+    return w;
+}
+// =1: the streamed nodal-trace image where the order has both forms (A/B switch)
+bool forceStreamed() {
+    static const bool force = [] { const char* e = std::getenv("BDG_SW2D_CURVED_STREAM"); return e && e[0] == '1'; }();
+    return force;
+}
+// resident rounds of nodal-trace workgroups (0: one). A second round re-stages the operator image and balances no better
+// (=2..4 measured 1-4 % slower at N = 3, 6, 8)
+unsigned launchRounds() {
+    static const unsigned rounds = [] { const char* e = std::getenv("BDG_SW2D_CURVED_ROUNDS"); return e ? static_cast<unsigned>(std::atoi(e)) : 0u; }();
+    return rounds;
+}
+#ifdef BDG_PHASE_CLOCK
+// profiling build only, read when the process exits: where the per-wave phase cycles go
+const char* phaseClockFile() { return std::getenv("BDG_PHASE_CLOCK_FILE"); }
+#endif
+
 int opsTiles(int ncb, int fb) { return O::tiles(ncb, fb); }
 int stageTiles(int ncb, int fb) { return O::tiles(ncb, fb); }
 void opsOffsets(int ncb, int fb, int* off) {
@@ -44,15 +69,6 @@ hipError_t gauss(const CurvedParams& p, hipStream_t stream) {
 
 template <int MODE, bool FILTER, int FB, int WAVES, bool MAPM = false>
 hipError_t launchStageFb(const CurvedParams& p, hipStream_t stream);
-
-// Register budget: BDG_SW2D_CURVED_WAVES = 1 | 2 waves per SIMD (A/B switch; default below).
-int curvedWaves() {
-    static const int w = [] {
-        const char* e = std::getenv("BDG_SW2D_CURVED_WAVES");
-        return (e && e[0] == '2') ? 2 : ((e && e[0] == '1') ? 1 : kDefaultWaves);
-    }();
-    return w;
-}
 
 // What a launch of the general stage kernel decides on the host (also what kernelInfo reports): the register budget (a rewired
 // interior map is rare and has one budget only), and whether the operator image is staged in LDS or read from global memory.
@@ -138,7 +154,7 @@ size_t ntLdsStreamed(int ncb, int fb, bool filter) {
 // where both exist: A/B switch). An image that does not fit the form(s) of its order keeps the first kernels.
 constexpr bool kNtResident = BDG_ORDER <= 6, kNtStream = BDG_ORDER >= 5;
 bool ntStreamed(int ncb, int fb) {
-    static const bool force = [] { const char* e = std::getenv("BDG_SW2D_CURVED_STREAM"); return e && e[0] == '1'; }();
+    const bool force = forceStreamed();
     if (!kNtStream) return false;
     return !kNtResident || force || ntLdsResident(ncb, fb) > static_cast<size_t>(kLdsBudgetBytes);
 }
@@ -162,9 +178,7 @@ hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
     // resident workgroups: WAVES per SIMD = WAVES workgroups of four waves per CU, as far as LDS allows
     const int wgPerCu = std::max(1, std::min<int>(WAVES, static_cast<int>(kLdsLimitBytes / std::max<size_t>(lds, 1))));
     const unsigned ntiles = (static_cast<unsigned>(p.K - p.kbegin) + 15u) / 16u, wgs = (ntiles + 3u) / 4u;
-    static const unsigned rounds = [] { const char* e = std::getenv("BDG_SW2D_CURVED_ROUNDS"); return e ? static_cast<unsigned>(std::atoi(e)) : 0u; }();
-    // one resident round of workgroups (each wave loops over its tiles): a second round re-stages the operator image and balances
-    // no better (BDG_SW2D_CURVED_ROUNDS=2..4 measured 1-4 % slower at N = 3, 6, 8)
+    const unsigned rounds = launchRounds(); // one resident round of workgroups: each wave loops over its tiles
     const unsigned slots = 256u * static_cast<unsigned>(wgPerCu) * (rounds ? rounds : 1u);
     const unsigned reserve = std::min(static_cast<unsigned>(std::max(p.gridReserve, 0)), slots / 2u);
     const unsigned grid = std::max(1u, std::min(wgs, slots - reserve));
@@ -177,7 +191,7 @@ hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
         std::memset(clockBuf, 0, 4096 * 12 * sizeof(unsigned long long));
         static unsigned long long* dump = clockBuf;
         std::atexit([] {
-            const char* name = std::getenv("BDG_PHASE_CLOCK_FILE");
+            const char* name = phaseClockFile();
             if (FILE* f = name ? std::fopen(name, "w") : nullptr) {
                 for (unsigned w = 0; w < 4096; ++w) {
                     std::fprintf(f, "%u", w);

@@ -762,6 +762,20 @@ typedef struct bdg_sw2d_curved_desc {
  * 192 ceil(num_gauss / 16)) * ld * 8 must stay below 4 GiB (ld = num_elements rounded up to 64): 2.8 million elements at
  * N = 4 with the builders' default rules, 2.5 million at N = 8. BDG_ERR_ARGUMENT beyond it: partition the mesh. */
 int bdg_sw2d_curved_create(const bdg_sw2d_curved_desc* desc, bdg_sw2d_curved** out);
+/* What bdg_sw2d_curved_create would decide for this descriptor, from its host tables alone: no device is touched, so it runs
+ * on a machine without a GPU (desc->device is ignored). The same functions build the tables in both calls. The first
+ * min(n, 8) of
+ *   out[0] form           0 general, 1 nodal-trace (bdg_sw2d_curved_form), after BDG_SW2D_CURVED_GENERAL
+ *   out[1] identity_m     1 when gmapM is the identity
+ *   out[2] num_curved     distinct elements of curvedEls
+ *   out[3] num_affine     straight elements the general form holds compressed (BDG_SW2D_CURVED_NO_AFFINE: 0)
+ *   out[4] num_affine_nt  straight elements the nodal-trace form holds compressed (0 on the general form)
+ *   out[5] kref           element whose cubature weights the general form's compression refers to (-1: none)
+ *   out[6] kref_nt        likewise for the nodal-trace form
+ *   out[7] order_tiles    tiles in the nodal-trace form's tile order (0: mesh order)
+ * Refusals carry the texts of bdg_sw2d_curved_create. */
+#define BDG_SW2D_CURVED_PLAN_FIELDS 8
+int bdg_sw2d_curved_plan(const bdg_sw2d_curved_desc* desc, int* out, int n);
 void bdg_sw2d_curved_destroy(bdg_sw2d_curved* s);
 /* The reference function itself: host (Np, K) fields in, host RHS out; filter != 0 returns Filter * RHS
  * (what the driver applies next, sw2d_curved.py:250-253). The resident state is not disturbed. */

@@ -65,21 +65,41 @@ def pad_to_odd(deformed, K):
     raise ValueError("every tile with a deformed element is all deformed")
 
 
-def problem(order, nx, ny, ngauss=None, ncub=None, shuffle=0, rewire_gmapM=False, seed=7, odd_curved=True):
+def bump(x0, y0):
+    """A deformation that moves the two triangles of the middle cell of a 3 x 3 box and nothing else."""
+    b = np.clip(1.0 - (x0 ** 2 + y0 ** 2) / 0.3 ** 2, 0.0, None) ** 3
+    return x0 + 0.02 * b * np.cos(1.3 * y0), y0 + 0.05 * b
+
+
+def narrow_first_column(x0, y0):
+    """The first column of cells of a 3 x 3 box 0.8 times as wide, the other two wider: piecewise linear in x with its kink on
+    a mesh line, so every element stays straight-sided and the areas of the first column differ from the others' by 27 %."""
+    kink = -1.0 + 2.0 / 3.0
+    left = -1.0 + 0.8 * (x0 + 1.0)
+    right = 1.0 - (1.0 - (-1.0 + 0.8 * (kink + 1.0))) / (1.0 - kink) * (1.0 - x0)
+    return np.where(x0 <= kink, left, right), y0
+
+
+def problem(order, nx, ny, ngauss=None, ncub=None, shuffle=0, rewire_gmapM=False, seed=7, odd_curved=True, deformation=None,
+            listed=None):
     """A deformed nx x ny box (shuffleSeed = shuffle) at `order` with a Gauss rule of `ngauss` points per face (default 2 (N + 1))
     and a cubature rule of degree `ncub` (default 3 (N + 1)): contexts from this repository's builders and the oracle's tables.
     `seed` (of the momentum noise) and `odd_curved=False` (curvedEls = the deformed elements as they are, no straight one
-    added) exist for test_sw2d_curved_gpu.big_problem alone, whose problems stay what they were; no case of CASES sets them."""
+    added) exist for test_sw2d_curved_gpu.big_problem alone, whose problems stay what they were; no case of CASES sets them.
+    `deformation` replaces deform() of this module, `listed` the elements of curvedEls (default: the deformed ones)."""
     mesh = dg.MeshManager()
     mesh.buildBoxMesh(nx, ny, shuffleSeed=shuffle)
     nodes = dg.TriangleNodesProvisioner(order, mesh)
     nodes.buildFilter(0.9 * order, order)
     ctx = nodes.dgContext()
     x0, y0 = ctx.x, ctx.y
-    x, y = deform(x0, y0)
+    x, y = (deformation or deform)(x0, y0)
     deformed = np.where((np.abs(x - x0) + np.abs(y - y0)).max(axis=0) > 0)[0].astype(np.int32)
     K = int(ctx.numElements)
-    curvedEls = pad_to_odd(deformed, K) if odd_curved else deformed
+    if listed is not None:
+        curvedEls = np.asarray(listed, dtype=np.int32)
+    else:
+        curvedEls = pad_to_odd(deformed, K) if odd_curved else deformed
     nodes.setCoordinates(x, y)
     J = (ctx.Dr @ x) * (ctx.Ds @ y) - (ctx.Ds @ x) * (ctx.Dr @ y)
     NG = 2 * (order + 1) if ngauss is None else int(ngauss)
@@ -96,6 +116,18 @@ def problem(order, nx, ny, ngauss=None, ncub=None, shuffle=0, rewire_gmapM=False
              Filter=ctx.filter)
     return types.SimpleNamespace(order=order, nx=nx, ny=ny, K=K, NGauss=NG, nodes=nodes, ctx=ctx, cub=cub, gauss=gauss, x=x, y=y,
                                  J=J, gmapM=gmapM, gmapP=gmapP, deformed=deformed, curvedEls=curvedEls, t=t, q=q, ph=ph)
+
+
+def kref_case(order=3):
+    """Every element straight-sided, the first column of cells narrower than the rest, and the two triangles of the first cell
+    listed in curvedEls (the reference takes any list): the general form's reference element is element 0, the nodal-trace
+    form's the first unlisted one, of another area."""
+    c = problem(order, 3, 3, deformation=narrow_first_column, listed=[0, 1])
+    first_unlisted = 2
+    a0, a1 = c.J[0, 0], c.J[0, first_unlisted]
+    assert np.ptp(c.J, axis=0).max() < 1e-12 * a0                     # every element is geometrically straight
+    assert abs(a1 - a0) >= 0.01 * a0, (a0, a1)
+    return c
 
 
 def solver(c):
