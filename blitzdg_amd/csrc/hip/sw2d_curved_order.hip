@@ -2,10 +2,9 @@
 #include "sw2d_curved_kernel.hpp"
 #include "sw2d_curved_kernel_info.hpp"
 #include "sw2d_curved_nt_kernel.hpp"
+#include "sw2d_launch_host.hpp"
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 
 #ifndef BDG_ORDER
 #error "compile with -DBDG_ORDER=<polynomial order>"
@@ -13,6 +12,8 @@
 
 namespace bdg_dev {
 namespace {
+
+static_assert(TriModes::RHS == CMODE_RHS && TriModes::LSERK == CMODE_LSERK && TriModes::COMBINE == CMODE_COMBINE, "sw2d_dispatch.hpp");
 
 constexpr int kN = BDG_ORDER;
 using O = CurvedOps<kN>;
@@ -43,10 +44,7 @@ unsigned launchRounds() {
     static const unsigned rounds = [] { const char* e = std::getenv("BDG_SW2D_CURVED_ROUNDS"); return e ? static_cast<unsigned>(std::atoi(e)) : 0u; }();
     return rounds;
 }
-#ifdef BDG_PHASE_CLOCK
-// profiling build only, read when the process exits: where the per-wave phase cycles go
-const char* phaseClockFile() { return std::getenv("BDG_PHASE_CLOCK_FILE"); }
-#endif
+// (profiling build only, read when the process exits: BDG_PHASE_CLOCK_FILE, sw2d_launch_host.hpp)
 
 int opsTiles(int ncb, int fb) { return O::tiles(ncb, fb); }
 int stageTiles(int ncb, int fb) { return O::tiles(ncb, fb); }
@@ -97,11 +95,7 @@ hipError_t launchStageFb(const CurvedParams& p, hipStream_t stream) {
     if (stageImageInLds(p.ncb, p.fb)) {
         const size_t lds = stageImageBytes(p.ncb, p.fb);
         auto kern = sw2d_curved_stage_kernel<kN, MODE, FILTER, true, FB, WAVES, MAPM>;
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-        }
+        if (const hipError_t e = allowDynamicLds(kern, lds); e != hipSuccess) return e;
         const int wgPerCu = std::max(1, static_cast<int>(160 * 1024 / std::max<size_t>(lds, 1)));
         hipLaunchKernelGGL(kern, dim3(gridFor(p.K, std::min(wgPerCu, 2))), dim3(256), lds, stream, p);
     } else {
@@ -112,12 +106,7 @@ hipError_t launchStageFb(const CurvedParams& p, hipStream_t stream) {
 }
 
 hipError_t stage(int mode, bool filter, const CurvedParams& p, hipStream_t stream) {
-    switch (mode) {
-    case CMODE_RHS: return filter ? launchStage<CMODE_RHS, true>(p, stream) : launchStage<CMODE_RHS, false>(p, stream);
-    case CMODE_LSERK: return filter ? launchStage<CMODE_LSERK, true>(p, stream) : launchStage<CMODE_LSERK, false>(p, stream);
-    case CMODE_COMBINE: return filter ? launchStage<CMODE_COMBINE, true>(p, stream) : launchStage<CMODE_COMBINE, false>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return curvedForMode(mode, filter, [&](auto m, auto f) { return launchStage<decltype(m)::value, decltype(f)::value>(p, stream); });
 }
 
 template <int MODE, bool FILTER>
@@ -129,12 +118,7 @@ hipError_t launchFixup(const CurvedParams& p, hipStream_t stream) {
 }
 
 hipError_t fixup(int mode, bool filter, const CurvedParams& p, hipStream_t stream) {
-    switch (mode) {
-    case CMODE_RHS: return filter ? launchFixup<CMODE_RHS, true>(p, stream) : launchFixup<CMODE_RHS, false>(p, stream);
-    case CMODE_LSERK: return filter ? launchFixup<CMODE_LSERK, true>(p, stream) : launchFixup<CMODE_LSERK, false>(p, stream);
-    case CMODE_COMBINE: return filter ? launchFixup<CMODE_COMBINE, true>(p, stream) : launchFixup<CMODE_COMBINE, false>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return curvedForMode(mode, filter, [&](auto m, auto f) { return launchFixup<decltype(m)::value, decltype(f)::value>(p, stream); });
 }
 
 // ---- nodal-trace form (sw2d_curved_nt_kernel.hpp)
@@ -170,11 +154,7 @@ template <int MODE, bool FILTER, int STREAM, int FB, int RL>
 hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
     constexpr int WAVES = kNtWaves;
     auto kern = sw2d_curved_nt_kernel<kN, MODE, FILTER, STREAM, FB, WAVES, RL>;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = allowDynamicLds(kern, lds); e != hipSuccess) return e;
     // resident workgroups: WAVES per SIMD = WAVES workgroups of four waves per CU, as far as LDS allows
     const int wgPerCu = std::max(1, std::min<int>(WAVES, static_cast<int>(kLdsLimitBytes / std::max<size_t>(lds, 1))));
     const unsigned ntiles = (static_cast<unsigned>(p.K - p.kbegin) + 15u) / 16u, wgs = (ntiles + 3u) / 4u;
@@ -183,27 +163,9 @@ hipError_t launchNT(const CurvedParams& p, hipStream_t stream, size_t lds) {
     const unsigned reserve = std::min(static_cast<unsigned>(std::max(p.gridReserve, 0)), slots / 2u);
     const unsigned grid = std::max(1u, std::min(wgs, slots - reserve));
 #ifdef BDG_PHASE_CLOCK
-    // profiling build: the per-wave phase cycles of the last launch (workgroups 0..1023) go to $BDG_PHASE_CLOCK_FILE when the
-    // process exits (pinned host memory the kernel writes directly, so nothing of HIP is needed at that point)
-    static unsigned long long* clockBuf = nullptr;
-    if (!clockBuf) {
-        if (hipHostMalloc(&clockBuf, 4096 * 12 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) return hipErrorOutOfMemory;
-        std::memset(clockBuf, 0, 4096 * 12 * sizeof(unsigned long long));
-        static unsigned long long* dump = clockBuf;
-        std::atexit([] {
-            const char* name = phaseClockFile();
-            if (FILE* f = name ? std::fopen(name, "w") : nullptr) {
-                for (unsigned w = 0; w < 4096; ++w) {
-                    std::fprintf(f, "%u", w);
-                    for (int i = 0; i < 12; ++i) std::fprintf(f, " %llu", dump[w * 12 + i]);
-                    std::fprintf(f, "\n");
-                }
-                std::fclose(f);
-            }
-        });
-    }
     CurvedParams pc = p;
-    pc.phaseClock = clockBuf;
+    pc.phaseClock = phaseClockBuffer<4096, 12>(); // per workgroup
+    if (!pc.phaseClock) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, pc);
     return hipGetLastError();
 #else
@@ -254,12 +216,7 @@ hipError_t launchStageNT(const CurvedParams& p, hipStream_t stream) {
 }
 
 hipError_t stageNT(int mode, bool filter, const CurvedParams& p, hipStream_t stream) {
-    switch (mode) {
-    case CMODE_RHS: return filter ? launchStageNT<CMODE_RHS, true>(p, stream) : launchStageNT<CMODE_RHS, false>(p, stream);
-    case CMODE_LSERK: return filter ? launchStageNT<CMODE_LSERK, true>(p, stream) : launchStageNT<CMODE_LSERK, false>(p, stream);
-    case CMODE_COMBINE: return filter ? launchStageNT<CMODE_COMBINE, true>(p, stream) : launchStageNT<CMODE_COMBINE, false>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return curvedForMode(mode, filter, [&](auto m, auto f) { return launchStageNT<decltype(m)::value, decltype(f)::value>(p, stream); });
 }
 
 // Which instance a solver with these sizes launches, from the helpers the launches use: form, streamed, image_in_lds, fb,
@@ -286,8 +243,6 @@ const CurvedKernelTable kTable = {kN, O::Np, O::KV, O::MT, opsTiles, stageTiles,
 
 } // namespace
 
-#define BDG_CAT2(a, b) a##b
-#define BDG_CAT(a, b) BDG_CAT2(a, b)
 const CurvedKernelTable* BDG_CAT(curved_kernel_table_order, BDG_ORDER)() { return &kTable; }
 // (beside the table, whose declaration is shared with the device code in sw2d_curved_kernel.hpp)
 CurvedKernelInfoFn BDG_CAT(curved_kernel_info_order, BDG_ORDER)() { return &kernelInfo; }

@@ -18,6 +18,7 @@
 #include "blitzdg/LSERK4.hpp"
 #include "halo_transport.hpp"
 #include "sw2d_launch.hpp"
+#include "sw2d_launch_host.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -254,9 +255,8 @@ struct bdg_sw2d {
     // kept for operator images built after creation; the last three are Filter * (Dr, Ds, Lift): the filtered RHS of an affine
     // element is linear in these (empty without a Filter)
     std::vector<double> hostDr, hostDs, hostLift, hostFilter, hostFDr, hostFDs, hostFLift;
-    int affineVariant = 0; // 0: unrolled, register-resident state; 2/3: unrolled, streamed state at 2/3 waves
-                           // per SIMD; 1: rolled, one field per wave; 4: rolled, three fields per lane; 5: matrix cores (MFMA f64),
-                           // whole tile unrolled; 6: matrix cores, face-by-face / chunked schedule at 2 waves per SIMD
+    using AffineVariant = bdg_dev::AffineVariant;
+    AffineVariant affineVariant = AffineVariant::Unrolled; // kernel family of the straight three-field stage (sw2d_launch.hpp)
     bool variantForced = false;                 // BDG_SW2D_AFFINE_VARIANT given
     // elements below which the matrix-core kernel is the faster one, per order (measured crossovers:
     // N=2 near 10 k, N=3 near 125 k, N=4 between 125 k and 250 k; N=1 never ahead; N=5 runs on
@@ -404,12 +404,12 @@ struct bdg_sw2d {
     }
     // variant B's stage kernel on the state-once schedule where it exists (sw2d_mfma3src_kernel.hpp, PHYS = 2);
     // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernel
-    bool variantBStateOnce() const {
-        return kt->mfma3SrcFields >= 3 && !env::sourcesTwoWave() && static_cast<long long>(3) * Np * ld * 8 <= 4294967295LL;
-    }
+    bool variantBStateOnce() const { return kt->mfma3SrcFields >= 3 && !env::sourcesTwoWave() && fitsOneDescriptor(3); }
     // unfiltered evaluation on a state-once kernel with sources: F' is the identity, the sources are added pointwise (IDF instance;
     // BDG_SW2D_SOURCES_PRODUCT=1 keeps the products with the identity tiles for A/B runs and cross-checks -- bit-identical)
-    static int srcIdentity(bool filter) { return (!filter && !env::sourcesProduct()) ? bdg_dev::kSrcIdentity : 0; }
+    static bool srcIdentity(bool filter) { return !filter && !env::sourcesProduct(); }
+    // the state-once kernels address an array of `fields` planes through ONE buffer descriptor
+    bool fitsOneDescriptor(int fields) const { return bdg_dev::fitsOneDescriptor(fields, Np, ld); }
     // ... and at N >= 5 the strip kernel's workgroups (one 16-element tile each, three waves; two fit a CU, none fits beside an
     // interior workgroup's 120 KB of LDS) need free CUs, or the strip -- which sits on the exchange chain -- runs in many rounds.
     // Round 3 left one CU per strip tile (cap 218-232). Round 4, with the chains meeting inside the kernels, swept the cap in
@@ -434,12 +434,12 @@ struct bdg_sw2d {
         // the latency of one wavefront, not by HBM: the matrix-core kernel gives each wave 16 elements
         // instead of 64 (measured at N=4: 750 elements 7 us vs 19 us; 125 k elements 48 us vs 56 us;
         // 250 k elements 136 us vs 109 us -- DESIGN.md section 4).
-        int variant = affineVariant;
+        AffineVariant variant = affineVariant;
         // BDG_SW2D_SMALL_LAUNCH=n pins the crossover (A/B runs; the partition-boundary strip keeps the table's value: halosFold)
         const int smallPinned = env::smallLaunchPinned();
         const int smallLaunch = (smallPinned >= 0 && p.kbegin == 0) ? smallPinned : kSmallLaunch[N];
-        if (!variantForced && affine && N <= 5 && p.kend - p.kbegin < smallLaunch) variant = 5;
-        if (p.syncSignal && !(affine && !variantB && !variantD && (variant == 5 || variant == 7)))
+        if (!variantForced && affine && N <= 5 && p.kend - p.kbegin < smallLaunch) variant = AffineVariant::Mfma;
+        if (p.syncSignal && !(affine && !variantB && !variantD && (variant == AffineVariant::Mfma || variant == AffineVariant::Mfma3)))
             throw std::logic_error("in-kernel stage dependencies were requested for a launch whose kernel has no SYNC instance");
         if (!affine && (variantB || variantD)) {
             // per-node geometry tables: the general (rolled) form of variants B / C / D
@@ -450,59 +450,48 @@ struct bdg_sw2d {
                 vb.lam = lamBuf.p;
                 vb.lamNext = nullptr;
                 lamStateFor = nullptr;
-                hipCheck(kt->stageVn(mode, 2, p, vd, vb, opsVn.p, filt, vnRaw.p, vbPartials.p, lamBuf.p, !lamExternal, st), what);
+                hipCheck(kt->stageVn(mode, true, p, vd, vb, opsVn.p, filt, vnRaw.p, vbPartials.p, lamBuf.p, !lamExternal, st), what);
             } else {
                 bdg_dev::VdParams v = vd;
                 v.cbase = 0;
-                hipCheck(kt->stageVn(mode, 1, p, v, vb, opsVn.p, filt, vnRaw.p, nullptr, nullptr, false, st), what);
+                hipCheck(kt->stageVn(mode, false, p, v, vb, opsVn.p, filt, vnRaw.p, nullptr, nullptr, false, st), what);
             }
         } else if (variantB) {
+            using bdg_dev::SrcForm;
+            using bdg_dev::VbStage;
             vb.tide = tideAt(timeNow);
-            if (lamExternal) {
-                // partitioned run: the global speed of this state was reduced over all ranks into lamBuf beforehand
-                // (globalSpeedOf); every kernel family runs without its own speed pass
-                vb.lam = lamBuf.p;
-                vb.lamNext = nullptr;
-                lamStateFor = nullptr;
-                if (fastSources) {
-                    p.opsAffine = opsAffine.p;
-                    hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 2, filter ? filterT.p : nullptr, st), what);
-                } else if (mfmaSources) {
-                    p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
-                    hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
-                } else {
-                    p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
-                    hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 6, nullptr, st), what);
-                }
-            } else if (fastSources) {
-                // The unrolled kernel also reduces the global speed of the state it writes (for the tide value
-                // the next evaluation is expected to see). If this launch reads exactly that state at exactly
-                // that tide over the whole mesh, the separate speed pass is skipped.
+            // Where the global speed of this state comes from. Reduced: over all ranks of a partitioned run, into lamBuf
+            // beforehand (globalSpeedOf). Reused: the unrolled kernel also reduces the speed of the state it writes (for the tide
+            // value the next evaluation is expected to see); a launch that reads exactly that state at exactly that tide over
+            // the whole mesh finds it in lamPair. OwnPass: a speed pass into lamBuf in front of the stage kernel.
+            enum class Speed { Reduced, Reused, OwnPass };
+            const bool whole = p.kbegin == 0 && p.kend == numOwned;
+            const bool reusable = fastSources && whole && lamStateFor == p.qin && lamTideFor == vb.tide && !env::speedPass();
+            const Speed speed = lamExternal ? Speed::Reduced : (reusable ? Speed::Reused : Speed::OwnPass);
+            const bool ownPass = speed == Speed::OwnPass;
+            const int cur = lamSlot, nxt = lamSlot ^ 1;
+            vb.lam = speed == Speed::Reused ? lamPair.p + cur : lamBuf.p;
+            vb.lamNext = nullptr;
+            lamStateFor = nullptr;
+            if (fastSources && !lamExternal && whole && mode != bdg_dev::MODE_RHS) { // ... and this launch leaves the next one its speed
+                hipCheck(hipMemsetAsync(lamPair.p + nxt, 0, sizeof(double), st), "hipMemset");
+                vb.lamNext = reinterpret_cast<unsigned long long*>(lamPair.p + nxt);
+                vb.tideNext = tideAt(nextEvalTime);
+                lamStateFor = p.qout;
+                lamTideFor = vb.tideNext;
+                lamSlot = nxt;
+            }
+            if (fastSources) {
                 p.opsAffine = opsAffine.p;
-                const bool whole = p.kbegin == 0 && p.kend == numOwned;
-                const bool reuse = whole && lamStateFor == p.qin && lamTideFor == vb.tide && !env::speedPass();
-                const int cur = lamSlot, nxt = lamSlot ^ 1;
-                vb.lam = reuse ? lamPair.p + cur : lamBuf.p;
-                vb.lamNext = nullptr;
-                lamStateFor = nullptr;
-                if (whole && mode != bdg_dev::MODE_RHS) {
-                    hipCheck(hipMemsetAsync(lamPair.p + nxt, 0, sizeof(double), st), "hipMemset");
-                    vb.lamNext = reinterpret_cast<unsigned long long*>(lamPair.p + nxt);
-                    vb.tideNext = tideAt(nextEvalTime);
-                    lamStateFor = p.qout;
-                    lamTideFor = vb.tideNext;
-                    lamSlot = nxt;
-                }
-                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, reuse ? 2 : 1, filter ? filterT.p : nullptr, st), what);
+                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, ownPass, VbStage::Unrolled, filter ? filterT.p : nullptr, st), what);
             } else if (mfmaSources) {
-                // N >= 6: speed pass, then the matrix-core kernel with variant B's surface term and sources
-                vb.lam = lamBuf.p;
-                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 4, nullptr, st), what);
+                // N >= 5: the matrix-core kernel with variant B's surface term and sources
+                if (ownPass) hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, true, VbStage::None, nullptr, st), what);
                 p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
-                hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? (6 | srcIdentity(filter)) : 2, st), what);
+                hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? SrcForm::OnceVariantB : SrcForm::VariantB, srcIdentity(filter), st), what);
             } else {
                 p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
-                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, 0, nullptr, st), what);
+                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, ownPass, VbStage::Rolled, nullptr, st), what);
             }
         } else if (variantD && fastSources) {
             // three conserved fields on the unrolled kernel with the sources folded in, the tracer (if
@@ -512,9 +501,9 @@ struct bdg_sw2d {
             ph.fmat = filter ? filterT.p : nullptr;
             p.opsAffine = opsAffine.p;
             if (nf == 4 && !env::tracerPass()) {
-                hipCheck(kt->stageAffineSrc(mode, p, ph, 1, st), what);    // the tracer rides in the same pass
+                hipCheck(kt->stageAffineSrc(mode, p, ph, true, st), what);    // the tracer rides in the same pass
             } else {
-                hipCheck(kt->stageAffineSrc(mode, p, ph, 0, st), what);
+                hipCheck(kt->stageAffineSrc(mode, p, ph, false, st), what);
                 if (nf == 4) { // own pass; the tracer has no sources: pre-filtered operators as in variant A
                     p.opsAffine = filter ? opsAffineFiltered.p : opsAffine.p;
                     hipCheck(kt->stageTracer(mode, p, st), what);
@@ -522,42 +511,42 @@ struct bdg_sw2d {
             }
         } else if (variantD && mfmaSources) {
             // N >= 6: three conserved fields with sources on the matrix cores, then the tracer pass
+            using bdg_dev::SrcForm;
             const bdg_dev::PhysParams ph = physD();
+            const bool identity = srcIdentity(filter);
             p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
             // state-once schedule where it exists (sw2d_mfma3src_kernel.hpp: N = 5, 6, 7 with and without the tracer, N = 8 three fields;
             // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernels below for A/B runs and cross-checks)
             const bool stateOnceSrc = !env::sourcesTwoWave();
-            if (stateOnceSrc && kt->mfma3SrcFields >= nf && !env::tracerPass() &&
-                static_cast<long long>(nf) * Np * ld * 8 <= 4294967295LL) {
-                hipCheck(kt->stageMfma2Src(mode, p, ph, (nf == 4 ? 5 : 4) | srcIdentity(filter), st), what);
-            } else if (stateOnceSrc && kt->mfma3TracerPhase && nf == 4 && !env::tracerPass() &&
-                       static_cast<long long>(4) * Np * ld * 8 <= 4294967295LL) {
+            if (stateOnceSrc && kt->mfma3SrcFields >= nf && !env::tracerPass() && fitsOneDescriptor(nf)) {
+                hipCheck(kt->stageMfma2Src(mode, p, ph, nf == 4 ? SrcForm::OnceSourcesTracer : SrcForm::OnceSources, identity, st), what);
+            } else if (stateOnceSrc && kt->mfma3TracerPhase && nf == 4 && !env::tracerPass() && fitsOneDescriptor(4)) {
                 // N = 8: the tracer equation as a second phase of every tile, from the state tile still in LDS (one launch, state read once)
-                hipCheck(kt->stageMfma2Src(mode, p, ph, 7 | srcIdentity(filter), st), what);
-            } else if (stateOnceSrc && kt->mfma3SrcFields == 3 && nf == 4 && static_cast<long long>(3) * Np * ld * 8 <= 4294967295LL) {
+                hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::OnceTracerPhase, identity, st), what);
+            } else if (stateOnceSrc && kt->mfma3SrcFields == 3 && nf == 4 && fitsOneDescriptor(3)) {
                 // N = 8: three conserved fields with sources on the state-once schedule, the tracer in its own pass
-                hipCheck(kt->stageMfma2Src(mode, p, ph, 4 | srcIdentity(filter), st), what);
+                hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::OnceSources, identity, st), what);
                 p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
-                hipCheck(kt->stageMfma2Src(mode, p, ph, 1, st), what);
+                hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::TracerPass, false, st), what);
             } else if (nf == 4 && kt->mfmaMT <= 2 && !env::tracerPass()) {
-                hipCheck(kt->stageMfma2Src(mode, p, ph, 3, st), what);     // N <= 6: the tracer rides in the same pass
+                hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::SourcesTracer, false, st), what); // N <= 6: the tracer rides in the same pass
             } else {
-                hipCheck(kt->stageMfma2Src(mode, p, ph, 0, st), what);
+                hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::Sources, false, st), what);
                 if (nf == 4) {
                     p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
-                    hipCheck(kt->stageMfma2Src(mode, p, ph, 1, st), what);
+                    hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::TracerPass, false, st), what);
                 }
             }
         } else if (variantD) {
             p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
             hipCheck(kt->stageVd(mode, p, vd, st), what);
-        } else if (affine && variant == 5) {
+        } else if (affine && variant == AffineVariant::Mfma) {
             p.opsAffine = filter ? opsMfmaFiltered.p : opsMfma.p;
             hipCheck(kt->stageMfma(mode, p, st), what);
-        } else if (affine && variant == 7) {
+        } else if (affine && variant == AffineVariant::Mfma3) {
             p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
             hipCheck(kt->stageMfma3(mode, p, st), what);
-        } else if (affine && variant == 6) {
+        } else if (affine && variant == AffineVariant::Mfma2) {
             p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
             hipCheck(kt->stageMfma2(mode, p, st), what);
         } else if (affine) {
@@ -654,7 +643,7 @@ struct bdg_sw2d {
         p.qin = state;
         vb.tide = tideAt(timeNow);
         vb.lam = lamBuf.p;
-        hipCheck(kt->stageVb(bdg_dev::MODE_RHS, p, vb, vbPartials.p, lamBuf.p, 4, nullptr, stream), "sw2d_vb_speed_kernel");
+        hipCheck(kt->stageVb(bdg_dev::MODE_RHS, p, vb, vbPartials.p, lamBuf.p, true, bdg_dev::VbStage::None, nullptr, stream), "sw2d_vb_speed_kernel");
         if (halo.comm && halo.world > 1)
             ncclCheck(rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, halo.comm, stream), "ncclAllReduce");
     }
@@ -687,13 +676,13 @@ struct bdg_sw2d {
     bool flagSyncUsable() const {
         if (env::eventSync() || !syncBuf.p || !halosFold()) return false;
         if (env::stripThroughput() || env::haloVariant()) return false;
-        if (N >= 5) return affineVariant == 7 && (numOwned - numInterior + 15) / 16 <= 1024;
+        if (N >= 5) return affineVariant == AffineVariant::Mfma3 && (numOwned - numInterior + 15) / 16 <= 1024;
         // N <= 4: only while the interior share is small enough for the matrix-core kernel (8-way split of C3). A SYNC instance of
         // the unrolled kernel (the wait in front of its one big basic block, ring waves storing write-through) was built and
         // measured in the 2- and 4-way rehearsal: 0.332 / 0.164 ms per stage against 0.220 / 0.121 with the events -- the branch
         // at the top costs that kernel its load batching (profiles/r04_rehearsal_experiments.txt); larger shares keep the events.
         const int smallPinned = env::smallLaunchPinned();
-        return numInterior > 0 && affineVariant == 0 && numInterior < (smallPinned >= 0 ? smallPinned : kSmallLaunch[N]);
+        return numInterior > 0 && affineVariant == AffineVariant::Unrolled && numInterior < (smallPinned >= 0 ? smallPinned : kSmallLaunch[N]);
     }
     // a bounded in-kernel wait that gave up (sync_wait) left a mark: report it the next time the host looks at the device
     bool takeSyncMark() { // true (and the mark cleared) if a wait of this device gave up since the last look
@@ -730,7 +719,7 @@ struct bdg_sw2d {
         if (N >= 5) { // the kernel family the interior (and a single-domain run) uses: bit-identical arithmetic
             p.opsAffine = opsMfma2.p;
             static const char* haloVariant = env::haloVariant(); // A/B switch: "6" = two-waves schedule
-            const bool two = affineVariant == 6 || (haloVariant && haloVariant[0] == '6');
+            const bool two = affineVariant == AffineVariant::Mfma2 || (haloVariant && haloVariant[0] == '6');
             hipCheck(two ? kt->stageMfma2Halo(p, on) : kt->stageMfma3Halo(p, on), "sw2d boundary stage kernel <LSERK, halo>");
         } else {
             p.opsAffine = opsMfma.p;
@@ -1135,11 +1124,11 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     // (N=5, 640 k elements: 0.454 ms unrolled, 0.405 ms matrix cores).
     // From N = 5 the default is the state-once matrix-core schedule (variant 7; measured against variant 6 at
     // 640 k / 500 k / 250 k / 250 k elements: N=5 0.36 vs 0.42 ms, N=6 0.33 vs 0.40, N=7 0.24 vs 0.28, N=8 0.30 vs 0.39).
-    s->affineVariant = s->N <= 4 ? 0 : 7;
+    s->affineVariant = s->N <= 4 ? bdg_dev::AffineVariant::Unrolled : bdg_dev::AffineVariant::Mfma3;
     if (const char* e = env::affineVariantPin()) {
         const int v = std::atoi(e);
         if (v >= 0 && v <= 9) {
-            s->affineVariant = v;
+            s->affineVariant = static_cast<bdg_dev::AffineVariant>(v);
             s->variantForced = true;
         }
     }

@@ -16,15 +16,53 @@
 
 namespace bdg_dev {
 
-constexpr int kSrcIdentity = 16; // stageMfma2Src's tracer argument, state-once forms: "the image's F' tiles are the identity" (no filter)
+// ---- the kernel forms a table entry chooses between, by name
+
+// stageAffine: the families of the straight three-field stage. The numbers are the values of BDG_SW2D_AFFINE_VARIANT
+// (DESIGN.md); Mfma, Mfma2 and Mfma3 have table entries of their own (stageMfma, stageMfma2, stageMfma3) and are the
+// solver's to route -- stageAffine runs Unrolled for them.
+enum class AffineVariant : int {
+    Unrolled = 0,   // fully unrolled, register-resident state, one wave per SIMD
+    FieldSplit = 1, // rolled, one field per wave (every order)
+    Stream2 = 2,    // unrolled, streamed state at two waves per SIMD (N <= 5; above: FieldSplit)
+    Stream3 = 3,    // ... at three waves per SIMD
+    Rolled = 4,     // rolled, three fields per lane (N <= 6; above: FieldSplit)
+    Mfma = 5,       // matrix cores, whole tile unrolled
+    Mfma2 = 6,      // matrix cores, face-by-face schedule at two waves per SIMD
+    Mfma3 = 7,      // matrix cores, state-once schedule
+    Lean = 8,       // state-resident at two waves per SIMD, LSERK stages (N <= 5; other modes and orders: Unrolled)
+    Xchg = 9        // in-wave neighbour traces through LDS, LSERK stages (N <= 5; other modes and orders: Unrolled)
+};
+
+// stageMfma2Src (N >= 5): what the matrix-core kernel with sources computes, and on which schedule. The image in p.opsAffine is
+// MfmaOps2 + MT*KV tiles of F' (identity or Filter), except for TracerPass (plain MfmaOps2 image). The Once* forms are the
+// state-once schedule (sw2d_mfma3src_kernel.hpp); they exist where KernelTable::mfma3SrcFields / mfma3TracerPhase say so and
+// the state fits one buffer descriptor, hipErrorNotSupported otherwise.
+enum class SrcForm {
+    Sources,           // momentum sources of variants C / D, three fields, two waves per SIMD
+    TracerPass,        // the tracer equation alone (field 3 of a four-field state)
+    VariantB,          // variant B's surface term and sources, two waves per SIMD
+    SourcesTracer,     // sources + tracer in one pass (MT <= 2, i.e. N <= 6)
+    OnceSources,       // state-once: sources, three fields
+    OnceSourcesTracer, // state-once: sources + tracer, four fields (mfma3SrcFields = 4)
+    OnceVariantB,      // state-once: variant B
+    OnceTracerPhase    // state-once: three fields with sources, the tracer as a second phase of every tile (mfma3TracerPhase)
+};
+
+// stageVb: the stage kernel that follows variant B's speed pass
+enum class VbStage {
+    None,    // speed pass alone (the stage runs on another entry: stageMfma2Src, or none at all)
+    Rolled,  // rolled kernel, VdOps image (plain or filtered) in p.opsAffine
+    Unrolled // unrolled kernel (N <= 4), plain AffineOps in p.opsAffine, the filter applied at the end
+};
 
 struct KernelTable {
     int order, Np, Nfp, ldsDoubles;
-    // mode: StageMode; launches one fused RHS(+stage update) pass over K elements.
+    // mode: StageMode; launches one fused RHS(+stage update) pass over K elements (per-node geometry, vector kernel).
     hipError_t (*stage)(int mode, bool filter, const StageParams& p, hipStream_t stream);
     // affine-geometry fast path (no FILTER template: the filter is folded into the operators)
     int affineOpsDoubles;
-    hipError_t (*stageAffine)(int mode, int variant, const StageParams& p, hipStream_t stream);
+    hipError_t (*stageAffine)(int mode, AffineVariant variant, const StageParams& p, hipStream_t stream);
     // matrix-core path (v_mfma_f64_16x16x4_f64), straight-sided elements; needs ldsBytes of dynamic LDS
     int mfmaOpsDoubles, mfmaMT, mfmaKV, mfmaKS;
     hipError_t (*stageMfma)(int mode, const StageParams& p, hipStream_t stream);
@@ -39,32 +77,30 @@ struct KernelTable {
     hipError_t (*stageMfma3Halo)(const StageParams& p, hipStream_t stream); // MODE_LSERK with the halo staging folded in
     // per-node geometry (geo / fgeo planes); filter: plain operators + MT*KV Filter tiles in the image
     hipError_t (*stageMfma3Nodal)(int mode, bool filter, const StageParams& p, hipStream_t stream);
-    // N >= 5: the same kernel with momentum sources (image = MfmaOps2 + MT*KV tiles of F'); tracer = 1: the
-    // tracer-equation pass (plain MfmaOps2 image); tracer = 2: variant B (image as for the sources); tracer = 3: sources +
-    // tracer in one pass (MT <= 2); tracer = 4 / 5: sources without / with the tracer on the state-once schedule
-    // (sw2d_mfma3src_kernel.hpp; hipErrorNotSupported where its LDS tiles or registers do not fit: see mfma3SrcFields)
-    hipError_t (*stageMfma2Src)(int mode, const StageParams& p, const PhysParams& ph, int tracer, hipStream_t stream);
+    // N >= 5: the matrix-core kernels with sources, one SrcForm each. identity (Once* forms only): the image's F' tiles are the
+    // identity (no filter) -- the instance that adds the sources pointwise instead of multiplying by them
+    hipError_t (*stageMfma2Src)(int mode, const StageParams& p, const PhysParams& ph, SrcForm form, bool identity, hipStream_t stream);
     int mfma3SrcFields; // 0: no state-once kernel with sources at this order; else the number of fields it takes (up to)
-    int mfma3TracerPhase; // 1: tracer = 7 exists -- the three-field state-once kernel with the tracer equation as a second phase of every tile (N = 8)
+    int mfma3TracerPhase; // 1: SrcForm::OnceTracerPhase exists (N = 8)
     // variant D (tracer + sources), straight-sided elements, nf = 3 or 4 waves per 64 elements
     int vdOpsDoubles;
     hipError_t (*stageVd)(int mode, const StageParams& p, const VdParams& vp, hipStream_t stream);
-    // unrolled affine kernel + momentum sources (3 fields; N <= 6), the fast path of variants C/D
-    hipError_t (*stageAffineSrc)(int mode, const StageParams& p, const PhysParams& ph, int tracer, hipStream_t stream);
-    // tracer equation alone (field 3 of a four-field state), unrolled; N <= 6
+    // unrolled affine kernel + momentum sources (N <= 4), the fast path of variants C / D; tracer: four-field state, the tracer
+    // equation in the same pass
+    hipError_t (*stageAffineSrc)(int mode, const StageParams& p, const PhysParams& ph, bool tracer, hipStream_t stream);
+    // tracer equation alone (field 3 of a four-field state), unrolled; N <= 4
     hipError_t (*stageTracer)(int mode, const StageParams& p, hipStream_t stream);
-    // variant B (depth, star states, open boundary, global Lax-Friedrichs speed, sources): speed pass over
-    // [kbegin, kend) into partials (one double per 256 elements) and *lam, then the fused stage pass
-    // unrolled != 0 (N <= 5): the unrolled stage kernel with plain AffineOps in p.opsAffine and the filter
-    // (filterT, [m][i] = F[i][m], or nullptr) applied at the end; 2: the same without the speed pass (vp.lam is
-    // current); 4: speed pass only; 0: speed pass + rolled kernel with a VdOps image
-    hipError_t (*stageVb)(int mode, const StageParams& p, const VbParams& vp, double* partials, double* lam,
-                          int unrolled, const double* filterT, hipStream_t stream);
-    // variants B (phys = 2) and C / D (phys = 1) on per-node geometry (sw2d_vn_kernel.hpp): ops = VnOps image; filt != nullptr:
+    // variant B (depth, star states, open boundary, global Lax-Friedrichs speed, sources). speedPass: the speed of the state over
+    // [kbegin, kend) is reduced into partials (one double per 256 elements) and *lam first (else vp.lam is current: accumulated by
+    // the launch that wrote the state, or reduced over all ranks beforehand); then the `then` kernel. filterT (Unrolled only):
+    // [m][i] = F[i][m], or nullptr
+    hipError_t (*stageVb)(int mode, const StageParams& p, const VbParams& vp, double* partials, double* lam, bool speedPass,
+                          VbStage then, const double* filterT, hipStream_t stream);
+    // variant B (variantB) and variants C / D (else) on per-node geometry (sw2d_vn_kernel.hpp): ops = VnOps image; filt != nullptr:
     // the filtered RHS in two passes (unfiltered rows to raw, nf planes; then Filter and the update); speedPass: variant B's
     // global speed of this state is reduced into *lam first (else vb.lam is current)
     int vnOpsDoubles;
-    hipError_t (*stageVn)(int mode, int phys, const StageParams& p, const VdParams& vd, const VbParams& vb, const double* ops,
+    hipError_t (*stageVn)(int mode, bool variantB, const StageParams& p, const VdParams& vd, const VbParams& vb, const double* ops,
                           const double* filt, double* raw, double* partials, double* lam, bool speedPass, hipStream_t stream);
     // per-block partial maxima (2 doubles per block of 256 elements)
     hipError_t (*dt)(const double* q, const double* fscale, const double* H, long long ld, int K, double g,

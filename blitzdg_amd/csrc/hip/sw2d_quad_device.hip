@@ -15,7 +15,7 @@
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "sw2d_quad4_kernel.hpp"
-#include "sw2d_quad_dispatch.hpp"
+#include "sw2d_dispatch.hpp"
 #include "sw2d_quad_drifter_kernel.hpp"
 #include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
@@ -43,28 +43,28 @@ namespace bdg_dev {
 namespace {
 // the per-order launchers exist for 1..BDG_SW2DQ_MAX_ORDER (the Makefile's QUAD_ORDERS)
 template <class F>
-hipError_t forOrder(int order, F&& f) { return quadForOrder<BDG_SW2DQ_MAX_ORDER>(order, std::forward<F>(f)); }
+hipError_t forQuadOrder(int order, F&& f) { return forOrder<BDG_SW2DQ_MAX_ORDER>(order, std::forward<F>(f)); }
 } // namespace
 
 hipError_t sw2d_quad_stage(int order, int mode, bool filter, bool general, const QuadParams& p, hipStream_t stream) {
-    return forOrder(order, [&](auto n) { return sw2d_quad_launch<decltype(n)::value>(mode, filter, general, p, stream); });
+    return forQuadOrder(order, [&](auto n) { return sw2d_quad_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quad4_stage(int order, int mode, bool filter, bool general, bool sources, const Quad4Params& p,
                             hipStream_t stream) {
-    return forOrder(order, [&](auto n) { return sw2d_quad4_launch<decltype(n)::value>(mode, filter, general, sources, p, stream); });
+    return forQuadOrder(order, [&](auto n) { return sw2d_quad4_launch<decltype(n)::value>(mode, filter, general, sources, p, stream); });
 }
 
 hipError_t sw2d_quad_output(int order, int fields, const QuadOutParams& p, hipStream_t stream) {
-    return forOrder(order, [&](auto n) { return sw2d_quad_output_launch<decltype(n)::value>(fields, p, stream); });
+    return forQuadOrder(order, [&](auto n) { return sw2d_quad_output_launch<decltype(n)::value>(fields, p, stream); });
 }
 
 hipError_t sw2d_quadb_stage(int order, int mode, bool filter, bool general, const QuadBParams& p, hipStream_t stream) {
-    return forOrder(order, [&](auto n) { return sw2d_quadb_launch<decltype(n)::value>(mode, filter, general, p, stream); });
+    return forQuadOrder(order, [&](auto n) { return sw2d_quadb_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quadb4_stage(int order, int mode, bool filter, bool general, const QuadB4Params& p, hipStream_t stream) {
-    return forOrder(order, [&](auto n) { return sw2d_quadb4_launch<decltype(n)::value>(mode, filter, general, p, stream); });
+    return forQuadOrder(order, [&](auto n) { return sw2d_quadb4_launch<decltype(n)::value>(mode, filter, general, p, stream); });
 }
 
 hipError_t sw2d_quadb_speed(int order, bool general, const QuadBParams& p, double* out, hipStream_t stream) {

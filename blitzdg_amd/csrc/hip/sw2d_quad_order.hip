@@ -3,7 +3,7 @@
 // (mode, filter, geometry form, sources) instance of the four-field sw2d_quad4_stage_kernel<N>; and the output step
 // sw2d_quad_output_kernel<N> for three and four fields, with and without the lattice interpolation.
 #include "sw2d_quad4_kernel.hpp"
-#include "sw2d_quad_dispatch.hpp"
+#include "sw2d_dispatch.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 
 #ifndef BDG_ORDER
@@ -11,6 +11,9 @@
 #endif
 
 namespace bdg_dev {
+
+static_assert(QuadModes::RHS == QMODE_RHS && QuadModes::COMBINE == QMODE_COMBINE && QuadModes::LSERK == QMODE_LSERK &&
+              QuadModes::HEUN == QMODE_HEUN, "sw2d_dispatch.hpp");
 
 namespace {
 template <int N, int MODE, bool FILT>

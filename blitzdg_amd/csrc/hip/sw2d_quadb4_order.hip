@@ -2,7 +2,7 @@
 // sw2d_quadb_order.hip): every (mode, filter, geometry form) instance of sw2d_quadb4_stage_kernel<N>: RHS, COMBINE and
 // HEUN plain and filtered, LSERK plain.
 #include "sw2d_quadb4_kernel.hpp"
-#include "sw2d_quad_dispatch.hpp"
+#include "sw2d_dispatch.hpp"
 
 #ifndef BDG_ORDER
 #error "compile with -DBDG_ORDER=N"

@@ -10,8 +10,9 @@ top of every vector kernel takes its `xcd < r8` branch both ways), K % 64 = 26 a
 matrix-core tile). Each case runs in the mesh's element order (KEEP_ORDER) and renumbered (REORDER: the face links through the
 permutation).
 
-Which kernel a pinned BDG_SW2D_AFFINE_VARIANT runs (sw2d_order.hip: stageAffine, launchAffine, launchStream; sw2d_device.hip:
-launchStage). A pinned variant bypasses the small-launch crossover. "split" is the rolled field-split kernel
+Which kernel a pinned BDG_SW2D_AFFINE_VARIANT runs (the numbers are the values of AffineVariant in sw2d_launch.hpp; sw2d_order.hip:
+stageAffine with launchAffine, launchStream and launchRolled; sw2d_device.hip: launchStage, which takes 5, 6 and 7 to stageMfma,
+stageMfma2 and stageMfma3). A pinned variant bypasses the small-launch crossover. "split" is the rolled field-split kernel
 (sw2d_stage_affine_rolled_kernel, FIELDS = 1, one field per wave); "unrolled" is sw2d_stage_affine_kernel (LSERK at N <= 4: the
 face-link FIRST / MID / LAST instances; combine with a sponge: the SPONGE instance).
 
