@@ -434,7 +434,10 @@ template <int MODE>
 hipError_t launchVb(const StageParams& p, const VbParams& vp, double* partials, double* lam, bool speedPass, VbStage then,
                     const double* filterT, hipStream_t stream) {
     if (emptyRange(p)) return hipSuccess;
-    if (speedPass) launchSpeed(sw2d_vb_speed_kernel<kN>, p, vp, partials, lam, stream);
+    // (a solver on per-node geometry has no affine table: its speed alone is asked for here by the partitioned steppers,
+    // and comes from the kernel its own stage launches run in front of them, launchVn)
+    if (speedPass && p.ageo) launchSpeed(sw2d_vb_speed_kernel<kN>, p, vp, partials, lam, stream);
+    else if (speedPass) launchSpeed(sw2d_vn_speed_kernel<kN>, p, vp, partials, lam, stream);
     if (then == VbStage::None) return hipGetLastError();
     if constexpr (!kNoUnrolledSources) {
         if (then == VbStage::Unrolled) {

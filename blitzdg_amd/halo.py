@@ -264,10 +264,11 @@ class NativeDistributedSw2d:
     stage loops issued by one C call (no per-stage Python). PyTorch is not involved."""
 
     def __init__(self, plan, order, g=9.81, device=0, unique_id=None, loopback=False, filter_args=None, fields=3,
-                 sources=None):
+                 sources=None, flags=0):
         """loopback=True: schedule rehearsal on ONE GPU -- this process computes `plan.rank`'s share
         of a `plan.world`-way split, and every neighbour exchange is a send-to-self of the same size
-        (ghost values are then not the neighbours' -- timing only, never results)."""
+        (ghost values are then not the neighbours' -- timing only, never results). flags: Sw2dSolver's
+        (NODAL_GEOMETRY), OR-ed with KEEP_ORDER, which a partition needs."""
         from . import pyblitzdg as dg
         from . import sw2d
         from ._capi import byref, c_double, check, lib
@@ -279,14 +280,15 @@ class NativeDistributedSw2d:
         if filter_args is not None:
             self.nodes.buildFilter(*filter_args)
         # fields = 4 / sources: variants C / D (tracer; Coriolis, drag, bed slope), sources as a function
-        # (x, y) -> dict(zx=, zy=, f=, CD=) of the rank-local coordinates
+        # (x, y) -> dict(zx=, zy=, f=, CD=) of the rank-local coordinates, or that dict; fields = 4 without sources is
+        # the tracer-only solver
+        flags = int(flags) | sw2d.KEEP_ORDER
         if fields == 4 or sources is not None:
             ctx = self.nodes.dgContext()
-            src = sources(ctx.x, ctx.y) if callable(sources) else (sources or {"f": 0.0, "CD": 0.0})
-            self.solver = sw2d.Sw2dSolver(nodes=self.nodes, g=g, device=device, flags=sw2d.KEEP_ORDER, fields=fields,
-                                          sources=src)
+            src = sources(ctx.x, ctx.y) if callable(sources) else sources
+            self.solver = sw2d.Sw2dSolver(nodes=self.nodes, g=g, device=device, flags=flags, fields=fields, sources=src)
         else:
-            self.solver = sw2d.Sw2dSolver(nodes=self.nodes, g=g, device=device, flags=sw2d.KEEP_ORDER)
+            self.solver = sw2d.Sw2dSolver(nodes=self.nodes, g=g, device=device, flags=flags)
         self.Np = self.solver.Np
         attach_native(self.solver._h, "bdg_sw2d", plan, unique_id, loopback)
         self.global_elements = None
@@ -339,7 +341,8 @@ class NativeDistributedSw2d:
     def enable_variant_b(self, fields_fn, **kwargs):
         """Variant B on this rank's part: fields_fn(x, y) -> H of the rank-local nodes (owned and ghost elements);
         bed slopes from this rank's operators, open boundary = this rank's BCmap[2] (owned elements keep the global
-        mesh's tags). kwargs: CD, f, tide*, as Sw2dSolver.enableVariantB."""
+        mesh's tags). kwargs: CD, f, tide*, sponge (the coefficient array on the rank-local nodes), as
+        Sw2dSolver.enableVariantB."""
         ctx = self.nodes.dgContext()
         H = fields_fn(ctx.x, ctx.y)
         Hx, Hy = self.nodes.bedSlopes(H)

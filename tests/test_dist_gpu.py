@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import launch, launch_group, launch_ranks
+from partition_cases import B_KW, B_TIME, b_state as _b_state, bed as _bed, open_left_edge as _open_left_edge
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -405,23 +406,7 @@ def test_native_multi_process_path_matches_single_domain(tmp_path, world, order,
 # ---- variants B and D partitioned: one process per rank, the library's own communicator; variant B's global speed is
 # ---- one ncclAllReduce(max) per RHS evaluation on the solver's stream
 
-def _open_left_edge(mesh):
-    verts = np.asarray(mesh.vertices).reshape(-1, 3)
-    etov = np.asarray(mesh.elements).reshape(-1, 3)
-    bc = np.asarray(mesh.bcType).reshape(-1, 3).copy()
-    xmin = verts[:, 0].min()
-    for f, (a, b) in enumerate(((0, 1), (1, 2), (2, 0))):
-        left = (np.abs(verts[etov[:, a], 0] - xmin) < 1e-12) & (np.abs(verts[etov[:, b], 0] - xmin) < 1e-12)
-        bc[left & (bc[:, f] == 3), f] = 2
-    mesh.setBCType(bc)
-
-
-def _bed(x, y):
-    return 12.0 + 1.5 * x - 0.8 * y * y + 0.3 * np.sin(3 * x) * np.cos(2 * y)
-
-
-def _b_state(x, y):
-    return _bed(x, y) + 0.4 * np.exp(-6 * x * x - 6 * y * y), 0.8 * np.sin(3 * x + 1) * np.cos(2 * y), 0.8 * np.cos(2 * x - y)
+# (the open left side, the bed and the state of the variant-B cases: tests/partition_cases.py, which steps them too)
 
 
 def _d_state(x, y):
@@ -433,8 +418,6 @@ def _d_sources(x, y):
     return {"zx": -0.5 + 0 * x, "zy": 0.5 * y, "f": 1e-1 * (1.0 + 0.5 * y), "CD": 2.5e-2}
 
 
-B_KW = dict(CD=2.5e-3, f=1.0070e-4)
-B_TIME = 0.37 * 3600 * 12.42
 VARIANT_MESH = (26, 18)
 
 

@@ -246,39 +246,20 @@ def _reference4(order, kind):
     """NumPy replay (oracle_np.sw2d_rhs4) of RK2 +- filter and SSP-RK2 +- filter with the sponge on the ragged mesh, once per
     (order, solver kind), shared by the source switches."""
     from oracle.oracle_np import sw2d_rhs4
+    from partition_cases import filtered, four_field_problem, replay_rk2, replay_ssprk2
     if (order, kind) in _REF4:
         return _REF4[order, kind]
     _, t, o = _ragged(order)
-    x, y = t["x"], t["y"]
-    h, hu, hv = _amplified(seeded_fields(x, y, seed=order + 200))
-    q0 = (h, hu, hv, h * (0.5 + 0.3 * np.sin(2 * x + 0.5) * np.cos(3 * y)))
-    g = 9.81
-    if kind == "tracer":
-        src, zx, zy, f, CD = None, np.zeros_like(x), np.zeros_like(x), 0.0, 0.0
-    else:
-        zx, zy = 0.2 * np.cos(2 * x) * np.sin(y + 0.3), -0.15 * np.sin(3 * y) * np.cos(x)
-        f, CD = 0.3 * (1.0 + 0.5 * y), 2.5e-3
-        src = {"zx": zx, "zy": zy, "f": f, "CD": CD}
-    F = t["Filter"]
-
-    def rhs(q, filt):
-        r = sw2d_rhs4(*q, zx, zy, g, f, CD, t)
-        return [F @ a for a in r] if filt else list(r)
-
-    def relax(q, sp):
-        return [q[0], q[1] / (1.0 + sp * q[1] * q[1]), q[2] / (1.0 + sp * q[2] * q[2]), q[3]]
+    q0, src, args = four_field_problem(t, order, kind)       # the state, sources and (zx, zy, g, f, CD) the partitioned cases step too
+    h, hu, hv = q0[:3]
+    plain = lambda q: list(sw2d_rhs4(*q, *args, t))          # noqa: E731
+    rhs = {False: plain, True: filtered(plain, t["Filter"])}
 
     def rk2(q, dt, n, filt):
-        for _ in range(n):
-            q1 = [a + 0.5 * dt * b for a, b in zip(q, rhs(q, filt))]
-            q = [a + dt * b for a, b in zip(q, rhs(q1, filt))]
-        return q
+        return replay_rk2(rhs[filt], q, dt, n)
 
     def ssp(q, dt, n, filt, sp):
-        for _ in range(n):
-            q1 = relax([a + dt * b for a, b in zip(q, rhs(q, filt))], sp)
-            q = relax([0.5 * (a + b + dt * c) for a, b, c in zip(q, q1, rhs(q1, filt))], sp)
-        return q
+        return replay_ssprk2(rhs[filt], q, dt, n, sp)
 
     dt = 0.3 * o.dt(h, hu, hv, CFL, order)
     r = {"q0": q0, "dt": dt, "src": src}
