@@ -84,6 +84,11 @@ class Sw2dqMonitorDesc(Structure):
                 ("gauge_r", c_void_p), ("gauge_s", c_void_p), ("stride", c_int), ("capacity", c_int)]
 
 
+class Sw2dMonitorDesc(Structure):
+    _fields_ = [("weights", c_void_p), ("H", c_void_p), ("num_gauges", c_int), ("gauge_element", c_void_p),
+                ("gauge_row", c_void_p), ("stride", c_int), ("capacity", c_int)]
+
+
 class Sw2dqDrifterDesc(Structure):
     _fields_ = [("count", c_int), ("element", c_void_p), ("r", c_void_p), ("s", c_void_p), ("bilinear", c_void_p),
                 ("neighbours", c_void_p), ("bary", c_void_p), ("stride", c_int), ("capacity", c_int)]
@@ -300,6 +305,17 @@ _SIGNATURES = {
     "bdg_element_order_wanted": (c_int, [_P, c_int, c_int]),
     "bdg_sw2d_device_bytes": (c_size_t, [_P]),
     "bdg_sw2d_stream": (c_void_p, [_P]),
+    "bdg_trinodes_quadrature_weights": (c_int, [_P, _P]),
+    "bdg_trinodes_locate_points": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),
+    "bdg_trinodes_interpolation_rows": (c_int, [_P, _P, _P, c_int, _P]),
+    "bdg_sw2d_enable_monitor": (c_int, [_P, POINTER(Sw2dMonitorDesc)]),
+    "bdg_sw2d_monitor_sample": (c_int, [_P]),
+    "bdg_sw2d_monitor_count": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2d_monitor_read": (c_int, [_P, c_int, c_int, _P]),
+    "bdg_sw2d_monitor_width": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2d_monitor_reset": (c_int, [_P]),
+    "bdg_sw2d_monitor_reduce": (c_int, [_P]),
+    "bdg_sw2d_monitor_time": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_sw2d_curved_create": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(_P)]),
     "bdg_sw2d_curved_plan": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(c_int), c_int]),
     "bdg_sw2d_curved_destroy": (None, [_P]),

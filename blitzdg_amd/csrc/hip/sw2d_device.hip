@@ -12,6 +12,7 @@
 //   ops         Dr|Ds interleaved, Lift, Filter (copied to LDS by every workgroup)
 // Elements may be renumbered internally (BDG_SW2D_REORDER); all I/O is in the
 // caller's numbering.
+// After bdg_sw2d_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 #include "../host/capi_internal.hpp"
 #include "../host/element_order.hpp"
 #include "../host/parallel_for.hpp"
@@ -19,6 +20,7 @@
 #include "halo_transport.hpp"
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
+#include "sw2d_monitor_kernel.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -293,6 +295,16 @@ struct bdg_sw2d {
     long long stageCount = 0; // LSERK stage counter (stage index = count % 5)
     double dtStage = 0.0;
     std::vector<int> permHost; // caller element -> device slot (empty = identity)
+    // run monitor (bdg_sw2d_enable_monitor): sw2d_monitor_kernel.hpp
+    struct Monitor {
+        bool on = false;
+        int stride = 1, capacity = 0, numGauges = 0, width = 0;
+        int count = 0;        // records taken
+        int reduced = 0;      // records [0, reduced) have been all-reduced
+        long long steps = 0;  // completed steps since set_state / monitor_reset
+        DevBuf<double> w, H, row, partials, rec, stage, scratch;
+        DevBuf<int> slot;     // device slot of each gauge's element
+    } mon;
 
     ~bdg_sw2d() {
         for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evPacked[0], evPacked[1], evCopied[0], evCopied[1]})
@@ -343,6 +355,7 @@ struct bdg_sw2d {
         uploadFields(f, qcur);
         hipCheck(hipMemsetAsync(res.p, 0, res.n * sizeof(double), stream), "hipMemset");
         stageCount = 0;
+        mon.steps = 0;
         lamStateFor = nullptr; // a speed accumulated for the previous contents of this buffer is void
         hipCheck(hipStreamSynchronize(stream), "set_state sync");
     }
@@ -924,6 +937,71 @@ struct bdg_sw2d {
         filterT.upload(ft, bytes, "filter upload");
     }
 
+    // ---- run monitor
+    // records a stepping call of `steps` further completed steps would take; refused before anything is launched
+    void monitorReserve(long long steps, const char* fn) const {
+        if (!mon.on) return;
+        const long long take = (mon.steps + steps) / mon.stride - mon.steps / mon.stride;
+        if (take > mon.capacity - mon.count)
+            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " monitor records and " +
+                            std::to_string(mon.capacity - mon.count) + " are free (bdg_sw2d_monitor_read, then bdg_sw2d_monitor_reset)");
+    }
+    // completed LSERK4 steps among the next `stages` stages
+    long long lserkSteps(long long stages) const {
+        return (stageCount + stages) / blitzdg::LSERK4::numStages - stageCount / blitzdg::LSERK4::numStages;
+    }
+    // one record of the resident state into rec[column * capacity + slot], two launches on the solver's stream. The range
+    // reduced is the owned device slots [0, numOwned); H: the monitor's own, else the solver's resident one, else none
+    void monitorLaunch(double* rec, int capacity, int slot) {
+        using namespace bdg_dev;
+        const double* Hm = mon.H.p ? mon.H.p : (hasH ? Hbuf.p : nullptr);
+        const TriMonParams rp{qcur, mon.w.p, Hm, ld, Np, nf, numOwned, triMonChunk(numOwned), g};
+        hipLaunchKernelGGL(sw2d_monitor_reduce_kernel, dim3(kTriMonBlocks), dim3(kTriMonThreads), 0, stream, rp, mon.partials.p);
+        hipCheck(hipGetLastError(), "sw2d_monitor_reduce_kernel launch");
+        const TriMonFinish fp{mon.partials.p, qcur, Hm, mon.slot.p, mon.row.p, rec, ld, Np, nf, numOwned, mon.numGauges, capacity,
+                              slot, timeNow};
+        hipLaunchKernelGGL(sw2d_monitor_finish_kernel, dim3(1), dim3(kTriMonThreads), 0, stream, fp);
+        hipCheck(hipGetLastError(), "sw2d_monitor_finish_kernel launch");
+    }
+    void monitorSample() {
+        monitorLaunch(mon.rec.p, mon.capacity, mon.count);
+        ++mon.count;
+    }
+    // after every completed step of a stepping call whose launches are all on the solver's stream (room was reserved by the caller)
+    void stepDone() {
+        if (mon.on && ++mon.steps % mon.stride == 0) monitorSample();
+    }
+    // `numStages` LSERK4 stages on the whole mesh, a record after every stride-th completed step
+    void lserkStagesMonitored(int numStages) {
+        for (int i = 0; i < numStages; ++i) {
+            launchLserkStage();
+            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone();
+        }
+    }
+    // ... of a partitioned run. The two-chain schedule is issued in pieces that end where a record is due: a piece starts
+    // behind everything queued on the solver's stream (the sample) and ends with that stream behind its last boundary launch
+    void lserkStagesExchangedMonitored(double dt, int numStages) {
+        if (!mon.on) {
+            launchLserkStagesExchanged(dt, numStages);
+            return;
+        }
+        int left = numStages;
+        while (left > 0) {
+            // stages up to and including the one that completes the next step at which a record is due
+            const int toStep = blitzdg::LSERK4::numStages - static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
+            const long long stepsToDue = mon.stride - mon.steps % mon.stride;
+            const long long want = toStep + (stepsToDue - 1) * blitzdg::LSERK4::numStages;
+            const int piece = static_cast<int>(std::min<long long>(left, want));
+            const long long done = lserkSteps(piece);
+            launchLserkStagesExchanged(dt, piece);
+            left -= piece;
+            if (done > 0) {
+                mon.steps += done - 1;
+                stepDone();
+            }
+        }
+    }
+
     // Returns {max |Fscale|*spd, max |eta|}; NaN if any entry is NaN.
     void reduceDt(double out[2]) {
         const int nblocks = (numOwned + 255) / 256;
@@ -1332,8 +1410,12 @@ int stepCall(bdg_sw2d* s, const char* fn, int num_steps, Step&& step) {
     return guard([&] {
         requireSolver(s, fn);
         if (num_steps < 0) throw arg_error(std::string(fn) + ": num_steps < 0");
+        s->monitorReserve(num_steps, fn);
         s->use();
-        for (int i = 0; i < num_steps; ++i) step();
+        for (int i = 0; i < num_steps; ++i) {
+            step();
+            s->stepDone();
+        }
     });
 }
 
@@ -1560,9 +1642,10 @@ int bdg_sw2d_lserk4_stages(bdg_sw2d* s, double dt, int num_stages) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_lserk4_stages");
         if (num_stages < 0) throw arg_error("bdg_sw2d_lserk4_stages: num_stages < 0");
+        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2d_lserk4_stages");
         s->use();
         s->dtStage = dt;
-        for (int i = 0; i < num_stages; ++i) s->launchLserkStage();
+        s->lserkStagesMonitored(num_stages);
     });
 }
 
@@ -1572,9 +1655,10 @@ int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps) {
         if (num_steps < 0) throw arg_error("bdg_sw2d_step_lserk4: num_steps < 0");
         if (s->stageCount % blitzdg::LSERK4::numStages != 0)
             throw arg_error("bdg_sw2d_step_lserk4: a previous step was left part-way through its stages");
+        s->monitorReserve(num_steps, "bdg_sw2d_step_lserk4");
         s->use();
         s->dtStage = dt;
-        for (int i = 0; i < num_steps * blitzdg::LSERK4::numStages; ++i) s->launchLserkStage();
+        s->lserkStagesMonitored(num_steps * blitzdg::LSERK4::numStages);
     });
 }
 
@@ -1619,7 +1703,10 @@ int bdg_sw2d_run_adaptive(bdg_sw2d* s, double cfl, double final_time, int max_st
         s->use();
         double t = *t_inout, dt = *dt_inout;
         while (t < final_time && (max_steps <= 0 || done < max_steps)) {
+            // the number of steps is not known in advance: room for this step's record is checked before the step is launched
+            s->monitorReserve(1, "bdg_sw2d_run_adaptive");
             s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole);
+            s->stepDone();
             double r[2];
             s->reduceDt(r);
             if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
@@ -1938,8 +2025,9 @@ int bdg_sw2d_lserk4_stages_exchanged(bdg_sw2d* s, double dt, int num_stages) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_lserk4_stages_exchanged");
         if (num_stages < 0) throw arg_error("bdg_sw2d_lserk4_stages_exchanged: num_stages < 0");
+        s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2d_lserk4_stages_exchanged");
         s->use();
-        s->launchLserkStagesExchanged(dt, num_stages);
+        s->lserkStagesExchangedMonitored(dt, num_stages);
     });
 }
 
@@ -1991,6 +2079,151 @@ int bdg_sw2d_barrier(bdg_sw2d* s) {
         hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize");
         if (mine) throw std::runtime_error(bdg_sw2d::syncErrorText());
         if (any != 0.0) throw std::runtime_error(std::string("on another rank: ") + bdg_sw2d::syncErrorText());
+    });
+}
+
+// ---- run monitor
+int bdg_sw2d_enable_monitor(bdg_sw2d* s, const bdg_sw2d_monitor_desc* d) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2d_enable_monitor");
+        if (!d || !d->weights) throw arg_error("bdg_sw2d_enable_monitor: the descriptor and its weights are required");
+        if (s->mon.on) throw arg_error("bdg_sw2d_enable_monitor: the monitor is already enabled");
+        if (d->stride < 1 || d->capacity < 1) throw arg_error("bdg_sw2d_enable_monitor: stride and capacity must be >= 1");
+        const int ng = d->num_gauges, Np = s->Np;
+        if (ng < 0 || (ng > 0 && (!d->gauge_element || !d->gauge_row))) throw arg_error("bdg_sw2d_enable_monitor: bad gauge list");
+        // the gauges' elements in device slots (the caller's numbering through the renumbering, if there is one)
+        std::vector<int> slots(static_cast<size_t>(std::max(1, ng)), 0);
+        for (int i = 0; i < ng; ++i) {
+            const int e = d->gauge_element[i];
+            if (e < 0 || e >= s->K)
+                throw arg_error("bdg_sw2d_enable_monitor: gauge " + std::to_string(i) + " names an element outside [0, K)");
+            slots[i] = s->permHost.empty() ? e : s->permHost[e];
+        }
+        const int width = 7 + s->nf + ng * s->nf;
+        s->use();
+        bdg_sw2d::Monitor& m = s->mon;
+        const size_t bytesBefore = s->bytes;
+        try {
+            // the weight plane (and H) zero-padded and through the solver's own upload, so that they follow the renumbering
+            s->uploadPlane(d->weights, m.w);
+            if (d->H) s->uploadPlane(d->H, m.H);
+            m.row.alloc(static_cast<size_t>(std::max(1, ng)) * Np, s->bytes, s->stream);
+            m.slot.alloc(slots.size(), s->bytes, s->stream);
+            if (ng > 0) {
+                hipCheck(hipMemcpyAsync(m.row.p, d->gauge_row, static_cast<size_t>(ng) * Np * sizeof(double), hipMemcpyHostToDevice,
+                                        s->stream), "hipMemcpy (gauge rows)");
+                hipCheck(hipMemcpyAsync(m.slot.p, slots.data(), static_cast<size_t>(ng) * sizeof(int), hipMemcpyHostToDevice, s->stream),
+                         "hipMemcpy (gauges)");
+            }
+            m.partials.alloc(static_cast<size_t>(bdg_dev::kTriMonBlocks) * bdg_dev::kTriMonPartial, s->bytes, s->stream);
+            m.rec.alloc(static_cast<size_t>(width) * d->capacity, s->bytes, s->stream);
+            m.scratch.alloc(static_cast<size_t>(width), s->bytes, s->stream); // the record bdg_sw2d_monitor_time writes
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vector dies here
+        } catch (...) { // nothing changes: the solver stays without a monitor
+            (void)hipStreamSynchronize(s->stream);
+            for (DevBuf<double>* b : {&m.w, &m.H, &m.row, &m.partials, &m.rec, &m.scratch}) b->release();
+            m.slot.release();
+            s->bytes = bytesBefore;
+            throw;
+        }
+        m.on = true;
+        m.stride = d->stride; m.capacity = d->capacity; m.numGauges = ng; m.width = width;
+    });
+}
+
+namespace {
+void requireMonitorOn(const bdg_sw2d* s, const char* fn) {
+    requireSolver(s, fn);
+    if (!s->mon.on) throw arg_error(std::string(fn) + ": the monitor is not enabled (bdg_sw2d_enable_monitor)");
+}
+} // namespace
+
+int bdg_sw2d_monitor_sample(bdg_sw2d* s) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_sample");
+        if (s->mon.count >= s->mon.capacity) throw arg_error("bdg_sw2d_monitor_sample: no free record (bdg_sw2d_monitor_reset)");
+        s->use();
+        s->monitorSample();
+    });
+}
+
+int bdg_sw2d_monitor_count(const bdg_sw2d* s, int* n) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_count");
+        if (!n) throw arg_error("bdg_sw2d_monitor_count: NULL argument");
+        *n = s->mon.count;
+    });
+}
+
+int bdg_sw2d_monitor_width(const bdg_sw2d* s, int* width) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_width");
+        if (!width) throw arg_error("bdg_sw2d_monitor_width: NULL argument");
+        *width = s->mon.width;
+    });
+}
+
+int bdg_sw2d_monitor_read(bdg_sw2d* s, int first, int count, double* records) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_read");
+        if (first < 0 || count < 0 || first > s->mon.count - count || (count > 0 && !records))
+            throw arg_error("bdg_sw2d_monitor_read: bad record range");
+        if (count == 0) return;
+        s->use();
+        const int width = s->mon.width;
+        std::vector<double> cols(static_cast<size_t>(width) * count); // by column, as on the device
+        hipCheck(hipMemcpy2DAsync(cols.data(), count * sizeof(double), s->mon.rec.p + first, s->mon.capacity * sizeof(double),
+                                  count * sizeof(double), width, hipMemcpyDeviceToHost, s->stream), "hipMemcpy2D (records)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        for (int n = 0; n < count; ++n)
+            for (int c = 0; c < width; ++c) records[static_cast<size_t>(n) * width + c] = cols[static_cast<size_t>(c) * count + n];
+    });
+}
+
+int bdg_sw2d_monitor_reset(bdg_sw2d* s) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_reset");
+        s->mon.count = 0;
+        s->mon.reduced = 0;
+        s->mon.steps = 0;
+    });
+}
+
+int bdg_sw2d_monitor_reduce(bdg_sw2d* s) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_reduce");
+        if (!s->halo.comm) throw arg_error("bdg_sw2d_monitor_reduce: no communicator: call bdg_sw2d_comm_init first");
+        bdg_sw2d::Monitor& m = s->mon;
+        const int n = m.count - m.reduced;
+        if (n <= 0) return;
+        s->use();
+        // the new records of every column but t, packed by column; the columns that share an operator are contiguous
+        const int cols = m.width - 1, nf = s->nf;
+        if (!m.stage.p) m.stage.alloc(static_cast<size_t>(cols) * m.capacity, s->bytes);
+        hipCheck(hipMemcpy2DAsync(m.stage.p, n * sizeof(double), m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double),
+                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
+        auto reduce = [&](int firstCol, int numCols, ncclRedOp_t op) {
+            if (numCols <= 0) return;
+            double* at = m.stage.p + static_cast<size_t>(firstCol) * n;
+            ncclCheck(rccl().AllReduce(at, at, static_cast<size_t>(numCols) * n, ncclDouble, op, s->halo.comm, s->stream), "ncclAllReduce");
+        };
+        reduce(0, nf + 1, ncclSum);                 // integrals and E
+        reduce(nf + 1, 1, ncclMin);                 // min h
+        reduce(nf + 2, 3, ncclMax);                 // max h, max|hu|, max|hv|
+        reduce(nf + 5, cols - (nf + 5), ncclSum);   // NaN count and gauges
+        hipCheck(hipMemcpy2DAsync(m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double), m.stage.p, n * sizeof(double),
+                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
+        m.reduced = m.count;
+    });
+}
+
+int bdg_sw2d_monitor_time(bdg_sw2d* s, int count, float* ms) {
+    return guard([&] {
+        requireMonitorOn(s, "bdg_sw2d_monitor_time");
+        if (count < 1 || !ms) throw arg_error("bdg_sw2d_monitor_time: bad argument");
+        s->use();
+        s->monitorLaunch(s->mon.scratch.p, 1, 0); // once before the clock starts
+        *ms = bdg_dev::timePerRun(s->stream, count, [&] { s->monitorLaunch(s->mon.scratch.p, 1, 0); });
     });
 }
 

@@ -388,6 +388,33 @@ int bdg_quadnodes_lagrange_basis(const bdg_quadnodes* nodes, const double* r, in
     });
 }
 
+// ---- the same set-up for the triangle solver's monitor (bdg_sw2d_enable_monitor): weights, point location, interpolation rows
+int bdg_trinodes_quadrature_weights(const bdg_trinodes* nodes, double* w) {
+    return guard([&] {
+        if (!nodes || !w) throw bdg_detail::arg_error("bdg_trinodes_quadrature_weights: NULL argument");
+        real_matrix_type m;
+        nodes->prov.quadratureWeights(m);
+        std::copy(m.data(), m.data() + static_cast<size_t>(m.rows()) * m.cols(), w);
+    });
+}
+
+int bdg_trinodes_locate_points(const bdg_trinodes* nodes, const double* x, const double* y, int n, int* element, double* r,
+                               double* s) {
+    return guard([&] {
+        if (!nodes || n < 0 || (n > 0 && (!x || !y || !element || !r || !s)))
+            throw bdg_detail::arg_error("bdg_trinodes_locate_points: bad argument");
+        nodes->prov.locatePoints(x, y, n, element, r, s);
+    });
+}
+
+int bdg_trinodes_interpolation_rows(const bdg_trinodes* nodes, const double* r, const double* s, int n, double* rows) {
+    return guard([&] {
+        if (!nodes || n < 0 || (n > 0 && (!r || !s || !rows)))
+            throw bdg_detail::arg_error("bdg_trinodes_interpolation_rows: bad argument");
+        nodes->prov.interpolationRows(r, s, n, rows);
+    });
+}
+
 // ---- set-up of the drifters (bdg_sw2dq_enable_drifters): bilinear map, neighbour table, barycentric weights
 int bdg_quadnodes_drifter_tables(const bdg_quadnodes* nodes, const int* mapO, int num_out, double* bilinear, int* neighbours,
                                  double* bary) {

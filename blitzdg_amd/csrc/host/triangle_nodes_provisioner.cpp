@@ -571,6 +571,158 @@ void TriangleNodesProvisioner::splitElements(const real_matrix_type& x, const re
             }
 }
 
+// ---------------------------------------------------------------- run monitor set-up
+
+void TriangleNodesProvisioner::quadratureWeights(real_matrix_type& w) const {
+    const index_type Np = NumLocalPoints, K = NumElements;
+    // m[n] = sum_i (Vinv^T Vinv)(i, n) = sum_k (sum_i Vinv(k, i)) Vinv(k, n)
+    std::vector<long double> rowSum(Np, 0.0L);
+    for (index_type k = 0; k < Np; ++k)
+        for (index_type i = 0; i < Np; ++i) rowSum[k] += static_cast<long double>(Vinv(k, i));
+    std::vector<real_type> m(Np);
+    for (index_type n = 0; n < Np; ++n) {
+        long double acc = 0.0L;
+        for (index_type k = 0; k < Np; ++k) acc += rowSum[k] * static_cast<long double>(Vinv(k, n));
+        m[n] = static_cast<real_type>(acc);
+    }
+    w.resizeUninitialized(Np, K);
+    for (index_type n = 0; n < Np; ++n)
+        for (index_type k = 0; k < K; ++k) w(n, k) = m[n] * J(n, k);
+}
+
+void TriangleNodesProvisioner::interpolationRows(const real_type* r, const real_type* s, index_type n, real_type* rows) const {
+    const index_type Np = NumLocalPoints;
+    real_vector_type rp(1), sp(1);
+    real_matrix_type P(1, Np);
+    for (index_type p = 0; p < n; ++p) {
+        real_type* row = rows + static_cast<std::size_t>(p) * Np;
+        index_type node = -1;
+        for (index_type m = 0; m < Np && node < 0; ++m)
+            if (r[p] == rGrid(m) && s[p] == sGrid(m)) node = m;
+        if (node >= 0) { // on a node: the unit vector, exactly
+            for (index_type m = 0; m < Np; ++m) row[m] = m == node ? 1.0 : 0.0;
+            continue;
+        }
+        rp(0) = r[p];
+        sp(0) = s[p];
+        computeVandermondeMatrix(NOrder, rp, sp, P);
+        for (index_type m = 0; m < Np; ++m) {
+            long double acc = 0.0L;
+            for (index_type j = 0; j < Np; ++j) acc += static_cast<long double>(P(0, j)) * static_cast<long double>(Vinv(j, m));
+            row[m] = static_cast<real_type>(acc);
+        }
+    }
+}
+
+void TriangleNodesProvisioner::locatePoints(const real_type* px, const real_type* py, index_type n, index_type* element,
+                                            real_type* rOut, real_type* sOut) const {
+    if (n <= 0) return;
+    const index_type Np = NumLocalPoints, K = NumElements;
+    constexpr real_type edge = 1e-10;
+    // bounding boxes of the elements' nodes, widened by 1e-9 of their size
+    std::vector<real_type> box(static_cast<std::size_t>(4) * K);
+    detail::parallelFor(K, [&](index_type k) {
+        real_type x0 = xGrid(0, k), x1 = x0, y0 = yGrid(0, k), y1 = y0;
+        for (index_type m = 1; m < Np; ++m) {
+            x0 = std::min(x0, xGrid(m, k)); x1 = std::max(x1, xGrid(m, k));
+            y0 = std::min(y0, yGrid(m, k)); y1 = std::max(y1, yGrid(m, k));
+        }
+        const real_type pad = 1e-9 * std::max(x1 - x0, y1 - y0);
+        box[4 * k] = x0 - pad; box[4 * k + 1] = x1 + pad; box[4 * k + 2] = y0 - pad; box[4 * k + 3] = y1 + pad;
+    });
+    // a uniform grid of about K cells over the mesh; cell (ix, iy) lists, in ascending order, the elements whose box meets it.
+    // cellOf is monotone, so a point inside an element's box lies in a cell of that element's range
+    real_type X0 = box[0], X1 = box[1], Y0 = box[2], Y1 = box[3];
+    for (index_type k = 1; k < K; ++k) {
+        X0 = std::min(X0, box[4 * k]); X1 = std::max(X1, box[4 * k + 1]);
+        Y0 = std::min(Y0, box[4 * k + 2]); Y1 = std::max(Y1, box[4 * k + 3]);
+    }
+    const real_type W = std::max(X1 - X0, std::numeric_limits<real_type>::min()), H = std::max(Y1 - Y0, std::numeric_limits<real_type>::min());
+    const index_type gx = static_cast<index_type>(std::min<real_type>(4096, std::max<real_type>(1, std::ceil(std::sqrt(K * W / H)))));
+    const index_type gy = static_cast<index_type>(std::min<real_type>(4096, std::max<real_type>(1, std::ceil(static_cast<real_type>(K) / gx))));
+    auto cellOf = [](real_type v, real_type lo, real_type width, index_type cells) {
+        const real_type c = std::floor((v - lo) / width * cells);
+        return c < 0 ? 0 : (c >= cells ? cells - 1 : static_cast<index_type>(c));
+    };
+    std::vector<index_type> start(static_cast<std::size_t>(gx) * gy + 1, 0), list;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (index_type k = 0; k < K; ++k) {
+            const index_type ix0 = cellOf(box[4 * k], X0, W, gx), ix1 = cellOf(box[4 * k + 1], X0, W, gx);
+            const index_type iy0 = cellOf(box[4 * k + 2], Y0, H, gy), iy1 = cellOf(box[4 * k + 3], Y0, H, gy);
+            for (index_type iy = iy0; iy <= iy1; ++iy)
+                for (index_type ix = ix0; ix <= ix1; ++ix) {
+                    const std::size_t c = static_cast<std::size_t>(iy) * gx + ix;
+                    if (pass == 0) ++start[c + 1];
+                    else list[start[c]++] = k;
+                }
+        }
+        if (pass == 0) {
+            for (std::size_t c = 0; c + 1 < start.size(); ++c) start[c + 1] += start[c];
+            list.resize(start.back());
+        } else { // the fill moved every start to its cell's end: shift back
+            for (std::size_t c = start.size() - 1; c > 0; --c) start[c] = start[c - 1];
+            start[0] = 0;
+        }
+    }
+    detail::parallelChunks(n, [&](index_type pBegin, index_type pEnd) {
+        // modal coefficients of the element's nodal map (relative to its first node: the rounding is then that of the
+        // element's size, not of its distance from the origin), and the basis row with its derivatives at one point
+        std::vector<real_type> cx(Np), cy(Np);
+        real_vector_type rp(1), sp(1);
+        real_matrix_type P(1, Np), Pr(1, Np), Ps(1, Np);
+        for (index_type p = pBegin; p < pEnd; ++p) {
+            element[p] = -1;
+            rOut[p] = 0;
+            sOut[p] = 0;
+            if (!(px[p] >= X0 && px[p] <= X1 && py[p] >= Y0 && py[p] <= Y1)) continue;
+            const std::size_t c = static_cast<std::size_t>(cellOf(py[p], Y0, H, gy)) * gx + cellOf(px[p], X0, W, gx);
+            for (index_type at = start[c]; at < start[c + 1]; ++at) {
+                const index_type k = list[at];
+                if (px[p] < box[4 * k] || px[p] > box[4 * k + 1] || py[p] < box[4 * k + 2] || py[p] > box[4 * k + 3]) continue;
+                const real_type x0 = xGrid(0, k), y0 = yGrid(0, k);
+                for (index_type j = 0; j < Np; ++j) {
+                    real_type a = 0, b = 0;
+                    for (index_type m = 0; m < Np; ++m) {
+                        a += Vinv(j, m) * (xGrid(m, k) - x0);
+                        b += Vinv(j, m) * (yGrid(m, k) - y0);
+                    }
+                    cx[j] = a; cy[j] = b;
+                }
+                const real_type qx = px[p] - x0, qy = py[p] - y0;
+                real_type r = -1.0 / 3.0, s = -1.0 / 3.0;
+                bool converged = false;
+                for (int it = 0; it < 50 && !converged; ++it) {
+                    rp(0) = r;
+                    sp(0) = s;
+                    computeVandermondeMatrix(NOrder, rp, sp, P);
+                    computeGradVandermondeMatrix(NOrder, rp, sp, Pr, Ps);
+                    real_type x = 0, y = 0, xr = 0, xs = 0, yr = 0, ys = 0;
+                    for (index_type j = 0; j < Np; ++j) {
+                        x += P(0, j) * cx[j]; y += P(0, j) * cy[j];
+                        xr += Pr(0, j) * cx[j]; yr += Pr(0, j) * cy[j];
+                        xs += Ps(0, j) * cx[j]; ys += Ps(0, j) * cy[j];
+                    }
+                    const real_type det = xr * ys - xs * yr;
+                    if (!(std::fabs(det) > 0)) break;
+                    const real_type fx = qx - x, fy = qy - y;
+                    const real_type dr = (ys * fx - xs * fy) / det, ds = (xr * fy - yr * fx) / det;
+                    r += dr;
+                    s += ds;
+                    if (!(std::fabs(r) < 10 && std::fabs(s) < 10)) break; // the point is far outside this element
+                    // as QuadNodesProvisioner::locatePoints: a step of 1e-12 leaves an error at the rounding of the map
+                    converged = std::max(std::fabs(dr), std::fabs(ds)) <= 1e-12;
+                }
+                if (converged && r >= -1.0 - edge && s >= -1.0 - edge && r + s <= edge) {
+                    element[p] = k;
+                    rOut[p] = r;
+                    sOut[p] = s;
+                    break; // ascending k: the lowest element index wins
+                }
+            }
+        }
+    }, 8);
+}
+
 DGContext2D TriangleNodesProvisioner::get_DGContext() const {
     // The gather/scatter maps need a sort over all Np*K nodes and are not read by the
     // RHS path: built eagerly only for small meshes, otherwise on get_gather().

@@ -363,6 +363,38 @@ class NativeDistributedSw2d:
     def barrier(self):
         self._check(self._lib.bdg_sw2d_barrier(self.solver._h))
 
+    def enable_monitor(self, H=None, gauges=None, stride=1, capacity=4096, global_nodes=None):
+        """Sw2dSolver.enableMonitor on the partition: the integrals and extrema cover this rank's owned elements, and each
+        gauge is evaluated by the rank that owns its element while the other ranks' entries stay 0 until ``monitor_records``
+        adds them up. ``gauges`` is the same list on every rank, in the numbering of the global mesh: a tuple
+        (global element, r, s), or an (n, 2) array of x, y that is located on ``global_nodes``, a TriangleNodesProvisioner of
+        the global mesh (``locatePoints``: a point on a shared edge goes to the lowest global element, so exactly one rank
+        owns it). ``H`` on the rank-local nodes. A gauge in no element raises ValueError on every rank."""
+        from .sw2d import _locate
+        n_own = self.plan.num_owned
+        loc = None
+        if gauges is not None:
+            if isinstance(gauges, tuple):                    # global element numbers, which may be of another rank
+                gel, r, s = (np.asarray(a).reshape(-1) for a in gauges)
+                if (gel < 0).any():
+                    raise ValueError(f"gauges {np.nonzero(gel < 0)[0].tolist()} lie in no element of the mesh")
+            else:
+                gel, r, s = _locate(gauges, global_nodes, "gauges")
+            local = {int(g): i for i, g in enumerate(np.asarray(self.plan.own_global))}
+            # a gauge of another rank names a ghost column, which the device leaves at 0
+            el = np.array([local.get(int(g), n_own) for g in gel], dtype=np.int32)
+            mine = el < n_own
+            if (~mine).any() and self.solver.K <= n_own:
+                raise ValueError("a gauge belongs to another rank, but this rank has no ghost element to name for it")
+            loc = (el, np.where(mine, r, -1.0), np.where(mine, s, -1.0))
+        self.solver.enableMonitor(self.nodes, H=H, gauges=loc, stride=stride, capacity=capacity)
+
+    def monitor_records(self):
+        """Sw2dSolver.monitorRecords of the whole mesh (collective): the records not yet reduced are all-reduced on the
+        device (sums for the integrals, the NaN count and the gauges, min / max for the extrema), then read."""
+        self._check(self._lib.bdg_sw2d_monitor_reduce(self.solver._h))
+        return self.solver.monitorRecords()
+
     def owned_mass(self, fn=None):
         """Integral of h over this rank's owned elements (nodal quadrature with the mass matrix' row sums);
         of the resident state, or of ``fn(x, y)[0]`` when a state function is given."""

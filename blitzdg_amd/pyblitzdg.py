@@ -339,6 +339,37 @@ class TriangleNodesProvisioner:
         check(lib.bdg_trinodes_split_operators(self._h, C.ptr(IM), C.ptr(tri)))
         return IM, tri
 
+    def quadratureWeights(self):
+        """(Np, K) nodal quadrature weights m[n] J[n, k], m the column sums of the reference mass matrix Vinv^T Vinv: the sum
+        of ``w * f`` is the integral of the nodal field f, exact for f in P^N on a straight-sided element (what
+        ``Sw2dSolver.enableMonitor`` integrates with). J is the provisioner's current one."""
+        _, Np, _, K = self._dims()
+        w = np.empty((Np, K))
+        check(lib.bdg_trinodes_quadrature_weights(self._h, C.ptr(w)))
+        return w
+
+    def locatePoints(self, x, y):
+        """(element, r, s) of the points (x[p], y[p]): the element that contains each and its reference coordinates, by
+        Newton iteration on the element's nodal map (deformed coordinates after ``setCoordinates`` included). A point on a
+        shared edge or vertex goes to the lowest element index; a point in no element gets element -1."""
+        x, y = C.as_f64(x).reshape(-1), C.as_f64(y).reshape(-1)
+        if x.size != y.size:
+            raise ValueError("locatePoints: x and y must have the same length")
+        el, r, s = np.empty(x.size, dtype=np.int32), np.empty(x.size), np.empty(x.size)
+        check(lib.bdg_trinodes_locate_points(self._h, C.ptr(x), C.ptr(y), x.size, C.ptr(el), C.ptr(r), C.ptr(s)))
+        return el, r, s
+
+    def interpolationRows(self, r, s):
+        """(n, Np): the nodal Lagrange basis at the reference points (r[p], s[p]), P(r, s) Vinv with P the orthonormal basis
+        row (a point that equals a reference node bit for bit gives the exact unit vector). ``rows @ f[:, k]`` interpolates
+        the nodal field of element k."""
+        r, s = C.as_f64(r).reshape(-1), C.as_f64(s).reshape(-1)
+        if r.size != s.size:
+            raise ValueError("interpolationRows: r and s must have the same length")
+        out = np.empty((r.size, self._dims()[1]))
+        check(lib.bdg_trinodes_interpolation_rows(self._h, C.ptr(r), C.ptr(s), r.size, C.ptr(out)))
+        return out
+
     def setCoordinates(self, x, y):
         _, Np, _, K = self._dims()
         xa, ya = C.as_f64(x, (Np, K), "x"), C.as_f64(y, (Np, K), "y")

@@ -21,6 +21,25 @@ NODAL_GEOMETRY = C.BDG_SW2D_NODAL_GEOMETRY
 KEEP_ORDER = C.BDG_SW2D_KEEP_ORDER
 
 
+def _locate(points, nodes, noun):
+    """(element, r, s) of ``points``: a tuple of reference coordinates as it is, or an (n, 2) array of x, y located on the
+    TriangleNodesProvisioner ``nodes``. ``noun`` names them in the messages."""
+    if isinstance(points, tuple):
+        el, r, s = C.as_i32(points[0]).reshape(-1), C.as_f64(points[1]).reshape(-1), C.as_f64(points[2]).reshape(-1)
+        if not (el.size == r.size == s.size):
+            raise ValueError(f"{noun}: element, r and s must have the same length")
+        return el, r, s
+    xy = C.as_f64(points)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError(f"{noun}: expected an (n, 2) array of x, y")
+    if nodes is None:
+        raise ValueError(f"{noun} given as x, y need `global_nodes`, a TriangleNodesProvisioner of the global mesh")
+    el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
+    if (el < 0).any():
+        raise ValueError(f"{noun} {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
+    return el, r, s
+
+
 class Sw2dSolver:
     """Device-resident shallow-water DG solver (one HIP device, one stream)."""
 
@@ -215,6 +234,62 @@ class Sw2dSolver:
         """Average device milliseconds per fused stage launch (HIP events on the solver's stream)."""
         ms = c_float()
         check(lib.bdg_sw2d_time_lserk4_stages(self._h, float(dt), int(nstages), byref(ms)))
+        return ms.value
+
+    # ---- run monitor
+    def enableMonitor(self, nodes, H=None, gauges=None, stride=1, capacity=4096):
+        """Switches on the run monitor: from now on stepLSERK4, lserk4Stages (a step is the fifth stage), stepRK2, stepSSPRK2
+        and runAdaptive record the mass, momentum, tracer and energy integrals, min / max h, max|hu|, max|hv|, a NaN count and
+        the primitive fields at the ``gauges`` after every ``stride``-th completed step, on the device and without waiting
+        for it; ``capacity`` records are held there. ``nodes``: the TriangleNodesProvisioner of the solver's mesh (weights,
+        point location, interpolation rows). ``H``: (Np, K) still-water depth of eta = h - H and of the potential energy
+        (without one the solver's own is used, from setBathymetry or enableVariantB, else H = 0). ``gauges``: (n, 2) array of
+        x, y, located with ``nodes.locatePoints`` (a gauge in no element raises ValueError), or a tuple (element, r, s) of
+        reference coordinates, the elements in the caller's numbering. Once per solver."""
+        shape = (self.Np, self.K)
+        w = C.as_f64(nodes.quadratureWeights(), shape, "weights")
+        Hh = None if H is None else C.as_f64(H, shape, "H")
+        if gauges is None:
+            el, r, s = np.empty(0, np.int32), np.empty(0), np.empty(0)
+        else:
+            el, r, s = _locate(gauges, nodes, "gauges")
+        rows = C.as_f64(nodes.interpolationRows(r, s), (el.size, self.Np), "rows")
+        d = C.Sw2dMonitorDesc(C.ptr(w), C.ptr(Hh), el.size, C.ptr(el) if el.size else None, C.ptr(rows) if el.size else None,
+                              int(stride), int(capacity))
+        check(lib.bdg_sw2d_enable_monitor(self._h, byref(d)))
+        self.numGauges = int(el.size)
+
+    def sampleMonitor(self):
+        """One record of the resident state now (at the model time ``time``)."""
+        check(lib.bdg_sw2d_monitor_sample(self._h))
+
+    def resetMonitor(self):
+        """Drops the records held on the device and restarts the step count."""
+        check(lib.bdg_sw2d_monitor_reset(self._h))
+
+    def monitorRecordArray(self):
+        """The records as a (records, width) array in the layout of include/blitzdg_hip.h; waits for the solver's stream."""
+        n, width = c_int(), c_int()
+        check(lib.bdg_sw2d_monitor_count(self._h, byref(n)))
+        check(lib.bdg_sw2d_monitor_width(self._h, byref(width)))
+        out = np.empty((n.value, width.value))
+        check(lib.bdg_sw2d_monitor_read(self._h, 0, n.value, C.ptr(out)))
+        return out
+
+    def monitorRecords(self):
+        """The records taken so far as a dict of arrays, one entry per record: ``t``, ``mass``, ``momentum`` (records, 2),
+        ``tracer`` (zeros on three fields), ``energy``, ``hmin``, ``hmax``, ``humax``, ``hvmax``, ``nan`` and ``gauges``
+        (records, n, fields) holding eta, u, v (, N)."""
+        a, nf = self.monitorRecordArray(), self.fields
+        rec = {"t": a[:, 0], "mass": a[:, 1], "momentum": a[:, 2:4], "tracer": a[:, 4] if nf == 4 else np.zeros(len(a)),
+               "energy": a[:, nf + 1], "hmin": a[:, nf + 2], "hmax": a[:, nf + 3], "humax": a[:, nf + 4], "hvmax": a[:, nf + 5],
+               "nan": a[:, nf + 6], "gauges": a[:, nf + 7:].reshape(len(a), -1, nf)}
+        return {k: np.ascontiguousarray(v) for k, v in rec.items()}
+
+    def timeMonitor(self, count):
+        """Average device milliseconds of one monitor sample (both launches); takes no records."""
+        ms = c_float()
+        check(lib.bdg_sw2d_monitor_time(self._h, int(count), byref(ms)))
         return ms.value
 
     def probeStageTraffic(self, repeats=20):

@@ -80,6 +80,22 @@ public:
     /// ry, sx, sy of this provisioner are recomputed from the current node coordinates as a side effect.
     CubatureContext2D buildCubatureVolumeMesh(index_type NCubature);
 
+    // ---- set-up of the run monitor (bdg_sw2d_enable_monitor)
+    /// w (Np, K), w(n, k) = m[n] J(n, k), m the column sums of the reference mass matrix Vinv^T Vinv (summed in long double,
+    /// rounded once): sum w f is the integral of the nodal field f, exact for f in P^N on a straight-sided element. The J is
+    /// the provisioner's current one.
+    void quadratureWeights(real_matrix_type& w) const;
+    /// The element that contains each point (x[p], y[p]) and its reference coordinates, by Newton iteration on the element's
+    /// own nodal map (one step on straight-sided elements; deformed coordinates after setCoordinates work too). Inside:
+    /// r >= -1 - 1e-10, s >= -1 - 1e-10, r + s <= 1e-10. A point on a shared edge or vertex goes to the lowest element index,
+    /// a point in no element gets -1 (r = s = 0). Candidates come from a uniform grid over the elements' bounding boxes.
+    void locatePoints(const real_type* x, const real_type* y, index_type n, index_type* element, real_type* r,
+                      real_type* s) const;
+    /// rows (n, Np), rows[p, :] = P(r[p], s[p]) Vinv with P the orthonormal basis row of computeVandermondeMatrix (the product
+    /// summed in long double over ascending modes, rounded once): the values of the nodal Lagrange basis at the point. A point
+    /// that equals a reference node bit for bit gives the exact unit vector.
+    void interpolationRows(const real_type* r, const real_type* s, index_type n, real_type* rows) const;
+
     // ---- accessors
     const real_matrix_type& get_xGrid() const { return xGrid; }
     const real_matrix_type& get_yGrid() const { return yGrid; }

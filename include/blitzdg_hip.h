@@ -719,6 +719,72 @@ size_t bdg_sw2d_device_bytes(const bdg_sw2d* s);
 /* The raw stream (hipStream_t) launches are issued on, for callers that interleave their own work. */
 void* bdg_sw2d_stream(bdg_sw2d* s);
 
+/* ---- run monitor of the triangle solver: conservation diagnostics and gauges recorded on the device during the stepping
+ * calls, with no host round trip and no state download (csrc/hip/sw2d_monitor_kernel.hpp), the counterpart of the
+ * bdg_sw2dq_* group above with the same record layout. Host set-up, from a triangle provisioner (none of the three touches
+ * a GPU; BDG_ERR_ARGUMENT for a NULL handle or argument):
+ * quadrature_weights: w (Np, K), w[n, k] = m[n] J[n, k], m the column sums of the reference mass matrix Vinv^T Vinv (the
+ * provisioner's current J): sum w f is exact for f in P^N on a straight-sided element.
+ * locate_points: for each (x[p], y[p]) the element that contains it and its reference coordinates, by Newton iteration on
+ * the element's own nodal map (one step on straight-sided elements; deformed coordinates after set_coordinates work too);
+ * r >= -1 - 1e-10, s >= -1 - 1e-10, r + s <= 1e-10 counts as inside, a point on a shared edge or vertex goes to the lowest
+ * element index, a point in no element gets element -1 (r = s = 0). Candidates come from a uniform grid over the mesh.
+ * interpolation_rows: rows (n, Np), rows[p, :] = P(r[p], s[p]) Vinv, P the orthonormal basis row of the provisioner's
+ * Vandermonde matrix: the nodal Lagrange basis at the point, what the gauges interpolate with; a point that equals a
+ * reference node bit for bit gives the exact unit vector. */
+int bdg_trinodes_quadrature_weights(const bdg_trinodes* nodes, double* w);
+int bdg_trinodes_locate_points(const bdg_trinodes* nodes, const double* x, const double* y, int n, int* element, double* r,
+                               double* s);
+int bdg_trinodes_interpolation_rows(const bdg_trinodes* nodes, const double* r, const double* s, int n, double* rows);
+/* One record is `width` = 7 + fields + fields * num_gauges doubles:
+ *   t, int h, int hu, int hv, (int hN,) E, min h, max h, max|hu|, max|hv|, NaN count, then per gauge eta, u, v (, N)
+ * t = the model time (bdg_sw2d_get_time); E = int (hu^2 + hv^2) / (2h) + g (h - H)^2 / 2; the NaN count covers every
+ * field; eta = h - H, u = hu / h, v = hv / h, N = hN / h are formed at the nodes of the gauge's element exactly as
+ * bdg_sw2d_output_fields forms them and interpolated as sum_n row[n] f[n] over ascending n from 0.0, so a gauge on a node
+ * is that node's output value (IM = NULL) bit for bit. H: the descriptor's if given, else the solver's resident one
+ * (bdg_sw2d_set_bathymetry or variant B), else 0. The summation order of the integrals is fixed (a fixed grid, a fixed
+ * range of device slots per workgroup, each thread its elements and their nodes in ascending order with acc = acc + w f, an
+ * LDS tree, partials added in ascending order; no floating-point atomics): equal states give equal records bit for bit.
+ * A solver that renumbered its elements (bdg_sw2d_is_renumbered) sums in the order of its device slots: the weights are
+ * uploaded through the renumbering, and the records of a renumbered and a BDG_SW2D_KEEP_ORDER solver agree to the summation
+ * bound, not bit for bit. Gauge elements are given in the caller's numbering. Straight-sided solvers only
+ * (bdg_sw2d_curved has cubature weights and per-element mass matrices: no monitor). */
+typedef struct bdg_sw2d_monitor_desc {
+    const double* weights;      /* (Np, K), bdg_trinodes_quadrature_weights */
+    const double* H;            /* (Np, K) or NULL (the solver's resident H if it has one) */
+    int num_gauges;             /* may be 0 */
+    const int* gauge_element;   /* caller numbering, each in [0, K) */
+    const double* gauge_row;    /* (num_gauges, Np), bdg_trinodes_interpolation_rows */
+    int stride;                 /* sample after every stride-th completed step, >= 1 */
+    int capacity;               /* records held on the device, >= 1 */
+} bdg_sw2d_monitor_desc;
+/* Once per solver. BDG_ERR_ARGUMENT, changing nothing, for a NULL handle or descriptor or weights, a gauge list without
+ * elements or rows, a gauge element outside [0, K), stride < 1, capacity < 1, and a second call. From then on step_lserk4,
+ * lserk4_stages (a step is the fifth stage), step_rk2, step_ssprk2, run_adaptive and the _exchanged forms take a record
+ * after every stride-th completed step (counted over calls; set_state, set_state4 and monitor_reset restart the count),
+ * two launches on the solver's stream behind the step and no host wait. A stepping call that would take more records than
+ * the capacity has left returns BDG_ERR_ARGUMENT before it launches anything; run_adaptive, whose step count is not known in
+ * advance (with or without max_steps), checks before each step and stops with that error, steps_done telling the steps it
+ * made. lserk4_stage_part, group_lserk4_stages,
+ * time_lserk4_stages, probe_stage_traffic and the RHS calls take no records. Without this call no stepping call launches
+ * anything it did not launch before. */
+int bdg_sw2d_enable_monitor(bdg_sw2d* s, const bdg_sw2d_monitor_desc* desc);
+int bdg_sw2d_monitor_sample(bdg_sw2d* s);            /* one record of the resident state now */
+int bdg_sw2d_monitor_count(const bdg_sw2d* s, int* n);
+/* records [first, first + count) as count x width doubles; synchronises the solver's stream */
+int bdg_sw2d_monitor_read(bdg_sw2d* s, int first, int count, double* records);
+int bdg_sw2d_monitor_width(const bdg_sw2d* s, int* width);
+int bdg_sw2d_monitor_reset(bdg_sw2d* s);             /* count = 0, step counter = 0 */
+/* Partitioned runs: the reduction covers the owned elements, and a gauge whose element is a ghost (>= num_owned) is not
+ * evaluated, its entries stay 0: pass each gauge to the rank that owns its element and any ghost element to the others.
+ * monitor_reduce is the one collective (after comm_init): it all-reduces the stored records that no earlier call has
+ * reduced, in place on the solver's stream: sum for the integrals, E, the gauges and the NaN count, minimum / maximum for
+ * the extrema, t left alone. Call it once before reading, not per sample. */
+int bdg_sw2d_monitor_reduce(bdg_sw2d* s);
+/* Average device milliseconds of one sample (both launches), `count` of them bracketed by events on the solver's stream;
+ * takes no records (the launches write a scratch record). */
+int bdg_sw2d_monitor_time(bdg_sw2d* s, int count, float* ms);
+
 /* ---------------------------------------------------------------- sw2d, curved / over-integrated RHS
  * reference: swhelpers.rhs.sw2dComputeRHS_curved(h, hu, hv, hN, zx, zy, g, H, f, CD, ctx, cub_ctx, gauss_ctx,
  * curvedEls, J, gmapM, gmapP) (swhelpers/rhs.py:6-176), driven by sw2d_curved.py:246-277 (RHS, Filter, midpoint
