@@ -94,6 +94,11 @@ class Sw2dqDrifterDesc(Structure):
                 ("neighbours", c_void_p), ("bary", c_void_p), ("stride", c_int), ("capacity", c_int)]
 
 
+class Sw2dDrifterDesc(Structure):
+    _fields_ = [("count", c_int), ("element", c_void_p), ("r", c_void_p), ("s", c_void_p), ("vertices", c_void_p),
+                ("neighbours", c_void_p), ("vinv", c_void_p), ("jacobi", c_void_p), ("stride", c_int), ("capacity", c_int)]
+
+
 class Sw2dCurvedDesc(Structure):
     _fields_ = [("order", c_int), ("num_elements", c_int), ("num_cub", c_int), ("num_gauss", c_int),
                 ("V", c_void_p), ("Filter", c_void_p), ("J", c_void_p),
@@ -316,6 +321,14 @@ _SIGNATURES = {
     "bdg_sw2d_monitor_reset": (c_int, [_P]),
     "bdg_sw2d_monitor_reduce": (c_int, [_P]),
     "bdg_sw2d_monitor_time": (c_int, [_P, c_int, POINTER(c_float)]),
+    "bdg_trinodes_drifter_tables": (c_int, [_P, _P, c_int, _P, _P, _P, _P]),
+    "bdg_sw2d_enable_drifters": (c_int, [_P, POINTER(Sw2dDrifterDesc)]),
+    "bdg_sw2d_drifters_advance": (c_int, [_P, c_double, c_int]),
+    "bdg_sw2d_drifters_time": (c_int, [_P, c_double, c_int, POINTER(c_float)]),
+    "bdg_sw2d_drifters_state": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2d_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "bdg_sw2d_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "bdg_sw2d_drifters_reset": (c_int, [_P]),
     "bdg_sw2d_curved_create": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(_P)]),
     "bdg_sw2d_curved_plan": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(c_int), c_int]),
     "bdg_sw2d_curved_destroy": (None, [_P]),

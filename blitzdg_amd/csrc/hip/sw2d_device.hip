@@ -13,6 +13,7 @@
 // Elements may be renumbered internally (BDG_SW2D_REORDER); all I/O is in the
 // caller's numbering.
 // After bdg_sw2d_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
+// After bdg_sw2d_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_drifter_kernel.hpp).
 #include "../host/capi_internal.hpp"
 #include "../host/element_order.hpp"
 #include "../host/parallel_for.hpp"
@@ -20,6 +21,7 @@
 #include "halo_transport.hpp"
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
+#include "sw2d_drifter_kernel.hpp"
 #include "sw2d_monitor_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -305,6 +307,18 @@ struct bdg_sw2d {
         DevBuf<double> w, H, row, partials, rec, stage, scratch;
         DevBuf<int> slot;     // device slot of each gauge's element
     } mon;
+    // drifters (bdg_sw2d_enable_drifters): sw2d_drifter_kernel.hpp; elements and neighbours in device slots
+    struct Drifters {
+        bool on = false;
+        int n = 0, stride = 1, capacity = 0;
+        int count = 0;        // records taken
+        long long steps = 0;  // advances made
+        double t = 0.0;       // time of the next record: the model time in the stepping calls, + dt per bdg_sw2d_drifters_advance
+        DevBuf<double> vert, vinvT, jac, x, y, r, s, u0, v0, recT, recX, recY;
+        DevBuf<int> neigh, k, status, recStatus;
+        std::vector<int> callerOf; // device slot -> caller element (empty = identity)
+    } drf;
+    bool partitionSet = false; // bdg_sw2d_set_partition has been called
 
     ~bdg_sw2d() {
         for (hipEvent_t e : {evA[0], evA[1], evB[0], evB[1], evPacked[0], evPacked[1], evCopied[0], evCopied[1]})
@@ -357,6 +371,7 @@ struct bdg_sw2d {
         stageCount = 0;
         mon.steps = 0;
         lamStateFor = nullptr; // a speed accumulated for the previous contents of this buffer is void
+        drifterResample();
         hipCheck(hipStreamSynchronize(stream), "set_state sync");
     }
     void getFields(double* const* f) {
@@ -967,15 +982,49 @@ struct bdg_sw2d {
         monitorLaunch(mon.rec.p, mon.capacity, mon.count);
         ++mon.count;
     }
-    // after every completed step of a stepping call whose launches are all on the solver's stream (room was reserved by the caller)
-    void stepDone() {
+    // ---- drifters
+    // as monitorReserve: records `steps` further advances would take
+    void drifterReserve(long long steps, const char* fn) const {
+        if (!drf.on) return;
+        const long long take = (drf.steps + steps) / drf.stride - drf.steps / drf.stride;
+        if (take > drf.capacity - drf.count)
+            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " drifter records and " +
+                            std::to_string(drf.capacity - drf.count) + " are free (bdg_sw2d_drifters_read, then bdg_sw2d_drifters_reset)");
+    }
+    // one launch of the drifter kernel on the solver's stream, reading the current state; slot < 0: no record
+    void drifterLaunch(int mode, double dt, int slot) {
+        using namespace bdg_dev;
+        const TriDriftParams p{qcur, drf.vert.p, drf.neigh.p, drf.vinvT.p, drf.jac.p, drf.x.p, drf.y.p, drf.r.p, drf.s.p, drf.u0.p,
+                               drf.v0.p, drf.k.p, drf.status.p, drf.recT.p, drf.recX.p, drf.recY.p, drf.recStatus.p, ld, N, drf.n,
+                               mode, slot, dt, drf.t};
+        hipLaunchKernelGGL(sw2d_drifter_kernel, dim3((drf.n + kTriDriftThreads - 1) / kTriDriftThreads), dim3(kTriDriftThreads), 0,
+                           stream, p);
+        hipCheck(hipGetLastError(), "sw2d_drifter_kernel launch");
+    }
+    // one advance in the resident state, with the record of time drf.t if one is due (room was reserved by the caller)
+    void drifterAdvance(double dt, bool record = true) {
+        const bool due = record && ++drf.steps % drf.stride == 0;
+        drifterLaunch(bdg_dev::kTriDriftAdvance, dt, due ? drf.count : -1);
+        if (due) ++drf.count;
+    }
+    // (u0, v0) again after the state under the drifters has been replaced
+    void drifterResample() {
+        if (drf.on) drifterLaunch(bdg_dev::kTriDriftSample, 0.0, -1);
+    }
+    // after every completed step (of size dt) of a stepping call whose launches are all on the solver's stream (room was reserved
+    // by the caller): the monitor's sample, then the drifters' advance (drifters exist on unpartitioned solvers only)
+    void stepDone(double dt) {
         if (mon.on && ++mon.steps % mon.stride == 0) monitorSample();
+        if (drf.on) {
+            drf.t = timeNow;
+            drifterAdvance(dt);
+        }
     }
     // `numStages` LSERK4 stages on the whole mesh, a record after every stride-th completed step
     void lserkStagesMonitored(int numStages) {
         for (int i = 0; i < numStages; ++i) {
             launchLserkStage();
-            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone();
+            if (stageCount % blitzdg::LSERK4::numStages == 0) stepDone(dtStage);
         }
     }
     // ... of a partitioned run. The two-chain schedule is issued in pieces that end where a record is due: a piece starts
@@ -997,7 +1046,7 @@ struct bdg_sw2d {
             left -= piece;
             if (done > 0) {
                 mon.steps += done - 1;
-                stepDone();
+                stepDone(dt);
             }
         }
     }
@@ -1406,15 +1455,16 @@ void requireFields(const bdg_sw2d* s, const char* fn, int count, const char* oth
 
 // the four bdg_sw2d_step_*rk2* calls: their prologue, then `step()` num_steps times
 template <class Step>
-int stepCall(bdg_sw2d* s, const char* fn, int num_steps, Step&& step) {
+int stepCall(bdg_sw2d* s, const char* fn, double dt, int num_steps, Step&& step) {
     return guard([&] {
         requireSolver(s, fn);
         if (num_steps < 0) throw arg_error(std::string(fn) + ": num_steps < 0");
         s->monitorReserve(num_steps, fn);
+        s->drifterReserve(num_steps, fn);
         s->use();
         for (int i = 0; i < num_steps; ++i) {
             step();
-            s->stepDone();
+            s->stepDone(dt);
         }
     });
 }
@@ -1643,6 +1693,7 @@ int bdg_sw2d_lserk4_stages(bdg_sw2d* s, double dt, int num_stages) {
         requireSolver(s, "bdg_sw2d_lserk4_stages");
         if (num_stages < 0) throw arg_error("bdg_sw2d_lserk4_stages: num_stages < 0");
         s->monitorReserve(s->lserkSteps(num_stages), "bdg_sw2d_lserk4_stages");
+        s->drifterReserve(s->lserkSteps(num_stages), "bdg_sw2d_lserk4_stages");
         s->use();
         s->dtStage = dt;
         s->lserkStagesMonitored(num_stages);
@@ -1656,6 +1707,7 @@ int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps) {
         if (s->stageCount % blitzdg::LSERK4::numStages != 0)
             throw arg_error("bdg_sw2d_step_lserk4: a previous step was left part-way through its stages");
         s->monitorReserve(num_steps, "bdg_sw2d_step_lserk4");
+        s->drifterReserve(num_steps, "bdg_sw2d_step_lserk4");
         s->use();
         s->dtStage = dt;
         s->lserkStagesMonitored(num_steps * blitzdg::LSERK4::numStages);
@@ -1663,21 +1715,21 @@ int bdg_sw2d_step_lserk4(bdg_sw2d* s, double dt, int num_steps) {
 }
 
 int bdg_sw2d_step_rk2(bdg_sw2d* s, double dt, int num_steps, int filter) {
-    return stepCall(s, "bdg_sw2d_step_rk2", num_steps, [&] { s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole); });
+    return stepCall(s, "bdg_sw2d_step_rk2", dt, num_steps, [&] { s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole); });
 }
 
 int bdg_sw2d_step_ssprk2(bdg_sw2d* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return stepCall(s, "bdg_sw2d_step_ssprk2", num_steps,
+    return stepCall(s, "bdg_sw2d_step_ssprk2", dt, num_steps,
                     [&] { s->sspRk2Step(dt, filter != 0, sponge_coeff, bdg_sw2d::Eval::Whole); });
 }
 
 int bdg_sw2d_step_rk2_exchanged(bdg_sw2d* s, double dt, int num_steps, int filter) {
-    return stepCall(s, "bdg_sw2d_step_rk2_exchanged", num_steps,
+    return stepCall(s, "bdg_sw2d_step_rk2_exchanged", dt, num_steps,
                     [&] { s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Exchanged); });
 }
 
 int bdg_sw2d_step_ssprk2_exchanged(bdg_sw2d* s, double dt, int num_steps, int filter, double sponge_coeff) {
-    return stepCall(s, "bdg_sw2d_step_ssprk2_exchanged", num_steps,
+    return stepCall(s, "bdg_sw2d_step_ssprk2_exchanged", dt, num_steps,
                     [&] { s->sspRk2Step(dt, filter != 0, sponge_coeff, bdg_sw2d::Eval::Exchanged); });
 }
 
@@ -1705,8 +1757,9 @@ int bdg_sw2d_run_adaptive(bdg_sw2d* s, double cfl, double final_time, int max_st
         while (t < final_time && (max_steps <= 0 || done < max_steps)) {
             // the number of steps is not known in advance: room for this step's record is checked before the step is launched
             s->monitorReserve(1, "bdg_sw2d_run_adaptive");
+            s->drifterReserve(1, "bdg_sw2d_run_adaptive");
             s->rk2Step(dt, filter != 0, bdg_sw2d::Eval::Whole);
-            s->stepDone();
+            s->stepDone(dt);
             double r[2];
             s->reduceDt(r);
             if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
@@ -1744,6 +1797,8 @@ int bdg_sw2d_time_lserk4_stages(bdg_sw2d* s, double dt, int num_stages, float* m
 int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_set_partition");
+        if (s->drf.on)
+            throw arg_error("bdg_sw2d_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
         if (!s->permHost.empty())
             throw arg_error("bdg_sw2d_set_partition: the solver renumbered its elements; create it with BDG_SW2D_KEEP_ORDER");
         if (num_interior < 0 || num_interior > num_owned || num_owned > s->K || num_send < 0 ||
@@ -1762,6 +1817,7 @@ int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const i
         s->numInterior = num_interior;
         s->numOwned = num_owned;
         s->numSend = num_send;
+        s->partitionSet = true;
         // the first interior element with a partition-boundary neighbour: interior tiles from there on read what the boundary
         // launch of the previous stage writes (and overwrite what it reads); tiles before it depend on interior elements only
         {
@@ -2224,6 +2280,164 @@ int bdg_sw2d_monitor_time(bdg_sw2d* s, int count, float* ms) {
         s->use();
         s->monitorLaunch(s->mon.scratch.p, 1, 0); // once before the clock starts
         *ms = bdg_dev::timePerRun(s->stream, count, [&] { s->monitorLaunch(s->mon.scratch.p, 1, 0); });
+    });
+}
+
+// ---- drifters
+int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* d) {
+    return guard([&] {
+        using namespace bdg_dev;
+        const std::string fn = "bdg_sw2d_enable_drifters";
+        requireSolver(s, fn.c_str());
+        if (!d || d->count < 1 || !d->element || !d->r || !d->s || !d->vertices || !d->neighbours || !d->vinv || !d->jacobi)
+            throw arg_error(fn + ": the descriptor, at least one drifter and the tables of bdg_trinodes_drifter_tables are required");
+        if (d->stride < 1 || d->capacity < 1) throw arg_error(fn + ": stride and capacity must be >= 1");
+        if (s->drf.on) throw arg_error(fn + ": drifters are already enabled on this solver; the call is made once");
+        if (s->partitionSet || s->numOwned != s->K || s->halo.comm || s->localGroup)
+            throw arg_error(fn + ": the solver has a partition set; drifters do not migrate between ranks (single domain only)");
+        const int n = d->count, K = s->K, Np = s->Np, Nq = s->N + 1;
+        if (static_cast<long long>(n) * d->capacity >= (1LL << 31)) throw arg_error(fn + ": count * capacity must stay below 2^31");
+        const int* perm = s->permHost.empty() ? nullptr : s->permHost.data();
+        std::vector<int> slots(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) {
+            const int e = d->element[i];
+            if (e < 0 || e >= K) throw arg_error(fn + ": drifter " + std::to_string(i) + " names an element outside [0, K)");
+            const double r = d->r[i], t = d->s[i];
+            if (!(-1.0 - t <= 1e-10) || !(r + t <= 1e-10) || !(-1.0 - r <= 1e-10))
+                throw arg_error(fn + ": drifter " + std::to_string(i) + " lies outside its element (r, s >= -1, r + s <= 0)");
+            slots[i] = perm ? perm[e] : e;
+        }
+        // the tables in device slots; the kernel follows the neighbour entries without a further check
+        std::vector<int> nb(static_cast<size_t>(4) * K, kTriDriftWall);
+        std::vector<double> vert(static_cast<size_t>(8) * K);
+        std::vector<int> callerOf(static_cast<size_t>(K));
+        for (int k = 0; k < K; ++k) {
+            const int slot = perm ? perm[k] : k;
+            callerOf[slot] = k;
+            const double* line = d->vertices + static_cast<size_t>(8) * k;
+            std::copy(line, line + 8, vert.begin() + static_cast<size_t>(8) * slot);
+            for (int f = 0; f < 3; ++f) {
+                const int v = d->neighbours[static_cast<size_t>(f) * K + k];
+                if (v < kTriDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
+                nb[static_cast<size_t>(4) * slot + f] = v < 0 ? v : (perm ? perm[v] : v);
+            }
+        }
+        std::vector<double> vinvT(static_cast<size_t>(Np) * Np);
+        for (int m = 0; m < Np; ++m)
+            for (int c = 0; c < Np; ++c) vinvT[static_cast<size_t>(c) * Np + m] = d->vinv[static_cast<size_t>(m) * Np + c];
+        s->use();
+        bdg_sw2d::Drifters& m = s->drf;
+        const size_t bytesBefore = s->bytes, cells = static_cast<size_t>(n) * d->capacity;
+        try {
+            auto put = [&](auto& buf, const auto* src, size_t count) {
+                buf.alloc(count, s->bytes);
+                hipCheck(hipMemcpyAsync(buf.p, src, count * sizeof(*src), hipMemcpyHostToDevice, s->stream), "hipMemcpy (drifters)");
+            };
+            put(m.vert, vert.data(), vert.size());
+            put(m.neigh, nb.data(), nb.size());
+            put(m.vinvT, vinvT.data(), vinvT.size());
+            put(m.jac, d->jacobi, static_cast<size_t>(Nq + 1) * Nq * 3);
+            put(m.k, slots.data(), slots.size());
+            put(m.r, d->r, static_cast<size_t>(n));
+            put(m.s, d->s, static_cast<size_t>(n));
+            for (DevBuf<double>* b : {&m.x, &m.y, &m.u0, &m.v0}) b->alloc(static_cast<size_t>(n), s->bytes, s->stream);
+            m.status.alloc(static_cast<size_t>(n), s->bytes, s->stream);
+            m.recT.alloc(static_cast<size_t>(d->capacity), s->bytes, s->stream);
+            m.recX.alloc(cells, s->bytes, s->stream);
+            m.recY.alloc(cells, s->bytes, s->stream);
+            m.recStatus.alloc(cells, s->bytes, s->stream);
+            m.n = n;
+            s->drifterLaunch(kTriDriftInit, 0.0, -1); // x, y from the map, (u0, v0) from the resident state
+            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
+        } catch (...) { // nothing changes: the solver stays without drifters
+            (void)hipStreamSynchronize(s->stream);
+            for (DevBuf<double>* b : {&m.vert, &m.vinvT, &m.jac, &m.x, &m.y, &m.r, &m.s, &m.u0, &m.v0, &m.recT, &m.recX, &m.recY}) b->release();
+            for (DevBuf<int>* b : {&m.neigh, &m.k, &m.status, &m.recStatus}) b->release();
+            m.n = 0;
+            s->bytes = bytesBefore;
+            throw;
+        }
+        m.callerOf = perm ? std::move(callerOf) : std::vector<int>();
+        m.on = true;
+        m.stride = d->stride; m.capacity = d->capacity; m.count = 0; m.steps = 0; m.t = s->timeNow;
+    });
+}
+
+namespace {
+void requireDriftersOn(const bdg_sw2d* s, const char* fn) {
+    requireSolver(s, fn);
+    if (!s->drf.on) throw arg_error(std::string(fn) + ": drifters are not enabled (bdg_sw2d_enable_drifters)");
+}
+} // namespace
+
+int bdg_sw2d_drifters_advance(bdg_sw2d* s, double dt, int num_steps) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_advance");
+        if (num_steps < 0) throw arg_error("bdg_sw2d_drifters_advance: num_steps < 0");
+        s->drifterReserve(num_steps, "bdg_sw2d_drifters_advance");
+        s->use();
+        for (int i = 0; i < num_steps; ++i) {
+            s->drf.t += dt;
+            s->drifterAdvance(dt);
+        }
+    });
+}
+
+int bdg_sw2d_drifters_time(bdg_sw2d* s, double dt, int count, float* ms) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_time");
+        if (!ms || count < 1) throw arg_error("bdg_sw2d_drifters_time: bad argument");
+        s->use();
+        *ms = bdg_dev::timePerRun(s->stream, count, [&] { s->drifterAdvance(dt, false); });
+    });
+}
+
+int bdg_sw2d_drifters_state(bdg_sw2d* s, double* x, double* y, int* element, double* r, double* sref, int* status) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_state");
+        s->use();
+        const bdg_sw2d::Drifters& m = s->drf;
+        const size_t n = static_cast<size_t>(m.n);
+        const std::pair<double*, const double*> dbl[] = {{x, m.x.p}, {y, m.y.p}, {r, m.r.p}, {sref, m.s.p}};
+        for (const auto& c : dbl)
+            if (c.first) hipCheck(hipMemcpyAsync(c.first, c.second, n * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        if (element) hipCheck(hipMemcpyAsync(element, m.k.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        if (status) hipCheck(hipMemcpyAsync(status, m.status.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        if (element && !m.callerOf.empty()) // device slots back to the caller's numbering
+            for (size_t i = 0; i < n; ++i) element[i] = m.callerOf[element[i]];
+    });
+}
+
+int bdg_sw2d_drifters_count(const bdg_sw2d* s, int* num_records, int* num_drifters) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_count");
+        if (num_records) *num_records = s->drf.count;
+        if (num_drifters) *num_drifters = s->drf.n;
+    });
+}
+
+int bdg_sw2d_drifters_read(bdg_sw2d* s, int first, int count, double* t, double* x, double* y, int* status) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_read");
+        const bdg_sw2d::Drifters& m = s->drf;
+        if (first < 0 || count < 0 || first > m.count - count) throw arg_error("bdg_sw2d_drifters_read: bad record range");
+        if (count == 0) return;
+        s->use();
+        const size_t at = static_cast<size_t>(first) * m.n, cells = static_cast<size_t>(count) * m.n;
+        if (t) hipCheck(hipMemcpyAsync(t, m.recT.p + first, count * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (x) hipCheck(hipMemcpyAsync(x, m.recX.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (y) hipCheck(hipMemcpyAsync(y, m.recY.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        if (status)
+            hipCheck(hipMemcpyAsync(status, m.recStatus.p + at, cells * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2d_drifters_reset(bdg_sw2d* s) {
+    return guard([&] {
+        requireDriftersOn(s, "bdg_sw2d_drifters_reset");
+        s->drf.count = 0;
     });
 }
 

@@ -1,0 +1,234 @@
+// sw2d_drifter_kernel.hpp -- Lagrangian drifters of the triangle sw2d solver (gfx950 / CDNA4, wave64): points that move with the
+// velocity (hu / h, hv / h) of the resident state, are followed from element to element and recorded, all on the device. The
+// counterpart of sw2d_quad_drifter_kernel.hpp. One launch per advance, on the solver's stream, no atomics, no host synchronisation:
+//
+//   sw2d_drifter_kernel   lane = drifter, kTriDriftThreads per workgroup. mode kTriDriftAdvance: one Heun advance by dt and, with
+//                         slot >= 0, the record of that step; kTriDriftSample: (u0, v0) sampled again from the state (after
+//                         set_state); kTriDriftInit: x, y from (element, r, s), then the sample.
+//
+// The order is a run-time argument (as in sw2d_monitor_kernel.hpp): one instance serves N = 1..8. The kernel reads the state planes
+// 0..2 in the solver's device layout q[node * ld + slot] (plane stride Np * ld) and the tables below, and writes only the drifter
+// arrays and the record buffer. Elements are device slots throughout (the host maps the caller's numbering both ways).
+//
+// Tables (bdg_trinodes_drifter_tables). vert[8 k + (x0, y0, x1, y1, x2, y2, -, -)]: the corner nodes of element k, one 64-byte
+// line per element; vertex 0, 1, 2 sit at (r, s) = (-1, -1), (1, -1), (-1, 1), so face 0 (s = -1) runs from vertex 0 to 1, face 1
+// (r + s = 0) from 1 to 2 and face 2 (r = -1) from 2 to 0. With e1 = v1 - v0, e2 = v2 - v0 the affine map is
+//   x(r, s) = x0 + ((0.5 (1 + r)) e1x + (0.5 (1 + s)) e2x),  y likewise.
+// neigh[4 k + f], f = 0..2: the element across face f, kTriDriftWall or kTriDriftOpen (entry 3 pads to 16 bytes).
+// vinvT[n Np + m] = Vinv[m][n], the inverse Vandermonde matrix transposed. jac[(g (N + 1) + n) 3 + (A, B, C)], g = 0 .. N + 1: the
+// three-term recurrences p_0 = A_0, p_n = (A_n x + B_n) p_{n-1} + C_n p_{n-2} (C_1 = 0) of sqrt(2) P_n^(0,0) (g = 0) and of the
+// orthonormal Jacobi polynomials P_n^(2i+1,0) (g = i + 1): the kernel takes no square roots.
+//
+// locate(x, y, k): at most kTriDriftHops hops. In each, with d = (x, y) - v0 and det = e1x e2y - e2x e1y of element k,
+//   r = 2 ((dx e2y - e2x dy) / det) - 1,  s = 2 ((e1x dy - dx e1y) / det) - 1
+// (the closed-form inverse of the affine map, no iteration); r or s not finite loses the drifter. The violations of the faces 0..2
+// are (-1 - s, r + s, -1 - r): the largest <= 1e-12 is "found in k"; otherwise the face of the largest (lowest index on a tie) is
+// crossed: to the neighbour; at an open face the drifter has exited; at a wall, with a -> b the face's vertices, the point is
+// projected orthogonally onto the face's line, t = ((p - a).(b - a)) / ((b - a).(b - a)) (not clamped), p = a + t (b - a), the
+// wall bit is set and the same element is searched again (the drifter slides along the wall). Corners: when a wall face is
+// crossed and an earlier wall crossing of the same search was at another face (another element or another face index than the
+// FIRST wall face of the search), the point goes instead to the end vertex of the face now crossed that is nearer to it
+// (|p - a|^2 <= |p - b|^2: a), so alternating projections cannot use up the hops in an acute corner. Hops used up: lost.
+//
+// Basis at (r, s): a = 2 (1 + r) / (1 - s) - 1 (a = -1 at s = 1), b = s; column (i, j), i = 0..N outer, j = 0..N - i, holds
+//   P_ij = (L_i(a) (1 - b)^i) J^i_j(b),
+// L_i by the recurrence g = 0, (1 - b)^i by repeated multiplication from 1.0, J^i_j by the recurrence g = i + 1: the basis of
+// TriangleNodesProvisioner::computeVandermondeMatrix.
+//
+// Velocity at (k, r, s): u = hu / h, v = hv / h at the element's nodes, value = sum_n row[n] f[n] with row[n] = sum_m P_m vinvT[n][m],
+// every sum ascending from 0.0, no contraction: the gauge rule of sw2d_monitor_kernel.hpp with the row formed on the device. A
+// velocity that is not finite loses the drifter.
+//
+// One advance (Heun): predictor (x*, y*) = (x, y) + dt (u0, v0), located from k, (u*, v*) sampled there (an open face met by the
+// predictor only ends its search: the sample is taken where it stopped); corrector (x, y) += (dt / 2) ((u0, v0) + (u*, v*)),
+// located from the old k; (u0, v0) sampled at the new position. Status: 0 moving, 1 exited through an open face (frozen at the
+// corrector position), 2 lost (frozen where it was before the advance), + 4 once it has touched a wall. Frozen drifters are
+// recorded and not moved. Records are record-major: recT[slot], recX / recY / recStatus[slot * n + drifter].
+//
+// The basis values of a lane live in LDS, sb[m][lane] (run-time indexed, so not in registers; one column per lane: consecutive
+// lanes read consecutive 8-byte words, no bank conflicts, and no barrier). vinvT and jac are read with wave-uniform addresses
+// (scalar loads); four rows are formed per pass over the column, each in its own ascending order. The state reads are scattered
+// 8-byte gathers, 3 Np per evaluation.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace bdg_dev {
+
+constexpr int kTriDriftThreads = 128;
+constexpr int kTriDriftMaxNp = 45;      // N = 8
+constexpr int kTriDriftHops = 32;
+constexpr int kTriDriftWall = -1;       // neighbour entries
+constexpr int kTriDriftOpen = -2;
+constexpr int kTriDriftExited = 1;      // status
+constexpr int kTriDriftLost = 2;
+constexpr int kTriDriftTouched = 4;
+enum { kTriDriftAdvance = 0, kTriDriftSample = 1, kTriDriftInit = 2 };
+
+struct TriDriftParams {
+    const double* q;        // the state: planes of Np*ld, 0..2 read
+    const double* vert;     // 8 per element
+    const int* neigh;       // 4 per element
+    const double* vinvT;    // Np x Np
+    const double* jac;      // (N+2) x (N+1) x 3
+    double* x; double* y; double* r; double* s; double* u0; double* v0;   // per drifter
+    int* k; int* status;
+    double* recT;           // [capacity]
+    double* recX;           // [capacity * n], record-major
+    double* recY;
+    int* recStatus;
+    long long ld;
+    int N, n, mode, slot;   // slot < 0: no record
+    double dt, t;
+};
+
+// 0 found, kTriDriftExited or kTriDriftLost; k, r, s and (at a wall) x, y updated; wall: kTriDriftTouched or 0
+__device__ inline int triDriftLocate(const double* __restrict__ vert, const int* __restrict__ neigh, double& x, double& y, int& k,
+                                     double& r, double& s, int& wall) {
+#pragma clang fp contract(off)
+    int wk = -1, wf = -1; // the first wall face this search crossed
+    for (int hop = 0; hop < kTriDriftHops; ++hop) {
+        const double* c = vert + 8LL * k;
+        const double x0 = c[0], y0 = c[1], x1 = c[2], y1 = c[3], x2 = c[4], y2 = c[5];
+        const double e1x = x1 - x0, e1y = y1 - y0, e2x = x2 - x0, e2y = y2 - y0;
+        const double det = e1x * e2y - e2x * e1y;
+        const double dx = x - x0, dy = y - y0;
+        r = 2.0 * ((dx * e2y - e2x * dy) / det) - 1.0;
+        s = 2.0 * ((e1x * dy - dx * e1y) / det) - 1.0;
+        if (!(fabs(r) < __builtin_inf()) || !(fabs(s) < __builtin_inf())) return kTriDriftLost;
+        int f = 0;
+        double worst = -1.0 - s;
+        if (r + s > worst) { worst = r + s; f = 1; }
+        if (-1.0 - r > worst) { worst = -1.0 - r; f = 2; }
+        if (worst <= 1e-12) return 0;
+        const int nb = neigh[4LL * k + f];
+        if (nb >= 0) { k = nb; continue; }
+        if (nb != kTriDriftWall) return kTriDriftExited;
+        const double ax = f == 0 ? x0 : (f == 1 ? x1 : x2), ay = f == 0 ? y0 : (f == 1 ? y1 : y2);
+        const double bx = f == 0 ? x1 : (f == 1 ? x2 : x0), by = f == 0 ? y1 : (f == 1 ? y2 : y0);
+        if (wk >= 0 && (wk != k || wf != f)) { // a corner: to the nearer end of this face
+            const double da = (x - ax) * (x - ax) + (y - ay) * (y - ay), db = (x - bx) * (x - bx) + (y - by) * (y - by);
+            if (da <= db) { x = ax; y = ay; } else { x = bx; y = by; }
+        } else {
+            const double ex = bx - ax, ey = by - ay;
+            const double t = ((x - ax) * ex + (y - ay) * ey) / (ex * ex + ey * ey);
+            x = ax + t * ex;
+            y = ay + t * ey;
+        }
+        if (wk < 0) { wk = k; wf = f; }
+        wall = kTriDriftTouched;
+    }
+    return kTriDriftLost;
+}
+
+// the orthonormal simplex basis at (r, s) into the lane's LDS column P[m * kTriDriftThreads]
+__device__ inline void triDriftBasis(const double* __restrict__ jac, int N, double r, double s, double* P) {
+#pragma clang fp contract(off)
+    const int Nq = N + 1;
+    const double a = s != 1.0 ? 2.0 * (1.0 + r) / (1.0 - s) - 1.0 : -1.0;
+    const double om = 1.0 - s;
+    double pw = 1.0, lp = 0.0, lc = 0.0;
+    int col = 0;
+    for (int i = 0; i <= N; ++i) {
+        const double* cl = jac + 3 * i;
+        const double ln = i == 0 ? cl[0] : (cl[0] * a + cl[1]) * lc + cl[2] * lp;
+        lp = lc; lc = ln;
+        if (i > 0) pw = pw * om;
+        const double fa = lc * pw;
+        const double* cj = jac + 3 * Nq * (i + 1);
+        double jp = 0.0, jc = 0.0;
+        for (int j = 0; j <= N - i; ++j) {
+            const double jn = j == 0 ? cj[0] : (cj[3 * j] * s + cj[3 * j + 1]) * jc + cj[3 * j + 2] * jp;
+            jp = jc; jc = jn;
+            P[col * kTriDriftThreads] = fa * jc;
+            ++col;
+        }
+    }
+}
+
+// (u, v) at (k, r, s); false if either is not finite
+__device__ inline bool triDriftVelocity(const TriDriftParams& p, int k, double r, double s, double* P, double& u, double& v) {
+#pragma clang fp contract(off)
+    const int Np = (p.N + 1) * (p.N + 2) / 2;
+    const long long plane = static_cast<long long>(Np) * p.ld;
+    const double* __restrict__ q = p.q;
+    const double* __restrict__ vt = p.vinvT;
+    triDriftBasis(p.jac, p.N, r, s, P);
+    double su = 0.0, sv = 0.0;
+    for (int n0 = 0; n0 < Np; n0 += 4) {
+        // rows n0 .. n0 + 3 (past the end: the last row again, not used), one pass over the lane's column
+        const double* v0 = vt + static_cast<long long>(n0) * Np;
+        const double* v1 = vt + static_cast<long long>(min(n0 + 1, Np - 1)) * Np;
+        const double* v2 = vt + static_cast<long long>(min(n0 + 2, Np - 1)) * Np;
+        const double* v3 = vt + static_cast<long long>(min(n0 + 3, Np - 1)) * Np;
+        double row[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int m = 0; m < Np; ++m) {
+            const double pm = P[m * kTriDriftThreads];
+            row[0] = row[0] + pm * v0[m];
+            row[1] = row[1] + pm * v1[m];
+            row[2] = row[2] + pm * v2[m];
+            row[3] = row[3] + pm * v3[m];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (n0 + j < Np) {
+                const long long o = (n0 + j) * p.ld + k;
+                const double h = q[o];
+                su = su + row[j] * (q[plane + o] / h);
+                sv = sv + row[j] * (q[2 * plane + o] / h);
+            }
+        }
+    }
+    u = su; v = sv;
+    return fabs(su) < __builtin_inf() && fabs(sv) < __builtin_inf();
+}
+
+__global__ __launch_bounds__(kTriDriftThreads) void sw2d_drifter_kernel(TriDriftParams p) {
+#pragma clang fp contract(off)
+    __shared__ double sb[kTriDriftMaxNp][kTriDriftThreads];
+    const int i = blockIdx.x * kTriDriftThreads + threadIdx.x;
+    if (i == 0 && p.slot >= 0) p.recT[p.slot] = p.t;
+    if (i >= p.n) return;
+    double* P = &sb[0][threadIdx.x];
+    int k = p.k[i], st = p.status[i];
+    double x = p.x[i], y = p.y[i], r = p.r[i], s = p.s[i], u0 = p.u0[i], v0 = p.v0[i];
+    const bool frozen = (st & (kTriDriftExited | kTriDriftLost)) != 0;
+    if (p.mode != kTriDriftAdvance) {
+        if (p.mode == kTriDriftInit) {
+            const double* c = p.vert + 8LL * k;
+            const double wr = 0.5 * (1.0 + r), ws = 0.5 * (1.0 + s);
+            x = c[0] + (wr * (c[2] - c[0]) + ws * (c[4] - c[0]));
+            y = c[1] + (wr * (c[3] - c[1]) + ws * (c[5] - c[1]));
+            p.x[i] = x; p.y[i] = y;
+        }
+        if (!frozen) {
+            if (!triDriftVelocity(p, k, r, s, P, u0, v0)) p.status[i] = st | kTriDriftLost;
+            p.u0[i] = u0; p.v0[i] = v0;
+        }
+        return;
+    }
+    if (!frozen) {
+        // every result into temporaries: a lost drifter stays where it was
+        int wall = 0, kp = k, kc = k, res;
+        double xp = x + p.dt * u0, yp = y + p.dt * v0, rp, sp, up, vp;
+        bool ok = triDriftLocate(p.vert, p.neigh, xp, yp, kp, rp, sp, wall) != kTriDriftLost;
+        ok = ok && triDriftVelocity(p, kp, rp, sp, P, up, vp);
+        if (ok) {
+            double xn = x + (0.5 * p.dt) * (u0 + up), yn = y + (0.5 * p.dt) * (v0 + vp), rn, sn, un = u0, vn = v0;
+            res = triDriftLocate(p.vert, p.neigh, xn, yn, kc, rn, sn, wall);
+            ok = res != kTriDriftLost && (res == kTriDriftExited || triDriftVelocity(p, kc, rn, sn, P, un, vn));
+            if (ok) {
+                x = xn; y = yn; k = kc; r = rn; s = sn; u0 = un; v0 = vn;
+                st |= res;
+                p.x[i] = x; p.y[i] = y; p.r[i] = r; p.s[i] = s; p.u0[i] = u0; p.v0[i] = v0; p.k[i] = k;
+            }
+        }
+        st |= wall | (ok ? 0 : kTriDriftLost);
+        p.status[i] = st;
+    }
+    if (p.slot >= 0) {
+        const long long o = static_cast<long long>(p.slot) * p.n + i;
+        p.recX[o] = x; p.recY[o] = y; p.recStatus[o] = st;
+    }
+}
+
+} // namespace bdg_dev

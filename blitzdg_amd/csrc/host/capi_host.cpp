@@ -415,6 +415,20 @@ int bdg_trinodes_interpolation_rows(const bdg_trinodes* nodes, const double* r, 
     });
 }
 
+// ---- set-up of the triangle solver's drifters (bdg_sw2d_enable_drifters): corner vertices, neighbour table, basis tables
+int bdg_trinodes_drifter_tables(const bdg_trinodes* nodes, const int* mapO, int num_out, double* vertices, int* neighbours,
+                                double* vinv, double* jacobi) {
+    return guard([&] {
+        if (!nodes || !vertices || !neighbours || !vinv || !jacobi || num_out < 0 || (num_out > 0 && !mapO))
+            throw bdg_detail::arg_error("bdg_trinodes_drifter_tables: bad argument");
+        try {
+            nodes->prov.drifterTables(mapO, num_out, vertices, neighbours, vinv, jacobi);
+        } catch (const std::invalid_argument& e) {
+            throw bdg_detail::arg_error(std::string("bdg_trinodes_drifter_tables: ") + e.what());
+        }
+    });
+}
+
 // ---- set-up of the drifters (bdg_sw2dq_enable_drifters): bilinear map, neighbour table, barycentric weights
 int bdg_quadnodes_drifter_tables(const bdg_quadnodes* nodes, const int* mapO, int num_out, double* bilinear, int* neighbours,
                                  double* bary) {

@@ -723,6 +723,90 @@ void TriangleNodesProvisioner::locatePoints(const real_type* px, const real_type
     }, 8);
 }
 
+// ---------------------------------------------------------------- drifter set-up
+
+void TriangleNodesProvisioner::drifterTables(const index_type* mapO, index_type numOut, real_type* vertices,
+                                             index_type* neighbours, real_type* vinv, real_type* jacobi) const {
+    const index_type N = NOrder, Np = NumLocalPoints, Nfp = NumFacePoints, K = NumElements, NFN = 3 * Nfp;
+    // the corner nodes: those nearest (r, s) = (-1, -1), (1, -1), (-1, 1)
+    index_type corner[3];
+    const real_type cr[3] = {-1, 1, -1}, cs[3] = {-1, -1, 1};
+    for (index_type c = 0; c < 3; ++c) {
+        corner[c] = 0;
+        for (index_type m = 1; m < Np; ++m)
+            if (std::hypot(rGrid(m) - cr[c], sGrid(m) - cs[c]) < std::hypot(rGrid(corner[c]) - cr[c], sGrid(corner[c]) - cs[c]))
+                corner[c] = m;
+    }
+    for (index_type k = 0; k < K; ++k) {
+        real_type* v = vertices + static_cast<std::size_t>(8) * k;
+        for (index_type c = 0; c < 3; ++c) {
+            v[2 * c] = xGrid(corner[c], k);
+            v[2 * c + 1] = yGrid(corner[c], k);
+        }
+        v[6] = v[7] = 0;
+        const real_type e1x = v[2] - v[0], e1y = v[3] - v[1], e2x = v[4] - v[0], e2y = v[5] - v[1];
+        const real_type area = 0.5 * (e1x * e2y - e2x * e1y);
+        if (!(area > 0) || !(area < std::numeric_limits<real_type>::infinity()))
+            throw std::invalid_argument("drifterTables: the signed area of element " + std::to_string(k) + " is not positive and finite");
+        // a mesh whose nodes have left the affine map of the corners (deformed or blended elements): the drifters cannot follow it
+        const real_type size = std::max(std::hypot(e1x, e1y), std::hypot(e2x, e2y));
+        for (index_type m = 0; m < Np; ++m) {
+            const real_type wr = 0.5 * (1 + rGrid(m)), ws = 0.5 * (1 + sGrid(m));
+            const real_type ex = v[0] + (wr * e1x + ws * e2x) - xGrid(m, k), ey = v[1] + (wr * e1y + ws * e2y) - yGrid(m, k);
+            if (!(std::hypot(ex, ey) <= 1e-10 * size))
+                throw std::invalid_argument("drifterTables: the nodes of element " + std::to_string(k) + " differ from the affine map "
+                                            "of its corners; drifters need straight-sided elements");
+        }
+    }
+    // faces in Fmask order (s = -1, r + s = 0, r = -1), which is the mesh's face order
+    const index_vector_type& E2E = Mesh2D->get_EToE();
+    std::vector<char> open(static_cast<std::size_t>(3) * K, 0);
+    for (index_type i = 0; i < numOut; ++i) {
+        if (mapO[i] < 0 || mapO[i] >= NFN * K) throw std::invalid_argument("drifterTables: open-boundary node index out of range");
+        open[static_cast<std::size_t>(mapO[i] / NFN) * 3 + mapO[i] % NFN / Nfp] = 1;
+    }
+    for (index_type k = 0; k < K; ++k)
+        for (index_type f = 0; f < 3; ++f) {
+            const index_type k2 = E2E(3 * k + f);
+            // (a boundary face is its own neighbour in EToE and maps its nodes onto themselves)
+            const std::size_t g = (static_cast<std::size_t>(k) * 3 + f) * Nfp;
+            const bool boundary = k2 == k && vmapP(g) == vmapM(g);
+            neighbours[static_cast<std::size_t>(f) * K + k] = boundary ? (open[static_cast<std::size_t>(k) * 3 + f] ? -2 : -1) : k2;
+        }
+    for (index_type m = 0; m < Np; ++m)
+        for (index_type n = 0; n < Np; ++n) vinv[static_cast<std::size_t>(m) * Np + n] = Vinv(m, n);
+    // a_m = 2 / (2 m + alpha) * m (m + alpha) / sqrt((2 m + alpha - 1) (2 m + alpha + 1)) of the orthonormal P^(alpha, 0)
+    // (JacobiBuilders::computeJacobiPolynomial with beta = 0)
+    const index_type Nq = N + 1;
+    for (index_type g = 0; g <= N + 1; ++g) {
+        const long double al = g == 0 ? 0.0L : 2.0L * (g - 1) + 1.0L;
+        auto a = [al](index_type m) {
+            const long double h = 2.0L * m + al;
+            return 2.0L / h * (m * (m + al)) / std::sqrt((h - 1) * (h + 1));
+        };
+        for (index_type n = 0; n < Nq; ++n) {
+            long double A, B = 0, C = 0;
+            if (n == 0) {
+                A = std::sqrt((al + 1) / std::pow(2.0L, al + 1)); // 1 / sqrt(gamma0), gamma0 = 2^(alpha+1) / (alpha+1)
+                if (g == 0) A *= std::sqrt(2.0L);
+            } else if (n == 1) {
+                const long double w = std::sqrt((al + 3) / (al + 1));
+                A = (al + 2) / 2 * w;
+                B = al / 2 * w;
+            } else {
+                const long double h = 2.0L * (n - 1) + al;
+                A = 1 / a(n);
+                B = al * al / (h * (h + 2)) / a(n);
+                C = -a(n - 1) / a(n);
+            }
+            real_type* out = jacobi + (static_cast<std::size_t>(g) * Nq + n) * 3;
+            out[0] = static_cast<real_type>(A);
+            out[1] = static_cast<real_type>(B);
+            out[2] = static_cast<real_type>(C);
+        }
+    }
+}
+
 DGContext2D TriangleNodesProvisioner::get_DGContext() const {
     // The gather/scatter maps need a sort over all Np*K nodes and are not read by the
     // RHS path: built eagerly only for small meshes, otherwise on get_gather().

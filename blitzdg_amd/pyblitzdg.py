@@ -370,6 +370,22 @@ class TriangleNodesProvisioner:
         check(lib.bdg_trinodes_interpolation_rows(self._h, C.ptr(r), C.ptr(s), r.size, C.ptr(out)))
         return out
 
+    def drifterTables(self, mapO=None):
+        """(vertices, neighbours, (Vinv, jacobi)) of ``Sw2dSolver.enableDrifters``: (K, 8) x0, y0, x1, y1, x2, y2 of each
+        element's corner nodes in face order (face 0, s = -1, runs from vertex 0 to 1; face 1, r + s = 0, from 1 to 2; face 2,
+        r = -1, from 2 to 0) and two pad entries; (3, K) the element across each face, -1 for a wall, -2 for a boundary face
+        with a node in ``mapO`` (flat face-node numbering (3 k + f) Nfp + i); the basis tables: Vinv (Np, Np) and the
+        (N + 2, N + 1, 3) three-term-recurrence coefficients of sqrt(2) P_n^(0,0) (row 0) and the orthonormal P_n^(2i+1,0)
+        (row i + 1). A mesh whose nodes have left the affine map of their corners, or an element without a positive area,
+        raises BdgError."""
+        N, Np, _, K = self._dims()
+        mo = C.as_i32([] if mapO is None else mapO).reshape(-1)
+        vert, neigh = np.empty((K, 8)), np.empty((3, K), dtype=np.int32)
+        vinv, jac = np.empty((Np, Np)), np.empty((N + 2, N + 1, 3))
+        check(lib.bdg_trinodes_drifter_tables(self._h, C.ptr(mo) if mo.size else None, mo.size, C.ptr(vert), C.ptr(neigh),
+                                              C.ptr(vinv), C.ptr(jac)))
+        return vert, neigh, (vinv, jac)
+
     def setCoordinates(self, x, y):
         _, Np, _, K = self._dims()
         xa, ya = C.as_f64(x, (Np, K), "x"), C.as_f64(y, (Np, K), "y")

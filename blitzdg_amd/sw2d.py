@@ -292,6 +292,57 @@ class Sw2dSolver:
         check(lib.bdg_sw2d_monitor_time(self._h, int(count), byref(ms)))
         return ms.value
 
+    # ---- drifters
+    def enableDrifters(self, nodes, points, mapO=None, stride=1, capacity=1024):
+        """Switches on Lagrangian drifters: points that move with the velocity (hu / h, hv / h) of the resident state. From now
+        on stepLSERK4, lserk4Stages (a step is the fifth stage), stepRK2, stepSSPRK2 and runAdaptive advance them on the device
+        by that step's dt after every completed step (Heun; one launch, no state download) and keep their positions after every
+        ``stride``-th advance, ``capacity`` records at most. ``nodes``: the TriangleNodesProvisioner of the solver's mesh, whose
+        elements must be straight-sided. ``points``: (n, 2) array of x, y, located with ``nodes.locatePoints`` (a point in no
+        element raises ValueError), or a tuple (element, r, s) of reference coordinates, the elements in the caller's numbering.
+        ``mapO``: the open-boundary face nodes of ``enableVariantB``; a drifter that crosses one of their faces has exited
+        (status 1), at every other boundary face it slides along the wall (status bit 4) and comes to rest in a corner. Set the
+        state first; once per solver; not on a partitioned solver."""
+        el, r, s = _locate(points, nodes, "points")
+        vert, neigh, (vinv, jac) = nodes.drifterTables(mapO)
+        d = C.Sw2dDrifterDesc(el.size, C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(vert), C.ptr(neigh), C.ptr(vinv), C.ptr(jac),
+                              int(stride), int(capacity))
+        check(lib.bdg_sw2d_enable_drifters(self._h, byref(d)))
+        self.numDrifters = int(el.size)
+
+    def advanceDrifters(self, dt, nsteps=1):
+        """``nsteps`` advances by ``dt`` in the resident state as it is (a steady flow); the records' time moves on, the model
+        time does not."""
+        check(lib.bdg_sw2d_drifters_advance(self._h, float(dt), int(nsteps)))
+
+    def timeDrifters(self, dt, count):
+        """Average device milliseconds per advance (no records taken; the drifters move)."""
+        ms = c_float()
+        check(lib.bdg_sw2d_drifters_time(self._h, float(dt), int(count), byref(ms)))
+        return ms.value
+
+    def drifterState(self):
+        """dict of the drifters now: ``xy`` (n, 2), ``element`` (caller numbering), ``r``, ``s``, ``status`` (0 moving, 1 exited,
+        2 lost, + 4 once it has touched a wall); waits for the solver's stream."""
+        n = self.numDrifters
+        x, y, r, s = (np.empty(n) for _ in range(4))
+        el, st = np.empty(n, np.int32), np.empty(n, np.int32)
+        check(lib.bdg_sw2d_drifters_state(self._h, C.ptr(x), C.ptr(y), C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(st)))
+        return {"xy": np.stack([x, y], axis=1), "element": el, "r": r, "s": s, "status": st}
+
+    def drifterTracks(self):
+        """(t, xy, status) of the records taken so far: (m,), (m, n, 2), (m, n); waits for the solver's stream."""
+        m, n = c_int(), c_int()
+        check(lib.bdg_sw2d_drifters_count(self._h, byref(m), byref(n)))
+        m, n = m.value, n.value
+        t, x, y, st = np.empty(m), np.empty((m, n)), np.empty((m, n)), np.empty((m, n), np.int32)
+        check(lib.bdg_sw2d_drifters_read(self._h, 0, m, C.ptr(t), C.ptr(x), C.ptr(y), C.ptr(st)))
+        return t, np.stack([x, y], axis=2), st
+
+    def resetDrifterTracks(self):
+        """Drops the records held on the device (the drifters stay where they are)."""
+        check(lib.bdg_sw2d_drifters_reset(self._h))
+
     def probeStageTraffic(self, repeats=20):
         """Milliseconds of a launch with the stage kernel's memory accesses but no gathers / arithmetic."""
         ms = c_float()

@@ -96,6 +96,17 @@ public:
     /// that equals a reference node bit for bit gives the exact unit vector.
     void interpolationRows(const real_type* r, const real_type* s, index_type n, real_type* rows) const;
 
+    // ---- set-up of the drifters (bdg_sw2d_enable_drifters)
+    /// vertices (K, 8): x0, y0, x1, y1, x2, y2 of each element's corner nodes (vertex 0, 1, 2 at (r, s) = (-1, -1), (1, -1),
+    /// (-1, 1)) and two pad entries (0). neighbours (3, K): the element across each face, -1 for a wall, -2 for a boundary face
+    /// with a face node in mapO (flat face-node numbering (3 k + f) Nfp + i). vinv (Np, Np): Vinv. jacobi (N + 2, N + 1, 3):
+    /// the recurrences p_0 = A_0, p_n = (A_n x + B_n) p_{n-1} + C_n p_{n-2} of sqrt(2) P_n^(0,0) (row 0) and of the orthonormal
+    /// P_n^(2i+1,0) (row i + 1), each (A, B, C) formed in long double and rounded once. std::invalid_argument for a mesh on which
+    /// a node lies off the affine map of its element's corners by more than 1e-10 of the element's size, for an element whose
+    /// signed area is not positive and finite, and for a mapO entry out of range.
+    void drifterTables(const index_type* mapO, index_type numOut, real_type* vertices, index_type* neighbours, real_type* vinv,
+                       real_type* jacobi) const;
+
     // ---- accessors
     const real_matrix_type& get_xGrid() const { return xGrid; }
     const real_matrix_type& get_yGrid() const { return yGrid; }

@@ -785,6 +785,62 @@ int bdg_sw2d_monitor_reduce(bdg_sw2d* s);
  * takes no records (the launches write a scratch record). */
 int bdg_sw2d_monitor_time(bdg_sw2d* s, int count, float* ms);
 
+/* ---- drifters of the triangle solver: points that move with the velocity (hu / h, hv / h) of the resident state, followed
+ * from element to element and recorded on the device, one launch per advance on the solver's stream and no host wait
+ * (csrc/hip/sw2d_drifter_kernel.hpp, which states the algorithm); the counterpart of the bdg_sw2dq_*drifter* group above with
+ * the same statuses and record layout. Single domain and straight-sided (affine) elements only.
+ * Host set-up, from a triangle provisioner (no GPU): vertices (K, 8), per element x0, y0, x1, y1, x2, y2 of its corner nodes
+ * and two pad entries; the vertices are in face order: face 0 (s = -1) runs from vertex 0 to 1, face 1 (r + s = 0) from 1 to 2,
+ * face 2 (r = -1) from 2 to 0. neighbours (3, K): the element across each face, -1 for a wall, -2 for an open boundary face: a
+ * boundary face with a node in mapO (the list of bdg_sw2d_enable_variant_b, flat face-node numbering (3 k + f) Nfp + i; may be
+ * empty). vinv (Np, Np): the provisioner's inverse Vandermonde matrix. jacobi (N + 2, N + 1, 3): the three-term recurrences
+ * p_0 = A_0, p_n = (A_n x + B_n) p_{n-1} + C_n p_{n-2} of sqrt(2) P_n^(0,0) (row 0) and of the orthonormal Jacobi polynomials
+ * P_n^(2i+1,0) (row i + 1, i = 0..N), n <= N, entries (A, B, C): the device evaluates the orthonormal simplex basis P(r, s) of
+ * the provisioner and the rows P(r, s) Vinv from them without square roots. BDG_ERR_ARGUMENT for a NULL argument, a mapO
+ * entry out of range, a mesh on which a node lies off the affine map of its element's corners by more than 1e-10 of the
+ * element's size (deformed or blended elements), and an element whose signed area is not positive and finite. */
+int bdg_trinodes_drifter_tables(const bdg_trinodes* nodes, const int* mapO, int num_out, double* vertices, int* neighbours,
+                                double* vinv, double* jacobi);
+typedef struct bdg_sw2d_drifter_desc {
+    int count;                  /* number of drifters, >= 1 */
+    const int* element;         /* initial positions: element in [0, K), caller numbering, and reference coordinates with */
+    const double* r;            /* -1 - s, r + s, -1 - r <= 1e-10 (bdg_trinodes_locate_points) */
+    const double* s;
+    const double* vertices;     /* (K, 8), (3, K), (Np, Np), (N + 2, N + 1, 3): bdg_trinodes_drifter_tables */
+    const int* neighbours;
+    const double* vinv;
+    const double* jacobi;
+    int stride;                 /* record after every stride-th advance, >= 1 */
+    int capacity;               /* records held on the device, >= 1 */
+} bdg_sw2d_drifter_desc;
+/* Status of a drifter: 0 moving, 1 exited through an open face (frozen there), 2 lost (frozen where it was: the search ran
+ * out of hops or a coordinate or the velocity was not finite), + 4 once it has touched a wall (it slides along it; in a corner
+ * it rests on the vertex).
+ * enable_drifters: once per solver; computes x, y from the map and samples the velocity of the resident state (set_state
+ * first). BDG_ERR_ARGUMENT, changing nothing, for a NULL or incomplete descriptor, count, stride or capacity < 1, an element
+ * outside [0, K), a point outside its element, a neighbour entry outside [-2, K), a second call, and a solver with a partition
+ * set; bdg_sw2d_set_partition in turn refuses a solver that has drifters. From then on step_lserk4, lserk4_stages (a step is
+ * the fifth stage), step_rk2, step_ssprk2 and run_adaptive advance the drifters by that step's dt after every completed step
+ * (Heun: the velocity sampled before the step and the one of the new state), behind the monitor's sample if there is one, and
+ * store a record with t = the model time after every stride-th advance; a call that would take more records than the capacity
+ * has left returns BDG_ERR_ARGUMENT before it launches anything (run_adaptive checks before every step, as for the monitor).
+ * set_state and set_state4 sample the velocity again. A solver that renumbered its elements keeps the drifters' elements and
+ * the neighbour table in its device slots; everything passed or read here is in the caller's numbering, and nothing in a
+ * drifter's arithmetic depends on the numbering.
+ * drifters_advance: num_steps advances by dt in the resident state as it is (steady flows); the records' time moves on by dt per
+ * advance, the model time does not. drifters_time: average device milliseconds of `count` such advances, no records taken.
+ * drifters_state: the current x, y, element, r, s, status (count entries each; any may be NULL). drifters_count: records
+ * taken and drifters. drifters_read: records [first, first + num): t (num), x, y, status (num x count each, record-major; any
+ * may be NULL); synchronises the solver's stream. drifters_reset drops the records only.
+ * (bdg_sw2d_curved has curved elements: no drifters.) */
+int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* desc);
+int bdg_sw2d_drifters_advance(bdg_sw2d* s, double dt, int num_steps);
+int bdg_sw2d_drifters_time(bdg_sw2d* s, double dt, int count, float* ms);
+int bdg_sw2d_drifters_state(bdg_sw2d* s, double* x, double* y, int* element, double* r, double* sref, int* status);
+int bdg_sw2d_drifters_count(const bdg_sw2d* s, int* num_records, int* num_drifters);
+int bdg_sw2d_drifters_read(bdg_sw2d* s, int first, int num, double* t, double* x, double* y, int* status);
+int bdg_sw2d_drifters_reset(bdg_sw2d* s);
+
 /* ---------------------------------------------------------------- sw2d, curved / over-integrated RHS
  * reference: swhelpers.rhs.sw2dComputeRHS_curved(h, hu, hv, hN, zx, zy, g, H, f, CD, ctx, cub_ctx, gauss_ctx,
  * curvedEls, J, gmapM, gmapP) (swhelpers/rhs.py:6-176), driven by sw2d_curved.py:246-277 (RHS, Filter, midpoint
