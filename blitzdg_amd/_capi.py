@@ -111,6 +111,11 @@ class Sw2dCurvedDesc(Structure):
                 ("drag", c_void_p), ("drag_const", c_double), ("g", c_double), ("device", c_int), ("flags", c_int)]
 
 
+class Sw2dCurvedDriverDesc(Structure):
+    _fields_ = [("Fscale", c_void_p), ("vmapM", c_void_p), ("c", c_void_p), ("c_const", c_double), ("H", c_void_p),
+                ("Dr", c_void_p), ("Ds", c_void_p), ("rx", c_void_p), ("sx", c_void_p), ("ry", c_void_p), ("sy", c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -352,6 +357,12 @@ _SIGNATURES = {
     "bdg_sw2d_curved_lserk4_stages_exchanged": (c_int, [_P, c_double, c_int]),
     "bdg_sw2d_curved_exchange": (c_int, [_P, c_int]),
     "bdg_sw2d_curved_barrier": (c_int, [_P]),
+    "bdg_sw2d_curved_enable_driver": (c_int, [_P, POINTER(Sw2dCurvedDriverDesc)]),
+    "bdg_sw2d_curved_compute_dt": (c_int, [_P, c_double, POINTER(c_double), POINTER(c_double)]),
+    "bdg_sw2d_curved_run_adaptive": (c_int, [_P, c_double, c_double, c_int, c_int, POINTER(c_double),
+                                             POINTER(c_double), POINTER(c_int)]),
+    "bdg_sw2d_curved_output_fields": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2d_curved_time_driver": (c_int, [_P, c_int, _P, c_int, POINTER(c_float)]),
 }
 
 #: every symbol include/blitzdg_hip.h declares (checked by tests/test_capi_symbols.py)

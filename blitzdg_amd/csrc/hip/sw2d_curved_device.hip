@@ -1,13 +1,16 @@
 // C ABI of the curved / over-integrated sw2d solver (include/blitzdg_hip.h, bdg_sw2d_curved_*): device layout, uploads of
-// the host tables (host/curved_tables.cpp), launches. Kernels: sw2d_curved_kernel.hpp, sw2d_curved_nt_kernel.hpp.
-// Reference: swhelpers/rhs.py:6-176 (the RHS), sw2d_curved.py:246-277 (the time loop).
+// the host tables (host/curved_tables.cpp), launches. Kernels: sw2d_curved_kernel.hpp, sw2d_curved_nt_kernel.hpp; the driver's
+// adaptive step, blow-up check and output fields (bdg_sw2d_curved_enable_driver): sw2d_curved_driver_kernel.hpp.
+// Reference: swhelpers/rhs.py:6-176 (the RHS), sw2d_curved.py:231-302 (the time loop).
 #include "../host/capi_internal.hpp"
 #include "../host/curved_tables.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "partition_schedule.hpp"
+#include "sw2d_curved_driver_kernel.hpp"
 #include "sw2d_curved_kernel.hpp"
 #include "sw2d_curved_kernel_info.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <memory>
 #include <string>
@@ -34,6 +37,7 @@ const CurvedKernelTable* curved_kernel_table(int order) { return curvedOrder(ord
 using bdg_detail::arg_error;
 using bdg_detail::guard;
 using bdg_detail::hip_error;
+using bdg_detail::unstable_error;
 
 using bdg_dev::DevBuf;
 using bdg_dev::hipCheck;
@@ -101,6 +105,16 @@ struct bdg_sw2d_curved {
     bdg_halo::Partition part;
     bdg_halo::Transport halo;
     bdg_halo::TwoChains chains;
+    // the driver's tables (bdg_sw2d_curved_enable_driver; sw2d_curved_driver_kernel.hpp): the dt formula's Fscale and c planes
+    // and face-node list, H, the derivative matrices (Dr, then Ds) and the metric planes (rx, sx, ry, sy) of the vorticity,
+    // the lattice matrix of the latest output call, the six output planes, the reduction's partials and its three results
+    struct Driver {
+        bool on = false, hasC = false, hasH = false;
+        int nFace = 0;
+        double cConst = 0.0;
+        DevBuf<double> fscale, c, H, deriv, metric, IM, out, partials, result;
+        DevBuf<int> faceNodes;
+    } drv;
 
     ~bdg_sw2d_curved() { // both streams drained before the members destroy the events, the communicator and the exchange stream
         (void)hipSetDevice(device);
@@ -141,6 +155,12 @@ struct bdg_sw2d_curved {
     void upload(DevBuf<T>& buf, const std::vector<T>& host, const char* what) {
         queueUpload(buf, host, what);
         hipCheck(hipStreamSynchronize(stream), what);
+    }
+
+    // a zeroed (rows, ld) buffer with the host's (rows, K) in it, waited for
+    void uploadPlanes(DevBuf<double>& buf, const double* host, int rows) {
+        buf.alloc(static_cast<size_t>(rows) * ld, bytes, stream);
+        uploadRows(host, buf.p, rows);
     }
 
     void requireFilter(bool filter) const { if (filter && !hasFilter) throw arg_error(kNoFilter); }
@@ -250,6 +270,56 @@ struct bdg_sw2d_curved {
             }
         });
     }
+
+    // ---- the driver (sw2d_curved_driver_kernel.hpp). The elements its passes cover: the owned ones of a partitioned run
+    int owned() const { return part.numOwned > 0 ? part.numOwned : K; }
+    void dtPass() {
+        bdg_dev::CurvedDtParams p{};
+        p.q = qA.p; p.fscale = drv.fscale.p; p.c = drv.hasC ? drv.c.p : nullptr; p.faceNodes = drv.faceNodes.p;
+        p.ld = ld; p.Np = Np; p.nFace = drv.nFace; p.count = owned();
+        p.cConst = drv.cConst; p.fac = (N + 1) * (N + 1) * 0.5;
+        const int nblocks = (p.count + bdg_dev::kCurvedDrvThreads - 1) / bdg_dev::kCurvedDrvThreads;
+        hipLaunchKernelGGL(bdg_dev::sw2d_curved_dt_kernel, dim3(nblocks), dim3(bdg_dev::kCurvedDrvThreads), 0, stream, p, drv.partials.p);
+        hipCheck(hipGetLastError(), "sw2d_curved_dt_kernel");
+        hipLaunchKernelGGL(bdg_dev::sw2d_curved_dt_finish_kernel, dim3(1), dim3(bdg_dev::kCurvedDrvThreads), 0, stream, drv.partials.p,
+                           nblocks, drv.result.p);
+        hipCheck(hipGetLastError(), "sw2d_curved_dt_finish_kernel");
+    }
+    // {speed maximum, max|h|}; throws on the script's blow-up conditions (after `out` is filled)
+    void reduceDt(double out[2]) {
+        double r[3];
+        dtPass();
+        hipCheck(hipMemcpyAsync(r, drv.result.p, sizeof(r), hipMemcpyDeviceToHost, stream), "D2H copy");
+        hipCheck(hipStreamSynchronize(stream), "reduce sync");
+        out[0] = r[0]; out[1] = r[1];
+        if (r[2] > 0.0 || std::isnan(r[0]) || std::isnan(r[1]) || r[1] > 1e8)
+            throw unstable_error("A numerical instability has occurred.");
+    }
+    // one launch for the fields of `mask`; lattice: drv.IM holds the matrix
+    void outputLaunch(int mask, bool lattice) {
+        bdg_dev::CurvedOutParams p{};
+        const size_t pl = plane(), mm = static_cast<size_t>(Np) * Np;
+        p.q = qA.p; p.H = drv.hasH ? drv.H.p : nullptr; p.Dr = drv.deriv.p; p.Ds = drv.deriv.p + mm;
+        p.rx = drv.metric.p; p.sx = drv.metric.p + pl; p.ry = drv.metric.p + 2 * pl; p.sy = drv.metric.p + 3 * pl;
+        p.IM = lattice ? drv.IM.p : nullptr; p.out = drv.out.p; p.ld = ld; p.Np = Np; p.count = owned(); p.mask = mask;
+        const dim3 grid((p.count + 63) / 64), block(64 * bdg_dev::kCurvedOutWaves);
+        auto launch = [&](auto lat, auto cls) {
+            hipLaunchKernelGGL((bdg_dev::sw2d_curved_output_kernel<decltype(lat)::value, decltype(cls)::value>), grid, block, 0, stream, p);
+        };
+        auto sized = [&](auto lat) { // the LDS size class of this order (curvedOutClass)
+            switch (bdg_dev::curvedOutClass(Np)) {
+            case 15: return launch(lat, std::integral_constant<int, 15>{});
+            case 28: return launch(lat, std::integral_constant<int, 28>{});
+            default: return launch(lat, std::integral_constant<int, bdg_dev::kCurvedDrvMaxNp>{});
+            }
+        };
+        if (lattice) sized(std::true_type{});
+        else sized(std::false_type{});
+        hipCheck(hipGetLastError(), "sw2d_curved_output_kernel");
+    }
+    void stageLattice(const double* IM) { // queued on the stream: the caller's matrix must live until the stream is waited for
+        hipCheck(hipMemcpyAsync(drv.IM.p, IM, drv.IM.n * sizeof(double), hipMemcpyHostToDevice, stream), "lattice upload");
+    }
 };
 
 namespace {
@@ -272,6 +342,34 @@ int prologue(bdg_sw2d_curved* s, const char* fn, bool comm, const char* countNam
 }
 template <class Body> int curvedCall(bdg_sw2d_curved* s, const char* fn, Body&& body) { return prologue(s, fn, false, nullptr, 0, body); }
 template <class Body> int commCall(bdg_sw2d_curved* s, const char* fn, Body&& body) { return prologue(s, fn, true, nullptr, 0, body); }
+// ... of the calls that need bdg_sw2d_curved_enable_driver first
+template <class Body>
+int driverCall(bdg_sw2d_curved* s, const char* fn, Body&& body) {
+    return guard([&] {
+        requireCurved(s, fn);
+        if (!s->drv.on) throw arg_error(std::string(fn) + ": call bdg_sw2d_curved_enable_driver first");
+        s->use();
+        body();
+    });
+}
+
+// The face-node list of the dt formula from ctx.vmapM: entry j of element k must be a node of element k, and the local part must
+// be the same list in every element.
+std::vector<int> driverFaceNodes(const int* vmapM, int Np, int nFace, int K) {
+    std::vector<int> local(static_cast<size_t>(nFace));
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < nFace; ++j) {
+            const long long v = vmapM[j + static_cast<size_t>(nFace) * k], n = v - static_cast<long long>(Np) * k;
+            if (n < 0 || n >= Np)
+                throw arg_error("bdg_sw2d_curved_enable_driver: vmapM entry " + std::to_string(j) + " of element " + std::to_string(k) +
+                                " is not a node of that element");
+            if (k == 0) local[static_cast<size_t>(j)] = static_cast<int>(n);
+            else if (local[static_cast<size_t>(j)] != n)
+                throw arg_error("bdg_sw2d_curved_enable_driver: the face-node list of element " + std::to_string(k) +
+                                " differs from element 0's");
+        }
+    return local;
+}
 
 // What the host tables need of the order's kernel table, for this descriptor's sizes.
 tables::KernelSizes kernelSizes(const bdg_dev::CurvedKernelTable& kt, const bdg_sw2d_curved_desc& d) {
@@ -567,6 +665,107 @@ int bdg_sw2d_curved_kernel_info(const bdg_sw2d_curved* s, int filter, int* out, 
         if (!order || !order->info()(s->useNT, s->ncb, s->ng, s->fb, !s->identityM, filter != 0, v))
             throw arg_error("bdg_sw2d_curved_kernel_info: no compiled kernel serves this solver");
         std::copy(v, v + std::min(n, BDG_SW2D_CURVED_KERNEL_INFO_FIELDS), out);
+    });
+}
+
+// ---- the driver's adaptive step, blow-up check and output fields (sw2d_curved.py:231-302)
+
+int bdg_sw2d_curved_enable_driver(bdg_sw2d_curved* s, const bdg_sw2d_curved_driver_desc* d) {
+    return curvedCall(s, "bdg_sw2d_curved_enable_driver", [&] {
+        if (!d || !d->Fscale || !d->vmapM || !d->Dr || !d->Ds || !d->rx || !d->sx || !d->ry || !d->sy)
+            throw arg_error("bdg_sw2d_curved_enable_driver: NULL argument (Fscale, vmapM, Dr, Ds, rx, sx, ry, sy are required)");
+        const int Np = s->Np, nFace = 3 * (s->N + 1);
+        const std::vector<int> faceNodes = driverFaceNodes(d->vmapM, Np, nFace, s->K); // nothing is changed before this passes
+        bdg_sw2d_curved::Driver& v = s->drv;
+        v.on = false;
+        v.nFace = nFace;
+        s->uploadPlanes(v.fscale, d->Fscale, nFace);
+        v.hasC = d->c != nullptr;
+        v.cConst = d->c_const;
+        if (d->c) s->uploadPlanes(v.c, d->c, Np);
+        v.hasH = d->H != nullptr;
+        if (d->H) s->uploadPlanes(v.H, d->H, Np);
+        const size_t mm = static_cast<size_t>(Np) * Np;
+        std::vector<double> deriv(d->Dr, d->Dr + mm);
+        deriv.insert(deriv.end(), d->Ds, d->Ds + mm);
+        s->queueUpload(v.deriv, deriv, "Dr, Ds upload");
+        s->queueUpload(v.faceNodes, faceNodes, "face-node list upload");
+        v.metric.alloc(4 * s->plane(), s->bytes, s->stream);
+        const double* metric[4] = {d->rx, d->sx, d->ry, d->sy};
+        for (int i = 0; i < 4; ++i) s->uploadRows(metric[i], v.metric.p + i * s->plane(), Np); // (waits: deriv, faceNodes are up)
+        v.IM.alloc(mm, s->bytes);
+        v.out.alloc(bdg_dev::CURVED_OUT_FIELDS * s->plane(), s->bytes, s->stream);
+        v.partials.alloc(static_cast<size_t>(3) * ((s->K + bdg_dev::kCurvedDrvThreads - 1) / bdg_dev::kCurvedDrvThreads), s->bytes);
+        v.result.alloc(3, s->bytes);
+        hipCheck(hipStreamSynchronize(s->stream), "driver tables sync");
+        v.on = true;
+    });
+}
+
+int bdg_sw2d_curved_compute_dt(bdg_sw2d_curved* s, double cfl, double* dt, double* h_max) {
+    return driverCall(s, "bdg_sw2d_curved_compute_dt", [&] {
+        double r[2] = {0.0, 0.0};
+        try {
+            s->reduceDt(r);
+        } catch (const unstable_error&) { // the values are reported with the verdict
+            if (h_max) *h_max = r[1];
+            if (dt) *dt = cfl / r[0];
+            throw;
+        }
+        if (h_max) *h_max = r[1];
+        if (dt) *dt = cfl / r[0];
+    });
+}
+
+int bdg_sw2d_curved_run_adaptive(bdg_sw2d_curved* s, double cfl, double final_time, int max_steps, int filter, double* t_inout,
+                                 double* dt_inout, int* steps_done) {
+    int done = 0;
+    const int rc = driverCall(s, "bdg_sw2d_curved_run_adaptive", [&] {
+        if (!t_inout || !dt_inout) throw arg_error("bdg_sw2d_curved_run_adaptive: NULL argument");
+        if (s->halo.comm) throw arg_error("bdg_sw2d_curved_run_adaptive: not available on a solver with a communicator (no rank-global dt)");
+        s->requireFilter(filter != 0);
+        double t = *t_inout, dt = *dt_inout;
+        while (t < final_time && (max_steps <= 0 || done < max_steps)) { // the script's loop, in its order
+            s->stepRk2(dt, 1, filter != 0, bdg_sw2d_curved::Eval::Whole);
+            t += dt;
+            double r[2];
+            s->reduceDt(r);
+            dt = cfl / r[0];
+            ++done;
+            *t_inout = t;
+            *dt_inout = dt;
+        }
+    });
+    if (steps_done) *steps_done = done;
+    return rc;
+}
+
+int bdg_sw2d_curved_output_fields(bdg_sw2d_curved* s, const double* IM, double* eta, double* u, double* v, double* B, double* h,
+                                  double* vort) {
+    return driverCall(s, "bdg_sw2d_curved_output_fields", [&] {
+        double* target[bdg_dev::CURVED_OUT_FIELDS] = {eta, u, v, B, h, vort};
+        int mask = 0;
+        for (int c = 0; c < bdg_dev::CURVED_OUT_FIELDS; ++c) mask |= target[c] ? 1 << c : 0;
+        if (!mask) return;
+        if (IM) s->stageLattice(IM);
+        s->outputLaunch(mask, IM != nullptr);
+        // the owned columns of each row alone: the caller's ghost columns stay as they are
+        const size_t width = static_cast<size_t>(s->owned()) * sizeof(double);
+        for (int c = 0; c < bdg_dev::CURVED_OUT_FIELDS; ++c)
+            if (target[c])
+                copyRows(target[c], static_cast<size_t>(s->K) * sizeof(double), s->drv.out.p + c * s->plane(),
+                         static_cast<size_t>(s->ld) * sizeof(double), width, static_cast<size_t>(s->Np), hipMemcpyDeviceToHost, s->stream);
+    });
+}
+
+int bdg_sw2d_curved_time_driver(bdg_sw2d_curved* s, int which, const double* IM, int count, float* ms) {
+    return driverCall(s, "bdg_sw2d_curved_time_driver", [&] {
+        if (!ms || count < 1 || (which != 0 && which != 1)) throw arg_error("bdg_sw2d_curved_time_driver: bad argument");
+        if (which == 1 && IM) s->stageLattice(IM);
+        const int all = (1 << bdg_dev::CURVED_OUT_FIELDS) - 1;
+        auto launch = [&] { which == 0 ? s->dtPass() : s->outputLaunch(all, IM != nullptr); };
+        for (int i = 0; i < 10; ++i) launch(); // untimed
+        *ms = bdg_dev::timePerRun(s->stream, count, launch);
     });
 }
 

@@ -708,7 +708,9 @@ class VtkOutputter:
         primitive variables and lattice interpolation happen on the device, the host only cuts the
         lattice into triangles and writes. Returns the file paths. On a QuadNodesProvisioner ``solver`` is a
         ``sw2dquads.Sw2dQuadSolver`` (one device launch for eta = h - H, u, v and, with four fields, N; the host cuts the
-        lattice into quadrilaterals); ``H`` is the still-water depth of that solver's eta (None: eta = h)."""
+        lattice into quadrilaterals); ``H`` is the still-water depth of that solver's eta (None: eta = h). A
+        ``sw2d_curved.Sw2dCurvedSolver`` (after ``enableDriver``, which takes its H) gets the six files of the reference's
+        sw2d_curved.py, ``{eta,u,v,B,h,vort}NNNNNNN.vtu``, the same way."""
         import os
         if self._quads:
             return self._writeQuadSolverFields(solver, tstep, directory, H)
@@ -726,7 +728,10 @@ class VtkOutputter:
                 self._lattice = (IM, cut, xt, yt)
         IM, cut, xt, yt = self._lattice
         paths = []
-        fields = list(zip(("eta", "u", "v"), solver.outputFields(IM)))
+        if hasattr(solver, "enableDriver"):                      # sw2d_curved.Sw2dCurvedSolver: six fields, one launch
+            fields = list(solver.outputFields(IM).items())
+        else:
+            fields = list(zip(("eta", "u", "v"), solver.outputFields(IM)))
         if getattr(solver, "fields", 3) == 4:
             fields.append(("N", solver.outputTracer(IM)))       # the reference script's fourth output field
         for name, lat in fields:

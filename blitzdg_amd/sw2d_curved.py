@@ -81,6 +81,7 @@ class Sw2dCurvedSolver:
         self._h = h
         self.Np, self.K, self.order, self.Ncub, self.NGauss = Np, K, order, Ncub, NG
         self.hasFilter = d.Filter is not None
+        self.g = float(g)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -142,6 +143,70 @@ class Sw2dCurvedSolver:
     def rk2Phase(self, dt, phase, filter=True):
         """phase 0: intermediate = state + dt/2 RHS(state); phase 1: state += dt RHS(intermediate)."""
         check(lib.bdg_sw2d_curved_rk2_phase(self._h, float(dt), int(phase), int(bool(filter))))
+
+    # ---- the rest of the driver's loop (sw2d_curved.py:231-302): adaptive dt, blow-up check, output fields
+    OUTPUT_FIELDS = ("eta", "u", "v", "B", "h", "vort")
+
+    def enableDriver(self, ctx, H=None, c=None):
+        """Hands the tables of the driver's dt formula and output step to the device: Fscale, vmapM, Dr, Ds, rx, sx, ry, sy of
+        ``ctx`` (the provisioner's context is live: after ``setCoordinates`` its metrics are the deformed ones), the still-water
+        depth ``H`` of eta = h - H (None: eta = h) and the wave speed ``c`` of the dt formula, a scalar or an (Np, K) array
+        (default: sqrt(g mean(H)), the script's; required when H is None). A second call replaces the tables."""
+        Np, K = self.Np, self.K
+        nface = 3 * (self.order + 1)
+        d = C.Sw2dCurvedDriverDesc()
+        keep = [C.as_f64(ctx.Fscale, (nface, K), "ctx.Fscale"), C.as_i32(np.asarray(ctx.vmapM).reshape(-1))]
+        if keep[1].size != nface * K:
+            raise ValueError(f"ctx.vmapM: expected {nface * K} entries, got {keep[1].size}")
+        d.Fscale, d.vmapM = C.ptr(keep[0]), C.ptr(keep[1])
+        Harr = C.as_f64(H, (Np, K), "H") if H is not None else None
+        if c is None:
+            if Harr is None:
+                raise ValueError("enableDriver: c is required when H is None")
+            c = float(np.sqrt(self.g * np.mean(Harr)))
+        if np.ndim(c) == 0:
+            carr, d.c_const = None, float(c)
+        else:
+            carr, d.c_const = C.as_f64(c, (Np, K), "c"), 0.0
+        d.c, d.H = C.ptr(carr), C.ptr(Harr)
+        for name, shape in (("Dr", (Np, Np)), ("Ds", (Np, Np)), ("rx", (Np, K)), ("sx", (Np, K)), ("ry", (Np, K)), ("sy", (Np, K))):
+            keep.append(C.as_f64(getattr(ctx, name), shape, "ctx." + name))
+            setattr(d, name, C.ptr(keep[-1]))
+        check(lib.bdg_sw2d_curved_enable_driver(self._h, byref(d)))
+
+    def computeDt(self, CFL):
+        """(dt, max|h|) of the resident state by the script's formula (sw2d_curved.py:281), bit for bit; raises
+        NumericalInstability on a NaN or max|h| > 1e8."""
+        dt, hm = c_double(), c_double()
+        check(lib.bdg_sw2d_curved_compute_dt(self._h, float(CFL), byref(dt), byref(hm)))
+        return dt.value, hm.value
+
+    def runAdaptive(self, CFL, finalTime, t=0.0, dt=None, maxSteps=0, filter=True):
+        """The script's while-loop (sw2d_curved.py:246-288): RK2 + filter step with dt, t += dt, dt recomputed, blow-up check.
+        Returns (t, dt, steps); the conventions of Sw2dSolver.runAdaptive."""
+        if dt is None:
+            dt, _ = self.computeDt(CFL)
+        tt, dd, st = c_double(t), c_double(dt), C.c_int()
+        check(lib.bdg_sw2d_curved_run_adaptive(self._h, float(CFL), float(finalTime), int(maxSteps), int(bool(filter)),
+                                               byref(tt), byref(dd), byref(st)))
+        return tt.value, dd.value, st.value
+
+    def outputFields(self, IM=None, fields=OUTPUT_FIELDS):
+        """{eta, u, v, B, h, vort} of the resident state as (Np, K) arrays, formed on the device in one launch; with ``IM`` (from
+        ``nodes.splitOperators()``) interpolated there to the equispaced lattice the *.vtu writer uses. Ghost columns of a
+        partitioned solver are left at zero."""
+        m = C.as_f64(IM, (self.Np, self.Np), "IM") if IM is not None else None
+        out = {k: np.zeros((self.Np, self.K)) for k in fields}
+        check(lib.bdg_sw2d_curved_output_fields(self._h, C.ptr(m), *[C.ptr(out.get(k)) for k in self.OUTPUT_FIELDS]))
+        return out
+
+    def timeDriver(self, which, count, IM=None):
+        """Average device milliseconds of ``count`` dt passes (which = "dt") or six-field output launches (which = "output",
+        nodal or with ``IM``), after 10 untimed ones."""
+        m = C.as_f64(IM, (self.Np, self.Np), "IM") if IM is not None else None
+        ms = c_float()
+        check(lib.bdg_sw2d_curved_time_driver(self._h, {"dt": 0, "output": 1}[which], C.ptr(m), int(count), byref(ms)))
+        return ms.value
 
     KERNEL_INFO_FIELDS = ("form", "streamed", "image_in_lds", "fb", "live_steps", "waves", "mapm", "lds_bytes")
 

@@ -965,6 +965,45 @@ int bdg_sw2d_curved_form(const bdg_sw2d_curved* s);
 #define BDG_SW2D_CURVED_KERNEL_INFO_FIELDS 8
 int bdg_sw2d_curved_kernel_info(const bdg_sw2d_curved* s, int filter, int* out, int n);
 
+/* ---- The rest of the reference driver's loop (sw2d_curved.py:231-302) on the resident state: the time step recomputed after
+ * every step, the blow-up check, and the six output fields. Kernels: csrc/hip/sw2d_curved_driver_kernel.hpp. A solver on which
+ * enable_driver was never called launches exactly what it launched before these calls existed. */
+typedef struct bdg_sw2d_curved_driver_desc {
+    const double* Fscale;   /* (3 Nfp, K)  ctx.Fscale */
+    const int*    vmapM;    /* (3 Nfp K)   ctx.vmapM, flat, node + Np k */
+    const double* c;        /* (Np, K) wave speed of the dt formula, or NULL: c_const */
+    double        c_const;
+    const double* H;        /* (Np, K) or NULL: eta = h */
+    const double* Dr; const double* Ds;              /* (Np, Np) */
+    const double* rx; const double* sx; const double* ry; const double* sy;   /* (Np, K) */
+} bdg_sw2d_curved_driver_desc;
+/* Validated on the host before the device is touched: vmapM[j + 3 Nfp k] must be a node of element k, and its local part the
+ * same list of 3 Nfp face nodes in every element (that list is what the device gets). BDG_ERR_ARGUMENT, and nothing changed, for
+ * a NULL required pointer or a vmapM that fails either check. A second call replaces the tables. The calls below return
+ * BDG_ERR_ARGUMENT until this one has succeeded. */
+int bdg_sw2d_curved_enable_driver(bdg_sw2d_curved* s, const bdg_sw2d_curved_driver_desc* d);
+/* dt = cfl / max_{j,k} ( ((N+1)^2 0.5 |Fscale[j,k]|) (c[n_j,k] + sqrt(u[n_j,k]^2 + v[n_j,k]^2)) ),  u = hu / h, v = hv / h, n_j the
+ * face-node list, over the owned elements ([0, num_owned) after set_partition, else all), in that association with contraction
+ * off and correctly rounded division and square root: the NumPy expression of sw2d_curved.py:281 on the downloaded state, bit
+ * for bit. h_max = max|h|. BDG_ERR_UNSTABLE (dt and h_max still stored) when an owned h or a speed is NaN or h_max > 1e8. */
+int bdg_sw2d_curved_compute_dt(bdg_sw2d_curved* s, double cfl, double* dt, double* h_max);
+/* The script's loop in the script's order:
+ *   while t < final_time and (max_steps <= 0 or done < max_steps):
+ *       RK2 + filter step with dt;  t += dt;  dt = compute_dt (BDG_ERR_UNSTABLE on blow-up);  ++done;  t, dt written back
+ * The last step is not clipped to final_time (the script does not clip it either). One small device-to-host copy per step.
+ * BDG_ERR_ARGUMENT on a solver with a communicator (bdg_sw2d_curved_comm_init): there is no rank-global dt. */
+int bdg_sw2d_curved_run_adaptive(bdg_sw2d_curved* s, double cfl, double final_time, int max_steps, int filter,
+                                 double* t_inout, double* dt_inout, int* steps_done);
+/* eta = h - H, u = hu / h, v = hv / h, B = hN / h, h and vort = (rx Dr v + sx Ds v) - (ry Dr u + sy Ds u) of the resident state as
+ * (Np, K) arrays, one launch for all the non-NULL ones; only the owned columns are written. IM == NULL: nodal values (the five
+ * pointwise fields equal the expressions on the downloaded state bit for bit). Otherwise every field is multiplied by the
+ * (Np, Np) matrix of TriangleNodesProvisioner::splitOperators. Every sum runs over ascending node index from 0.0. */
+int bdg_sw2d_curved_output_fields(bdg_sw2d_curved* s, const double* IM, double* eta, double* u, double* v,
+                                  double* B, double* h, double* vort);
+/* Average device milliseconds (HIP events on the solver's stream, after 10 untimed launches) of `count` dt passes (which = 0) or
+ * output launches of all six fields (which = 1; IM as above). */
+int bdg_sw2d_curved_time_driver(bdg_sw2d_curved* s, int which, const double* IM, int count, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
