@@ -140,10 +140,12 @@ def build_sponge_coeff(t, mapO, strength, radius):
     return out
 
 
-def sw2d_rhs_b(h, hu, hv, H, Hx, Hy, g, f, CD, time, t, mapO=(), global_lf=True, tide=None, owned=None, reduce_speed=None):
+def sw2d_rhs_b(h, hu, hv, H, Hx, Hy, g, f, CD, time, t, mapO=(), global_lf=True, tide=None, owned=None, reduce_speed=None,
+               speeds_only=False):
     """main.cpp:279-484. t: tables as for sw2d_rhs4; mapO: open-boundary face nodes (BCmap[2]).
     Partitioned runs (tests): owned = number of owned elements of a rank-local mesh (the ghost elements behind them
-    take no part in the speed maximum), reduce_speed = the all-rank maximum of this rank's value."""
+    take no part in the speed maximum), reduce_speed = the all-rank maximum of this rank's value.
+    speeds_only: return the two per-face-node speeds (:400-414) whose maximum is the global speed, (spdM, spdP), instead."""
     Nfp = t["nx"].shape[0] // 3
     K = t["rx"].shape[1]
     vM, vP = np.asarray(t["vmapM"]), np.asarray(t["vmapP"])
@@ -179,7 +181,10 @@ def sw2d_rhs_b(h, hu, hv, H, Hx, Hy, g, f, CD, time, t, mapO=(), global_lf=True,
     FP, GP = (huP, F2P, G2P), (hvP, G2P, G3P)
     F2, G2, G3 = (hu * hu) / h + 0.5 * g * h * h, (hu * hv) / h, (hv * hv) / h + 0.5 * g * h * h
     F, G = (hu, F2, G2), (hv, G2, G3)
-    spd = np.maximum(np.sqrt(uM * uM + vMv * vMv) + np.sqrt(g * hM), np.sqrt(uP * uP + vPv * vPv) + np.sqrt(g * hP))
+    spdM, spdP = np.sqrt(uM * uM + vMv * vMv) + np.sqrt(g * hM), np.sqrt(uP * uP + vPv * vPv) + np.sqrt(g * hP)
+    if speeds_only:
+        return spdM, spdP
+    spd = np.maximum(spdM, spdP)
     if global_lf:
         top = spd.max() if owned is None else spd[:3 * Nfp * owned].max()
         lam = np.full_like(spd, top if reduce_speed is None else reduce_speed(top))   # :414

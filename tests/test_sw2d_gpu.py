@@ -19,6 +19,7 @@ import blitzdg_amd.pyblitzdg as dg
 from blitzdg_amd import sw2d
 from blitzdg_amd._capi import BdgError, NumericalInstability
 from conftest import launch, load_case, oracle_from, relmax, seeded_fields, tables_from_nodes
+from reduction_cases import dt_numpy
 from regimes import assert_fields_close
 
 pytestmark = pytest.mark.gpu
@@ -282,6 +283,9 @@ def test_full_size_properties(N, nx, ny):
     h0 = 10.0 + np.exp(-10 * x * x - 10 * y * y)
     s.setState(h0, z, z)
     dt, _ = s.computeDt(0.65)
+    # the documented expression, vectorised (tests/test_reduction_cases.py: the C oracle's value bit for bit): every trip of the
+    # finishing loop over 3907 (N = 4) / 977 (N = 8) blocks
+    assert dt == dt_numpy(h0, z, z, ctx.Fscale, ctx.vmapM, 9.81, 0.65, N)
     s.stepLSERK4(dt, 3)
     h1, hu1, hv1 = s.getState()
     mass0, mass1 = (w[:, None] * J * h0).sum(), (w[:, None] * J * h1).sum()

