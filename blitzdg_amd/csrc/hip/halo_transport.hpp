@@ -137,4 +137,8 @@ struct Transport {
     }
 };
 
+inline void requireComm(const Transport& halo, const std::string& prefix, const char* fn) {
+    if (!halo.comm) throw bdg_detail::arg_error(std::string(fn) + ": no communicator (call " + prefix + "_comm_init first)");
+}
+
 } // namespace bdg_halo

@@ -116,10 +116,6 @@ inline void commInit(const std::string& prefix, Transport& halo, const Partition
     hipCheck(hipStreamSynchronize(stream), "exchange buffers");
 }
 
-inline void requireComm(const Transport& halo, const std::string& prefix, const char* fn) {
-    if (!halo.comm) throw arg_error(std::string(fn) + ": no communicator (call " + prefix + "_comm_init first)");
-}
-
 namespace { // (calls the pack / unpack of this translation unit)
 // ghost columns of `state` (K columns of leading dimension ld) from their owners: pack -> grouped send / receive with
 // every neighbour -> unpack, in the order of stream `on`

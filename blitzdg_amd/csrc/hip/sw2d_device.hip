@@ -18,11 +18,10 @@
 #include "../host/element_order.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
-#include "halo_transport.hpp"
+#include "run_records.hpp"
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
 #include "sw2d_drifter_kernel.hpp"
-#include "sw2d_monitor_kernel.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -298,24 +297,13 @@ struct bdg_sw2d {
     double dtStage = 0.0;
     std::vector<int> permHost; // caller element -> device slot (empty = identity)
     // run monitor (bdg_sw2d_enable_monitor): sw2d_monitor_kernel.hpp
-    struct Monitor {
-        bool on = false;
-        int stride = 1, capacity = 0, numGauges = 0, width = 0;
-        int count = 0;        // records taken
-        int reduced = 0;      // records [0, reduced) have been all-reduced
-        long long steps = 0;  // completed steps since set_state / monitor_reset
-        DevBuf<double> w, H, row, partials, rec, stage, scratch;
-        DevBuf<int> slot;     // device slot of each gauge's element
+    struct Monitor : bdg_records::MonitorState {
+        DevBuf<double> row;     // (numGauges, Np): the nodal basis at each gauge
+        DevBuf<double> scratch; // the record bdg_sw2d_monitor_time writes
     } mon;
     // drifters (bdg_sw2d_enable_drifters): sw2d_drifter_kernel.hpp; elements and neighbours in device slots
-    struct Drifters {
-        bool on = false;
-        int n = 0, stride = 1, capacity = 0;
-        int count = 0;        // records taken
-        long long steps = 0;  // advances made
-        double t = 0.0;       // time of the next record: the model time in the stepping calls, + dt per bdg_sw2d_drifters_advance
-        DevBuf<double> vert, vinvT, jac, x, y, r, s, u0, v0, recT, recX, recY;
-        DevBuf<int> neigh, k, status, recStatus;
+    struct Drifters : bdg_records::DrifterState {
+        DevBuf<double> vert, vinvT, jac;
         std::vector<int> callerOf; // device slot -> caller element (empty = identity)
     } drf;
     bool partitionSet = false; // bdg_sw2d_set_partition has been called
@@ -952,64 +940,30 @@ struct bdg_sw2d {
         filterT.upload(ft, bytes, "filter upload");
     }
 
-    // ---- run monitor
+    // ---- run monitor and drifters (run_records.hpp)
     // records a stepping call of `steps` further completed steps would take; refused before anything is launched
-    void monitorReserve(long long steps, const char* fn) const {
-        if (!mon.on) return;
-        const long long take = (mon.steps + steps) / mon.stride - mon.steps / mon.stride;
-        if (take > mon.capacity - mon.count)
-            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " monitor records and " +
-                            std::to_string(mon.capacity - mon.count) + " are free (bdg_sw2d_monitor_read, then bdg_sw2d_monitor_reset)");
-    }
+    void monitorReserve(long long steps, const char* fn) const { mon.reserve(steps, fn, "bdg_sw2d"); }
+    void drifterReserve(long long steps, const char* fn) const { drf.reserve(steps, fn, "bdg_sw2d"); }
     // completed LSERK4 steps among the next `stages` stages
-    long long lserkSteps(long long stages) const {
-        return (stageCount + stages) / blitzdg::LSERK4::numStages - stageCount / blitzdg::LSERK4::numStages;
-    }
+    long long lserkSteps(long long stages) const { return bdg_records::lserkSteps(stageCount, stages, blitzdg::LSERK4::numStages); }
     // one record of the resident state into rec[column * capacity + slot], two launches on the solver's stream. The range
     // reduced is the owned device slots [0, numOwned); H: the monitor's own, else the solver's resident one, else none
     void monitorLaunch(double* rec, int capacity, int slot) {
-        using namespace bdg_dev;
         const double* Hm = mon.H.p ? mon.H.p : (hasH ? Hbuf.p : nullptr);
-        const TriMonParams rp{qcur, mon.w.p, Hm, ld, Np, nf, numOwned, triMonChunk(numOwned), g};
-        hipLaunchKernelGGL(sw2d_monitor_reduce_kernel, dim3(kTriMonBlocks), dim3(kTriMonThreads), 0, stream, rp, mon.partials.p);
-        hipCheck(hipGetLastError(), "sw2d_monitor_reduce_kernel launch");
-        const TriMonFinish fp{mon.partials.p, qcur, Hm, mon.slot.p, mon.row.p, rec, ld, Np, nf, numOwned, mon.numGauges, capacity,
-                              slot, timeNow};
-        hipLaunchKernelGGL(sw2d_monitor_finish_kernel, dim3(1), dim3(kTriMonThreads), 0, stream, fp);
-        hipCheck(hipGetLastError(), "sw2d_monitor_finish_kernel launch");
+        mon.launch({qcur, Hm, ld, Np, nf, numOwned, g, timeNow}, rec, capacity, slot, bdg_dev::sw2d_monitor_finish_kernel,
+                   "sw2d_monitor_finish_kernel launch", bdg_dev::MonRowGauges{mon.row.p}, stream);
     }
-    void monitorSample() {
-        monitorLaunch(mon.rec.p, mon.capacity, mon.count);
-        ++mon.count;
-    }
-    // ---- drifters
-    // as monitorReserve: records `steps` further advances would take
-    void drifterReserve(long long steps, const char* fn) const {
-        if (!drf.on) return;
-        const long long take = (drf.steps + steps) / drf.stride - drf.steps / drf.stride;
-        if (take > drf.capacity - drf.count)
-            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " drifter records and " +
-                            std::to_string(drf.capacity - drf.count) + " are free (bdg_sw2d_drifters_read, then bdg_sw2d_drifters_reset)");
-    }
+    void monitorSample() { monitorLaunch(mon.rec.p, mon.capacity, mon.count++); }
     // one launch of the drifter kernel on the solver's stream, reading the current state; slot < 0: no record
     void drifterLaunch(int mode, double dt, int slot) {
-        using namespace bdg_dev;
-        const TriDriftParams p{qcur, drf.vert.p, drf.neigh.p, drf.vinvT.p, drf.jac.p, drf.x.p, drf.y.p, drf.r.p, drf.s.p, drf.u0.p,
-                               drf.v0.p, drf.k.p, drf.status.p, drf.recT.p, drf.recX.p, drf.recY.p, drf.recStatus.p, ld, N, drf.n,
-                               mode, slot, dt, drf.t};
-        hipLaunchKernelGGL(sw2d_drifter_kernel, dim3((drf.n + kTriDriftThreads - 1) / kTriDriftThreads), dim3(kTriDriftThreads), 0,
-                           stream, p);
-        hipCheck(hipGetLastError(), "sw2d_drifter_kernel launch");
+        drf.launch(bdg_dev::sw2d_drifter_kernel, "sw2d_drifter_kernel launch",
+                   bdg_dev::TriDriftTables{drf.vert.p, drf.neigh.p, drf.vinvT.p, drf.jac.p}, qcur, ld, N, mode, dt, slot, stream);
     }
     // one advance in the resident state, with the record of time drf.t if one is due (room was reserved by the caller)
-    void drifterAdvance(double dt, bool record = true) {
-        const bool due = record && ++drf.steps % drf.stride == 0;
-        drifterLaunch(bdg_dev::kTriDriftAdvance, dt, due ? drf.count : -1);
-        if (due) ++drf.count;
-    }
+    void drifterAdvance(double dt, bool record = true) { drifterLaunch(bdg_dev::kDriftAdvance, dt, drf.takeSlot(record)); }
     // (u0, v0) again after the state under the drifters has been replaced
     void drifterResample() {
-        if (drf.on) drifterLaunch(bdg_dev::kTriDriftSample, 0.0, -1);
+        if (drf.on) drifterLaunch(bdg_dev::kDriftSample, 0.0, -1);
     }
     // after every completed step (of size dt) of a stepping call whose launches are all on the solver's stream (room was reserved
     // by the caller): the monitor's sample, then the drifters' advance (drifters exist on unpartitioned solvers only)
@@ -2138,66 +2092,42 @@ int bdg_sw2d_barrier(bdg_sw2d* s) {
     });
 }
 
-// ---- run monitor
+// ---- run monitor (what the quadrilateral solver has too: run_records.hpp)
 int bdg_sw2d_enable_monitor(bdg_sw2d* s, const bdg_sw2d_monitor_desc* d) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2d_enable_monitor");
-        if (!d || !d->weights) throw arg_error("bdg_sw2d_enable_monitor: the descriptor and its weights are required");
-        if (s->mon.on) throw arg_error("bdg_sw2d_enable_monitor: the monitor is already enabled");
-        if (d->stride < 1 || d->capacity < 1) throw arg_error("bdg_sw2d_enable_monitor: stride and capacity must be >= 1");
+        const std::string fn = "bdg_sw2d_enable_monitor";
+        requireSolver(s, fn.c_str());
+        bdg_sw2d::Monitor& m = s->mon;
+        m.checkEnable(fn, d, s->K);
         const int ng = d->num_gauges, Np = s->Np;
-        if (ng < 0 || (ng > 0 && (!d->gauge_element || !d->gauge_row))) throw arg_error("bdg_sw2d_enable_monitor: bad gauge list");
+        if (ng > 0 && !d->gauge_row) throw arg_error(fn + ": bad gauge list");
         // the gauges' elements in device slots (the caller's numbering through the renumbering, if there is one)
         std::vector<int> slots(static_cast<size_t>(std::max(1, ng)), 0);
-        for (int i = 0; i < ng; ++i) {
-            const int e = d->gauge_element[i];
-            if (e < 0 || e >= s->K)
-                throw arg_error("bdg_sw2d_enable_monitor: gauge " + std::to_string(i) + " names an element outside [0, K)");
-            slots[i] = s->permHost.empty() ? e : s->permHost[e];
-        }
-        const int width = 7 + s->nf + ng * s->nf;
+        for (int i = 0; i < ng; ++i) slots[i] = s->permHost.empty() ? d->gauge_element[i] : s->permHost[d->gauge_element[i]];
         s->use();
-        bdg_sw2d::Monitor& m = s->mon;
-        const size_t bytesBefore = s->bytes;
-        try {
+        m.enable(d->stride, d->capacity, ng, s->nf, slots.data(), {&m.row, &m.scratch}, &m.scratch, s->bytes, s->stream, [&] {
             // the weight plane (and H) zero-padded and through the solver's own upload, so that they follow the renumbering
             s->uploadPlane(d->weights, m.w);
             if (d->H) s->uploadPlane(d->H, m.H);
             m.row.alloc(static_cast<size_t>(std::max(1, ng)) * Np, s->bytes, s->stream);
-            m.slot.alloc(slots.size(), s->bytes, s->stream);
-            if (ng > 0) {
+            if (ng > 0)
                 hipCheck(hipMemcpyAsync(m.row.p, d->gauge_row, static_cast<size_t>(ng) * Np * sizeof(double), hipMemcpyHostToDevice,
                                         s->stream), "hipMemcpy (gauge rows)");
-                hipCheck(hipMemcpyAsync(m.slot.p, slots.data(), static_cast<size_t>(ng) * sizeof(int), hipMemcpyHostToDevice, s->stream),
-                         "hipMemcpy (gauges)");
-            }
-            m.partials.alloc(static_cast<size_t>(bdg_dev::kTriMonBlocks) * bdg_dev::kTriMonPartial, s->bytes, s->stream);
-            m.rec.alloc(static_cast<size_t>(width) * d->capacity, s->bytes, s->stream);
-            m.scratch.alloc(static_cast<size_t>(width), s->bytes, s->stream); // the record bdg_sw2d_monitor_time writes
-            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vector dies here
-        } catch (...) { // nothing changes: the solver stays without a monitor
-            (void)hipStreamSynchronize(s->stream);
-            for (DevBuf<double>* b : {&m.w, &m.H, &m.row, &m.partials, &m.rec, &m.scratch}) b->release();
-            m.slot.release();
-            s->bytes = bytesBefore;
-            throw;
-        }
-        m.on = true;
-        m.stride = d->stride; m.capacity = d->capacity; m.numGauges = ng; m.width = width;
+        });
     });
 }
 
 namespace {
 void requireMonitorOn(const bdg_sw2d* s, const char* fn) {
     requireSolver(s, fn);
-    if (!s->mon.on) throw arg_error(std::string(fn) + ": the monitor is not enabled (bdg_sw2d_enable_monitor)");
+    s->mon.requireOn(fn, "bdg_sw2d");
 }
 } // namespace
 
 int bdg_sw2d_monitor_sample(bdg_sw2d* s) {
     return guard([&] {
         requireMonitorOn(s, "bdg_sw2d_monitor_sample");
-        if (s->mon.count >= s->mon.capacity) throw arg_error("bdg_sw2d_monitor_sample: no free record (bdg_sw2d_monitor_reset)");
+        s->mon.requireFree("bdg_sw2d_monitor_sample", "bdg_sw2d");
         s->use();
         s->monitorSample();
     });
@@ -2222,54 +2152,24 @@ int bdg_sw2d_monitor_width(const bdg_sw2d* s, int* width) {
 int bdg_sw2d_monitor_read(bdg_sw2d* s, int first, int count, double* records) {
     return guard([&] {
         requireMonitorOn(s, "bdg_sw2d_monitor_read");
-        if (first < 0 || count < 0 || first > s->mon.count - count || (count > 0 && !records))
-            throw arg_error("bdg_sw2d_monitor_read: bad record range");
-        if (count == 0) return;
         s->use();
-        const int width = s->mon.width;
-        std::vector<double> cols(static_cast<size_t>(width) * count); // by column, as on the device
-        hipCheck(hipMemcpy2DAsync(cols.data(), count * sizeof(double), s->mon.rec.p + first, s->mon.capacity * sizeof(double),
-                                  count * sizeof(double), width, hipMemcpyDeviceToHost, s->stream), "hipMemcpy2D (records)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        for (int n = 0; n < count; ++n)
-            for (int c = 0; c < width; ++c) records[static_cast<size_t>(n) * width + c] = cols[static_cast<size_t>(c) * count + n];
+        s->mon.read("bdg_sw2d_monitor_read", first, count, records, s->stream);
     });
 }
 
 int bdg_sw2d_monitor_reset(bdg_sw2d* s) {
     return guard([&] {
         requireMonitorOn(s, "bdg_sw2d_monitor_reset");
-        s->mon.count = 0;
-        s->mon.reduced = 0;
-        s->mon.steps = 0;
+        s->mon.reset();
     });
 }
 
 int bdg_sw2d_monitor_reduce(bdg_sw2d* s) {
     return guard([&] {
         requireMonitorOn(s, "bdg_sw2d_monitor_reduce");
-        if (!s->halo.comm) throw arg_error("bdg_sw2d_monitor_reduce: no communicator: call bdg_sw2d_comm_init first");
-        bdg_sw2d::Monitor& m = s->mon;
-        const int n = m.count - m.reduced;
-        if (n <= 0) return;
+        bdg_halo::requireComm(s->halo, "bdg_sw2d", "bdg_sw2d_monitor_reduce");
         s->use();
-        // the new records of every column but t, packed by column; the columns that share an operator are contiguous
-        const int cols = m.width - 1, nf = s->nf;
-        if (!m.stage.p) m.stage.alloc(static_cast<size_t>(cols) * m.capacity, s->bytes);
-        hipCheck(hipMemcpy2DAsync(m.stage.p, n * sizeof(double), m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double),
-                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
-        auto reduce = [&](int firstCol, int numCols, ncclRedOp_t op) {
-            if (numCols <= 0) return;
-            double* at = m.stage.p + static_cast<size_t>(firstCol) * n;
-            ncclCheck(rccl().AllReduce(at, at, static_cast<size_t>(numCols) * n, ncclDouble, op, s->halo.comm, s->stream), "ncclAllReduce");
-        };
-        reduce(0, nf + 1, ncclSum);                 // integrals and E
-        reduce(nf + 1, 1, ncclMin);                 // min h
-        reduce(nf + 2, 3, ncclMax);                 // max h, max|hu|, max|hv|
-        reduce(nf + 5, cols - (nf + 5), ncclSum);   // NaN count and gauges
-        hipCheck(hipMemcpy2DAsync(m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double), m.stage.p, n * sizeof(double),
-                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
-        m.reduced = m.count;
+        s->mon.allReduce(s->halo.comm, s->stream, s->nf, s->bytes);
     });
 }
 
@@ -2291,12 +2191,9 @@ int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* d) {
         requireSolver(s, fn.c_str());
         if (!d || d->count < 1 || !d->element || !d->r || !d->s || !d->vertices || !d->neighbours || !d->vinv || !d->jacobi)
             throw arg_error(fn + ": the descriptor, at least one drifter and the tables of bdg_trinodes_drifter_tables are required");
-        if (d->stride < 1 || d->capacity < 1) throw arg_error(fn + ": stride and capacity must be >= 1");
-        if (s->drf.on) throw arg_error(fn + ": drifters are already enabled on this solver; the call is made once");
-        if (s->partitionSet || s->numOwned != s->K || s->halo.comm || s->localGroup)
-            throw arg_error(fn + ": the solver has a partition set; drifters do not migrate between ranks (single domain only)");
+        bdg_sw2d::Drifters& m = s->drf;
+        m.checkEnable(fn, d->count, d->stride, d->capacity, s->partitionSet || s->numOwned != s->K || s->halo.comm || s->localGroup);
         const int n = d->count, K = s->K, Np = s->Np, Nq = s->N + 1;
-        if (static_cast<long long>(n) * d->capacity >= (1LL << 31)) throw arg_error(fn + ": count * capacity must stay below 2^31");
         const int* perm = s->permHost.empty() ? nullptr : s->permHost.data();
         std::vector<int> slots(static_cast<size_t>(n));
         for (int i = 0; i < n; ++i) {
@@ -2308,7 +2205,7 @@ int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* d) {
             slots[i] = perm ? perm[e] : e;
         }
         // the tables in device slots; the kernel follows the neighbour entries without a further check
-        std::vector<int> nb(static_cast<size_t>(4) * K, kTriDriftWall);
+        std::vector<int> nb(static_cast<size_t>(4) * K, kDriftWall);
         std::vector<double> vert(static_cast<size_t>(8) * K);
         std::vector<int> callerOf(static_cast<size_t>(K));
         for (int k = 0; k < K; ++k) {
@@ -2318,55 +2215,29 @@ int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* d) {
             std::copy(line, line + 8, vert.begin() + static_cast<size_t>(8) * slot);
             for (int f = 0; f < 3; ++f) {
                 const int v = d->neighbours[static_cast<size_t>(f) * K + k];
-                if (v < kTriDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
+                if (v < kDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
                 nb[static_cast<size_t>(4) * slot + f] = v < 0 ? v : (perm ? perm[v] : v);
             }
         }
         std::vector<double> vinvT(static_cast<size_t>(Np) * Np);
-        for (int m = 0; m < Np; ++m)
-            for (int c = 0; c < Np; ++c) vinvT[static_cast<size_t>(c) * Np + m] = d->vinv[static_cast<size_t>(m) * Np + c];
+        for (int r = 0; r < Np; ++r)
+            for (int c = 0; c < Np; ++c) vinvT[static_cast<size_t>(c) * Np + r] = d->vinv[static_cast<size_t>(r) * Np + c];
         s->use();
-        bdg_sw2d::Drifters& m = s->drf;
-        const size_t bytesBefore = s->bytes, cells = static_cast<size_t>(n) * d->capacity;
-        try {
-            auto put = [&](auto& buf, const auto* src, size_t count) {
-                buf.alloc(count, s->bytes);
-                hipCheck(hipMemcpyAsync(buf.p, src, count * sizeof(*src), hipMemcpyHostToDevice, s->stream), "hipMemcpy (drifters)");
-            };
-            put(m.vert, vert.data(), vert.size());
-            put(m.neigh, nb.data(), nb.size());
-            put(m.vinvT, vinvT.data(), vinvT.size());
-            put(m.jac, d->jacobi, static_cast<size_t>(Nq + 1) * Nq * 3);
-            put(m.k, slots.data(), slots.size());
-            put(m.r, d->r, static_cast<size_t>(n));
-            put(m.s, d->s, static_cast<size_t>(n));
-            for (DevBuf<double>* b : {&m.x, &m.y, &m.u0, &m.v0}) b->alloc(static_cast<size_t>(n), s->bytes, s->stream);
-            m.status.alloc(static_cast<size_t>(n), s->bytes, s->stream);
-            m.recT.alloc(static_cast<size_t>(d->capacity), s->bytes, s->stream);
-            m.recX.alloc(cells, s->bytes, s->stream);
-            m.recY.alloc(cells, s->bytes, s->stream);
-            m.recStatus.alloc(cells, s->bytes, s->stream);
-            m.n = n;
-            s->drifterLaunch(kTriDriftInit, 0.0, -1); // x, y from the map, (u0, v0) from the resident state
-            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
-        } catch (...) { // nothing changes: the solver stays without drifters
-            (void)hipStreamSynchronize(s->stream);
-            for (DevBuf<double>* b : {&m.vert, &m.vinvT, &m.jac, &m.x, &m.y, &m.r, &m.s, &m.u0, &m.v0, &m.recT, &m.recX, &m.recY}) b->release();
-            for (DevBuf<int>* b : {&m.neigh, &m.k, &m.status, &m.recStatus}) b->release();
-            m.n = 0;
-            s->bytes = bytesBefore;
-            throw;
-        }
+        m.enable(n, d->stride, d->capacity, s->timeNow, nb, slots.data(), d->r, d->s, {&m.vert, &m.vinvT, &m.jac}, s->bytes, s->stream,
+                 [&] {
+                     m.put(m.vert, vert.data(), vert.size(), s->bytes, s->stream);
+                     m.put(m.vinvT, vinvT.data(), vinvT.size(), s->bytes, s->stream);
+                     m.put(m.jac, d->jacobi, static_cast<size_t>(Nq + 1) * Nq * 3, s->bytes, s->stream);
+                 },
+                 [&] { s->drifterLaunch(kDriftInit, 0.0, -1); });
         m.callerOf = perm ? std::move(callerOf) : std::vector<int>();
-        m.on = true;
-        m.stride = d->stride; m.capacity = d->capacity; m.count = 0; m.steps = 0; m.t = s->timeNow;
     });
 }
 
 namespace {
 void requireDriftersOn(const bdg_sw2d* s, const char* fn) {
     requireSolver(s, fn);
-    if (!s->drf.on) throw arg_error(std::string(fn) + ": drifters are not enabled (bdg_sw2d_enable_drifters)");
+    s->drf.requireOn(fn, "bdg_sw2d");
 }
 } // namespace
 
@@ -2396,16 +2267,7 @@ int bdg_sw2d_drifters_state(bdg_sw2d* s, double* x, double* y, int* element, dou
     return guard([&] {
         requireDriftersOn(s, "bdg_sw2d_drifters_state");
         s->use();
-        const bdg_sw2d::Drifters& m = s->drf;
-        const size_t n = static_cast<size_t>(m.n);
-        const std::pair<double*, const double*> dbl[] = {{x, m.x.p}, {y, m.y.p}, {r, m.r.p}, {sref, m.s.p}};
-        for (const auto& c : dbl)
-            if (c.first) hipCheck(hipMemcpyAsync(c.first, c.second, n * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        if (element) hipCheck(hipMemcpyAsync(element, m.k.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        if (status) hipCheck(hipMemcpyAsync(status, m.status.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        if (element && !m.callerOf.empty()) // device slots back to the caller's numbering
-            for (size_t i = 0; i < n; ++i) element[i] = m.callerOf[element[i]];
+        s->drf.downloadState(x, y, element, r, sref, status, s->drf.callerOf, s->stream); // (device slots back to the caller's numbering)
     });
 }
 
@@ -2420,17 +2282,8 @@ int bdg_sw2d_drifters_count(const bdg_sw2d* s, int* num_records, int* num_drifte
 int bdg_sw2d_drifters_read(bdg_sw2d* s, int first, int count, double* t, double* x, double* y, int* status) {
     return guard([&] {
         requireDriftersOn(s, "bdg_sw2d_drifters_read");
-        const bdg_sw2d::Drifters& m = s->drf;
-        if (first < 0 || count < 0 || first > m.count - count) throw arg_error("bdg_sw2d_drifters_read: bad record range");
-        if (count == 0) return;
         s->use();
-        const size_t at = static_cast<size_t>(first) * m.n, cells = static_cast<size_t>(count) * m.n;
-        if (t) hipCheck(hipMemcpyAsync(t, m.recT.p + first, count * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (x) hipCheck(hipMemcpyAsync(x, m.recX.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (y) hipCheck(hipMemcpyAsync(y, m.recY.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (status)
-            hipCheck(hipMemcpyAsync(status, m.recStatus.p + at, cells * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        s->drf.readTracks("bdg_sw2d_drifters_read", first, count, t, x, y, status, s->stream);
     });
 }
 

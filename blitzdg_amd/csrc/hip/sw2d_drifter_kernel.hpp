@@ -1,10 +1,9 @@
 // sw2d_drifter_kernel.hpp -- Lagrangian drifters of the triangle sw2d solver (gfx950 / CDNA4, wave64): points that move with the
 // velocity (hu / h, hv / h) of the resident state, are followed from element to element and recorded, all on the device. The
-// counterpart of sw2d_quad_drifter_kernel.hpp. One launch per advance, on the solver's stream, no atomics, no host synchronisation:
+// launch, its modes, the Heun advance, the status bits and the records are those of sw2d_drifter_driver.hpp, shared with
+// sw2d_quad_drifter_kernel.hpp; this file is the triangle: the tables, the init map, locate and the velocity.
 //
-//   sw2d_drifter_kernel   lane = drifter, kTriDriftThreads per workgroup. mode kTriDriftAdvance: one Heun advance by dt and, with
-//                         slot >= 0, the record of that step; kTriDriftSample: (u0, v0) sampled again from the state (after
-//                         set_state); kTriDriftInit: x, y from (element, r, s), then the sample.
+//   sw2d_drifter_kernel   the driver's body with the policy TriDrift
 //
 // The order is a run-time argument (as in sw2d_monitor_kernel.hpp): one instance serves N = 1..8. The kernel reads the state planes
 // 0..2 in the solver's device layout q[node * ld + slot] (plane stride Np * ld) and the tables below, and writes only the drifter
@@ -14,7 +13,7 @@
 // line per element; vertex 0, 1, 2 sit at (r, s) = (-1, -1), (1, -1), (-1, 1), so face 0 (s = -1) runs from vertex 0 to 1, face 1
 // (r + s = 0) from 1 to 2 and face 2 (r = -1) from 2 to 0. With e1 = v1 - v0, e2 = v2 - v0 the affine map is
 //   x(r, s) = x0 + ((0.5 (1 + r)) e1x + (0.5 (1 + s)) e2x),  y likewise.
-// neigh[4 k + f], f = 0..2: the element across face f, kTriDriftWall or kTriDriftOpen (entry 3 pads to 16 bytes).
+// neigh[4 k + f], f = 0..2: the element across face f, kDriftWall or kDriftOpen (entry 3 pads to 16 bytes).
 // vinvT[n Np + m] = Vinv[m][n], the inverse Vandermonde matrix transposed. jac[(g (N + 1) + n) 3 + (A, B, C)], g = 0 .. N + 1: the
 // three-term recurrences p_0 = A_0, p_n = (A_n x + B_n) p_{n-1} + C_n p_{n-2} (C_1 = 0) of sqrt(2) P_n^(0,0) (g = 0) and of the
 // orthonormal Jacobi polynomials P_n^(2i+1,0) (g = i + 1): the kernel takes no square roots.
@@ -39,49 +38,26 @@
 // every sum ascending from 0.0, no contraction: the gauge rule of sw2d_monitor_kernel.hpp with the row formed on the device. A
 // velocity that is not finite loses the drifter.
 //
-// One advance (Heun): predictor (x*, y*) = (x, y) + dt (u0, v0), located from k, (u*, v*) sampled there (an open face met by the
-// predictor only ends its search: the sample is taken where it stopped); corrector (x, y) += (dt / 2) ((u0, v0) + (u*, v*)),
-// located from the old k; (u0, v0) sampled at the new position. Status: 0 moving, 1 exited through an open face (frozen at the
-// corrector position), 2 lost (frozen where it was before the advance), + 4 once it has touched a wall. Frozen drifters are
-// recorded and not moved. Records are record-major: recT[slot], recX / recY / recStatus[slot * n + drifter].
-//
 // The basis values of a lane live in LDS, sb[m][lane] (run-time indexed, so not in registers; one column per lane: consecutive
 // lanes read consecutive 8-byte words, no bank conflicts, and no barrier). vinvT and jac are read with wave-uniform addresses
 // (scalar loads); four rows are formed per pass over the column, each in its own ascending order. The state reads are scattered
 // 8-byte gathers, 3 Np per evaluation.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sw2d_drifter_driver.hpp"
 
 namespace bdg_dev {
 
-constexpr int kTriDriftThreads = 128;
 constexpr int kTriDriftMaxNp = 45;      // N = 8
 constexpr int kTriDriftHops = 32;
-constexpr int kTriDriftWall = -1;       // neighbour entries
-constexpr int kTriDriftOpen = -2;
-constexpr int kTriDriftExited = 1;      // status
-constexpr int kTriDriftLost = 2;
-constexpr int kTriDriftTouched = 4;
-enum { kTriDriftAdvance = 0, kTriDriftSample = 1, kTriDriftInit = 2 };
 
-struct TriDriftParams {
-    const double* q;        // the state: planes of Np*ld, 0..2 read
+struct TriDriftTables {
     const double* vert;     // 8 per element
     const int* neigh;       // 4 per element
     const double* vinvT;    // Np x Np
     const double* jac;      // (N+2) x (N+1) x 3
-    double* x; double* y; double* r; double* s; double* u0; double* v0;   // per drifter
-    int* k; int* status;
-    double* recT;           // [capacity]
-    double* recX;           // [capacity * n], record-major
-    double* recY;
-    int* recStatus;
-    long long ld;
-    int N, n, mode, slot;   // slot < 0: no record
-    double dt, t;
 };
 
-// 0 found, kTriDriftExited or kTriDriftLost; k, r, s and (at a wall) x, y updated; wall: kTriDriftTouched or 0
+// 0 found, kDriftExited or kDriftLost; k, r, s and (at a wall) x, y updated; wall: kDriftTouched or unchanged
 __device__ inline int triDriftLocate(const double* __restrict__ vert, const int* __restrict__ neigh, double& x, double& y, int& k,
                                      double& r, double& s, int& wall) {
 #pragma clang fp contract(off)
@@ -94,7 +70,7 @@ __device__ inline int triDriftLocate(const double* __restrict__ vert, const int*
         const double dx = x - x0, dy = y - y0;
         r = 2.0 * ((dx * e2y - e2x * dy) / det) - 1.0;
         s = 2.0 * ((e1x * dy - dx * e1y) / det) - 1.0;
-        if (!(fabs(r) < __builtin_inf()) || !(fabs(s) < __builtin_inf())) return kTriDriftLost;
+        if (!(fabs(r) < __builtin_inf()) || !(fabs(s) < __builtin_inf())) return kDriftLost;
         int f = 0;
         double worst = -1.0 - s;
         if (r + s > worst) { worst = r + s; f = 1; }
@@ -102,7 +78,7 @@ __device__ inline int triDriftLocate(const double* __restrict__ vert, const int*
         if (worst <= 1e-12) return 0;
         const int nb = neigh[4LL * k + f];
         if (nb >= 0) { k = nb; continue; }
-        if (nb != kTriDriftWall) return kTriDriftExited;
+        if (nb != kDriftWall) return kDriftExited;
         const double ax = f == 0 ? x0 : (f == 1 ? x1 : x2), ay = f == 0 ? y0 : (f == 1 ? y1 : y2);
         const double bx = f == 0 ? x1 : (f == 1 ? x2 : x0), by = f == 0 ? y1 : (f == 1 ? y2 : y0);
         if (wk >= 0 && (wk != k || wf != f)) { // a corner: to the nearer end of this face
@@ -115,12 +91,12 @@ __device__ inline int triDriftLocate(const double* __restrict__ vert, const int*
             y = ay + t * ey;
         }
         if (wk < 0) { wk = k; wf = f; }
-        wall = kTriDriftTouched;
+        wall = kDriftTouched;
     }
-    return kTriDriftLost;
+    return kDriftLost;
 }
 
-// the orthonormal simplex basis at (r, s) into the lane's LDS column P[m * kTriDriftThreads]
+// the orthonormal simplex basis at (r, s) into the lane's LDS column P[m * kDriftThreads]
 __device__ inline void triDriftBasis(const double* __restrict__ jac, int N, double r, double s, double* P) {
 #pragma clang fp contract(off)
     const int Nq = N + 1;
@@ -139,20 +115,21 @@ __device__ inline void triDriftBasis(const double* __restrict__ jac, int N, doub
         for (int j = 0; j <= N - i; ++j) {
             const double jn = j == 0 ? cj[0] : (cj[3 * j] * s + cj[3 * j + 1]) * jc + cj[3 * j + 2] * jp;
             jp = jc; jc = jn;
-            P[col * kTriDriftThreads] = fa * jc;
+            P[col * kDriftThreads] = fa * jc;
             ++col;
         }
     }
 }
 
 // (u, v) at (k, r, s); false if either is not finite
-__device__ inline bool triDriftVelocity(const TriDriftParams& p, int k, double r, double s, double* P, double& u, double& v) {
+__device__ inline bool triDriftVelocity(const DriftParams& p, const TriDriftTables& tab, int k, double r, double s, double* P,
+                                        double& u, double& v) {
 #pragma clang fp contract(off)
     const int Np = (p.N + 1) * (p.N + 2) / 2;
     const long long plane = static_cast<long long>(Np) * p.ld;
     const double* __restrict__ q = p.q;
-    const double* __restrict__ vt = p.vinvT;
-    triDriftBasis(p.jac, p.N, r, s, P);
+    const double* __restrict__ vt = tab.vinvT;
+    triDriftBasis(tab.jac, p.N, r, s, P);
     double su = 0.0, sv = 0.0;
     for (int n0 = 0; n0 < Np; n0 += 4) {
         // rows n0 .. n0 + 3 (past the end: the last row again, not used), one pass over the lane's column
@@ -162,7 +139,7 @@ __device__ inline bool triDriftVelocity(const TriDriftParams& p, int k, double r
         const double* v3 = vt + static_cast<long long>(min(n0 + 3, Np - 1)) * Np;
         double row[4] = {0.0, 0.0, 0.0, 0.0};
         for (int m = 0; m < Np; ++m) {
-            const double pm = P[m * kTriDriftThreads];
+            const double pm = P[m * kDriftThreads];
             row[0] = row[0] + pm * v0[m];
             row[1] = row[1] + pm * v1[m];
             row[2] = row[2] + pm * v2[m];
@@ -182,53 +159,28 @@ __device__ inline bool triDriftVelocity(const TriDriftParams& p, int k, double r
     return fabs(su) < __builtin_inf() && fabs(sv) < __builtin_inf();
 }
 
-__global__ __launch_bounds__(kTriDriftThreads) void sw2d_drifter_kernel(TriDriftParams p) {
+// the triangle as the element policy of sw2d_drifter_driver.hpp
+struct TriDrift {
+    using Tables = TriDriftTables;
+    static constexpr int kRows = kTriDriftMaxNp;
+    __device__ static void init(const Tables& tab, int k, double r, double s, double& x, double& y) {
 #pragma clang fp contract(off)
-    __shared__ double sb[kTriDriftMaxNp][kTriDriftThreads];
-    const int i = blockIdx.x * kTriDriftThreads + threadIdx.x;
-    if (i == 0 && p.slot >= 0) p.recT[p.slot] = p.t;
-    if (i >= p.n) return;
-    double* P = &sb[0][threadIdx.x];
-    int k = p.k[i], st = p.status[i];
-    double x = p.x[i], y = p.y[i], r = p.r[i], s = p.s[i], u0 = p.u0[i], v0 = p.v0[i];
-    const bool frozen = (st & (kTriDriftExited | kTriDriftLost)) != 0;
-    if (p.mode != kTriDriftAdvance) {
-        if (p.mode == kTriDriftInit) {
-            const double* c = p.vert + 8LL * k;
-            const double wr = 0.5 * (1.0 + r), ws = 0.5 * (1.0 + s);
-            x = c[0] + (wr * (c[2] - c[0]) + ws * (c[4] - c[0]));
-            y = c[1] + (wr * (c[3] - c[1]) + ws * (c[5] - c[1]));
-            p.x[i] = x; p.y[i] = y;
-        }
-        if (!frozen) {
-            if (!triDriftVelocity(p, k, r, s, P, u0, v0)) p.status[i] = st | kTriDriftLost;
-            p.u0[i] = u0; p.v0[i] = v0;
-        }
-        return;
+        const double* c = tab.vert + 8LL * k;
+        const double wr = 0.5 * (1.0 + r), ws = 0.5 * (1.0 + s);
+        x = c[0] + (wr * (c[2] - c[0]) + ws * (c[4] - c[0]));
+        y = c[1] + (wr * (c[3] - c[1]) + ws * (c[5] - c[1]));
     }
-    if (!frozen) {
-        // every result into temporaries: a lost drifter stays where it was
-        int wall = 0, kp = k, kc = k, res;
-        double xp = x + p.dt * u0, yp = y + p.dt * v0, rp, sp, up, vp;
-        bool ok = triDriftLocate(p.vert, p.neigh, xp, yp, kp, rp, sp, wall) != kTriDriftLost;
-        ok = ok && triDriftVelocity(p, kp, rp, sp, P, up, vp);
-        if (ok) {
-            double xn = x + (0.5 * p.dt) * (u0 + up), yn = y + (0.5 * p.dt) * (v0 + vp), rn, sn, un = u0, vn = v0;
-            res = triDriftLocate(p.vert, p.neigh, xn, yn, kc, rn, sn, wall);
-            ok = res != kTriDriftLost && (res == kTriDriftExited || triDriftVelocity(p, kc, rn, sn, P, un, vn));
-            if (ok) {
-                x = xn; y = yn; k = kc; r = rn; s = sn; u0 = un; v0 = vn;
-                st |= res;
-                p.x[i] = x; p.y[i] = y; p.r[i] = r; p.s[i] = s; p.u0[i] = u0; p.v0[i] = v0; p.k[i] = k;
-            }
-        }
-        st |= wall | (ok ? 0 : kTriDriftLost);
-        p.status[i] = st;
+    __device__ static int locate(const Tables& tab, double& x, double& y, int& k, double& r, double& s, int& wall) {
+        return triDriftLocate(tab.vert, tab.neigh, x, y, k, r, s, wall);
     }
-    if (p.slot >= 0) {
-        const long long o = static_cast<long long>(p.slot) * p.n + i;
-        p.recX[o] = x; p.recY[o] = y; p.recStatus[o] = st;
+    __device__ static bool velocity(const DriftParams& p, const Tables& tab, int k, double r, double s, double* P, double& u,
+                                    double& v) {
+        return triDriftVelocity(p, tab, k, r, s, P, u, v);
     }
+};
+
+__global__ __launch_bounds__(kDriftThreads) void sw2d_drifter_kernel(DriftParams p, TriDriftTables tab) {
+    driftBody<TriDrift>(p, tab);
 }
 
 } // namespace bdg_dev

@@ -10,14 +10,14 @@
 // sw2d_quadb_speed_kernel, then sw2d_quadb_stage_kernel (sw2d_quadb_kernel.hpp), which reads the speed from device memory.
 // After bdg_sw2dq_enable_variant_b4 a four-field solver does the same with the tracer as a fourth equation
 // (sw2d_quadb4_stage_kernel, sw2d_quadb4_kernel.hpp; the speed pass is the three-field one).
-// After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_quad_monitor_kernel.hpp).
+// After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2dq_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_quad_drifter_kernel.hpp).
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
+#include "run_records.hpp"
 #include "sw2d_quad4_kernel.hpp"
 #include "sw2d_dispatch.hpp"
 #include "sw2d_quad_drifter_kernel.hpp"
-#include "sw2d_quad_monitor_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 #include "sw2d_quadb4_kernel.hpp"
 #include "sw2d_quadb_kernel.hpp"
@@ -193,25 +193,13 @@ struct bdg_sw2dq {
     bdg_halo::Partition part;
     bdg_halo::Transport halo;
     bdg_halo::TwoChains chains;
-    // run monitor (bdg_sw2dq_enable_monitor): sw2d_quad_monitor_kernel.hpp
-    struct Monitor {
-        bool on = false;
-        int stride = 1, capacity = 0, numGauges = 0, width = 0;
-        int count = 0;        // records taken
-        int reduced = 0;      // records [0, reduced) have been all-reduced
-        long long steps = 0;  // completed steps since set_state / monitor_reset
-        DevBuf<double> w, H, lr, ls, partials, rec, stage;
-        DevBuf<int> element;
+    // run monitor (bdg_sw2dq_enable_monitor): sw2d_monitor_kernel.hpp, the tensor gauge rule
+    struct Monitor : bdg_records::MonitorState {
+        DevBuf<double> lr, ls; // (numGauges, N+1): the 1-D basis at each gauge's r and s
     } mon;
     // drifters (bdg_sw2dq_enable_drifters): sw2d_quad_drifter_kernel.hpp
-    struct Drifters {
-        bool on = false;
-        int n = 0, stride = 1, capacity = 0;
-        int count = 0;        // records taken
-        long long steps = 0;  // advances made
-        double t = 0.0;       // time of the next record: the model time in the stepping calls, + dt per bdg_sw2dq_drifters_advance
-        DevBuf<double> bil, r1d, bary, x, y, r, s, u0, v0, recT, recX, recY;
-        DevBuf<int> neigh, k, status, recStatus;
+    struct Drifters : bdg_records::DrifterState {
+        DevBuf<double> bil, r1d, bary;
     } drf;
 
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
@@ -418,59 +406,29 @@ struct bdg_sw2dq {
         return count;
     }
 
-    // ---- run monitor
+    // ---- run monitor and drifters (run_records.hpp)
     // records a stepping call of `steps` further completed steps would take; refused before anything is launched
-    void monitorReserve(long long steps, const char* fn) const {
-        if (!mon.on) return;
-        const long long take = (mon.steps + steps) / mon.stride - mon.steps / mon.stride;
-        if (take > mon.capacity - mon.count)
-            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " monitor records and " +
-                            std::to_string(mon.capacity - mon.count) + " are free (bdg_sw2dq_monitor_read, then bdg_sw2dq_monitor_reset)");
-    }
+    void monitorReserve(long long steps, const char* fn) const { mon.reserve(steps, fn, "bdg_sw2dq"); }
+    void drifterReserve(long long steps, const char* fn) const { drf.reserve(steps, fn, "bdg_sw2dq"); }
     // completed LSERK4 steps among the next `stages` stages
-    long long lserkSteps(long long stages) const {
-        return (stageCount + stages) / blitzdg::LSERK4::numStages - stageCount / blitzdg::LSERK4::numStages;
-    }
-    // one record of the resident state, two launches on the solver's stream
+    long long lserkSteps(long long stages) const { return bdg_records::lserkSteps(stageCount, stages, blitzdg::LSERK4::numStages); }
+    // one record of the resident state, two launches on the solver's stream; H: the monitor's own, else variant B's, else none
     void monitorSample() {
         const int count = part.numOwned > 0 ? part.numOwned : K;
         const double* Hm = mon.H.p ? mon.H.p : (variantB ? vbH.p : nullptr);
-        const QuadMonParams rp{q.p, mon.w.p, Hm, ld, N, fields, count, quadMonChunk(count), g};
-        hipLaunchKernelGGL(sw2d_quad_monitor_reduce_kernel, dim3(kQuadMonBlocks), dim3(kQuadMonThreads), 0, stream, rp, mon.partials.p);
-        hipCheck(hipGetLastError(), "sw2d_quad_monitor_reduce_kernel launch");
-        const QuadMonFinish fp{mon.partials.p, q.p, Hm, mon.element.p, mon.lr.p, mon.ls.p, mon.rec.p, ld, N, fields, count,
-                               mon.numGauges, mon.capacity, mon.count, timeNow};
-        hipLaunchKernelGGL(sw2d_quad_monitor_finish_kernel, dim3(1), dim3(kQuadMonThreads), 0, stream, fp);
-        hipCheck(hipGetLastError(), "sw2d_quad_monitor_finish_kernel launch");
-        ++mon.count;
-    }
-    // ---- drifters
-    // as monitorReserve: records `steps` further advances would take
-    void drifterReserve(long long steps, const char* fn) const {
-        if (!drf.on) return;
-        const long long take = (drf.steps + steps) / drf.stride - drf.steps / drf.stride;
-        if (take > drf.capacity - drf.count)
-            throw arg_error(std::string(fn) + ": the call would take " + std::to_string(take) + " drifter records and " +
-                            std::to_string(drf.capacity - drf.count) + " are free (bdg_sw2dq_drifters_read, then bdg_sw2dq_drifters_reset)");
+        mon.sample({q.p, Hm, ld, Np, fields, count, g, timeNow}, sw2d_quad_monitor_finish_kernel, "sw2d_quad_monitor_finish_kernel launch",
+                   MonTensorGauges{mon.lr.p, mon.ls.p, N + 1}, stream);
     }
     // one launch of the drifter kernel on the solver's stream; slot < 0: no record
     void drifterLaunch(int mode, double dt, int slot) {
-        const QuadDriftParams p{q.p, drf.bil.p, drf.neigh.p, drf.r1d.p, drf.bary.p, drf.x.p, drf.y.p, drf.r.p, drf.s.p, drf.u0.p,
-                                drf.v0.p, drf.k.p, drf.status.p, drf.recT.p, drf.recX.p, drf.recY.p, drf.recStatus.p, ld, N, drf.n,
-                                mode, slot, dt, drf.t};
-        hipLaunchKernelGGL(sw2d_quad_drifter_kernel, dim3((drf.n + kQuadDriftThreads - 1) / kQuadDriftThreads), dim3(kQuadDriftThreads),
-                           0, stream, p);
-        hipCheck(hipGetLastError(), "sw2d_quad_drifter_kernel launch");
+        drf.launch(sw2d_quad_drifter_kernel, "sw2d_quad_drifter_kernel launch",
+                   QuadDriftTables{drf.bil.p, drf.neigh.p, drf.r1d.p, drf.bary.p}, q.p, ld, N, mode, dt, slot, stream);
     }
     // one advance in the resident state, with the record of time drf.t if one is due (room was reserved by the caller)
-    void drifterAdvance(double dt, bool record = true) {
-        const bool due = record && ++drf.steps % drf.stride == 0;
-        drifterLaunch(kQuadDriftAdvance, dt, due ? drf.count : -1);
-        if (due) ++drf.count;
-    }
+    void drifterAdvance(double dt, bool record = true) { drifterLaunch(kDriftAdvance, dt, drf.takeSlot(record)); }
     // (u0, v0) again after the state under the drifters has been replaced
     void drifterResample() {
-        if (drf.on) drifterLaunch(kQuadDriftSample, 0.0, -1);
+        if (drf.on) drifterLaunch(kDriftSample, 0.0, -1);
     }
     // after every completed step (of size dt) of a stepping call: the monitor's sample, then the drifters' advance. two: the call
     // runs the two-chain schedule, whose chains are joined in front of the sample and started again behind it (the sample reads
@@ -1156,23 +1114,18 @@ int bdg_sw2dq_barrier(bdg_sw2dq* s) {
     });
 }
 
-// ---- run monitor
+// ---- run monitor (what the triangle solver has too: run_records.hpp)
 int bdg_sw2dq_enable_monitor(bdg_sw2dq* s, const bdg_sw2dq_monitor_desc* d) {
     return guard([&] {
-        requireSolver(s, "bdg_sw2dq_enable_monitor");
-        if (!d || !d->weights) throw arg_error("bdg_sw2dq_enable_monitor: the descriptor and its weights are required");
-        if (s->mon.on) throw arg_error("bdg_sw2dq_enable_monitor: the monitor is already enabled");
-        if (d->stride < 1 || d->capacity < 1) throw arg_error("bdg_sw2dq_enable_monitor: stride and capacity must be >= 1");
+        const std::string fn = "bdg_sw2dq_enable_monitor";
+        requireSolver(s, fn.c_str());
+        bdg_sw2dq::Monitor& m = s->mon;
+        m.checkEnable(fn, d, s->K);
         const int ng = d->num_gauges, Nq = s->N + 1;
-        if (ng < 0 || (ng > 0 && (!d->gauge_element || !d->gauge_r || !d->gauge_s)))
-            throw arg_error("bdg_sw2dq_enable_monitor: bad gauge list");
-        for (int i = 0; i < ng; ++i) {
-            if (d->gauge_element[i] < 0 || d->gauge_element[i] >= s->K)
-                throw arg_error("bdg_sw2dq_enable_monitor: gauge " + std::to_string(i) + " names an element outside [0, K)");
+        if (ng > 0 && (!d->gauge_r || !d->gauge_s)) throw arg_error(fn + ": bad gauge list");
+        for (int i = 0; i < ng; ++i)
             if (!(std::fabs(d->gauge_r[i]) <= 1.0 + 1e-10) || !(std::fabs(d->gauge_s[i]) <= 1.0 + 1e-10))
-                throw arg_error("bdg_sw2dq_enable_monitor: gauge " + std::to_string(i) + " lies outside its element (|r|, |s| <= 1)");
-        }
-        const int width = 7 + s->fields + ng * s->fields;
+                throw arg_error(fn + ": gauge " + std::to_string(i) + " lies outside its element (|r|, |s| <= 1)");
         // the 1-D basis at every gauge, on the solver's Gauss-Lobatto points
         blitzdg::real_vector_type r1d(Nq);
         blitzdg::JacobiBuilders().computeGaussLobottoPoints(0.0, 0.0, s->N, r1d);
@@ -1182,9 +1135,7 @@ int bdg_sw2dq_enable_monitor(bdg_sw2dq* s, const bdg_sw2dq_monitor_desc* d) {
             blitzdg::QuadNodesProvisioner::lagrangeBasis1D(r1d.data(), Nq, d->gauge_s[i], ls.data() + static_cast<size_t>(i) * Nq);
         }
         s->use();
-        bdg_sw2dq::Monitor& m = s->mon;
-        const size_t bytesBefore = s->bytes;
-        try {
+        m.enable(d->stride, d->capacity, ng, s->fields, d->gauge_element, {&m.lr, &m.ls}, nullptr, s->bytes, s->stream, [&] {
             const long long plane = s->plane();
             m.w.alloc(plane, s->bytes, s->stream);
             s->upload(m.w.p, d->weights, s->Np);
@@ -1194,38 +1145,23 @@ int bdg_sw2dq_enable_monitor(bdg_sw2dq* s, const bdg_sw2dq_monitor_desc* d) {
             }
             m.lr.alloc(lr.size(), s->bytes);
             m.ls.alloc(ls.size(), s->bytes);
-            m.element.alloc(static_cast<size_t>(std::max(1, ng)), s->bytes, s->stream);
             hipCheck(hipMemcpyAsync(m.lr.p, lr.data(), lr.size() * sizeof(double), hipMemcpyHostToDevice, s->stream), "hipMemcpy (basis)");
             hipCheck(hipMemcpyAsync(m.ls.p, ls.data(), ls.size() * sizeof(double), hipMemcpyHostToDevice, s->stream), "hipMemcpy (basis)");
-            if (ng > 0)
-                hipCheck(hipMemcpyAsync(m.element.p, d->gauge_element, static_cast<size_t>(ng) * sizeof(int), hipMemcpyHostToDevice,
-                                        s->stream), "hipMemcpy (gauges)");
-            m.partials.alloc(static_cast<size_t>(kQuadMonBlocks) * kQuadMonPartial, s->bytes, s->stream);
-            m.rec.alloc(static_cast<size_t>(width) * d->capacity, s->bytes, s->stream);
-            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
-        } catch (...) { // nothing changes: the solver stays without a monitor
-            (void)hipStreamSynchronize(s->stream);
-            for (DevBuf<double>* b : {&m.w, &m.H, &m.lr, &m.ls, &m.partials, &m.rec}) b->release();
-            m.element.release();
-            s->bytes = bytesBefore;
-            throw;
-        }
-        m.on = true;
-        m.stride = d->stride; m.capacity = d->capacity; m.numGauges = ng; m.width = width;
+        });
     });
 }
 
 namespace {
 void requireMonitor(const bdg_sw2dq* s, const char* fn) {
     requireSolver(s, fn);
-    if (!s->mon.on) throw arg_error(std::string(fn) + ": the monitor is not enabled (bdg_sw2dq_enable_monitor)");
+    s->mon.requireOn(fn, "bdg_sw2dq");
 }
 } // namespace
 
 int bdg_sw2dq_monitor_sample(bdg_sw2dq* s) {
     return guard([&] {
         requireMonitor(s, "bdg_sw2dq_monitor_sample");
-        if (s->mon.count >= s->mon.capacity) throw arg_error("bdg_sw2dq_monitor_sample: no free record (bdg_sw2dq_monitor_reset)");
+        s->mon.requireFree("bdg_sw2dq_monitor_sample", "bdg_sw2dq");
         s->use();
         s->monitorSample();
     });
@@ -1250,26 +1186,15 @@ int bdg_sw2dq_monitor_width(const bdg_sw2dq* s, int* width) {
 int bdg_sw2dq_monitor_read(bdg_sw2dq* s, int first, int count, double* records) {
     return guard([&] {
         requireMonitor(s, "bdg_sw2dq_monitor_read");
-        if (first < 0 || count < 0 || first > s->mon.count - count || (count > 0 && !records))
-            throw arg_error("bdg_sw2dq_monitor_read: bad record range");
-        if (count == 0) return;
         s->use();
-        const int width = s->mon.width;
-        std::vector<double> cols(static_cast<size_t>(width) * count); // by column, as on the device
-        hipCheck(hipMemcpy2DAsync(cols.data(), count * sizeof(double), s->mon.rec.p + first, s->mon.capacity * sizeof(double),
-                                  count * sizeof(double), width, hipMemcpyDeviceToHost, s->stream), "hipMemcpy2D (records)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        for (int n = 0; n < count; ++n)
-            for (int c = 0; c < width; ++c) records[static_cast<size_t>(n) * width + c] = cols[static_cast<size_t>(c) * count + n];
+        s->mon.read("bdg_sw2dq_monitor_read", first, count, records, s->stream);
     });
 }
 
 int bdg_sw2dq_monitor_reset(bdg_sw2dq* s) {
     return guard([&] {
         requireMonitor(s, "bdg_sw2dq_monitor_reset");
-        s->mon.count = 0;
-        s->mon.reduced = 0;
-        s->mon.steps = 0;
+        s->mon.reset();
     });
 }
 
@@ -1277,28 +1202,8 @@ int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s) {
     return guard([&] {
         requireMonitor(s, "bdg_sw2dq_monitor_reduce");
         bdg_halo::requireComm(s->halo, "bdg_sw2dq", "bdg_sw2dq_monitor_reduce");
-        bdg_sw2dq::Monitor& m = s->mon;
-        const int n = m.count - m.reduced;
-        if (n <= 0) return;
         s->use();
-        // the new records of every column but t, packed by column; the columns that share an operator are contiguous
-        const int cols = m.width - 1, nf = s->fields;
-        if (!m.stage.p) m.stage.alloc(static_cast<size_t>(cols) * m.capacity, s->bytes);
-        hipCheck(hipMemcpy2DAsync(m.stage.p, n * sizeof(double), m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double),
-                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
-        auto reduce = [&](int firstCol, int numCols, ncclRedOp_t op) {
-            if (numCols <= 0) return;
-            double* at = m.stage.p + static_cast<size_t>(firstCol) * n;
-            bdg_rccl::ncclCheck(bdg_rccl::rccl().AllReduce(at, at, static_cast<size_t>(numCols) * n, ncclDouble, op, s->halo.comm, s->stream),
-                                "ncclAllReduce");
-        };
-        reduce(0, nf + 1, ncclSum);                 // integrals and E
-        reduce(nf + 1, 1, ncclMin);                 // min h
-        reduce(nf + 2, 3, ncclMax);                 // max h, max|hu|, max|hv|
-        reduce(nf + 5, cols - (nf + 5), ncclSum);   // NaN count and gauges
-        hipCheck(hipMemcpy2DAsync(m.rec.p + m.capacity + m.reduced, m.capacity * sizeof(double), m.stage.p, n * sizeof(double),
-                                  n * sizeof(double), cols, hipMemcpyDeviceToDevice, s->stream), "hipMemcpy2D (records)");
-        m.reduced = m.count;
+        s->mon.allReduce(s->halo.comm, s->stream, s->fields, s->bytes);
     });
 }
 
@@ -1309,12 +1214,9 @@ int bdg_sw2dq_enable_drifters(bdg_sw2dq* s, const bdg_sw2dq_drifter_desc* d) {
         requireSolver(s, fn.c_str());
         if (!d || d->count < 1 || !d->element || !d->r || !d->s || !d->bilinear || !d->neighbours || !d->bary)
             throw arg_error(fn + ": the descriptor, at least one drifter and the tables of bdg_quadnodes_drifter_tables are required");
-        if (d->stride < 1 || d->capacity < 1) throw arg_error(fn + ": stride and capacity must be >= 1");
-        if (s->drf.on) throw arg_error(fn + ": drifters are already enabled on this solver; the call is made once");
-        if (s->part.numOwned > 0 || s->halo.comm)
-            throw arg_error(fn + ": the solver has a partition set; drifters do not migrate between ranks (single domain only)");
+        bdg_sw2dq::Drifters& m = s->drf;
+        m.checkEnable(fn, d->count, d->stride, d->capacity, s->part.numOwned > 0 || s->halo.comm);
         const int n = d->count, K = s->K, Nq = s->N + 1;
-        if (static_cast<long long>(n) * d->capacity >= (1LL << 31)) throw arg_error(fn + ": count * capacity must stay below 2^31");
         for (int i = 0; i < n; ++i) {
             if (d->element[i] < 0 || d->element[i] >= K)
                 throw arg_error(fn + ": drifter " + std::to_string(i) + " names an element outside [0, K)");
@@ -1326,52 +1228,26 @@ int bdg_sw2dq_enable_drifters(bdg_sw2dq* s, const bdg_sw2dq_drifter_desc* d) {
         for (int f = 0; f < 4; ++f)
             for (int k = 0; k < K; ++k) {
                 const int v = d->neighbours[static_cast<size_t>(f) * K + k];
-                if (v < kQuadDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
+                if (v < kDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
                 nb[static_cast<size_t>(4) * k + f] = v;
             }
         blitzdg::real_vector_type r1d(Nq);
         blitzdg::JacobiBuilders().computeGaussLobottoPoints(0.0, 0.0, s->N, r1d);
         s->use();
-        bdg_sw2dq::Drifters& m = s->drf;
-        const size_t bytesBefore = s->bytes, cells = static_cast<size_t>(n) * d->capacity;
-        try {
-            auto put = [&](auto& buf, const auto* src, size_t count) {
-                buf.alloc(count, s->bytes);
-                hipCheck(hipMemcpyAsync(buf.p, src, count * sizeof(*src), hipMemcpyHostToDevice, s->stream), "hipMemcpy (drifters)");
-            };
-            put(m.bil, d->bilinear, static_cast<size_t>(8) * K);
-            put(m.neigh, nb.data(), nb.size());
-            put(m.r1d, r1d.data(), static_cast<size_t>(Nq));
-            put(m.bary, d->bary, static_cast<size_t>(Nq));
-            put(m.k, d->element, static_cast<size_t>(n));
-            put(m.r, d->r, static_cast<size_t>(n));
-            put(m.s, d->s, static_cast<size_t>(n));
-            for (DevBuf<double>* b : {&m.x, &m.y, &m.u0, &m.v0}) b->alloc(static_cast<size_t>(n), s->bytes, s->stream);
-            m.status.alloc(static_cast<size_t>(n), s->bytes, s->stream);
-            m.recT.alloc(static_cast<size_t>(d->capacity), s->bytes, s->stream);
-            m.recX.alloc(cells, s->bytes, s->stream);
-            m.recY.alloc(cells, s->bytes, s->stream);
-            m.recStatus.alloc(cells, s->bytes, s->stream);
-            m.n = n;
-            s->drifterLaunch(kQuadDriftInit, 0.0, -1); // x, y from the map, (u0, v0) from the resident state
-            hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the host staging vectors die here
-        } catch (...) { // nothing changes: the solver stays without drifters
-            (void)hipStreamSynchronize(s->stream);
-            for (DevBuf<double>* b : {&m.bil, &m.r1d, &m.bary, &m.x, &m.y, &m.r, &m.s, &m.u0, &m.v0, &m.recT, &m.recX, &m.recY}) b->release();
-            for (DevBuf<int>* b : {&m.neigh, &m.k, &m.status, &m.recStatus}) b->release();
-            m.n = 0;
-            s->bytes = bytesBefore;
-            throw;
-        }
-        m.on = true;
-        m.stride = d->stride; m.capacity = d->capacity; m.count = 0; m.steps = 0; m.t = s->timeNow;
+        m.enable(n, d->stride, d->capacity, s->timeNow, nb, d->element, d->r, d->s, {&m.bil, &m.r1d, &m.bary}, s->bytes, s->stream,
+                 [&] {
+                     m.put(m.bil, d->bilinear, static_cast<size_t>(8) * K, s->bytes, s->stream);
+                     m.put(m.r1d, r1d.data(), static_cast<size_t>(Nq), s->bytes, s->stream);
+                     m.put(m.bary, d->bary, static_cast<size_t>(Nq), s->bytes, s->stream);
+                 },
+                 [&] { s->drifterLaunch(kDriftInit, 0.0, -1); });
     });
 }
 
 namespace {
 void requireDrifters(const bdg_sw2dq* s, const char* fn) {
     requireSolver(s, fn);
-    if (!s->drf.on) throw arg_error(std::string(fn) + ": drifters are not enabled (bdg_sw2dq_enable_drifters)");
+    s->drf.requireOn(fn, "bdg_sw2dq");
 }
 } // namespace
 
@@ -1401,14 +1277,7 @@ int bdg_sw2dq_drifters_state(bdg_sw2dq* s, double* x, double* y, int* element, d
     return guard([&] {
         requireDrifters(s, "bdg_sw2dq_drifters_state");
         s->use();
-        const bdg_sw2dq::Drifters& m = s->drf;
-        const size_t n = static_cast<size_t>(m.n);
-        const std::pair<double*, const double*> dbl[] = {{x, m.x.p}, {y, m.y.p}, {r, m.r.p}, {sref, m.s.p}};
-        for (const auto& c : dbl)
-            if (c.first) hipCheck(hipMemcpyAsync(c.first, c.second, n * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        if (element) hipCheck(hipMemcpyAsync(element, m.k.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        if (status) hipCheck(hipMemcpyAsync(status, m.status.p, n * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (drifters)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        s->drf.downloadState(x, y, element, r, sref, status, {}, s->stream);
     });
 }
 
@@ -1423,17 +1292,8 @@ int bdg_sw2dq_drifters_count(const bdg_sw2dq* s, int* num_records, int* num_drif
 int bdg_sw2dq_drifters_read(bdg_sw2dq* s, int first, int count, double* t, double* x, double* y, int* status) {
     return guard([&] {
         requireDrifters(s, "bdg_sw2dq_drifters_read");
-        const bdg_sw2dq::Drifters& m = s->drf;
-        if (first < 0 || count < 0 || first > m.count - count) throw arg_error("bdg_sw2dq_drifters_read: bad record range");
-        if (count == 0) return;
         s->use();
-        const size_t at = static_cast<size_t>(first) * m.n, cells = static_cast<size_t>(count) * m.n;
-        if (t) hipCheck(hipMemcpyAsync(t, m.recT.p + first, count * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (x) hipCheck(hipMemcpyAsync(x, m.recX.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (y) hipCheck(hipMemcpyAsync(y, m.recY.p + at, cells * sizeof(double), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        if (status)
-            hipCheck(hipMemcpyAsync(status, m.recStatus.p + at, cells * sizeof(int), hipMemcpyDeviceToHost, s->stream), "hipMemcpy (tracks)");
-        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+        s->drf.readTracks("bdg_sw2dq_drifters_read", first, count, t, x, y, status, s->stream);
     });
 }
 

@@ -370,23 +370,8 @@ class NativeDistributedSw2d:
         (global element, r, s), or an (n, 2) array of x, y that is located on ``global_nodes``, a TriangleNodesProvisioner of
         the global mesh (``locatePoints``: a point on a shared edge goes to the lowest global element, so exactly one rank
         owns it). ``H`` on the rank-local nodes. A gauge in no element raises ValueError on every rank."""
-        from .sw2d import _locate
-        n_own = self.plan.num_owned
-        loc = None
-        if gauges is not None:
-            if isinstance(gauges, tuple):                    # global element numbers, which may be of another rank
-                gel, r, s = (np.asarray(a).reshape(-1) for a in gauges)
-                if (gel < 0).any():
-                    raise ValueError(f"gauges {np.nonzero(gel < 0)[0].tolist()} lie in no element of the mesh")
-            else:
-                gel, r, s = _locate(gauges, global_nodes, "gauges")
-            local = {int(g): i for i, g in enumerate(np.asarray(self.plan.own_global))}
-            # a gauge of another rank names a ghost column, which the device leaves at 0
-            el = np.array([local.get(int(g), n_own) for g in gel], dtype=np.int32)
-            mine = el < n_own
-            if (~mine).any() and self.solver.K <= n_own:
-                raise ValueError("a gauge belongs to another rank, but this rank has no ghost element to name for it")
-            loc = (el, np.where(mine, r, -1.0), np.where(mine, s, -1.0))
+        from ._records import partition_gauges
+        loc = partition_gauges(self.plan, self.solver.K, gauges, global_nodes, "TriangleNodesProvisioner", -1.0)
         self.solver.enableMonitor(self.nodes, H=H, gauges=loc, stride=stride, capacity=capacity)
 
     def monitor_records(self):

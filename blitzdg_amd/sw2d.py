@@ -15,33 +15,18 @@ import numpy as np
 
 from . import _capi as C
 from ._capi import byref, c_double, c_float, c_int, c_void_p, check, lib
+from ._records import RunRecords, locate
 
 REORDER = C.BDG_SW2D_REORDER
 NODAL_GEOMETRY = C.BDG_SW2D_NODAL_GEOMETRY
 KEEP_ORDER = C.BDG_SW2D_KEEP_ORDER
 
 
-def _locate(points, nodes, noun):
-    """(element, r, s) of ``points``: a tuple of reference coordinates as it is, or an (n, 2) array of x, y located on the
-    TriangleNodesProvisioner ``nodes``. ``noun`` names them in the messages."""
-    if isinstance(points, tuple):
-        el, r, s = C.as_i32(points[0]).reshape(-1), C.as_f64(points[1]).reshape(-1), C.as_f64(points[2]).reshape(-1)
-        if not (el.size == r.size == s.size):
-            raise ValueError(f"{noun}: element, r and s must have the same length")
-        return el, r, s
-    xy = C.as_f64(points)
-    if xy.ndim != 2 or xy.shape[1] != 2:
-        raise ValueError(f"{noun}: expected an (n, 2) array of x, y")
-    if nodes is None:
-        raise ValueError(f"{noun} given as x, y need `global_nodes`, a TriangleNodesProvisioner of the global mesh")
-    el, r, s = nodes.locatePoints(xy[:, 0], xy[:, 1])
-    if (el < 0).any():
-        raise ValueError(f"{noun} {np.nonzero(el < 0)[0].tolist()} lie in no element of the mesh")
-    return el, r, s
+class Sw2dSolver(RunRecords):
+    """Device-resident shallow-water DG solver (one HIP device, one stream). The monitor and drifter calls that
+    ``enableMonitor`` and ``enableDrifters`` switch on are those of ``RunRecords``."""
 
-
-class Sw2dSolver:
-    """Device-resident shallow-water DG solver (one HIP device, one stream)."""
+    _abi = "bdg_sw2d"
 
     def __init__(self, nodes=None, g=9.81, device=0, flags=0, tables=None, fields=3, sources=None):
         """Create from a ``pyblitzdg.TriangleNodesProvisioner`` (``nodes``) or from a dict of
@@ -246,45 +231,12 @@ class Sw2dSolver:
         (without one the solver's own is used, from setBathymetry or enableVariantB, else H = 0). ``gauges``: (n, 2) array of
         x, y, located with ``nodes.locatePoints`` (a gauge in no element raises ValueError), or a tuple (element, r, s) of
         reference coordinates, the elements in the caller's numbering. Once per solver."""
-        shape = (self.Np, self.K)
-        w = C.as_f64(nodes.quadratureWeights(), shape, "weights")
-        Hh = None if H is None else C.as_f64(H, shape, "H")
-        if gauges is None:
-            el, r, s = np.empty(0, np.int32), np.empty(0), np.empty(0)
-        else:
-            el, r, s = _locate(gauges, nodes, "gauges")
+        w, Hh, el, r, s = self._monitor_inputs(nodes, H, gauges, "TriangleNodesProvisioner")
         rows = C.as_f64(nodes.interpolationRows(r, s), (el.size, self.Np), "rows")
         d = C.Sw2dMonitorDesc(C.ptr(w), C.ptr(Hh), el.size, C.ptr(el) if el.size else None, C.ptr(rows) if el.size else None,
                               int(stride), int(capacity))
         check(lib.bdg_sw2d_enable_monitor(self._h, byref(d)))
         self.numGauges = int(el.size)
-
-    def sampleMonitor(self):
-        """One record of the resident state now (at the model time ``time``)."""
-        check(lib.bdg_sw2d_monitor_sample(self._h))
-
-    def resetMonitor(self):
-        """Drops the records held on the device and restarts the step count."""
-        check(lib.bdg_sw2d_monitor_reset(self._h))
-
-    def monitorRecordArray(self):
-        """The records as a (records, width) array in the layout of include/blitzdg_hip.h; waits for the solver's stream."""
-        n, width = c_int(), c_int()
-        check(lib.bdg_sw2d_monitor_count(self._h, byref(n)))
-        check(lib.bdg_sw2d_monitor_width(self._h, byref(width)))
-        out = np.empty((n.value, width.value))
-        check(lib.bdg_sw2d_monitor_read(self._h, 0, n.value, C.ptr(out)))
-        return out
-
-    def monitorRecords(self):
-        """The records taken so far as a dict of arrays, one entry per record: ``t``, ``mass``, ``momentum`` (records, 2),
-        ``tracer`` (zeros on three fields), ``energy``, ``hmin``, ``hmax``, ``humax``, ``hvmax``, ``nan`` and ``gauges``
-        (records, n, fields) holding eta, u, v (, N)."""
-        a, nf = self.monitorRecordArray(), self.fields
-        rec = {"t": a[:, 0], "mass": a[:, 1], "momentum": a[:, 2:4], "tracer": a[:, 4] if nf == 4 else np.zeros(len(a)),
-               "energy": a[:, nf + 1], "hmin": a[:, nf + 2], "hmax": a[:, nf + 3], "humax": a[:, nf + 4], "hvmax": a[:, nf + 5],
-               "nan": a[:, nf + 6], "gauges": a[:, nf + 7:].reshape(len(a), -1, nf)}
-        return {k: np.ascontiguousarray(v) for k, v in rec.items()}
 
     def timeMonitor(self, count):
         """Average device milliseconds of one monitor sample (both launches); takes no records."""
@@ -303,45 +255,12 @@ class Sw2dSolver:
         ``mapO``: the open-boundary face nodes of ``enableVariantB``; a drifter that crosses one of their faces has exited
         (status 1), at every other boundary face it slides along the wall (status bit 4) and comes to rest in a corner. Set the
         state first; once per solver; not on a partitioned solver."""
-        el, r, s = _locate(points, nodes, "points")
+        el, r, s = locate(points, nodes, "points", "TriangleNodesProvisioner")
         vert, neigh, (vinv, jac) = nodes.drifterTables(mapO)
         d = C.Sw2dDrifterDesc(el.size, C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(vert), C.ptr(neigh), C.ptr(vinv), C.ptr(jac),
                               int(stride), int(capacity))
         check(lib.bdg_sw2d_enable_drifters(self._h, byref(d)))
         self.numDrifters = int(el.size)
-
-    def advanceDrifters(self, dt, nsteps=1):
-        """``nsteps`` advances by ``dt`` in the resident state as it is (a steady flow); the records' time moves on, the model
-        time does not."""
-        check(lib.bdg_sw2d_drifters_advance(self._h, float(dt), int(nsteps)))
-
-    def timeDrifters(self, dt, count):
-        """Average device milliseconds per advance (no records taken; the drifters move)."""
-        ms = c_float()
-        check(lib.bdg_sw2d_drifters_time(self._h, float(dt), int(count), byref(ms)))
-        return ms.value
-
-    def drifterState(self):
-        """dict of the drifters now: ``xy`` (n, 2), ``element`` (caller numbering), ``r``, ``s``, ``status`` (0 moving, 1 exited,
-        2 lost, + 4 once it has touched a wall); waits for the solver's stream."""
-        n = self.numDrifters
-        x, y, r, s = (np.empty(n) for _ in range(4))
-        el, st = np.empty(n, np.int32), np.empty(n, np.int32)
-        check(lib.bdg_sw2d_drifters_state(self._h, C.ptr(x), C.ptr(y), C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(st)))
-        return {"xy": np.stack([x, y], axis=1), "element": el, "r": r, "s": s, "status": st}
-
-    def drifterTracks(self):
-        """(t, xy, status) of the records taken so far: (m,), (m, n, 2), (m, n); waits for the solver's stream."""
-        m, n = c_int(), c_int()
-        check(lib.bdg_sw2d_drifters_count(self._h, byref(m), byref(n)))
-        m, n = m.value, n.value
-        t, x, y, st = np.empty(m), np.empty((m, n)), np.empty((m, n)), np.empty((m, n), np.int32)
-        check(lib.bdg_sw2d_drifters_read(self._h, 0, m, C.ptr(t), C.ptr(x), C.ptr(y), C.ptr(st)))
-        return t, np.stack([x, y], axis=2), st
-
-    def resetDrifterTracks(self):
-        """Drops the records held on the device (the drifters stay where they are)."""
-        check(lib.bdg_sw2d_drifters_reset(self._h))
 
     def probeStageTraffic(self, repeats=20):
         """Milliseconds of a launch with the stage kernel's memory accesses but no gathers / arithmetic."""

@@ -521,7 +521,7 @@ int bdg_quadnodes_bed_slopes(const bdg_quadnodes* nodes, const double* H, double
 int bdg_quadnodes_sponge_coeff(const bdg_quadnodes* nodes, const int* mapO, int num_out, double strength, double radius,
                                double* coeff);
 /* ---- run monitor: conservation diagnostics and gauges recorded on the device during the stepping calls, with no host round
- * trip and no state download (csrc/hip/sw2d_quad_monitor_kernel.hpp). Host set-up, from a quadrilateral provisioner:
+ * trip and no state download (csrc/hip/sw2d_monitor_kernel.hpp). Host set-up, from a quadrilateral provisioner:
  * quadrature_weights: w (Np, K), w[(N+1) j + i, k] = w1[j] w1[i] J[(N+1) j + i, k], w1 the 1-D Gauss-Lobatto weights (the row
  * sums of the 1-D mass matrix). locate_points: for each (x[p], y[p]) the element that contains it and its reference
  * coordinates, by Newton iteration on the element's own nodal map (either geometry form); |r|, |s| <= 1 + 1e-10 counts as
@@ -573,7 +573,7 @@ int bdg_sw2dq_monitor_reset(bdg_sw2dq* s);             /* count = 0, step counte
 int bdg_sw2dq_monitor_reduce(bdg_sw2dq* s);
 /* ---- drifters: points that move with the velocity (hu / h, hv / h) of the resident state, followed from element to element
  * and recorded on the device, one launch per advance on the solver's stream and no host wait
- * (csrc/hip/sw2d_quad_drifter_kernel.hpp, which states the algorithm). Single domain and bilinear elements only.
+ * (csrc/hip/sw2d_quad_drifter_kernel.hpp and sw2d_drifter_driver.hpp, which state the algorithm). Single domain and bilinear elements only.
  * Host set-up, from a quadrilateral provisioner: bilinear (K, 8), per element xc, ax, bx, cx, yc, ay, by, cy of the map
  * x(r, s) = xc + ax r + bx s + cx r s of its four corner nodes; neighbours (4, K), the element across each face (faces in
  * Fmask order: s = -1, r = +1, s = +1, r = -1), -1 for a wall, -2 for an open boundary face: a boundary face with a node in
@@ -787,7 +787,7 @@ int bdg_sw2d_monitor_time(bdg_sw2d* s, int count, float* ms);
 
 /* ---- drifters of the triangle solver: points that move with the velocity (hu / h, hv / h) of the resident state, followed
  * from element to element and recorded on the device, one launch per advance on the solver's stream and no host wait
- * (csrc/hip/sw2d_drifter_kernel.hpp, which states the algorithm); the counterpart of the bdg_sw2dq_*drifter* group above with
+ * (csrc/hip/sw2d_drifter_kernel.hpp and sw2d_drifter_driver.hpp, which state the algorithm); the counterpart of the bdg_sw2dq_*drifter* group above with
  * the same statuses and record layout. Single domain and straight-sided (affine) elements only.
  * Host set-up, from a triangle provisioner (no GPU): vertices (K, 8), per element x0, y0, x1, y1, x2, y2 of its corner nodes
  * and two pad entries; the vertices are in face order: face 0 (s = -1) runs from vertex 0 to 1, face 1 (r + s = 0) from 1 to 2,

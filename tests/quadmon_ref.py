@@ -1,4 +1,4 @@
-"""NumPy references of one record of the quadrilateral solver's run monitor (csrc/hip/sw2d_quad_monitor_kernel.hpp).
+"""NumPy references of one record of the quadrilateral solver's run monitor (csrc/hip/sw2d_monitor_kernel.hpp).
 
 record_ld forms every entry in np.longdouble (x87 80-bit), rounded only where it is compared, as tests/quadref_ld.py does; its
 1-D basis values come from its own longdouble barycentric formula on the (float64) Gauss-Lobatto points, not from the

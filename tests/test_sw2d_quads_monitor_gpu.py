@@ -1,5 +1,5 @@
 """The run monitor of the quadrilateral solver on the GPU: bdg_sw2dq_enable_monitor and the bdg_sw2dq_monitor_* group
-(csrc/hip/sw2d_quad_monitor_kernel.hpp), Sw2dQuadSolver.enableMonitor / sampleMonitor / monitorRecords / resetMonitor.
+(csrc/hip/sw2d_monitor_kernel.hpp), Sw2dQuadSolver.enableMonitor / sampleMonitor / monitorRecords / resetMonitor.
 
 Bounds, none of them taken from what the kernels give:
   integrals   n 2^-53 sum|w f| around the longdouble value (tests/quadmon_ref.py), n the number of summed terms: the rigorous
@@ -15,7 +15,8 @@ Bounds, none of them taken from what the kernels give:
               2.1e-16 of the initial mass, one unit in its last place (conservation_reference_drift below, run on the CPU);
               DRIFT_TOL = 10 x that.
 Shapes: the shuffled 13 x 11 boxes (K = 143: reduction workgroups of 64, 64 and 15 elements, 509 without one) in both geometry
-forms, and the jittered 5 x 4 box (one workgroup of 20 elements).
+forms, the jittered 5 x 4 box (one workgroup of 20 elements), and the 363 x 363 box at N = 1 (K = 131 769: reduction workgroups
+of 320 elements, so a thread visits two).
 """
 import ctypes
 
@@ -125,6 +126,37 @@ def test_one_sample_in_every_regime(name, order, fs):
     assert named["gauges"].shape == (5, 10, fields) and np.array_equal(named["mass"], recs[:, 1], equal_nan=True)
     assert np.array_equal(named["energy"], recs[:, fields + 1], equal_nan=True) and np.array_equal(named["nan"], recs[:, fields + 6])
     assert np.array_equal(named["tracer"], recs[:, 4] if fields == 4 else np.zeros(5), equal_nan=True)
+    s.close()
+
+
+def test_restatement_where_a_thread_visits_two_elements():
+    """N = 1, three fields, on the 363 x 363 box, K = 131 769. chunk = ceil(K / 512) rounded up to 64 exceeds the 256 threads of a
+    workgroup exactly when ceil(K / 512) > 256, that is K > 512 * 256 = 131 072; 363 x 363 is the smallest square box beyond that
+    (362^2 = 131 044). There chunk = 320, so threads 0 .. 63 of every full workgroup visit two elements: the shape that
+    tests/test_sw2d_monitor_gpu.py::test_keep_order_restatement_where_a_thread_visits_two_elements pins on triangles (K = 135 200,
+    the same chunk), reached here through the quadrilateral solver, which launches the same reduction kernel."""
+    mesh = dg.MeshManager()
+    mesh.buildMesh(*quadref.quad_box(363))
+    nodes = dg.QuadNodesProvisioner(1, mesh)
+    nodes.buildFilter(0.99, 4)
+    ctx = nodes.dgContext()
+    t = quadref.tables(ctx)
+    K = ctx.numElements
+    assert K == 131769 and K > 512 * 256 and mon.quad_mon_chunk(K) == 320
+    gauges = mon.gauge_points(nodes, ctx, seed=3, interior=2, edges=1)
+    H = bathymetry(t["x"], t["y"])
+    s = sw2dquads.Sw2dQuadSolver(nodes=nodes, g=ld.G)
+    s.enableMonitor(nodes, H=H, gauges=gauges, capacity=1)
+    q = ld.state(t, 3, "smooth", seed=4)
+    set_state(s, q)
+    s.sampleMonitor()
+    got = mon.split_record(s.monitorRecordArray()[0], 3)
+    basis = (nodes.lagrangeBasis(gauges[1]), nodes.lagrangeBasis(gauges[2]))
+    same = mon.record_f64(nodes.quadratureWeights(), q, ld.G, H, gauges=gauges, basis=basis)
+    for name in ("mass", "hu", "hv", "energy"):
+        assert got[name] == same[name], name
+    assert np.array_equal(got["gauges"], same["gauges"])
+    assert got["hmin"] == q[0].min() and got["hmax"] == q[0].max() and got["nan"] == 0
     s.close()
 
 
