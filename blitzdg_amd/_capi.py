@@ -23,6 +23,7 @@ BDG_SW2D_REORDER = 1
 BDG_SW2D_NODAL_GEOMETRY = 2
 BDG_SW2D_KEEP_ORDER = 4
 BDG_SW2DQ_GENERAL_GEOMETRY = 1
+(FIELD_STATS_SUM, FIELD_STATS_ETA_MAX, FIELD_STATS_H_MIN, FIELD_STATS_SPEED_MAX, FIELD_STATS_COS, FIELD_STATS_SIN) = range(6)
 
 # enum values, in header order
 (MESH_VERTICES, MESH_ELEMENTS, MESH_ETOE, MESH_ETOF, MESH_BCTYPE, MESH_EPART, MESH_NPART) = range(7)
@@ -97,6 +98,11 @@ class Sw2dqDrifterDesc(Structure):
 class Sw2dDrifterDesc(Structure):
     _fields_ = [("count", c_int), ("element", c_void_p), ("r", c_void_p), ("s", c_void_p), ("vertices", c_void_p),
                 ("neighbours", c_void_p), ("vinv", c_void_p), ("jacobi", c_void_p), ("stride", c_int), ("capacity", c_int)]
+
+
+class FieldStatsDesc(Structure):
+    _fields_ = [("H", c_void_p), ("stride", c_int), ("num_periods", c_int), ("periods", c_double * 4), ("mean", c_int),
+                ("envelope", c_int)]
 
 
 class Sw2dCurvedDesc(Structure):
@@ -334,6 +340,15 @@ _SIGNATURES = {
     "bdg_sw2d_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "bdg_sw2d_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
     "bdg_sw2d_drifters_reset": (c_int, [_P]),
+    **{f"{_abi}_{_name}": _sig for _abi in ("bdg_sw2d", "bdg_sw2dq") for _name, _sig in {
+        "enable_field_stats": (c_int, [_P, POINTER(FieldStatsDesc)]),
+        "field_stats_sample": (c_int, [_P]),
+        "field_stats_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+        "field_stats_read": (c_int, [_P, c_int, c_int, _P]),
+        "field_stats_samples": (c_int, [_P, c_int, c_int, _P]),
+        "field_stats_reset": (c_int, [_P]),
+        "field_stats_time": (c_int, [_P, c_int, POINTER(c_float)]),
+    }.items()},
     "bdg_sw2d_curved_create": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(_P)]),
     "bdg_sw2d_curved_plan": (c_int, [POINTER(Sw2dCurvedDesc), POINTER(c_int), c_int]),
     "bdg_sw2d_curved_destroy": (None, [_P]),

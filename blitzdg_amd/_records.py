@@ -1,6 +1,6 @@
-"""What ``Sw2dSolver`` and ``Sw2dQuadSolver`` share of the run monitor and the drifters over the C ABI: point location, the
-calls whose bodies differ only in the prefix of the library's functions (``bdg_sw2d`` / ``bdg_sw2dq``), and the gauge list of
-a partitioned run."""
+"""What ``Sw2dSolver`` and ``Sw2dQuadSolver`` share of the run monitor, the field statistics and the drifters over the C ABI:
+point location, the calls whose bodies differ only in the prefix of the library's functions (``bdg_sw2d`` / ``bdg_sw2dq``), the
+harmonic fit from the accumulated statistics, and the gauge list of a partitioned run."""
 import numpy as np
 
 from . import _capi as C
@@ -48,8 +48,45 @@ def partition_gauges(plan, K, gauges, global_nodes, provisioner, outside):
     return el, np.where(mine, r, outside), np.where(mine, s, outside)
 
 
+def harmonic_fit(stats):
+    """The least-squares fit f ~ a0 + sum_j (a_j cos(omega_j t) + b_j sin(omega_j t)) over the samples, for eta, u, v at every
+    node, from the dict ``stats`` of ``RunRecords.fieldStats``: pure NumPy. The normal matrix is sum b b^T with
+    b = [1, c_1, s_1, ..] from the sample log ``trig``; the right-hand sides are the accumulators ``sum``, ``cos``, ``sin``;
+    one solve serves all nodes. Returns a dict: ``mean`` (3, Np, K), the fitted constant a0 (the residual current for u and
+    v); ``amplitude`` and ``phase`` (m, 3, Np, K) with f ~ mean + sum_j A_j cos(omega_j t - phi_j), A = hypot(a, b),
+    phi = atan2(b, a); ``cond``, the 2-norm condition number of the normal matrix, which is left to the caller to judge (a
+    record much shorter than the beat period of two constituents cannot separate them). Needs the mean group and at least
+    one period; raises ValueError without them, if the solve fails or if ``cond`` is not finite."""
+    if "sum" not in stats or "cos" not in stats or "sin" not in stats:
+        raise ValueError("harmonicFit needs the mean group and at least one period (enableFieldStats(periods=..., mean=True))")
+    trig = np.asarray(stats["trig"], dtype=np.float64)
+    n, m = trig.shape[0], trig.shape[1] // 2
+    total, cos, sin = (np.asarray(stats[k], dtype=np.float64) for k in ("sum", "cos", "sin"))
+    if m < 1 or cos.shape[0] != m or sin.shape[0] != m:
+        raise ValueError("harmonicFit: the sample log and the accumulators disagree on the number of periods")
+    basis = np.concatenate([np.ones((n, 1)), trig], axis=1)              # rows b = [1, c_1, s_1, ..]
+    normal = basis.T @ basis
+    shape = total.shape                                                  # (3, Np, K)
+    rhs = np.empty((1 + 2 * m, total.size))
+    rhs[0] = total.reshape(-1)
+    for j in range(m):
+        rhs[1 + 2 * j] = cos[j].reshape(-1)
+        rhs[2 + 2 * j] = sin[j].reshape(-1)
+    try:
+        cond = float(np.linalg.cond(normal))
+        coef = np.linalg.solve(normal, rhs)
+    except np.linalg.LinAlgError as e:
+        raise ValueError(f"harmonicFit: the normal equations cannot be solved ({e})") from None
+    if not np.isfinite(cond):
+        raise ValueError("harmonicFit: the normal matrix is singular (no samples, or two equal periods)")
+    a = coef[1::2].reshape((m,) + shape)
+    b = coef[2::2].reshape((m,) + shape)
+    return {"mean": coef[0].reshape(shape), "amplitude": np.hypot(a, b), "phase": np.arctan2(b, a), "cond": cond}
+
+
 class RunRecords:
-    """The monitor and drifter calls of a solver with the handle ``_h``, ``fields``, ``numDrifters`` and the prefix ``_abi``."""
+    """The monitor, field-statistics and drifter calls of a solver with the handle ``_h``, ``Np``, ``K``, ``fields``,
+    ``numDrifters`` and the prefix ``_abi``."""
 
     _abi = None
 
@@ -92,6 +129,70 @@ class RunRecords:
                "energy": a[:, nf + 1], "hmin": a[:, nf + 2], "hmax": a[:, nf + 3], "humax": a[:, nf + 4], "hvmax": a[:, nf + 5],
                "nan": a[:, nf + 6], "gauges": a[:, nf + 7:].reshape(len(a), -1, nf)}
         return {k: np.ascontiguousarray(v) for k, v in rec.items()}
+
+    # ---- field statistics
+    def enableFieldStats(self, H=None, periods=(), stride=1, mean=True, envelope=True):
+        """Switches on the field statistics: from now on the stepping calls that feed the monitor accumulate on the device, at
+        every node and after every ``stride``-th completed step, the sums of eta, u, v (``mean``), the envelopes etaMax, hMin
+        and speedMax (``envelope``) and, for each of up to four ``periods`` T (seconds), the sums of f cos(2 pi t / T) and
+        f sin(2 pi t / T) at the model time t: one launch per sample, no state download. ``H``: (Np, K) still-water depth of
+        eta = h - H (without one the solver's own, else H = 0). A group that is off costs no memory and no traffic. Once per
+        solver; not on a partitioned solver. ``fieldStats`` reads the accumulators, ``harmonicFit`` turns them into the mean
+        (the residual current for u, v) and the amplitude and phase of every constituent."""
+        Hh = None if H is None else C.as_f64(H, (self.Np, self.K), "H")
+        T = [float(p) for p in periods]
+        if len(T) > 4:
+            raise ValueError("periods: at most 4")
+        d = C.FieldStatsDesc(C.ptr(Hh), int(stride), len(T), (C.c_double * 4)(*T), int(bool(mean)), int(bool(envelope)))
+        self._records_call("enable_field_stats", byref(d))
+        self._fieldStatsGroups = (bool(mean), bool(envelope))
+
+    def sampleFieldStats(self):
+        """One sample of the resident state now (at the solver's model time)."""
+        self._records_call("field_stats_sample")
+
+    def resetFieldStats(self):
+        """Accumulators as after enableFieldStats, no samples, and the step count restarted."""
+        self._records_call("field_stats_reset")
+
+    def timeFieldStats(self, count):
+        """Average device milliseconds of one sample; the accumulators and the sample log are left alone."""
+        ms = c_float()
+        self._records_call("field_stats_time", int(count), byref(ms))
+        return ms.value
+
+    def _stats_plane(self, which, index=0):
+        out = np.empty((self.Np, self.K))
+        self._records_call("field_stats_read", which, index, C.ptr(out))
+        return out
+
+    def fieldStats(self):
+        """dict of what has been accumulated, in the caller's numbering; waits for the solver's stream. ``n`` samples, their
+        model times ``t`` (n,) and ``trig`` (n, 2 m): cos, sin of 2 pi t / T_j per period, the values the device was given;
+        with the mean group ``sum`` (3, Np, K) of eta, u, v; with the envelope group ``etaMax``, ``hMin``, ``speedMax``
+        (Np, K); with m >= 1 periods ``cos`` and ``sin`` (m, 3, Np, K). The keys of a group that is off are absent."""
+        n, m = c_int(), c_int()
+        self._records_call("field_stats_count", byref(n), byref(m))
+        n, m = n.value, m.value
+        rows = np.empty((n, 1 + 2 * m))
+        self._records_call("field_stats_samples", 0, n, C.ptr(rows))
+        out = {"n": n, "t": np.ascontiguousarray(rows[:, 0]), "trig": np.ascontiguousarray(rows[:, 1:])}
+        mean, envelope = self._fieldStatsGroups
+        if mean:
+            out["sum"] = np.stack([self._stats_plane(C.FIELD_STATS_SUM, f) for f in range(3)])
+        if envelope:
+            out["etaMax"] = self._stats_plane(C.FIELD_STATS_ETA_MAX)
+            out["hMin"] = self._stats_plane(C.FIELD_STATS_H_MIN)
+            out["speedMax"] = self._stats_plane(C.FIELD_STATS_SPEED_MAX)
+        for key, which in (("cos", C.FIELD_STATS_COS), ("sin", C.FIELD_STATS_SIN)):
+            if m > 0:
+                out[key] = np.stack([self._stats_plane(which, i) for i in range(3 * m)]).reshape(m, 3, self.Np, self.K)
+        return out
+
+    def harmonicFit(self, stats=None):
+        """The least-squares fit f ~ mean + sum_j A_j cos(omega_j t - phi_j) of eta, u, v at every node, from ``stats``
+        (default: ``fieldStats()``), on the host: see ``harmonic_fit``."""
+        return harmonic_fit(self.fieldStats() if stats is None else stats)
 
     # ---- drifters
     def advanceDrifters(self, dt, nsteps=1):

@@ -1,5 +1,6 @@
 // run_records.hpp -- what the triangle solver (sw2d_device.hip) and the quadrilateral one (sw2d_quad_device.hip) share of
-// the run monitor (sw2d_monitor_kernel.hpp) and the drifters (sw2d_drifter_driver.hpp) on the host: the bookkeeping of the
+// the run monitor (sw2d_monitor_kernel.hpp), the field statistics (sw2d_stats_kernel.hpp) and the drifters
+// (sw2d_drifter_driver.hpp) on the host: the bookkeeping of the
 // records, their buffers, the launches, the reads and the all-reduce of a partitioned run. What differs stays with each
 // solver: the gauge and drifter tables and their checks, the choice of H, stepDone and the partition test. The per-order
 // objects never include this header.
@@ -9,6 +10,9 @@
 #include "halo_transport.hpp"
 #include "sw2d_drifter_driver.hpp"
 #include "sw2d_monitor_kernel.hpp"
+#include "sw2d_stats_kernel.hpp"
+#include <algorithm>
+#include <cmath>
 #include <initializer_list>
 #include <string>
 #include <utility>
@@ -155,6 +159,169 @@ struct MonitorState {
         hipCheck(hipMemcpy2DAsync(rec.p + capacity + reduced, capacity * sizeof(double), stage.p, n * sizeof(double),
                                   n * sizeof(double), cols, hipMemcpyDeviceToDevice, stream), "hipMemcpy2D (records)");
         reduced = count;
+    }
+};
+
+// what a sample of the field statistics reads: the resident state, the depth (or NULL), the owned range [0, count) and the
+// model time
+struct StatsView {
+    const double* q;
+    const double* H;
+    long long ld;
+    int Np, count;
+    double t;
+};
+
+// the field statistics (`prefix`_enable_field_stats, sw2d_stats_kernel.hpp): the accumulator planes on the device and, on the
+// host, the log of the samples: one row t, c_1, s_1, .. c_m, s_m per sample, exactly the values passed to the kernel
+struct FieldStatsState {
+    bool on = false, mean = false, envelope = false;
+    int stride = 1, m = 0;
+    long long steps = 0;  // completed steps since set_state / field_stats_reset
+    size_t plane = 0;     // entries of one plane, Np * ld
+    double omega[bdg_dev::kStatsMaxPeriods] = {};
+    DevBuf<double> acc, H;
+    std::vector<double> log;
+
+    int planes() const { return bdg_dev::statsPlanes(mean, envelope, m); }
+    int rowWidth() const { return 1 + 2 * m; }
+    int count() const { return static_cast<int>(log.size() / rowWidth()); }
+    void requireOn(const char* fn, const std::string& prefix) const {
+        if (!on) throw arg_error(std::string(fn) + ": field statistics are not enabled (" + prefix + "_enable_field_stats)");
+    }
+    // the checks of `prefix`_enable_field_stats; Desc: H, stride, num_periods, periods, mean, envelope
+    template <class Desc>
+    void checkEnable(const std::string& fn, const Desc* d, bool partitioned) const {
+        if (!d) throw arg_error(fn + ": the descriptor is required");
+        if (on) throw arg_error(fn + ": field statistics are already enabled on this solver; the call is made once");
+        if (d->stride < 1) throw arg_error(fn + ": stride must be >= 1");
+        if (d->num_periods < 0 || d->num_periods > bdg_dev::kStatsMaxPeriods)
+            throw arg_error(fn + ": num_periods must lie in [0, " + std::to_string(bdg_dev::kStatsMaxPeriods) + "]");
+        for (int j = 0; j < d->num_periods; ++j)
+            if (!(d->periods[j] > 0.0) || !std::isfinite(d->periods[j]))
+                throw arg_error(fn + ": period " + std::to_string(j) + " must be > 0 and finite");
+        if (!d->mean && !d->envelope && d->num_periods == 0)
+            throw arg_error(fn + ": nothing to accumulate (mean, envelope and periods are all off)");
+        if (partitioned)
+            throw arg_error(fn + ": the solver has a partition set; the field statistics of a partitioned run are not accumulated "
+                                 "(single domain only)");
+    }
+    // -inf, +inf, 0.0 in the envelopes and 0.0 everywhere else, on `stream`
+    void clear(double* to, hipStream_t stream) const {
+        using namespace bdg_dev;
+        hipCheck(hipMemsetAsync(to, 0, static_cast<size_t>(planes()) * plane * sizeof(double), stream), "hipMemset");
+        if (!envelope) return;
+        const unsigned grid = static_cast<unsigned>((plane + kStatsThreads - 1) / kStatsThreads);
+        double* env = to + static_cast<size_t>(statsEnvelopeBase(mean)) * plane;
+        hipLaunchKernelGGL(sw2d_stats_fill_kernel, dim3(grid), dim3(kStatsThreads), 0, stream, env, static_cast<long long>(plane),
+                           -__builtin_inf());
+        hipLaunchKernelGGL(sw2d_stats_fill_kernel, dim3(grid), dim3(kStatsThreads), 0, stream, env + plane,
+                           static_cast<long long>(plane), __builtin_inf());
+        hipCheck(hipGetLastError(), "sw2d_stats_fill_kernel launch");
+    }
+    // the buffers: `depth()` allocates and fills H where the caller gave one; the accumulators follow. A failure leaves the
+    // solver without field statistics and `bytes` where it was.
+    template <class Desc, class Depth>
+    void enable(const Desc& d, size_t plane_, size_t& bytes, hipStream_t stream, Depth&& depth) {
+        const size_t bytesBefore = bytes;
+        // the groups are members because planes() and clear() read them; a failure puts the unset state back
+        mean = d.mean != 0; envelope = d.envelope != 0; m = d.num_periods; plane = plane_;
+        try {
+            depth();
+            acc.alloc(static_cast<size_t>(planes()) * plane, bytes);
+            clear(acc.p, stream);
+            hipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        } catch (...) {
+            (void)hipStreamSynchronize(stream);
+            acc.release();
+            H.release();
+            bytes = bytesBefore;
+            mean = envelope = false; m = 0; plane = 0;
+            throw;
+        }
+        for (int j = 0; j < m; ++j) omega[j] = 2.0 * M_PI / d.periods[j];
+        on = true;
+        stride = d.stride; steps = 0;
+        log.clear();
+    }
+    // one launch of the kernel on `stream`: the sample of `v` with the row `trig` (c_1, s_1, ..) into the planes at `to`
+    void launch(const StatsView& v, const double* trig, double* to, hipStream_t stream) const {
+        bdg_dev::StatsParams p{v.q, v.H, to, v.ld, v.Np, v.count, {}, {}};
+        for (int j = 0; j < m; ++j) {
+            p.c[j] = trig[2 * j];
+            p.s[j] = trig[2 * j + 1];
+        }
+        hipCheck(bdg_dev::statsLaunch(mean, envelope, m, p, stream), "sw2d_stats_kernel launch");
+    }
+    // the row of a sample at the model time t: t, cos(omega_1 t), sin(omega_1 t), ..
+    void trigRow(double t, double* row) const {
+        row[0] = t;
+        for (int j = 0; j < m; ++j) {
+            row[1 + 2 * j] = std::cos(omega[j] * t);
+            row[2 + 2 * j] = std::sin(omega[j] * t);
+        }
+    }
+    // ... accumulated and logged
+    void sample(const StatsView& v, hipStream_t stream) {
+        double row[1 + 2 * bdg_dev::kStatsMaxPeriods];
+        trigRow(v.t, row);
+        launch(v, row + 1, acc.p, stream);
+        log.insert(log.end(), row, row + rowWidth());
+    }
+    // the device slot of a plane: `which` as BDG_FIELD_STATS_* of include/blitzdg_hip.h (sum, etaMax, hMin, speedMax, cos, sin),
+    // index the field (sum) or 3 j + field (cos, sin)
+    const double* planeOf(const char* fn, int which, int index) const {
+        using namespace bdg_dev;
+        const std::string f(fn);
+        int at = -1;
+        if (which == 0) {
+            if (!mean) throw arg_error(f + ": the mean group is not enabled");
+            if (index < 0 || index >= 3) throw arg_error(f + ": index outside [0, 3)");
+            at = index;
+        } else if (which >= 1 && which <= 3) {
+            if (!envelope) throw arg_error(f + ": the envelope group is not enabled");
+            if (index != 0) throw arg_error(f + ": index must be 0");
+            at = statsEnvelopeBase(mean) + which - 1;
+        } else if (which == 4 || which == 5) {
+            if (m == 0) throw arg_error(f + ": the harmonic group is not enabled (no periods)");
+            if (index < 0 || index >= 3 * m) throw arg_error(f + ": index outside [0, 3 * num_periods)");
+            at = statsHarmonicBase(mean, envelope) + 6 * (index / 3) + (which == 5 ? 3 : 0) + index % 3;
+        } else {
+            throw arg_error(f + ": unknown plane");
+        }
+        return acc.p + static_cast<size_t>(at) * plane;
+    }
+    // rows [first, first + n) of the sample log into `rows`
+    void samples(const char* fn, int first, int n, double* rows) const {
+        if (first < 0 || n < 0 || first > count() - n || (n > 0 && !rows)) throw arg_error(std::string(fn) + ": bad sample range");
+        std::copy(log.begin() + static_cast<size_t>(first) * rowWidth(), log.begin() + static_cast<size_t>(first + n) * rowWidth(), rows);
+    }
+    // accumulators, log and step counter as after enable
+    void reset(hipStream_t stream) {
+        clear(acc.p, stream);
+        log.clear();
+        steps = 0;
+    }
+    // average device milliseconds of one sample, `count` of them into scratch accumulators that live for the call
+    float time(const StatsView& v, int count_, size_t& bytes, hipStream_t stream) const {
+        const size_t bytesBefore = bytes;
+        DevBuf<double> scratch;
+        float ms = 0.0f;
+        try {
+            scratch.alloc(static_cast<size_t>(planes()) * plane, bytes);
+            clear(scratch.p, stream);
+            double row[1 + 2 * bdg_dev::kStatsMaxPeriods];
+            trigRow(v.t, row);
+            launch(v, row + 1, scratch.p, stream); // once before the clock starts
+            ms = bdg_dev::timePerRun(stream, count_, [&] { launch(v, row + 1, scratch.p, stream); });
+        } catch (...) {
+            (void)hipStreamSynchronize(stream);
+            bytes = bytesBefore;
+            throw;
+        }
+        hipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        bytes = bytesBefore;
+        return ms;
     }
 };
 

@@ -306,6 +306,8 @@ struct bdg_sw2d {
         DevBuf<double> vert, vinvT, jac;
         std::vector<int> callerOf; // device slot -> caller element (empty = identity)
     } drf;
+    // field statistics (bdg_sw2d_enable_field_stats): sw2d_stats_kernel.hpp
+    bdg_records::FieldStatsState fst;
     bool partitionSet = false; // bdg_sw2d_set_partition has been called
 
     ~bdg_sw2d() {
@@ -358,6 +360,7 @@ struct bdg_sw2d {
         hipCheck(hipMemsetAsync(res.p, 0, res.n * sizeof(double), stream), "hipMemset");
         stageCount = 0;
         mon.steps = 0;
+        fst.steps = 0;
         lamStateFor = nullptr; // a speed accumulated for the previous contents of this buffer is void
         drifterResample();
         hipCheck(hipStreamSynchronize(stream), "set_state sync");
@@ -965,10 +968,19 @@ struct bdg_sw2d {
     void drifterResample() {
         if (drf.on) drifterLaunch(bdg_dev::kDriftSample, 0.0, -1);
     }
+    // what a sample of the field statistics reads: the owned device slots; H by the monitor's rule: the statistics' own, else
+    // the solver's resident one, else none
+    bdg_records::StatsView statsView() const {
+        const double* Hm = fst.H.p ? fst.H.p : (hasH ? Hbuf.p : nullptr);
+        return {qcur, Hm, ld, Np, numOwned, timeNow};
+    }
+    void statsSample() { fst.sample(statsView(), stream); }
     // after every completed step (of size dt) of a stepping call whose launches are all on the solver's stream (room was reserved
-    // by the caller): the monitor's sample, then the drifters' advance (drifters exist on unpartitioned solvers only)
+    // by the caller): the monitor's sample, the sample of the field statistics, then the drifters' advance (statistics and
+    // drifters exist on unpartitioned solvers only)
     void stepDone(double dt) {
         if (mon.on && ++mon.steps % mon.stride == 0) monitorSample();
+        if (fst.on && ++fst.steps % fst.stride == 0) statsSample();
         if (drf.on) {
             drf.t = timeNow;
             drifterAdvance(dt);
@@ -1753,6 +1765,8 @@ int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const i
         requireSolver(s, "bdg_sw2d_set_partition");
         if (s->drf.on)
             throw arg_error("bdg_sw2d_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
+        if (s->fst.on)
+            throw arg_error("bdg_sw2d_set_partition: the solver has field statistics, which cover a single domain only");
         if (!s->permHost.empty())
             throw arg_error("bdg_sw2d_set_partition: the solver renumbered its elements; create it with BDG_SW2D_KEEP_ORDER");
         if (num_interior < 0 || num_interior > num_owned || num_owned > s->K || num_send < 0 ||
@@ -1871,6 +1885,7 @@ int bdg_sw2d_comm_init(bdg_sw2d* s, int rank, int world, const void* unique_id, 
             (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
             throw arg_error("bdg_sw2d_comm_init: bad argument");
         if (s->halo.comm) throw arg_error("bdg_sw2d_comm_init: communicator already initialised");
+        if (s->fst.on) throw arg_error("bdg_sw2d_comm_init: the solver has field statistics, which cover a single domain only");
         const int ghosts = s->K - s->numOwned;
         std::vector<bdg_halo::Peer> peers = bdg_halo::parsePeers("bdg_sw2d", "comm_init", peer_ranks, send_start, send_count, recv_start,
                                                                  recv_count, num_peers, s->numSend, ghosts, world);
@@ -1916,6 +1931,7 @@ int bdg_sw2d_local_peers(bdg_sw2d* s, int rank, const int* peer_ranks, const int
             (num_peers > 0 && (!peer_ranks || !send_start || !send_count || !recv_start || !recv_count)))
             throw arg_error("bdg_sw2d_local_peers: bad argument");
         if (s->halo.comm || s->localGroup) throw arg_error("bdg_sw2d_local_peers: a transport is already initialised");
+        if (s->fst.on) throw arg_error("bdg_sw2d_local_peers: the solver has field statistics, which cover a single domain only");
         const int ghosts = s->K - s->numOwned;
         // (no world here: any other rank of the group)
         std::vector<bdg_halo::Peer> peers = bdg_halo::parsePeers("bdg_sw2d", "local_peers", peer_ranks, send_start, send_count, recv_start,
@@ -2291,6 +2307,78 @@ int bdg_sw2d_drifters_reset(bdg_sw2d* s) {
     return guard([&] {
         requireDriftersOn(s, "bdg_sw2d_drifters_reset");
         s->drf.count = 0;
+    });
+}
+
+// ---- field statistics (what the quadrilateral solver has too: run_records.hpp)
+int bdg_sw2d_enable_field_stats(bdg_sw2d* s, const bdg_field_stats_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_enable_field_stats";
+        requireSolver(s, fn.c_str());
+        s->fst.checkEnable(fn, d, s->partitionSet || s->numOwned != s->K || s->halo.comm || s->localGroup);
+        s->use();
+        // H zero-padded and through the solver's own upload, so that it follows the renumbering
+        s->fst.enable(*d, s->planeSize(), s->bytes, s->stream, [&] {
+            if (d->H) s->uploadPlane(d->H, s->fst.H);
+        });
+    });
+}
+
+namespace {
+void requireStatsOn(const bdg_sw2d* s, const char* fn) {
+    requireSolver(s, fn);
+    s->fst.requireOn(fn, "bdg_sw2d");
+}
+} // namespace
+
+int bdg_sw2d_field_stats_sample(bdg_sw2d* s) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_sample");
+        s->use();
+        s->statsSample();
+    });
+}
+
+int bdg_sw2d_field_stats_count(const bdg_sw2d* s, int* samples, int* num_periods) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_count");
+        if (!samples || !num_periods) throw arg_error("bdg_sw2d_field_stats_count: NULL argument");
+        *samples = s->fst.count();
+        *num_periods = s->fst.m;
+    });
+}
+
+int bdg_sw2d_field_stats_read(bdg_sw2d* s, int which, int index, double* plane) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_read");
+        if (!plane) throw arg_error("bdg_sw2d_field_stats_read: NULL argument");
+        const double* dev = s->fst.planeOf("bdg_sw2d_field_stats_read", which, index);
+        s->use();
+        s->downloadRows(dev, plane, s->Np); // (device slots back to the caller's numbering)
+    });
+}
+
+int bdg_sw2d_field_stats_samples(const bdg_sw2d* s, int first, int count, double* rows) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_samples");
+        s->fst.samples("bdg_sw2d_field_stats_samples", first, count, rows);
+    });
+}
+
+int bdg_sw2d_field_stats_reset(bdg_sw2d* s) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_reset");
+        s->use();
+        s->fst.reset(s->stream);
+    });
+}
+
+int bdg_sw2d_field_stats_time(bdg_sw2d* s, int count, float* ms) {
+    return guard([&] {
+        requireStatsOn(s, "bdg_sw2d_field_stats_time");
+        if (count < 1 || !ms) throw arg_error("bdg_sw2d_field_stats_time: bad argument");
+        s->use();
+        *ms = s->fst.time(s->statsView(), count, s->bytes, s->stream);
     });
 }
 

@@ -201,6 +201,8 @@ struct bdg_sw2dq {
     struct Drifters : bdg_records::DrifterState {
         DevBuf<double> bil, r1d, bary;
     } drf;
+    // field statistics (bdg_sw2dq_enable_field_stats): sw2d_stats_kernel.hpp
+    bdg_records::FieldStatsState fst;
 
     void use() const { hipCheck(hipSetDevice(device), "hipSetDevice"); }
     long long plane() const { return static_cast<long long>(Np) * ld; }
@@ -430,15 +432,23 @@ struct bdg_sw2dq {
     void drifterResample() {
         if (drf.on) drifterLaunch(kDriftSample, 0.0, -1);
     }
-    // after every completed step (of size dt) of a stepping call: the monitor's sample, then the drifters' advance. two: the call
-    // runs the two-chain schedule, whose chains are joined in front of the sample and started again behind it (the sample reads
-    // columns the exchange stream wrote); drifters exist on unpartitioned solvers only
+    // what a sample of the field statistics reads; H by the monitor's rule: the statistics' own, else variant B's, else none
+    bdg_records::StatsView statsView() const {
+        const double* Hm = fst.H.p ? fst.H.p : (variantB ? vbH.p : nullptr);
+        return {q.p, Hm, ld, Np, K, timeNow};
+    }
+    void statsSample() { fst.sample(statsView(), stream); }
+    // after every completed step (of size dt) of a stepping call: the monitor's sample, the sample of the field statistics, then
+    // the drifters' advance. two: the call runs the two-chain schedule, whose chains are joined in front of the monitor's sample
+    // and started again behind it (the sample reads columns the exchange stream wrote); statistics and drifters exist on
+    // unpartitioned solvers only
     void stepDone(double dt, bool two = false) {
         if (mon.on && ++mon.steps % mon.stride == 0) {
             if (two) chains.end(stream, halo.stream);
             monitorSample();
             if (two) chains.begin(stream, halo.stream);
         }
+        if (fst.on && ++fst.steps % fst.stride == 0) statsSample();
         if (drf.on) {
             drf.t = timeNow;
             drifterAdvance(dt);
@@ -655,6 +665,7 @@ void setState(bdg_sw2dq* s, int nf, const double* const* in, const std::string& 
     s->res.zero(s->stream);
     s->stageCount = 0;
     s->mon.steps = 0;
+    s->fst.steps = 0;
     s->drifterResample();
     hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
 }
@@ -1070,6 +1081,8 @@ int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const
         requireSolver(s, "bdg_sw2dq_set_partition");
         if (s->drf.on)
             throw arg_error("bdg_sw2dq_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
+        if (s->fst.on)
+            throw arg_error("bdg_sw2dq_set_partition: the solver has field statistics, which cover a single domain only");
         s->use();
         s->part.set("bdg_sw2dq", s->K, s->maxNeighbourHost, num_interior, num_owned, send_elements, num_send, s->halo.comm != nullptr,
                     s->bytes, s->stream);
@@ -1080,6 +1093,7 @@ int bdg_sw2dq_comm_init(bdg_sw2dq* s, int rank, int world, const void* unique_id
                         const int* send_count, const int* recv_start, const int* recv_count, int num_peers) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_comm_init");
+        if (s->fst.on) throw arg_error("bdg_sw2dq_comm_init: the solver has field statistics, which cover a single domain only");
         s->use();
         bdg_halo::commInit("bdg_sw2dq", s->halo, s->part, s->chains, s->K, static_cast<size_t>(s->fields) * s->Np, rank, world, unique_id,
                            peer_ranks, send_start, send_count, recv_start, recv_count, num_peers, s->bytes, s->stream);
@@ -1301,6 +1315,80 @@ int bdg_sw2dq_drifters_reset(bdg_sw2dq* s) {
     return guard([&] {
         requireDrifters(s, "bdg_sw2dq_drifters_reset");
         s->drf.count = 0;
+    });
+}
+
+// ---- field statistics (what the triangle solver has too: run_records.hpp)
+int bdg_sw2dq_enable_field_stats(bdg_sw2dq* s, const bdg_field_stats_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2dq_enable_field_stats";
+        requireSolver(s, fn.c_str());
+        s->fst.checkEnable(fn, d, s->part.numOwned > 0 || s->halo.comm);
+        s->use();
+        s->fst.enable(*d, static_cast<size_t>(s->plane()), s->bytes, s->stream, [&] {
+            if (!d->H) return;
+            s->fst.H.alloc(static_cast<size_t>(s->plane()), s->bytes, s->stream);
+            s->upload(s->fst.H.p, d->H, s->Np);
+        });
+    });
+}
+
+namespace {
+void requireStats(const bdg_sw2dq* s, const char* fn) {
+    requireSolver(s, fn);
+    s->fst.requireOn(fn, "bdg_sw2dq");
+}
+} // namespace
+
+int bdg_sw2dq_field_stats_sample(bdg_sw2dq* s) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_sample");
+        s->use();
+        s->statsSample();
+    });
+}
+
+int bdg_sw2dq_field_stats_count(const bdg_sw2dq* s, int* samples, int* num_periods) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_count");
+        if (!samples || !num_periods) throw arg_error("bdg_sw2dq_field_stats_count: NULL argument");
+        *samples = s->fst.count();
+        *num_periods = s->fst.m;
+    });
+}
+
+int bdg_sw2dq_field_stats_read(bdg_sw2dq* s, int which, int index, double* plane) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_read");
+        if (!plane) throw arg_error("bdg_sw2dq_field_stats_read: NULL argument");
+        const double* dev = s->fst.planeOf("bdg_sw2dq_field_stats_read", which, index);
+        s->use();
+        s->download(plane, dev, s->Np);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    });
+}
+
+int bdg_sw2dq_field_stats_samples(const bdg_sw2dq* s, int first, int count, double* rows) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_samples");
+        s->fst.samples("bdg_sw2dq_field_stats_samples", first, count, rows);
+    });
+}
+
+int bdg_sw2dq_field_stats_reset(bdg_sw2dq* s) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_reset");
+        s->use();
+        s->fst.reset(s->stream);
+    });
+}
+
+int bdg_sw2dq_field_stats_time(bdg_sw2dq* s, int count, float* ms) {
+    return guard([&] {
+        requireStats(s, "bdg_sw2dq_field_stats_time");
+        if (count < 1 || !ms) throw arg_error("bdg_sw2dq_field_stats_time: bad argument");
+        s->use();
+        *ms = s->fst.time(s->statsView(), count, s->bytes, s->stream);
     });
 }
 

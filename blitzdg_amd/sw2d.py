@@ -24,7 +24,8 @@ KEEP_ORDER = C.BDG_SW2D_KEEP_ORDER
 
 class Sw2dSolver(RunRecords):
     """Device-resident shallow-water DG solver (one HIP device, one stream). The monitor and drifter calls that
-    ``enableMonitor`` and ``enableDrifters`` switch on are those of ``RunRecords``."""
+    ``enableMonitor`` and ``enableDrifters`` switch on, and the field statistics (``enableFieldStats``, ``fieldStats``,
+    ``harmonicFit``), are those of ``RunRecords``."""
 
     _abi = "bdg_sw2d"
 

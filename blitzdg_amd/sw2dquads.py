@@ -33,7 +33,8 @@ def _timed(fn, *args):
 
 class Sw2dQuadSolver(RunRecords):
     """Device-resident quadrilateral shallow-water DG solver (one HIP device, one stream). The monitor and drifter calls that
-    ``enableMonitor`` and ``enableDrifters`` switch on are those of ``RunRecords``."""
+    ``enableMonitor`` and ``enableDrifters`` switch on, and the field statistics (``enableFieldStats``, ``fieldStats``,
+    ``harmonicFit``), are those of ``RunRecords``."""
 
     _abi = "bdg_sw2dq"
 

@@ -841,6 +841,55 @@ int bdg_sw2d_drifters_count(const bdg_sw2d* s, int* num_records, int* num_drifte
 int bdg_sw2d_drifters_read(bdg_sw2d* s, int first, int num, double* t, double* x, double* y, int* status);
 int bdg_sw2d_drifters_reset(bdg_sw2d* s);
 
+/* ---- field statistics of the triangle and the quadrilateral solver: per node, over the samples of a run, the sums of
+ * eta, u, v (mean group), the envelopes etaMax, hMin, speedMax (envelope group) and, for up to four periods T_j, the sums of
+ * f cos(omega_j t) and f sin(omega_j t), omega_j = 2 pi / T_j (harmonic group), accumulated on the device with one launch
+ * per sample on the solver's stream, no host wait and no state download (csrc/hip/sw2d_stats_kernel.hpp, which states the
+ * arithmetic: eta = h - H, u = hu / h, v = hv / h by the rule of output_fields; acc = acc + f c with one multiply and one
+ * add; fmax / fmin skip NaNs; speed = sqrt(u u + v v); the envelopes start from -inf, +inf, 0). H: the descriptor's if given,
+ * else the solver's resident one (set_bathymetry or variant B), else 0. t is the model time of the sample, and cos / sin are
+ * formed on the host in double; the host keeps one row t, c_1, s_1, .. c_m, s_m per sample, exactly what the kernel was
+ * given, from which a caller forms the normal equations of a harmonic fit (blitzdg_amd/_records.py: harmonicFit). A group
+ * that is off allocates and moves nothing. hN of a four-field solver is not analysed. */
+typedef struct bdg_field_stats_desc {
+    const double* H;            /* (Np, K) or NULL */
+    int stride;                 /* sample after every stride-th completed step, >= 1 */
+    int num_periods;            /* 0 .. 4 */
+    double periods[4];          /* seconds, each > 0 */
+    int mean;                   /* nonzero: the mean group */
+    int envelope;               /* nonzero: the envelope group */
+} bdg_field_stats_desc;
+/* `which` of field_stats_read. SUM: index = field (0 eta, 1 u, 2 v); ETA_MAX, H_MIN, SPEED_MAX: index = 0; COS, SIN: index =
+ * 3 j + field for period j. */
+enum { BDG_FIELD_STATS_SUM = 0, BDG_FIELD_STATS_ETA_MAX = 1, BDG_FIELD_STATS_H_MIN = 2, BDG_FIELD_STATS_SPEED_MAX = 3,
+       BDG_FIELD_STATS_COS = 4, BDG_FIELD_STATS_SIN = 5 };
+/* enable_field_stats: once per solver. BDG_ERR_ARGUMENT, changing nothing (device_bytes included), for a NULL handle or
+ * descriptor, a second call, stride < 1, num_periods outside [0, 4], a period <= 0, a descriptor with every group off, and a
+ * solver with a partition or a transport set; set_partition, comm_init and local_peers in turn refuse a solver that has field
+ * statistics (the _exchanged steppers take no samples). From then on the stepping
+ * calls that feed the monitor take a sample after every stride-th completed step (counted over calls; set_state and
+ * set_state4 restart the count and leave the accumulators alone), behind the monitor's sample and in front of the drifters'
+ * advance. field_stats_sample: one sample of the resident state now. field_stats_count: samples taken and num_periods.
+ * field_stats_read: one accumulator plane as (Np, K) doubles in the caller's numbering; synchronises the solver's stream;
+ * BDG_ERR_ARGUMENT for a group that is off and for an index outside it. field_stats_samples: rows [first, first + count) of the
+ * sample log, 1 + 2 num_periods doubles each. field_stats_reset: accumulators as after enable, log empty, step count 0.
+ * field_stats_time: average device milliseconds of one sample, `count` of them into scratch accumulators that live for the
+ * call: neither the accumulators nor the log change. */
+int bdg_sw2d_enable_field_stats(bdg_sw2d* s, const bdg_field_stats_desc* desc);
+int bdg_sw2d_field_stats_sample(bdg_sw2d* s);
+int bdg_sw2d_field_stats_count(const bdg_sw2d* s, int* samples, int* num_periods);
+int bdg_sw2d_field_stats_read(bdg_sw2d* s, int which, int index, double* plane);
+int bdg_sw2d_field_stats_samples(const bdg_sw2d* s, int first, int count, double* rows);
+int bdg_sw2d_field_stats_reset(bdg_sw2d* s);
+int bdg_sw2d_field_stats_time(bdg_sw2d* s, int count, float* ms);
+int bdg_sw2dq_enable_field_stats(bdg_sw2dq* s, const bdg_field_stats_desc* desc);
+int bdg_sw2dq_field_stats_sample(bdg_sw2dq* s);
+int bdg_sw2dq_field_stats_count(const bdg_sw2dq* s, int* samples, int* num_periods);
+int bdg_sw2dq_field_stats_read(bdg_sw2dq* s, int which, int index, double* plane);
+int bdg_sw2dq_field_stats_samples(const bdg_sw2dq* s, int first, int count, double* rows);
+int bdg_sw2dq_field_stats_reset(bdg_sw2dq* s);
+int bdg_sw2dq_field_stats_time(bdg_sw2dq* s, int count, float* ms);
+
 /* ---------------------------------------------------------------- sw2d, curved / over-integrated RHS
  * reference: swhelpers.rhs.sw2dComputeRHS_curved(h, hu, hv, hN, zx, zy, g, H, f, CD, ctx, cub_ctx, gauss_ctx,
  * curvedEls, J, gmapM, gmapP) (swhelpers/rhs.py:6-176), driven by sw2d_curved.py:246-277 (RHS, Filter, midpoint
