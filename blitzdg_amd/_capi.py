@@ -5,7 +5,7 @@ There is no fallback: if the shared object is missing, importing this module rai
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_size_t, c_uint,
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint,
                     c_ulonglong, c_void_p)
 
 import numpy as np
@@ -320,6 +320,8 @@ _SIGNATURES = {
     "bdg_element_order": (c_int, [_P, c_int, c_int, _P]),
     "bdg_element_order_wanted": (c_int, [_P, c_int, c_int]),
     "bdg_sw2d_device_bytes": (c_size_t, [_P]),
+    "bdg_stage_tile": (c_uint, [c_uint, c_uint, c_uint]),
+    "bdg_sw2d_backward_launches": (c_longlong, [_P]),
     "bdg_sw2d_stream": (c_void_p, [_P]),
     "bdg_trinodes_quadrature_weights": (c_int, [_P, _P]),
     "bdg_trinodes_locate_points": (c_int, [_P, _P, _P, c_int, _P, _P, _P]),

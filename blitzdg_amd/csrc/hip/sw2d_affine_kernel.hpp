@@ -126,8 +126,7 @@ __global__ __launch_bounds__(256) void sw2d_stage_affine_kernel(const StageParam
     constexpr bool kReadRes = MODE == MODE_LSERK && KIND != STAGE_FIRST;
     constexpr bool kWriteRes = KIND != STAGE_LAST;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     // 32-bit element index: every row pointer below is wave-uniform (SGPR base) and the lane
     // part is a 32-bit offset, so a load needs no 64-bit vector address arithmetic.
     const unsigned k = static_cast<unsigned>(p.kbegin) + tile * blockDim.x + threadIdx.x;
@@ -489,8 +488,7 @@ __global__ __launch_bounds__(256, WAVES) void sw2d_stage_affine_stream_kernel(co
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const unsigned k = static_cast<unsigned>(p.kbegin) + tile * blockDim.x + threadIdx.x;
     if (k >= static_cast<unsigned>(p.kend)) return;
     const unsigned k8 = k * 8u, k4 = k * 4u;
@@ -708,8 +706,7 @@ __global__ __launch_bounds__(FIELDS == 3 ? 256 : 192, 2) void sw2d_stage_affine_
     constexpr int Np = E::Np, Nfp = E::Nfp;
     static_assert(FIELDS == 1 || FIELDS == 3, "FIELDS is 1 or 3");
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const int c = FIELDS == 3 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // field of this wave
     const unsigned k = static_cast<unsigned>(p.kbegin) +
                        (FIELDS == 3 ? tile * 256u + threadIdx.x : tile * 64u + (threadIdx.x & 63u));

@@ -22,8 +22,7 @@ __global__ __launch_bounds__(64) void sw2d_stage_affine_xchg_kernel(const StageP
     constexpr int Np = E::Np, Nfp = E::Nfp, NFN = E::NFN;
     __shared__ double xs[3 * Np * 64];
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const unsigned base = static_cast<unsigned>(p.kbegin) + tile * 64u, lane = threadIdx.x;
     // (lanes beyond kend leave, as in variant 0: no live lane has a neighbour there; a branch around the update instead cost
     // 1371 spilled scalar and 106 vector registers -- the unrolled body must stay one basic block)

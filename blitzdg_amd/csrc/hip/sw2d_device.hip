@@ -125,12 +125,12 @@ __global__ __launch_bounds__(256) void triad_kernel(double2* __restrict__ a, con
 // writes: residual and state, 6Np rows), with no gathers and almost no arithmetic: the time of
 // this launch is the memory-system floor for the stage kernel's own access pattern. With face
 // links: 3 index rows, no residual read (readRes = 0, first stage of a step) or no residual
-// write (writeRes = 0, last stage).
+// write (writeRes = 0, last stage). back = 1: the blocks from the high end, as the stage launches alternate (bdg_sw2d::nextSweep).
 __global__ __launch_bounds__(256) void stage_traffic_probe_kernel(const double* __restrict__ qin, double* __restrict__ qout,
                                                                  double* __restrict__ res, const double* __restrict__ ageo,
                                                                  const int* __restrict__ vmapP, int rows, int idxRows,
-                                                                 long long ld, int K, int readRes, int writeRes) {
-    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+                                                                 long long ld, int K, int readRes, int writeRes, int back) {
+    const unsigned k = (back ? gridDim.x - 1u - blockIdx.x : blockIdx.x) * blockDim.x + threadIdx.x;
     if (k >= static_cast<unsigned>(K)) return;
     double acc = 0.0;
     for (int r = 0; r < 13; ++r) acc += ageo[r * ld + k];
@@ -184,6 +184,11 @@ bool nodalVector() { return std::getenv("BDG_SW2D_NODAL_VECTOR") != nullptr; }  
 bool fullStageTraffic() {                                                            // no face links, residual read and written at every stage
     const char* e = std::getenv("BDG_SW2D_FULL_STAGE_TRAFFIC");
     return e && e[0] != '0';
+}
+// =forward: every whole-mesh stage launch walks the tiles from the low end (default: alternating, bdg_sw2d::nextSweep)
+bool sweepForward() {
+    const char* e = std::getenv("BDG_SW2D_SWEEP");
+    return e && std::string(e) == "forward";
 }
 // ... and again when variant B is enabled: variants B/C/D on the rolled kernels
 bool rolledSources() { return std::getenv("BDG_SW2D_ROLLED_SOURCES") != nullptr; }
@@ -252,6 +257,16 @@ struct bdg_sw2d {
     bool lamExternal = false; // variant B, partitioned: lamBuf holds the all-rank speed of the state about to be evaluated
     DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
     int lamSlot = 0;
+    // Direction of the tile sweep of whole-mesh stage launches (StageParams::sweepBack, sw2d_stage_tile.hpp): it alternates from
+    // one launch to the next, so that a launch starts on the tiles the launch before it touched last, whose rows are still in
+    // the Infinity Cache. BDG_SW2D_SWEEP=forward, read at creation: always forward.
+    bool sweepAlternates = true;
+    unsigned long long sweepLaunches = 0, backwardLaunches = 0;
+    // the next whole-mesh launch's direction into p; partitioned launches (wholeMesh = false) keep 0
+    void nextSweep(bdg_dev::StageParams& p, bool wholeMesh) {
+        p.sweepBack = (wholeMesh && sweepAlternates) ? static_cast<int>(sweepLaunches++ & 1ull) : 0;
+        backwardLaunches += static_cast<unsigned long long>(p.sweepBack);
+    }
     const double* lamStateFor = nullptr; // state buffer the accumulated speed belongs to (nullptr: none)
     double lamTideFor = 0.0;
     double nextEvalTime = 0.0;         // model time of the evaluation that will follow the current launch
@@ -446,9 +461,13 @@ struct bdg_sw2d {
 
     // One fused pass. The affine path takes the filter through pre-multiplied operators.
     // `on`: stream to launch on (default: the compute stream).
-    void launchStage(int mode, bool filter, bdg_dev::StageParams& p, const char* what, hipStream_t on = nullptr) {
+    // `wholeMesh`: every kernel launched here takes the next direction of the alternating tile sweep (nextSweep). False for the
+    // two launches of a partitioned stage: the interior launch orders its ring tiles last because they wait in the kernel for
+    // the previous boundary launch -- walked backwards, the waiting tiles would come first and hold their CUs.
+    void launchStage(int mode, bool filter, bdg_dev::StageParams& p, const char* what, hipStream_t on = nullptr, bool wholeMesh = true) {
         if (filter && !hasFilter) throw arg_error("filter requested but the solver was created without a Filter matrix");
         hipStream_t st = on ? on : stream;
+        auto sweep = [&] { nextSweep(p, wholeMesh); };
         // Small launches (a rank's share of a many-way split, its partition-boundary strip) are bound by
         // the latency of one wavefront, not by HBM: the matrix-core kernel gives each wave 16 elements
         // instead of 64 (measured at N=4: 750 elements 7 us vs 19 us; 125 k elements 48 us vs 56 us;
@@ -500,17 +519,22 @@ struct bdg_sw2d {
                 lamTideFor = vb.tideNext;
                 lamSlot = nxt;
             }
+            // the speed pass is a launch of its own over the same elements: it takes a direction, the stage kernel the other
+            if (ownPass) {
+                sweep();
+                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, true, VbStage::None, nullptr, st), what);
+            }
+            sweep();
             if (fastSources) {
                 p.opsAffine = opsAffine.p;
-                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, ownPass, VbStage::Unrolled, filter ? filterT.p : nullptr, st), what);
+                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, false, VbStage::Unrolled, filter ? filterT.p : nullptr, st), what);
             } else if (mfmaSources) {
                 // N >= 5: the matrix-core kernel with variant B's surface term and sources
-                if (ownPass) hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, true, VbStage::None, nullptr, st), what);
                 p.opsAffine = filter ? opsMfma2SrcFiltered.p : opsMfma2Src.p;
                 hipCheck(kt->stageMfma2Src(mode, p, physB(), variantBStateOnce() ? SrcForm::OnceVariantB : SrcForm::VariantB, srcIdentity(filter), st), what);
             } else {
                 p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
-                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, ownPass, VbStage::Rolled, nullptr, st), what);
+                hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, false, VbStage::Rolled, nullptr, st), what);
             }
         } else if (variantD && fastSources) {
             // three conserved fields on the unrolled kernel with the sources folded in, the tracer (if
@@ -519,12 +543,14 @@ struct bdg_sw2d {
             // filtered RHS: plain operators, Filter applied to flux terms + sources at the end
             ph.fmat = filter ? filterT.p : nullptr;
             p.opsAffine = opsAffine.p;
+            sweep();
             if (nf == 4 && !env::tracerPass()) {
                 hipCheck(kt->stageAffineSrc(mode, p, ph, true, st), what);    // the tracer rides in the same pass
             } else {
                 hipCheck(kt->stageAffineSrc(mode, p, ph, false, st), what);
                 if (nf == 4) { // own pass; the tracer has no sources: pre-filtered operators as in variant A
                     p.opsAffine = filter ? opsAffineFiltered.p : opsAffine.p;
+                    sweep();
                     hipCheck(kt->stageTracer(mode, p, st), what);
                 }
             }
@@ -537,6 +563,7 @@ struct bdg_sw2d {
             // state-once schedule where it exists (sw2d_mfma3src_kernel.hpp: N = 5, 6, 7 with and without the tracer, N = 8 three fields;
             // BDG_SW2D_SOURCES_TWO_WAVE=1 keeps the two-waves-per-SIMD kernels below for A/B runs and cross-checks)
             const bool stateOnceSrc = !env::sourcesTwoWave();
+            sweep();
             if (stateOnceSrc && kt->mfma3SrcFields >= nf && !env::tracerPass() && fitsOneDescriptor(nf)) {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, nf == 4 ? SrcForm::OnceSourcesTracer : SrcForm::OnceSources, identity, st), what);
             } else if (stateOnceSrc && kt->mfma3TracerPhase && nf == 4 && !env::tracerPass() && fitsOneDescriptor(4)) {
@@ -546,6 +573,7 @@ struct bdg_sw2d {
                 // N = 8: three conserved fields with sources on the state-once schedule, the tracer in its own pass
                 hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::OnceSources, identity, st), what);
                 p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
+                sweep();
                 hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::TracerPass, false, st), what);
             } else if (nf == 4 && kt->mfmaMT <= 2 && !env::tracerPass()) {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::SourcesTracer, false, st), what); // N <= 6: the tracer rides in the same pass
@@ -553,29 +581,37 @@ struct bdg_sw2d {
                 hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::Sources, false, st), what);
                 if (nf == 4) {
                     p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
+                    sweep();
                     hipCheck(kt->stageMfma2Src(mode, p, ph, SrcForm::TracerPass, false, st), what);
                 }
             }
         } else if (variantD) {
             p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
+            sweep();
             hipCheck(kt->stageVd(mode, p, vd, st), what);
         } else if (affine && variant == AffineVariant::Mfma) {
             p.opsAffine = filter ? opsMfmaFiltered.p : opsMfma.p;
+            sweep();
             hipCheck(kt->stageMfma(mode, p, st), what);
         } else if (affine && variant == AffineVariant::Mfma3) {
             p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
+            sweep();
             hipCheck(kt->stageMfma3(mode, p, st), what);
         } else if (affine && variant == AffineVariant::Mfma2) {
             p.opsAffine = filter ? opsMfma2Filtered.p : opsMfma2.p;
+            sweep();
             hipCheck(kt->stageMfma2(mode, p, st), what);
         } else if (affine) {
             p.opsAffine = filter ? opsAffineFiltered.p : opsAffine.p;
+            sweep();
             hipCheck(kt->stageAffine(mode, variant, p, st), what);
         } else if (nodalMfma) {
             // per-node geometry on the matrix cores (state-once schedule), every order
             p.opsAffine = filter ? opsMfma2NodalFilter.p : opsMfma2.p;
+            sweep();
             hipCheck(kt->stageMfma3Nodal(mode, filter, p, st), what);
         } else {
+            sweep();
             hipCheck(kt->stage(mode, filter, p, st), what);
         }
     }
@@ -632,7 +668,7 @@ struct bdg_sw2d {
         p.faceLink = faceLink.p;
         p.stageKind = p.ca == 0.0 ? bdg_dev::STAGE_FIRST : (lastOfStep ? bdg_dev::STAGE_LAST : bdg_dev::STAGE_MID);
         nextEvalTime = lastOfStep ? timeNow + dtStage : timeNow;
-        launchStage(bdg_dev::MODE_LSERK, false, p, "sw2d stage kernel <LSERK>", on);
+        launchStage(bdg_dev::MODE_LSERK, false, p, "sw2d stage kernel <LSERK>", on, part == 2);
         expectRing += signals;
         if (done && !recorded) hipCheck(hipEventRecord(done, on ? on : stream), "hipEventRecord");
         if (part != 0 && advance) lserkStageAdvance(s);
@@ -1218,6 +1254,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     // From N = 5 the default is the state-once matrix-core schedule (variant 7; measured against variant 6 at
     // 640 k / 500 k / 250 k / 250 k elements: N=5 0.36 vs 0.42 ms, N=6 0.33 vs 0.40, N=7 0.24 vs 0.28, N=8 0.30 vs 0.39).
     s->affineVariant = s->N <= 4 ? bdg_dev::AffineVariant::Unrolled : bdg_dev::AffineVariant::Mfma3;
+    s->sweepAlternates = !env::sweepForward();
     if (const char* e = env::affineVariantPin()) {
         const int v = std::atoi(e);
         if (v >= 0 && v <= 9) {
@@ -2412,12 +2449,14 @@ int bdg_sw2d_probe_stage_traffic(bdg_sw2d* s, int repeats, float* ms_per_launch)
         const unsigned grid = static_cast<unsigned>((s->K + 255) / 256);
         // with face links the launches cycle through the five stages of a step, as the stage kernel's do
         const bool links = s->faceLink.p != nullptr;
+        unsigned launches = 0; // the direction alternates as the stage launches' does
         auto launch = [&](int stage) {
             const int last = blitzdg::LSERK4::numStages - 1;
+            const int back = s->sweepAlternates ? static_cast<int>(launches++ & 1u) : 0;
             // aux / qalt are scratch here: the resident state is not modified
             hipLaunchKernelGGL(bdg_dev::stage_traffic_probe_kernel, dim3(grid), dim3(256), 0, s->stream, s->qcur, s->qalt,
                                s->aux.p, s->ageo.p, links ? s->faceLink.p : s->vmapP.p, 3 * s->Np, links ? 3 : s->NFN, s->ld,
-                               s->K, !links || stage != 0 ? 1 : 0, !links || stage != last ? 1 : 0);
+                               s->K, !links || stage != 0 ? 1 : 0, !links || stage != last ? 1 : 0, back);
         };
         launch(1);
         int i = 0;
@@ -2429,6 +2468,8 @@ int bdg_sw2d_uses_affine_geometry(const bdg_sw2d* s) { return s ? (s->affine ? 1
 int bdg_sw2d_is_renumbered(const bdg_sw2d* s) { return s ? (s->permHost.empty() ? 0 : 1) : -1; }
 
 size_t bdg_sw2d_device_bytes(const bdg_sw2d* s) { return s ? s->bytes : 0; }
+long long bdg_sw2d_backward_launches(const bdg_sw2d* s) { return s ? static_cast<long long>(s->backwardLaunches) : -1; }
+unsigned bdg_stage_tile(unsigned block, unsigned grid, unsigned back) { return bdg_dev::stage_tile(block, grid, back); }
 void* bdg_sw2d_stream(bdg_sw2d* s) { return s ? static_cast<void*>(s->stream) : nullptr; }
 
 } // extern "C"

@@ -24,6 +24,7 @@
 // dense-GEMM reshaping and no MFMA here on purpose.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "sw2d_stage_tile.hpp"
 
 namespace bdg_dev {
 
@@ -115,6 +116,9 @@ struct StageParams {
     int tileInterleave;
     // sw2d_stage_mfma3_kernel: workgroups start (blk mod 8) * stagger kilocycles apart (0: together)
     int stagger;
+    // 1: every XCD walks its chunk of tiles from the high end (stage_tile, sw2d_stage_tile.hpp). The host alternates it from one
+    // whole-mesh launch to the next; partitioned launches and the SYNC / HALO kernel instances always walk forward.
+    int sweepBack;
     // profiling builds (-DBDG_PHASE_CLOCK): 16 cycle counts per wave (LDS copy, k-steps, surface, update), else unused
     unsigned long long* phaseClock;
     // In-kernel dependencies between the two chains of a partitioned stage (round 4; SYNC instances of the matrix-core kernels,
@@ -191,10 +195,7 @@ __global__ __launch_bounds__(256) void sw2d_stage_kernel(const StageParams p) {
     for (int t = threadIdx.x; t < E::LDS_DOUBLES; t += blockDim.x) sOps[t] = p.ops[t];
     __syncthreads();
 
-    // XCD-aware block remap: consecutive tiles of elements (which share faces,
-    // hence gather lines) go to the same XCD's L2. Bijective for any grid size.
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const long long k = p.kbegin + static_cast<long long>(tile) * blockDim.x + threadIdx.x;
     if (k >= p.kend) return;
 

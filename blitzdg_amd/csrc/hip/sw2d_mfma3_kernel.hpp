@@ -129,23 +129,28 @@ __global__ __launch_bounds__(256, 1) void sw2d_stage_mfma3_kernel(const StagePar
     const int sBase = IMAGE + static_cast<int>(threadIdx.x >> 6) * Mfma3Lds<N>::TILE_DOUBLES + static_cast<int>(threadIdx.x & 15u);
 
     const unsigned lane = threadIdx.x & 63u, q = lane >> 4, j = lane & 15u;
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned nwg = gridDim.x, wgBefore = stage_chunk_first(blockIdx.x, nwg), wgHere = stage_chunk_length(blockIdx.x, nwg);
+    const unsigned blk = wgBefore + blockIdx.x / 8u;
     const unsigned wave = blk * 4u + (threadIdx.x >> 6), nwaves = nwg * 4u;
     const unsigned ntiles = (static_cast<unsigned>(p.kend - p.kbegin) + 15u) / 16u;
     const unsigned perWave = (ntiles + nwaves - 1u) / nwaves;
     unsigned tileEnd = min(ntiles, (wave + 1u) * perWave), tileStep = 1u;
     unsigned tile = wave * perWave;
+    // the XCD's range of tiles: what a backward sweep mirrors the walk in (elementOf)
+    unsigned xcdLo = min(ntiles, wgBefore * 4u * perWave), xcdHi = min(ntiles, (wgBefore + wgHere) * 4u * perWave);
     if (p.tileInterleave) {
         // the waves of one XCD walk its share of the tiles side by side: at any time the XCD works on one compact
         // patch of the mesh, whose interior face neighbours are in its L2 because a sibling wave is reading them
         // (its share of the tiles is proportional to its share of the workgroups: none if it has none)
-        const unsigned wgHere = (nwg + 7u - xcd) / 8u, wgBefore = blk - blockIdx.x / 8u;
-        tile = ntiles * wgBefore / nwg + (blockIdx.x / 8u) * 4u + (threadIdx.x >> 6);
-        tileEnd = ntiles * (wgBefore + wgHere) / nwg;
+        tile = xcdLo = ntiles * wgBefore / nwg;
+        tile += (blockIdx.x / 8u) * 4u + (threadIdx.x >> 6);
+        tileEnd = xcdHi = ntiles * (wgBefore + wgHere) / nwg;
         tileStep = wgHere * 4u;
     }
     if (tile >= tileEnd) return;
+    // StageParams::sweepBack: `tile` stays the logical walk, the elements are those of the mirrored tile. Partitioned launches
+    // (SYNC, HALO) never sweep back: their ring tiles, ordered last, wait for the other chain
+    const unsigned back = (SYNC || HALO) ? 0u : static_cast<unsigned>(p.sweepBack);
 
     const long long ld = p.ld, plane = static_cast<long long>(Np) * ld;
     const double g = p.g, halfg = 0.5 * p.g;
@@ -173,7 +178,7 @@ __global__ __launch_bounds__(256, 1) void sw2d_stage_mfma3_kernel(const StagePar
 
     // element of this lane in tile `tl` (padding lanes recompute the last element and store nothing)
     auto elementOf = [&](unsigned tl, bool& live) {
-        const unsigned kTrue = static_cast<unsigned>(p.kbegin) + tl * 16u + j;
+        const unsigned kTrue = static_cast<unsigned>(p.kbegin) + stage_tile_mirrored(tl, xcdLo, xcdHi, back) * 16u + j;
         live = kTrue <= kLast;
         return live ? kTrue : kLast;
     };

@@ -72,12 +72,12 @@ __global__ __launch_bounds__(256, 1) void sw2d_stage_mfma3src_kernel(const Stage
     const int sBase = IMAGE + static_cast<int>(threadIdx.x >> 6) * L::TILE_DOUBLES + static_cast<int>(threadIdx.x & 15u);
 
     const unsigned lane = threadIdx.x & 63u, q = lane >> 4, j = lane & 15u;
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned nwg = gridDim.x, wgBefore = stage_chunk_first(blockIdx.x, nwg), wgHere = stage_chunk_length(blockIdx.x, nwg);
     const unsigned ntiles = (static_cast<unsigned>(p.kend - p.kbegin) + 15u) / 16u;
-    // the waves of one XCD walk its share of the tiles side by side (sw2d_mfma3_kernel.hpp)
-    const unsigned wgHere = (nwg + 7u - xcd) / 8u, wgBefore = blk - blockIdx.x / 8u;
-    unsigned tile = ntiles * wgBefore / nwg + (blockIdx.x / 8u) * 4u + (threadIdx.x >> 6);
+    // the waves of one XCD walk its share of the tiles side by side (sw2d_mfma3_kernel.hpp); StageParams::sweepBack: `tile` stays
+    // the logical walk, the elements are those of the tile mirrored in the XCD's range (elementOf)
+    const unsigned xcdLo = ntiles * wgBefore / nwg;
+    unsigned tile = xcdLo + (blockIdx.x / 8u) * 4u + (threadIdx.x >> 6);
     const unsigned tileEnd = ntiles * (wgBefore + wgHere) / nwg, tileStep = wgHere * 4u;
     if (tile >= tileEnd) return;
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256, 1) void sw2d_stage_mfma3src_kernel(const Stage
     const double cd = ph.cd, slope = ph.slope, dragSign = ph.dragSign, fconst = ph.fconst;
 
     auto elementOf = [&](unsigned tl, bool& live) {
-        const unsigned kTrue = static_cast<unsigned>(p.kbegin) + tl * 16u + j;
+        const unsigned kTrue = static_cast<unsigned>(p.kbegin) + stage_tile_mirrored(tl, xcdLo, tileEnd, static_cast<unsigned>(p.sweepBack)) * 16u + j;
         live = kTrue <= kLast;
         return live ? kTrue : kLast;
     };

@@ -87,9 +87,10 @@ __global__ __launch_bounds__(THREADS, (N <= 4 ? 2 : BDG_MFMA_WAVES)) void sw2d_s
     __syncthreads();
 
     const unsigned lane = threadIdx.x & 63u, q = lane >> 4, j = lane & 15u;
-    // XCD-aware, contiguous chunks of tiles per wave (neighbouring tiles share an L2)
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    // XCD-aware, contiguous chunks of tiles per wave (neighbouring tiles share an L2); StageParams::sweepBack mirrors the
+    // workgroups inside their XCD's chunk (a partitioned launch never: its ring tiles, ordered last, wait for the other chain)
+    const unsigned nwg = gridDim.x;
+    const unsigned blk = stage_tile(blockIdx.x, nwg, (HALO || SYNC) ? 0u : static_cast<unsigned>(p.sweepBack));
     const unsigned wave = blk * WAVES + (threadIdx.x >> 6), nwaves = nwg * WAVES;
     const unsigned ntiles = (static_cast<unsigned>(p.kend - p.kbegin) + 15u) / 16u;
     const unsigned perWave = (ntiles + nwaves - 1u) / nwaves;
@@ -398,8 +399,8 @@ __global__ __launch_bounds__(256, BDG_MFMA2_WAVES) void sw2d_stage_mfma2_kernel(
     __syncthreads();
 
     const unsigned lane = threadIdx.x & 63u, q = lane >> 4, j = lane & 15u;
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned nwg = gridDim.x;
+    const unsigned blk = stage_tile(blockIdx.x, nwg, HALO ? 0u : static_cast<unsigned>(p.sweepBack));
     const unsigned wave = blk * 4u + (threadIdx.x >> 6), nwaves = nwg * 4u;
     const unsigned ntiles = (static_cast<unsigned>(p.kend - p.kbegin) + 15u) / 16u;
     const unsigned perWave = (ntiles + nwaves - 1u) / nwaves;
@@ -716,8 +717,8 @@ __global__ __launch_bounds__(256, 3) void sw2d_stage_mfma2_tracer_kernel(const S
     __syncthreads();
 
     const unsigned lane = threadIdx.x & 63u, q = lane >> 4, j = lane & 15u;
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned nwg = gridDim.x;
+    const unsigned blk = stage_tile(blockIdx.x, nwg, static_cast<unsigned>(p.sweepBack));
     const unsigned wave = blk * 4u + (threadIdx.x >> 6), nwaves = nwg * 4u;
     const unsigned ntiles = (static_cast<unsigned>(p.kend - p.kbegin) + 15u) / 16u;
     const unsigned perWave = (ntiles + nwaves - 1u) / nwaves;

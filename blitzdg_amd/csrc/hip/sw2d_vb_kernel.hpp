@@ -85,7 +85,9 @@ __global__ __launch_bounds__(256) void sw2d_vb_speed_kernel(const StageParams p,
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp;
     const long long ld = p.ld, plane = static_cast<long long>(Np) * ld;
-    const unsigned k = static_cast<unsigned>(p.kbegin) + blockIdx.x * 256u + threadIdx.x;
+    // (no XCD chunks here: blocks in launch order; StageParams::sweepBack walks them from the high end)
+    const unsigned blk = p.sweepBack ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
+    const unsigned k = static_cast<unsigned>(p.kbegin) + blk * 256u + threadIdx.x;
     double best = 0.0;
     bool bad = false;
     if (k < static_cast<unsigned>(p.kend)) {
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void sw2d_vb_speed_kernel(const StageParams p,
         if (static_cast<int>(threadIdx.x) < s) sA[threadIdx.x] = fmax(sA[threadIdx.x], sA[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = sBad ? __builtin_nan("") : sA[0];
+    if (threadIdx.x == 0) out[blk] = sBad ? __builtin_nan("") : sA[0];
 }
 
 template <int N> // (a template only so that every per-order translation unit may define it)
@@ -156,8 +158,7 @@ __global__ __launch_bounds__(192, 2) void sw2d_stage_vb_kernel(const StageParams
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const int c = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // field of this wave (0..2)
     const unsigned k = static_cast<unsigned>(p.kbegin) + tile * 64u + (threadIdx.x & 63u);
     if (k >= static_cast<unsigned>(p.kend)) return;
@@ -289,8 +290,7 @@ __global__ __launch_bounds__(256) void sw2d_stage_vb_unrolled_kernel(const Stage
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp, NFN = E::NFN;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     // Lanes past the end redo the last element (identical loads, identical stores) instead of leaving: the
     // wave-wide maximum at the end of the kernel then never reads a retired lane.
     const unsigned k = min(static_cast<unsigned>(p.kbegin) + tile * blockDim.x + threadIdx.x, static_cast<unsigned>(p.kend) - 1u);

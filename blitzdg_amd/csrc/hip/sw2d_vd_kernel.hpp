@@ -42,8 +42,7 @@ __global__ __launch_bounds__(256, 2) void sw2d_stage_vd_kernel(const StageParams
     using E = Elem<N>;
     constexpr int Np = E::Np, Nfp = E::Nfp;
 
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x % 8u, q8 = nwg / 8u, r8 = nwg % 8u;
-    const unsigned tile = (xcd < r8 ? xcd * (q8 + 1u) : r8 * (q8 + 1u) + (xcd - r8) * q8) + blockIdx.x / 8u;
+    const unsigned tile = stage_tile(blockIdx.x, gridDim.x, static_cast<unsigned>(p.sweepBack));
     const int c = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + vp.cbase; // field of this wave (0..nf-1)
     const unsigned k = static_cast<unsigned>(p.kbegin) + tile * 64u + (threadIdx.x & 63u);
     if (k >= static_cast<unsigned>(p.kend)) return;

@@ -281,6 +281,11 @@ class Sw2dSolver(RunRecords):
     def deviceBytes(self):
         return lib.bdg_sw2d_device_bytes(self._h)
 
+    @property
+    def backwardLaunches(self):
+        """Whole-mesh stage launches so far that walked their tiles from the high end (0 under BDG_SW2D_SWEEP=forward)."""
+        return int(lib.bdg_sw2d_backward_launches(self._h))
+
 
 def streamTriadGBps(device=0, bytesPerArray=1 << 30, repeats=10):
     """Measured STREAM-triad bandwidth of the device in GB/s (the practical HBM roof)."""

@@ -716,6 +716,13 @@ int bdg_element_order(const int* EToE, int num_elements, int patch, int* perm);
  * 0 if it keeps the caller's order, -1 on a bad argument. */
 int bdg_element_order_wanted(const int* EToE, int num_elements, int order);
 size_t bdg_sw2d_device_bytes(const bdg_sw2d* s);
+/* The tile of elements workgroup `block` of a stage launch of `grid` one-tile workgroups takes (no GPU): workgroups go to the
+ * eight XCDs round robin, each XCD owns one contiguous chunk of tiles and walks it from its low end (back = 0) or from its
+ * high end (back = 1). The same function the stage kernels call. Whole-mesh stage launches of a solver alternate the
+ * direction (BDG_SW2D_SWEEP=forward at creation: always 0); bdg_sw2d_backward_launches: how many of the solver's launches
+ * so far walked from the high end (-1: no solver). */
+unsigned bdg_stage_tile(unsigned block, unsigned grid, unsigned back);
+long long bdg_sw2d_backward_launches(const bdg_sw2d* s);
 /* The raw stream (hipStream_t) launches are issued on, for callers that interleave their own work. */
 void* bdg_sw2d_stream(bdg_sw2d* s);
 
