@@ -100,6 +100,10 @@ class Sw2dDrifterDesc(Structure):
                 ("neighbours", c_void_p), ("vinv", c_void_p), ("jacobi", c_void_p), ("stride", c_int), ("capacity", c_int)]
 
 
+class Sw2dCurvedDrifterDesc(Structure):
+    _fields_ = Sw2dDrifterDesc._fields_ + [("curved_slot", c_void_p), ("modal", c_void_p), ("num_curved", c_int)]
+
+
 class FieldStatsDesc(Structure):
     _fields_ = [("H", c_void_p), ("stride", c_int), ("num_periods", c_int), ("periods", c_double * 4), ("mean", c_int),
                 ("envelope", c_int)]
@@ -342,7 +346,7 @@ _SIGNATURES = {
     "bdg_sw2d_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "bdg_sw2d_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
     "bdg_sw2d_drifters_reset": (c_int, [_P]),
-    **{f"{_abi}_{_name}": _sig for _abi in ("bdg_sw2d", "bdg_sw2dq") for _name, _sig in {
+    **{f"{_abi}_{_name}": _sig for _abi in ("bdg_sw2d", "bdg_sw2dq", "bdg_sw2d_curved") for _name, _sig in {
         "enable_field_stats": (c_int, [_P, POINTER(FieldStatsDesc)]),
         "field_stats_sample": (c_int, [_P]),
         "field_stats_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
@@ -380,6 +384,23 @@ _SIGNATURES = {
                                              POINTER(c_double), POINTER(c_int)]),
     "bdg_sw2d_curved_output_fields": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "bdg_sw2d_curved_time_driver": (c_int, [_P, c_int, _P, c_int, POINTER(c_float)]),
+    "bdg_sw2d_curved_set_time": (c_int, [_P, c_double]),
+    "bdg_sw2d_curved_get_time": (c_int, [_P, POINTER(c_double)]),
+    "bdg_sw2d_curved_enable_monitor": (c_int, [_P, POINTER(Sw2dMonitorDesc)]),
+    "bdg_sw2d_curved_monitor_sample": (c_int, [_P]),
+    "bdg_sw2d_curved_monitor_count": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2d_curved_monitor_read": (c_int, [_P, c_int, c_int, _P]),
+    "bdg_sw2d_curved_monitor_width": (c_int, [_P, POINTER(c_int)]),
+    "bdg_sw2d_curved_monitor_reset": (c_int, [_P]),
+    "bdg_sw2d_curved_monitor_time": (c_int, [_P, c_int, POINTER(c_float)]),
+    "bdg_trinodes_curved_drifter_tables": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2d_curved_enable_drifters": (c_int, [_P, POINTER(Sw2dCurvedDrifterDesc)]),
+    "bdg_sw2d_curved_drifters_advance": (c_int, [_P, c_double, c_int]),
+    "bdg_sw2d_curved_drifters_time": (c_int, [_P, c_double, c_int, POINTER(c_float)]),
+    "bdg_sw2d_curved_drifters_state": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "bdg_sw2d_curved_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "bdg_sw2d_curved_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "bdg_sw2d_curved_drifters_reset": (c_int, [_P]),
 }
 
 #: every symbol include/blitzdg_hip.h declares (checked by tests/test_capi_symbols.py)

@@ -1,11 +1,14 @@
 // C ABI of the curved / over-integrated sw2d solver (include/blitzdg_hip.h, bdg_sw2d_curved_*): device layout, uploads of
 // the host tables (host/curved_tables.cpp), launches. Kernels: sw2d_curved_kernel.hpp, sw2d_curved_nt_kernel.hpp; the driver's
-// adaptive step, blow-up check and output fields (bdg_sw2d_curved_enable_driver): sw2d_curved_driver_kernel.hpp.
+// adaptive step, blow-up check and output fields (bdg_sw2d_curved_enable_driver): sw2d_curved_driver_kernel.hpp; the run monitor,
+// the field statistics and the drifters: run_records.hpp with sw2d_curved_drifter_kernel.hpp.
 // Reference: swhelpers/rhs.py:6-176 (the RHS), sw2d_curved.py:231-302 (the time loop).
 #include "../host/capi_internal.hpp"
 #include "../host/curved_tables.hpp"
 #include "blitzdg/LSERK4.hpp"
 #include "partition_schedule.hpp"
+#include "run_records.hpp"
+#include "sw2d_curved_drifter_kernel.hpp"
 #include "sw2d_curved_driver_kernel.hpp"
 #include "sw2d_curved_kernel.hpp"
 #include "sw2d_curved_kernel_info.hpp"
@@ -115,6 +118,19 @@ struct bdg_sw2d_curved {
         DevBuf<double> fscale, c, H, deriv, metric, IM, out, partials, result;
         DevBuf<int> faceNodes;
     } drv;
+    // the model time (bdg_sw2d_curved_set_time): + dt per completed step of step_rk2, lserk4_stages and run_adaptive
+    double timeNow = 0.0;
+    // run monitor, field statistics and drifters (run_records.hpp), single domain only. The columns are the caller's elements:
+    // nothing is renumbered
+    struct Monitor : bdg_records::MonitorState {
+        DevBuf<double> row;     // (numGauges, Np): the nodal basis at each gauge
+        DevBuf<double> scratch; // the record bdg_sw2d_curved_monitor_time writes
+    } mon;
+    bdg_records::FieldStatsState fst;
+    struct Drifters : bdg_records::DrifterState {
+        DevBuf<double> vert, vinvT, jac, modal;
+        DevBuf<int> slot;       // per element: -1 or its row in modal
+    } drf;
 
     ~bdg_sw2d_curved() { // both streams drained before the members destroy the events, the communicator and the exchange stream
         (void)hipSetDevice(device);
@@ -255,7 +271,10 @@ struct bdg_sw2d_curved {
     }
     void stepRk2(double dt, int steps, bool filter, Eval how) {
         run(how, [&] {
-            for (int i = 0; i < 2 * steps; ++i) rk2Half(i & 1, dt, filter, how);
+            for (int i = 0; i < 2 * steps; ++i) {
+                rk2Half(i & 1, dt, filter, how);
+                if (i & 1) stepDone(dt);
+            }
         });
     }
     // LSERK4 stages (reference src/advec1d/main.cpp:92-102 per stage): res = a res + dt RHS(q); q += b res. The general form
@@ -267,8 +286,44 @@ struct bdg_sw2d_curved {
                 const int st = static_cast<int>(stageCount % blitzdg::LSERK4::numStages);
                 eval(how, bdg_dev::CMODE_LSERK, false, qA.p, nullptr, useNT ? qB.p : qA.p, blitzdg::LSERK4::rk4a[st], blitzdg::LSERK4::rk4b[st], dt);
                 if (useNT) std::swap(qA.p, qB.p);
+                if ((stageCount + 1) % blitzdg::LSERK4::numStages == 0) stepDone(dt);
             }
         });
+    }
+
+    // ---- run monitor, field statistics and drifters (run_records.hpp). They exist on unpartitioned solvers only, whose stepping
+    // calls launch everything on the solver's stream
+    bool partitioned() const { return part.numOwned > 0 || halo.comm != nullptr; }
+    // H of eta = h - H: the records' own if given, else the driver's, else none
+    const double* recordsH(const DevBuf<double>& own) const { return own.p ? own.p : (drv.on && drv.hasH ? drv.H.p : nullptr); }
+    // records that `steps` further completed steps would take; refused before anything is launched
+    void reserveRecords(long long steps, const char* fn) const {
+        mon.reserve(steps, fn, "bdg_sw2d_curved");
+        drf.reserve(steps, fn, "bdg_sw2d_curved");
+    }
+    long long lserkSteps(long long stages) const { return bdg_records::lserkSteps(stageCount, stages, blitzdg::LSERK4::numStages); }
+    void monitorLaunch(double* rec, int capacity, int slot) {
+        mon.launch({qA.p, recordsH(mon.H), ld, Np, 4, K, g, timeNow}, rec, capacity, slot, bdg_dev::sw2d_monitor_finish_kernel,
+                   "sw2d_monitor_finish_kernel launch", bdg_dev::MonRowGauges{mon.row.p}, stream);
+    }
+    void monitorSample() { monitorLaunch(mon.rec.p, mon.capacity, mon.count++); }
+    bdg_records::StatsView statsView() const { return {qA.p, recordsH(fst.H), ld, Np, K, timeNow}; }
+    void drifterLaunch(int mode, double dt, int slot) {
+        drf.launch(bdg_dev::sw2d_curved_drifter_kernel, "sw2d_curved_drifter_kernel launch",
+                   bdg_dev::CurvedTriDriftTables{{drf.vert.p, drf.neigh.p, drf.vinvT.p, drf.jac.p}, drf.slot.p, drf.modal.p, N}, qA.p, ld,
+                   N, mode, dt, slot, stream);
+    }
+    void drifterAdvance(double dt, bool record = true) { drifterLaunch(bdg_dev::kDriftAdvance, dt, drf.takeSlot(record)); }
+    // after every completed step of size dt: the model time, then the monitor's sample, the sample of the field statistics and
+    // the drifters' advance (room was reserved by the caller). With nothing enabled: no launch
+    void stepDone(double dt) {
+        timeNow += dt;
+        if (mon.on && ++mon.steps % mon.stride == 0) monitorSample();
+        if (fst.on && ++fst.steps % fst.stride == 0) fst.sample(statsView(), stream);
+        if (drf.on) {
+            drf.t = timeNow;
+            drifterAdvance(dt);
+        }
     }
 
     // ---- the driver (sw2d_curved_driver_kernel.hpp). The elements its passes cover: the owned ones of a partitioned run
@@ -551,6 +606,9 @@ int bdg_sw2d_curved_set_state(bdg_sw2d_curved* s, const double* h, const double*
         for (int c = 0; c < 4; ++c) s->uploadRows(in[c], s->qA.p + c * s->plane(), s->Np);
         s->res.zero(s->stream);
         s->stageCount = 0;
+        s->mon.steps = 0;
+        s->fst.steps = 0;
+        if (s->drf.on) s->drifterLaunch(bdg_dev::kDriftSample, 0.0, -1); // (u0, v0) of the new state
     });
 }
 
@@ -563,13 +621,17 @@ int bdg_sw2d_curved_get_state(bdg_sw2d_curved* s, double* h, double* hu, double*
 }
 
 int bdg_sw2d_curved_step_rk2(bdg_sw2d_curved* s, double dt, int num_steps, int filter) {
-    return prologue(s, "bdg_sw2d_curved_step_rk2", false, "num_steps", num_steps,
-                    [&] { s->stepRk2(dt, num_steps, filter != 0, bdg_sw2d_curved::Eval::Whole); });
+    return prologue(s, "bdg_sw2d_curved_step_rk2", false, "num_steps", num_steps, [&] {
+        s->reserveRecords(num_steps, "bdg_sw2d_curved_step_rk2");
+        s->stepRk2(dt, num_steps, filter != 0, bdg_sw2d_curved::Eval::Whole);
+    });
 }
 
 int bdg_sw2d_curved_lserk4_stages(bdg_sw2d_curved* s, double dt, int num_stages) {
-    return prologue(s, "bdg_sw2d_curved_lserk4_stages", false, "num_stages", num_stages,
-                    [&] { s->lserkStages(dt, num_stages, bdg_sw2d_curved::Eval::Whole); });
+    return prologue(s, "bdg_sw2d_curved_lserk4_stages", false, "num_stages", num_stages, [&] {
+        s->reserveRecords(s->lserkSteps(num_stages), "bdg_sw2d_curved_lserk4_stages");
+        s->lserkStages(dt, num_stages, bdg_sw2d_curved::Eval::Whole);
+    });
 }
 
 int bdg_sw2d_curved_time_rk2(bdg_sw2d_curved* s, double dt, int num_steps, int filter, float* ms_per_rhs) {
@@ -577,6 +639,7 @@ int bdg_sw2d_curved_time_rk2(bdg_sw2d_curved* s, double dt, int num_steps, int f
         requireCurved(s, "bdg_sw2d_curved_time_rk2");
         if (num_steps < 1 || !ms_per_rhs) throw arg_error("bdg_sw2d_curved_time_rk2: bad argument");
         s->use();
+        s->reserveRecords(num_steps, "bdg_sw2d_curved_time_rk2"); // (the steps are steps like any other: they feed the records)
         // (one run: all the steps, two evaluations each)
         const float ms = bdg_dev::timePerRun(s->stream, 1, [&] { s->stepRk2(dt, num_steps, filter != 0, bdg_sw2d_curved::Eval::Whole); });
         *ms_per_rhs = ms / (2.0f * static_cast<float>(num_steps));
@@ -602,6 +665,8 @@ int bdg_sw2d_curved_rk2_phase(bdg_sw2d_curved* s, double dt, int phase, int filt
 
 int bdg_sw2d_curved_set_partition(bdg_sw2d_curved* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return curvedCall(s, "bdg_sw2d_curved_set_partition", [&] {
+        if (s->mon.on || s->fst.on || s->drf.on)
+            throw arg_error("bdg_sw2d_curved_set_partition: the solver has a monitor, field statistics or drifters, which cover a single domain only");
         s->part.set("bdg_sw2d_curved", s->K, s->maxNeighbourHost, num_interior, num_owned, send_elements, num_send,
                     s->halo.comm != nullptr, s->bytes, s->stream);
         std::vector<int> inner, outer; // columns of the side buffer whose element is an interior / a partition-boundary one
@@ -623,6 +688,8 @@ int bdg_sw2d_curved_comm_init(bdg_sw2d_curved* s, int rank, int world, const voi
                               const int* send_start, const int* send_count, const int* recv_start, const int* recv_count,
                               int num_peers) {
     return curvedCall(s, "bdg_sw2d_curved_comm_init", [&] {
+        if (s->mon.on || s->fst.on || s->drf.on)
+            throw arg_error("bdg_sw2d_curved_comm_init: the solver has a monitor, field statistics or drifters, which cover a single domain only");
         bdg_halo::commInit("bdg_sw2d_curved", s->halo, s->part, s->chains, s->K, static_cast<size_t>(4) * s->Np, rank, world, unique_id,
                            peer_ranks, send_start, send_count, recv_start, recv_count, num_peers, s->bytes, s->stream);
     });
@@ -725,9 +792,12 @@ int bdg_sw2d_curved_run_adaptive(bdg_sw2d_curved* s, double cfl, double final_ti
         if (s->halo.comm) throw arg_error("bdg_sw2d_curved_run_adaptive: not available on a solver with a communicator (no rank-global dt)");
         s->requireFilter(filter != 0);
         double t = *t_inout, dt = *dt_inout;
+        s->timeNow = t;
         while (t < final_time && (max_steps <= 0 || done < max_steps)) { // the script's loop, in its order
+            // the number of steps is not known in advance: room for this step's records is checked before the step is launched
+            s->reserveRecords(1, "bdg_sw2d_curved_run_adaptive");
             s->stepRk2(dt, 1, filter != 0, bdg_sw2d_curved::Eval::Whole);
-            t += dt;
+            t += dt; // (stepDone made the same sum)
             double r[2];
             s->reduceDt(r);
             dt = cfl / r[0];
@@ -766,6 +836,281 @@ int bdg_sw2d_curved_time_driver(bdg_sw2d_curved* s, int which, const double* IM,
         auto launch = [&] { which == 0 ? s->dtPass() : s->outputLaunch(all, IM != nullptr); };
         for (int i = 0; i < 10; ++i) launch(); // untimed
         *ms = bdg_dev::timePerRun(s->stream, count, launch);
+    });
+}
+
+// ---- model time (the convention of bdg_sw2d_set_time)
+int bdg_sw2d_curved_set_time(bdg_sw2d_curved* s, double t) {
+    return guard([&] {
+        requireCurved(s, "bdg_sw2d_curved_set_time");
+        s->timeNow = t;
+    });
+}
+
+int bdg_sw2d_curved_get_time(const bdg_sw2d_curved* s, double* t) {
+    return guard([&] {
+        requireCurved(s, "bdg_sw2d_curved_get_time");
+        if (!t) throw arg_error("bdg_sw2d_curved_get_time: NULL argument");
+        *t = s->timeNow;
+    });
+}
+
+// ---- run monitor (run_records.hpp; the records of the triangle solver on four fields)
+int bdg_sw2d_curved_enable_monitor(bdg_sw2d_curved* s, const bdg_sw2d_monitor_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_curved_enable_monitor";
+        requireCurved(s, fn.c_str());
+        bdg_sw2d_curved::Monitor& m = s->mon;
+        m.checkEnable(fn, d, s->K);
+        if (s->partitioned())
+            throw arg_error(fn + ": the solver has a partition set; the monitor of a partitioned curved run is not recorded (single domain only)");
+        const int ng = d->num_gauges, Np = s->Np;
+        if (ng > 0 && !d->gauge_row) throw arg_error(fn + ": bad gauge list");
+        s->use();
+        m.enable(d->stride, d->capacity, ng, 4, d->gauge_element, {&m.row, &m.scratch}, &m.scratch, s->bytes, s->stream, [&] {
+            s->uploadPlanes(m.w, d->weights, Np); // zero in the padding up to ld
+            if (d->H) s->uploadPlanes(m.H, d->H, Np);
+            m.row.alloc(static_cast<size_t>(std::max(1, ng)) * Np, s->bytes, s->stream);
+            if (ng > 0)
+                hipCheck(hipMemcpyAsync(m.row.p, d->gauge_row, static_cast<size_t>(ng) * Np * sizeof(double), hipMemcpyHostToDevice,
+                                        s->stream), "hipMemcpy (gauge rows)");
+        });
+    });
+}
+
+namespace {
+void requireCurvedMonitorOn(const bdg_sw2d_curved* s, const char* fn) {
+    requireCurved(s, fn);
+    s->mon.requireOn(fn, "bdg_sw2d_curved");
+}
+void requireCurvedStatsOn(const bdg_sw2d_curved* s, const char* fn) {
+    requireCurved(s, fn);
+    s->fst.requireOn(fn, "bdg_sw2d_curved");
+}
+void requireCurvedDriftersOn(const bdg_sw2d_curved* s, const char* fn) {
+    requireCurved(s, fn);
+    s->drf.requireOn(fn, "bdg_sw2d_curved");
+}
+} // namespace
+
+int bdg_sw2d_curved_monitor_sample(bdg_sw2d_curved* s) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_sample");
+        s->mon.requireFree("bdg_sw2d_curved_monitor_sample", "bdg_sw2d_curved");
+        s->use();
+        s->monitorSample();
+    });
+}
+
+int bdg_sw2d_curved_monitor_count(const bdg_sw2d_curved* s, int* n) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_count");
+        if (!n) throw arg_error("bdg_sw2d_curved_monitor_count: NULL argument");
+        *n = s->mon.count;
+    });
+}
+
+int bdg_sw2d_curved_monitor_width(const bdg_sw2d_curved* s, int* width) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_width");
+        if (!width) throw arg_error("bdg_sw2d_curved_monitor_width: NULL argument");
+        *width = s->mon.width;
+    });
+}
+
+int bdg_sw2d_curved_monitor_read(bdg_sw2d_curved* s, int first, int count, double* records) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_read");
+        s->use();
+        s->mon.read("bdg_sw2d_curved_monitor_read", first, count, records, s->stream);
+    });
+}
+
+int bdg_sw2d_curved_monitor_reset(bdg_sw2d_curved* s) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_reset");
+        s->mon.reset();
+    });
+}
+
+int bdg_sw2d_curved_monitor_time(bdg_sw2d_curved* s, int count, float* ms) {
+    return guard([&] {
+        requireCurvedMonitorOn(s, "bdg_sw2d_curved_monitor_time");
+        if (count < 1 || !ms) throw arg_error("bdg_sw2d_curved_monitor_time: bad argument");
+        s->use();
+        s->monitorLaunch(s->mon.scratch.p, 1, 0); // once before the clock starts
+        *ms = bdg_dev::timePerRun(s->stream, count, [&] { s->monitorLaunch(s->mon.scratch.p, 1, 0); });
+    });
+}
+
+// ---- field statistics (run_records.hpp)
+int bdg_sw2d_curved_enable_field_stats(bdg_sw2d_curved* s, const bdg_field_stats_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_curved_enable_field_stats";
+        requireCurved(s, fn.c_str());
+        s->fst.checkEnable(fn, d, s->partitioned());
+        s->use();
+        s->fst.enable(*d, s->plane(), s->bytes, s->stream, [&] {
+            if (d->H) s->uploadPlanes(s->fst.H, d->H, s->Np);
+        });
+    });
+}
+
+int bdg_sw2d_curved_field_stats_sample(bdg_sw2d_curved* s) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_sample");
+        s->use();
+        s->fst.sample(s->statsView(), s->stream);
+    });
+}
+
+int bdg_sw2d_curved_field_stats_count(const bdg_sw2d_curved* s, int* samples, int* num_periods) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_count");
+        if (!samples || !num_periods) throw arg_error("bdg_sw2d_curved_field_stats_count: NULL argument");
+        *samples = s->fst.count();
+        *num_periods = s->fst.m;
+    });
+}
+
+int bdg_sw2d_curved_field_stats_read(bdg_sw2d_curved* s, int which, int index, double* plane) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_read");
+        if (!plane) throw arg_error("bdg_sw2d_curved_field_stats_read: NULL argument");
+        const double* dev = s->fst.planeOf("bdg_sw2d_curved_field_stats_read", which, index);
+        s->use();
+        s->downloadRows(dev, plane, s->Np);
+    });
+}
+
+int bdg_sw2d_curved_field_stats_samples(const bdg_sw2d_curved* s, int first, int count, double* rows) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_samples");
+        s->fst.samples("bdg_sw2d_curved_field_stats_samples", first, count, rows);
+    });
+}
+
+int bdg_sw2d_curved_field_stats_reset(bdg_sw2d_curved* s) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_reset");
+        s->use();
+        s->fst.reset(s->stream);
+    });
+}
+
+int bdg_sw2d_curved_field_stats_time(bdg_sw2d_curved* s, int count, float* ms) {
+    return guard([&] {
+        requireCurvedStatsOn(s, "bdg_sw2d_curved_field_stats_time");
+        if (count < 1 || !ms) throw arg_error("bdg_sw2d_curved_field_stats_time: bad argument");
+        s->use();
+        *ms = s->fst.time(s->statsView(), count, s->bytes, s->stream);
+    });
+}
+
+// ---- drifters (run_records.hpp, sw2d_curved_drifter_kernel.hpp)
+int bdg_sw2d_curved_enable_drifters(bdg_sw2d_curved* s, const bdg_sw2d_curved_drifter_desc* d) {
+    return guard([&] {
+        using namespace bdg_dev;
+        const std::string fn = "bdg_sw2d_curved_enable_drifters";
+        requireCurved(s, fn.c_str());
+        if (!d || d->count < 1 || !d->element || !d->r || !d->s || !d->vertices || !d->neighbours || !d->vinv || !d->jacobi ||
+            !d->curved_slot || d->num_curved < 0 || (d->num_curved > 0 && !d->modal))
+            throw arg_error(fn + ": the descriptor, at least one drifter and the tables of bdg_trinodes_curved_drifter_tables are required");
+        bdg_sw2d_curved::Drifters& m = s->drf;
+        m.checkEnable(fn, d->count, d->stride, d->capacity, s->partitioned());
+        const int n = d->count, K = s->K, Np = s->Np, Nq = s->N + 1;
+        for (int i = 0; i < n; ++i) {
+            const int e = d->element[i];
+            if (e < 0 || e >= K) throw arg_error(fn + ": drifter " + std::to_string(i) + " names an element outside [0, K)");
+            const double r = d->r[i], t = d->s[i];
+            if (!(-1.0 - t <= 1e-10) || !(r + t <= 1e-10) || !(-1.0 - r <= 1e-10))
+                throw arg_error(fn + ": drifter " + std::to_string(i) + " lies outside its element (r, s >= -1, r + s <= 0)");
+        }
+        // the kernel follows the neighbour entries and the rows of the side tables without a further check
+        std::vector<int> nb(static_cast<size_t>(4) * K, kDriftWall);
+        for (int k = 0; k < K; ++k) {
+            for (int f = 0; f < 3; ++f) {
+                const int v = d->neighbours[static_cast<size_t>(f) * K + k];
+                if (v < kDriftOpen || v >= K) throw arg_error(fn + ": neighbour entry out of range");
+                nb[static_cast<size_t>(4) * k + f] = v;
+            }
+            if (d->curved_slot[k] < -1 || d->curved_slot[k] >= d->num_curved) throw arg_error(fn + ": curved_slot entry out of range");
+        }
+        std::vector<double> vinvT(static_cast<size_t>(Np) * Np);
+        for (int r = 0; r < Np; ++r)
+            for (int c = 0; c < Np; ++c) vinvT[static_cast<size_t>(c) * Np + r] = d->vinv[static_cast<size_t>(r) * Np + c];
+        s->use();
+        try {
+            m.enable(n, d->stride, d->capacity, s->timeNow, nb, d->element, d->r, d->s, {&m.vert, &m.vinvT, &m.jac, &m.modal}, s->bytes,
+                     s->stream,
+                     [&] {
+                         m.put(m.vert, d->vertices, static_cast<size_t>(8) * K, s->bytes, s->stream);
+                         m.put(m.vinvT, vinvT.data(), vinvT.size(), s->bytes, s->stream);
+                         m.put(m.jac, d->jacobi, static_cast<size_t>(Nq + 1) * Nq * 3, s->bytes, s->stream);
+                         m.put(m.slot, d->curved_slot, static_cast<size_t>(K), s->bytes, s->stream);
+                         m.modal.alloc(static_cast<size_t>(std::max(1, d->num_curved)) * 6 * Np, s->bytes, s->stream);
+                         if (d->num_curved > 0)
+                             hipCheck(hipMemcpyAsync(m.modal.p, d->modal, static_cast<size_t>(d->num_curved) * 6 * Np * sizeof(double),
+                                                     hipMemcpyHostToDevice, s->stream), "hipMemcpy (drifters)");
+                     },
+                     [&] { s->drifterLaunch(kDriftInit, 0.0, -1); });
+        } catch (...) {
+            m.slot.release(); // (its bytes were put back with the others')
+            throw;
+        }
+    });
+}
+
+int bdg_sw2d_curved_drifters_advance(bdg_sw2d_curved* s, double dt, int num_steps) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_advance");
+        if (num_steps < 0) throw arg_error("bdg_sw2d_curved_drifters_advance: num_steps < 0");
+        s->drf.reserve(num_steps, "bdg_sw2d_curved_drifters_advance", "bdg_sw2d_curved");
+        s->use();
+        for (int i = 0; i < num_steps; ++i) {
+            s->drf.t += dt;
+            s->drifterAdvance(dt);
+        }
+    });
+}
+
+int bdg_sw2d_curved_drifters_time(bdg_sw2d_curved* s, double dt, int count, float* ms) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_time");
+        if (!ms || count < 1) throw arg_error("bdg_sw2d_curved_drifters_time: bad argument");
+        s->use();
+        *ms = bdg_dev::timePerRun(s->stream, count, [&] { s->drifterAdvance(dt, false); });
+    });
+}
+
+int bdg_sw2d_curved_drifters_state(bdg_sw2d_curved* s, double* x, double* y, int* element, double* r, double* sref, int* status) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_state");
+        s->use();
+        s->drf.downloadState(x, y, element, r, sref, status, {}, s->stream);
+    });
+}
+
+int bdg_sw2d_curved_drifters_count(const bdg_sw2d_curved* s, int* num_records, int* num_drifters) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_count");
+        if (num_records) *num_records = s->drf.count;
+        if (num_drifters) *num_drifters = s->drf.n;
+    });
+}
+
+int bdg_sw2d_curved_drifters_read(bdg_sw2d_curved* s, int first, int count, double* t, double* x, double* y, int* status) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_read");
+        s->use();
+        s->drf.readTracks("bdg_sw2d_curved_drifters_read", first, count, t, x, y, status, s->stream);
+    });
+}
+
+int bdg_sw2d_curved_drifters_reset(bdg_sw2d_curved* s) {
+    return guard([&] {
+        requireCurvedDriftersOn(s, "bdg_sw2d_curved_drifters_reset");
+        s->drf.count = 0;
     });
 }
 

@@ -1,11 +1,11 @@
 // sw2d_drifter_driver.hpp -- what the drifter kernels of the triangle and the quadrilateral sw2d solvers share (gfx950 / CDNA4,
 // wave64): the arguments, the status and neighbour codes, the modes and the body of one launch. The element headers
-// (sw2d_drifter_kernel.hpp, sw2d_quad_drifter_kernel.hpp) supply a policy E each and instantiate the body in their kernel:
+// (sw2d_drifter_kernel.hpp, sw2d_quad_drifter_kernel.hpp, sw2d_curved_drifter_kernel.hpp) supply a policy E each and instantiate the body in their kernel:
 //
 //   E::Tables                                    the element tables, passed by value as the kernel's second argument
 //   E::kRows                                     LDS rows of kDriftThreads doubles a lane's basis values take
-//   E::init(tab, k, r, s, x, y)                  x, y from the element's map
-//   E::locate(tab, x, y, k, r, s, wall)          0 found, kDriftExited or kDriftLost; k, r, s and (at a wall) x, y updated;
+//   E::init(tab, k, r, s, sb, x, y)              x, y from the element's map
+//   E::locate(tab, x, y, k, r, s, sb, wall)      0 found, kDriftExited or kDriftLost; k, r, s and (at a wall) x, y updated;
 //                                                wall: kDriftTouched or unchanged
 //   E::velocity(p, tab, k, r, s, sb, u, v)       (u, v) at (k, r, s); false if either is not finite; sb: the lane's LDS column
 //
@@ -57,7 +57,7 @@ __device__ inline void driftBody(const DriftParams& p, const typename E::Tables&
     const bool frozen = (st & (kDriftExited | kDriftLost)) != 0;
     if (p.mode != kDriftAdvance) {
         if (p.mode == kDriftInit) {
-            E::init(tab, k, r, s, x, y);
+            E::init(tab, k, r, s, P, x, y);
             p.x[i] = x; p.y[i] = y;
         }
         if (!frozen) {
@@ -70,11 +70,11 @@ __device__ inline void driftBody(const DriftParams& p, const typename E::Tables&
         // every result into temporaries: a lost drifter stays where it was
         int wall = 0, kp = k, kc = k, res;
         double xp = x + p.dt * u0, yp = y + p.dt * v0, rp, sp, up, vp;
-        bool ok = E::locate(tab, xp, yp, kp, rp, sp, wall) != kDriftLost;
+        bool ok = E::locate(tab, xp, yp, kp, rp, sp, P, wall) != kDriftLost;
         ok = ok && E::velocity(p, tab, kp, rp, sp, P, up, vp);
         if (ok) {
             double xn = x + (0.5 * p.dt) * (u0 + up), yn = y + (0.5 * p.dt) * (v0 + vp), rn, sn, un = u0, vn = v0;
-            res = E::locate(tab, xn, yn, kc, rn, sn, wall);
+            res = E::locate(tab, xn, yn, kc, rn, sn, P, wall);
             ok = res != kDriftLost && (res == kDriftExited || E::velocity(p, tab, kc, rn, sn, P, un, vn));
             if (ok) {
                 x = xn; y = yn; k = kc; r = rn; s = sn; u0 = un; v0 = vn;

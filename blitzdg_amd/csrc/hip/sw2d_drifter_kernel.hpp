@@ -4,6 +4,7 @@
 // sw2d_quad_drifter_kernel.hpp; this file is the triangle: the tables, the init map, locate and the velocity.
 //
 //   sw2d_drifter_kernel   the driver's body with the policy TriDrift
+//   triDriftHop           one hop of locate; sw2d_curved_drifter_kernel.hpp takes it for its straight-sided elements
 //
 // The order is a run-time argument (as in sw2d_monitor_kernel.hpp): one instance serves N = 1..8. The kernel reads the state planes
 // 0..2 in the solver's device layout q[node * ld + slot] (plane stride Np * ld) and the tables below, and writes only the drifter
@@ -57,41 +58,50 @@ struct TriDriftTables {
     const double* jac;      // (N+2) x (N+1) x 3
 };
 
+// one hop of locate in the straight-sided element k: -1 to go on (k or x, y changed), else 0 found, kDriftExited or kDriftLost;
+// (wk, wf): the first wall face this search crossed (-1: none yet)
+__device__ inline int triDriftHop(const double* __restrict__ vert, const int* __restrict__ neigh, double& x, double& y, int& k,
+                                  double& r, double& s, int& wall, int& wk, int& wf) {
+#pragma clang fp contract(off)
+    const double* c = vert + 8LL * k;
+    const double x0 = c[0], y0 = c[1], x1 = c[2], y1 = c[3], x2 = c[4], y2 = c[5];
+    const double e1x = x1 - x0, e1y = y1 - y0, e2x = x2 - x0, e2y = y2 - y0;
+    const double det = e1x * e2y - e2x * e1y;
+    const double dx = x - x0, dy = y - y0;
+    r = 2.0 * ((dx * e2y - e2x * dy) / det) - 1.0;
+    s = 2.0 * ((e1x * dy - dx * e1y) / det) - 1.0;
+    if (!(fabs(r) < __builtin_inf()) || !(fabs(s) < __builtin_inf())) return kDriftLost;
+    int f = 0;
+    double worst = -1.0 - s;
+    if (r + s > worst) { worst = r + s; f = 1; }
+    if (-1.0 - r > worst) { worst = -1.0 - r; f = 2; }
+    if (worst <= 1e-12) return 0;
+    const int nb = neigh[4LL * k + f];
+    if (nb >= 0) { k = nb; return -1; }
+    if (nb != kDriftWall) return kDriftExited;
+    const double ax = f == 0 ? x0 : (f == 1 ? x1 : x2), ay = f == 0 ? y0 : (f == 1 ? y1 : y2);
+    const double bx = f == 0 ? x1 : (f == 1 ? x2 : x0), by = f == 0 ? y1 : (f == 1 ? y2 : y0);
+    if (wk >= 0 && (wk != k || wf != f)) { // a corner: to the nearer end of this face
+        const double da = (x - ax) * (x - ax) + (y - ay) * (y - ay), db = (x - bx) * (x - bx) + (y - by) * (y - by);
+        if (da <= db) { x = ax; y = ay; } else { x = bx; y = by; }
+    } else {
+        const double ex = bx - ax, ey = by - ay;
+        const double t = ((x - ax) * ex + (y - ay) * ey) / (ex * ex + ey * ey);
+        x = ax + t * ex;
+        y = ay + t * ey;
+    }
+    if (wk < 0) { wk = k; wf = f; }
+    wall = kDriftTouched;
+    return -1;
+}
+
 // 0 found, kDriftExited or kDriftLost; k, r, s and (at a wall) x, y updated; wall: kDriftTouched or unchanged
 __device__ inline int triDriftLocate(const double* __restrict__ vert, const int* __restrict__ neigh, double& x, double& y, int& k,
                                      double& r, double& s, int& wall) {
-#pragma clang fp contract(off)
-    int wk = -1, wf = -1; // the first wall face this search crossed
+    int wk = -1, wf = -1;
     for (int hop = 0; hop < kTriDriftHops; ++hop) {
-        const double* c = vert + 8LL * k;
-        const double x0 = c[0], y0 = c[1], x1 = c[2], y1 = c[3], x2 = c[4], y2 = c[5];
-        const double e1x = x1 - x0, e1y = y1 - y0, e2x = x2 - x0, e2y = y2 - y0;
-        const double det = e1x * e2y - e2x * e1y;
-        const double dx = x - x0, dy = y - y0;
-        r = 2.0 * ((dx * e2y - e2x * dy) / det) - 1.0;
-        s = 2.0 * ((e1x * dy - dx * e1y) / det) - 1.0;
-        if (!(fabs(r) < __builtin_inf()) || !(fabs(s) < __builtin_inf())) return kDriftLost;
-        int f = 0;
-        double worst = -1.0 - s;
-        if (r + s > worst) { worst = r + s; f = 1; }
-        if (-1.0 - r > worst) { worst = -1.0 - r; f = 2; }
-        if (worst <= 1e-12) return 0;
-        const int nb = neigh[4LL * k + f];
-        if (nb >= 0) { k = nb; continue; }
-        if (nb != kDriftWall) return kDriftExited;
-        const double ax = f == 0 ? x0 : (f == 1 ? x1 : x2), ay = f == 0 ? y0 : (f == 1 ? y1 : y2);
-        const double bx = f == 0 ? x1 : (f == 1 ? x2 : x0), by = f == 0 ? y1 : (f == 1 ? y2 : y0);
-        if (wk >= 0 && (wk != k || wf != f)) { // a corner: to the nearer end of this face
-            const double da = (x - ax) * (x - ax) + (y - ay) * (y - ay), db = (x - bx) * (x - bx) + (y - by) * (y - by);
-            if (da <= db) { x = ax; y = ay; } else { x = bx; y = by; }
-        } else {
-            const double ex = bx - ax, ey = by - ay;
-            const double t = ((x - ax) * ex + (y - ay) * ey) / (ex * ex + ey * ey);
-            x = ax + t * ex;
-            y = ay + t * ey;
-        }
-        if (wk < 0) { wk = k; wf = f; }
-        wall = kDriftTouched;
+        const int res = triDriftHop(vert, neigh, x, y, k, r, s, wall, wk, wf);
+        if (res >= 0) return res;
     }
     return kDriftLost;
 }
@@ -163,14 +173,14 @@ __device__ inline bool triDriftVelocity(const DriftParams& p, const TriDriftTabl
 struct TriDrift {
     using Tables = TriDriftTables;
     static constexpr int kRows = kTriDriftMaxNp;
-    __device__ static void init(const Tables& tab, int k, double r, double s, double& x, double& y) {
+    __device__ static void init(const Tables& tab, int k, double r, double s, double*, double& x, double& y) {
 #pragma clang fp contract(off)
         const double* c = tab.vert + 8LL * k;
         const double wr = 0.5 * (1.0 + r), ws = 0.5 * (1.0 + s);
         x = c[0] + (wr * (c[2] - c[0]) + ws * (c[4] - c[0]));
         y = c[1] + (wr * (c[3] - c[1]) + ws * (c[5] - c[1]));
     }
-    __device__ static int locate(const Tables& tab, double& x, double& y, int& k, double& r, double& s, int& wall) {
+    __device__ static int locate(const Tables& tab, double& x, double& y, int& k, double& r, double& s, double*, int& wall) {
         return triDriftLocate(tab.vert, tab.neigh, x, y, k, r, s, wall);
     }
     __device__ static bool velocity(const DriftParams& p, const Tables& tab, int k, double r, double s, double* P, double& u,
@@ -179,7 +189,8 @@ struct TriDrift {
     }
 };
 
-__global__ __launch_bounds__(kDriftThreads) void sw2d_drifter_kernel(DriftParams p, TriDriftTables tab) {
+// (static: sw2d_curved_drifter_kernel.hpp brings this header into a second device object, which does not launch this kernel)
+[[maybe_unused]] static __global__ __launch_bounds__(kDriftThreads) void sw2d_drifter_kernel(DriftParams p, TriDriftTables tab) {
     driftBody<TriDrift>(p, tab);
 }
 

@@ -128,13 +128,13 @@ __device__ inline bool quadDriftVelocity(const DriftParams& p, const QuadDriftTa
 struct QuadDrift {
     using Tables = QuadDriftTables;
     static constexpr int kRows = 2 * kQuadDriftMaxNq;
-    __device__ static void init(const Tables& tab, int k, double r, double s, double& x, double& y) {
+    __device__ static void init(const Tables& tab, int k, double r, double s, double*, double& x, double& y) {
 #pragma clang fp contract(off)
         const double* c = tab.bil + 8LL * k;
         x = c[0] + (c[1] * r + c[2] * s + c[3] * (r * s));
         y = c[4] + (c[5] * r + c[6] * s + c[7] * (r * s));
     }
-    __device__ static int locate(const Tables& tab, double& x, double& y, int& k, double& r, double& s, int& wall) {
+    __device__ static int locate(const Tables& tab, double& x, double& y, int& k, double& r, double& s, double*, int& wall) {
         return quadDriftLocate(tab.bil, tab.neigh, x, y, k, r, s, wall);
     }
     __device__ static bool velocity(const DriftParams& p, const Tables& tab, int k, double r, double s, double* sb, double& u,

@@ -429,6 +429,22 @@ int bdg_trinodes_drifter_tables(const bdg_trinodes* nodes, const int* mapO, int 
     });
 }
 
+// ... and of the curved solver's (bdg_sw2d_curved_enable_drifters): the same with the side tables of the listed elements
+int bdg_trinodes_curved_drifter_tables(const bdg_trinodes* nodes, const int* curved_els, int num_curved, const int* mapO, int num_out,
+                                       double* vertices, int* neighbours, double* vinv, double* jacobi, int* curved_slot,
+                                       double* modal) {
+    return guard([&] {
+        if (!nodes || !vertices || !neighbours || !vinv || !jacobi || !curved_slot || num_out < 0 || (num_out > 0 && !mapO) ||
+            num_curved < 0 || (num_curved > 0 && (!curved_els || !modal)))
+            throw bdg_detail::arg_error("bdg_trinodes_curved_drifter_tables: bad argument");
+        try {
+            nodes->prov.curvedDrifterTables(curved_els, num_curved, mapO, num_out, vertices, neighbours, vinv, jacobi, curved_slot, modal);
+        } catch (const std::invalid_argument& e) {
+            throw bdg_detail::arg_error(std::string("bdg_trinodes_curved_drifter_tables: ") + e.what());
+        }
+    });
+}
+
 // ---- set-up of the drifters (bdg_sw2dq_enable_drifters): bilinear map, neighbour table, barycentric weights
 int bdg_quadnodes_drifter_tables(const bdg_quadnodes* nodes, const int* mapO, int num_out, double* bilinear, int* neighbours,
                                  double* bary) {

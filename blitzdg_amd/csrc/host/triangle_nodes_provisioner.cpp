@@ -727,7 +727,22 @@ void TriangleNodesProvisioner::locatePoints(const real_type* px, const real_type
 
 void TriangleNodesProvisioner::drifterTables(const index_type* mapO, index_type numOut, real_type* vertices,
                                              index_type* neighbours, real_type* vinv, real_type* jacobi) const {
+    curvedDrifterTables(nullptr, 0, mapO, numOut, vertices, neighbours, vinv, jacobi, nullptr, nullptr);
+}
+
+void TriangleNodesProvisioner::curvedDrifterTables(const index_type* curvedEls, index_type numCurved, const index_type* mapO,
+                                                   index_type numOut, real_type* vertices, index_type* neighbours, real_type* vinv,
+                                                   real_type* jacobi, index_type* curvedSlot, real_type* modal) const {
     const index_type N = NOrder, Np = NumLocalPoints, Nfp = NumFacePoints, K = NumElements, NFN = 3 * Nfp;
+    // the row of each listed element in the side tables (-1: not listed)
+    std::vector<index_type> slot(K, -1);
+    for (index_type c = 0; c < numCurved; ++c) {
+        const index_type k = curvedEls[c];
+        if (k < 0 || k >= K) throw std::invalid_argument("drifterTables: curvedEls entry out of range");
+        if (slot[k] >= 0) throw std::invalid_argument("drifterTables: element " + std::to_string(k) + " is listed twice in curvedEls");
+        slot[k] = c;
+    }
+    if (curvedSlot) std::copy(slot.begin(), slot.end(), curvedSlot);
     // the corner nodes: those nearest (r, s) = (-1, -1), (1, -1), (-1, 1)
     index_type corner[3];
     const real_type cr[3] = {-1, 1, -1}, cs[3] = {-1, -1, 1};
@@ -750,12 +765,35 @@ void TriangleNodesProvisioner::drifterTables(const index_type* mapO, index_type 
             throw std::invalid_argument("drifterTables: the signed area of element " + std::to_string(k) + " is not positive and finite");
         // a mesh whose nodes have left the affine map of the corners (deformed or blended elements): the drifters cannot follow it
         const real_type size = std::max(std::hypot(e1x, e1y), std::hypot(e2x, e2y));
+        if (slot[k] >= 0) { // a listed element: the modal coefficients of its nodal map and of the map's derivatives instead
+            std::vector<long double> plane(static_cast<std::size_t>(6) * Np, 0.0L);
+            for (index_type m = 0; m < Np; ++m) {
+                long double xr = 0, xs = 0, yr = 0, ys = 0;
+                for (index_type j = 0; j < Np; ++j) {
+                    xr += static_cast<long double>(Dr(m, j)) * xGrid(j, k); xs += static_cast<long double>(Ds(m, j)) * xGrid(j, k);
+                    yr += static_cast<long double>(Dr(m, j)) * yGrid(j, k); ys += static_cast<long double>(Ds(m, j)) * yGrid(j, k);
+                }
+                if (!(xr * ys - xs * yr > 0))
+                    throw std::invalid_argument("drifterTables: the Jacobian of the listed element " + std::to_string(k) +
+                                                " is not positive at node " + std::to_string(m));
+                const long double val[6] = {xGrid(m, k), yGrid(m, k), xr, xs, yr, ys};
+                for (index_type q = 0; q < 6; ++q) plane[static_cast<std::size_t>(q) * Np + m] = val[q];
+            }
+            real_type* out = modal + static_cast<std::size_t>(6) * Np * slot[k];
+            for (index_type q = 0; q < 6; ++q)
+                for (index_type j = 0; j < Np; ++j) {
+                    long double acc = 0.0L;
+                    for (index_type m = 0; m < Np; ++m) acc += static_cast<long double>(Vinv(j, m)) * plane[static_cast<std::size_t>(q) * Np + m];
+                    out[static_cast<std::size_t>(q) * Np + j] = static_cast<real_type>(acc);
+                }
+            continue;
+        }
         for (index_type m = 0; m < Np; ++m) {
             const real_type wr = 0.5 * (1 + rGrid(m)), ws = 0.5 * (1 + sGrid(m));
             const real_type ex = v[0] + (wr * e1x + ws * e2x) - xGrid(m, k), ey = v[1] + (wr * e1y + ws * e2y) - yGrid(m, k);
             if (!(std::hypot(ex, ey) <= 1e-10 * size))
                 throw std::invalid_argument("drifterTables: the nodes of element " + std::to_string(k) + " differ from the affine map "
-                                            "of its corners; drifters need straight-sided elements");
+                                            "of its corners; drifters need straight-sided elements (or the element listed in curvedEls)");
         }
     }
     // faces in Fmask order (s = -1, r + s = 0, r = -1), which is the mesh's face order

@@ -386,6 +386,24 @@ class TriangleNodesProvisioner:
                                               C.ptr(vinv), C.ptr(jac)))
         return vert, neigh, (vinv, jac)
 
+    def curvedDrifterTables(self, curvedEls, mapO=None):
+        """``drifterTables`` for a mesh with curved elements (``Sw2dCurvedSolver.enableDrifters``): (vertices, neighbours,
+        (Vinv, jacobi), curvedSlot, modal). The affine check covers only the elements not listed in ``curvedEls``.
+        ``curvedSlot`` (K,): -1, or the element's row in ``modal``; ``modal`` (len(curvedEls), 6, Np): the modal coefficients
+        (Vinv times the nodal values) of x, y, Dr x, Ds x, Dr y, Ds y of each listed element, so that ``P(r, s) @ modal[c, p]``
+        with the orthonormal basis row P is the nodal map and its Jacobian at (r, s). A deformed element that is not listed, an
+        entry listed twice or a listed element with a nodal Jacobian <= 0 raises BdgError."""
+        N, Np, _, K = self._dims()
+        ce = C.as_i32([] if curvedEls is None else curvedEls).reshape(-1)
+        mo = C.as_i32([] if mapO is None else mapO).reshape(-1)
+        vert, neigh = np.empty((K, 8)), np.empty((3, K), dtype=np.int32)
+        vinv, jac = np.empty((Np, Np)), np.empty((N + 2, N + 1, 3))
+        slot, modal = np.empty(K, dtype=np.int32), np.empty((ce.size, 6, Np))
+        check(lib.bdg_trinodes_curved_drifter_tables(self._h, C.ptr(ce) if ce.size else None, ce.size, C.ptr(mo) if mo.size else None,
+                                                     mo.size, C.ptr(vert), C.ptr(neigh), C.ptr(vinv), C.ptr(jac), C.ptr(slot),
+                                                     C.ptr(modal) if ce.size else None))
+        return vert, neigh, (vinv, jac), slot, modal
+
     def setCoordinates(self, x, y):
         _, Np, _, K = self._dims()
         xa, ya = C.as_f64(x, (Np, K), "x"), C.as_f64(y, (Np, K), "y")
@@ -732,8 +750,8 @@ class VtkOutputter:
             fields = list(solver.outputFields(IM).items())
         else:
             fields = list(zip(("eta", "u", "v"), solver.outputFields(IM)))
-        if getattr(solver, "fields", 3) == 4:
-            fields.append(("N", solver.outputTracer(IM)))       # the reference script's fourth output field
+            if getattr(solver, "fields", 3) == 4:
+                fields.append(("N", solver.outputTracer(IM)))   # the reference script's fourth output field
         for name, lat in fields:
             ft = cut(lat)
             path = os.path.join(directory, self.generateFileName(name, tstep))

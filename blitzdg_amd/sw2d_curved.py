@@ -9,15 +9,35 @@
     solver.stepRK2(dt, nsteps, filter=True)
     h, hu, hv, hN = solver.getState()
 
+Run records on the device (``_records.RunRecords``): ``enableMonitor`` (conservation integrals, extrema, gauges),
+``enableFieldStats`` (residual currents, envelopes, tidal harmonics) and ``enableDrifters`` (Lagrangian tracks through curved
+elements and along curved walls) feed from ``stepRK2``, ``lserk4Stages`` and ``runAdaptive`` without a state download.
+
 There is no CPU fallback: without the HIP library / a GPU, construction raises.
 """
 import numpy as np
 
 from . import _capi as C
 from ._capi import POINTER, byref, c_double, c_float, c_void_p, check, lib
+from ._records import RunRecords, locate
 
 
-class Sw2dCurvedSolver:
+def quadrature_weights(V, J, cubV, cubW, curvedEls):
+    """``Sw2dCurvedSolver.quadratureWeights`` from the arrays themselves (no solver, no GPU): V (Np, Np), J (Np, K), cubV
+    (Ncub, Np) and cubW (Ncub, len(curvedEls)), the columns of cub_ctx.W of the listed elements."""
+    Vinv = np.linalg.inv(np.asarray(V, dtype=np.float64))
+    w = (Vinv.T @ Vinv).sum(axis=0)[:, None] * np.asarray(J, dtype=np.float64)
+    ce = np.asarray(curvedEls, dtype=np.int64).reshape(-1)
+    if ce.size:
+        w[:, ce] = np.asarray(cubV, dtype=np.float64).T @ np.asarray(cubW, dtype=np.float64)
+    return w
+
+
+class Sw2dCurvedSolver(RunRecords):
+    _abi = "bdg_sw2d_curved"
+    fields = 4
+    numDrifters = 0
+
     def __init__(self, ctx, cub_ctx, gauss_ctx, curvedEls, J, gmapM, gmapP, g=9.81, zx=None, zy=None, f=0.0, CD=0.0,
                  device=0):
         """ctx: DGContext2D-like (V, numLocalPoints, numElements, optional filter); cub_ctx: V, Dr, Ds, W, rx, ry, sx,
@@ -82,6 +102,10 @@ class Sw2dCurvedSolver:
         self.Np, self.K, self.order, self.Ncub, self.NGauss = Np, K, order, Ncub, NG
         self.hasFilter = d.Filter is not None
         self.g = float(g)
+        self.curvedEls = np.array(list(curvedEls), dtype=np.int32).reshape(-1)
+        # what quadratureWeights needs (copies: the caller's arrays may change)
+        self._weightArgs = (np.array(ctx.V, dtype=np.float64), np.array(J, dtype=np.float64).reshape(Np, K), cubV.copy(),
+                            np.asarray(cub_ctx.W, dtype=np.float64)[:, self.curvedEls])
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -124,6 +148,71 @@ class Sw2dCurvedSolver:
 
     def synchronize(self):
         check(lib.bdg_sw2d_curved_synchronize(self._h))
+
+    # ---- model time, run monitor, drifters (field statistics: RunRecords.enableFieldStats as it is)
+    @property
+    def time(self):
+        """The model time the records carry: + dt per completed step of stepRK2 and lserk4Stages; runAdaptive starts it from
+        its ``t``."""
+        t = c_double()
+        check(lib.bdg_sw2d_curved_get_time(self._h, byref(t)))
+        return t.value
+
+    @time.setter
+    def time(self, t):
+        check(lib.bdg_sw2d_curved_set_time(self._h, float(t)))
+
+    def quadratureWeights(self):
+        """(Np, K) weights w with sum(w * f) the integral of the nodal field f as THIS solver's scheme conserves it: on the
+        elements of ``curvedEls`` w[:, k] = cub_ctx.V.T @ cub_ctx.W[:, k], the column sums 1^T M_k of the element's cubature
+        mass matrix (the mass its Cholesky solve conserves); m[n] J[n, k] elsewhere, m the column sums of the reference mass
+        matrix. Plain NumPy from the constructor's arrays."""
+        V, J, cubV, cubW = self._weightArgs
+        return quadrature_weights(V, J, cubV, cubW, self.curvedEls)
+
+    def enableMonitor(self, nodes, H=None, gauges=None, stride=1, capacity=4096):
+        """Switches on the run monitor: from now on stepRK2, lserk4Stages (a step is the fifth stage) and runAdaptive record
+        the integrals of h, hu, hv, hN and of the energy, min / max h, max|hu|, max|hv|, a NaN count and eta, u, v, N at the
+        ``gauges`` after every ``stride``-th completed step, on the device and without waiting for it; ``capacity`` records
+        are held there. The weights are ``quadratureWeights()``. ``nodes``: the TriangleNodesProvisioner of the solver's mesh
+        with the deformed coordinates set (point location on the curved map, interpolation rows). ``H``: (Np, K) still-water
+        depth of eta = h - H and of the potential energy (without one enableDriver's, else 0). ``gauges``: (n, 2) array of
+        x, y or a tuple (element, r, s). Once per solver; not on a partitioned solver."""
+        shape = (self.Np, self.K)
+        w = C.as_f64(self.quadratureWeights(), shape, "weights")
+        Hh = None if H is None else C.as_f64(H, shape, "H")
+        if gauges is None:
+            el, r, s = np.empty(0, np.int32), np.empty(0), np.empty(0)
+        else:
+            el, r, s = locate(gauges, nodes, "gauges", "TriangleNodesProvisioner")
+        rows = C.as_f64(nodes.interpolationRows(r, s), (el.size, self.Np), "rows")
+        d = C.Sw2dMonitorDesc(C.ptr(w), C.ptr(Hh), el.size, C.ptr(el) if el.size else None, C.ptr(rows) if el.size else None,
+                              int(stride), int(capacity))
+        check(lib.bdg_sw2d_curved_enable_monitor(self._h, byref(d)))
+        self.numGauges = int(el.size)
+
+    def timeMonitor(self, count):
+        """Average device milliseconds of one monitor sample (both launches); takes no records."""
+        ms = c_float()
+        check(lib.bdg_sw2d_curved_monitor_time(self._h, int(count), byref(ms)))
+        return ms.value
+
+    def enableDrifters(self, nodes, points, curvedEls=None, mapO=None, stride=1, capacity=1024):
+        """Switches on Lagrangian drifters: points that move with (hu / h, hv / h) of the resident state. From now on stepRK2,
+        lserk4Stages and runAdaptive advance them on the device by that step's dt after every completed step (Heun; one
+        launch, no state download) and keep their positions after every ``stride``-th advance, ``capacity`` records at most.
+        ``nodes``: the TriangleNodesProvisioner of the solver's mesh with the deformed coordinates set. ``points``: (n, 2)
+        array of x, y, located with ``nodes.locatePoints``, or a tuple (element, r, s). ``curvedEls``: the elements followed
+        through their own nodal map (default: the solver's); every other element must be straight-sided. ``mapO``: flat
+        face-node numbers ((3 k + f) Nfp + i) of the open boundary faces, where a drifter exits (status 1); at every other
+        boundary face it slides along the wall, curved or not (status bit 4). Set the state first; once per solver; not on a
+        partitioned solver."""
+        el, r, s = locate(points, nodes, "points", "TriangleNodesProvisioner")
+        vert, neigh, (vinv, jac), slot, modal = nodes.curvedDrifterTables(self.curvedEls if curvedEls is None else curvedEls, mapO)
+        d = C.Sw2dCurvedDrifterDesc(el.size, C.ptr(el), C.ptr(r), C.ptr(s), C.ptr(vert), C.ptr(neigh), C.ptr(vinv), C.ptr(jac),
+                                    int(stride), int(capacity), C.ptr(slot), C.ptr(modal) if modal.size else None, modal.shape[0])
+        check(lib.bdg_sw2d_curved_enable_drifters(self._h, byref(d)))
+        self.numDrifters = int(el.size)
 
     # ---- element-partitioned runs: ghost columns in and out, the two halves of a step
     def getElements(self, first, count, intermediate=False):

@@ -106,6 +106,15 @@ public:
     /// signed area is not positive and finite, and for a mapO entry out of range.
     void drifterTables(const index_type* mapO, index_type numOut, real_type* vertices, index_type* neighbours, real_type* vinv,
                        real_type* jacobi) const;
+    /// drifterTables for a mesh with curved elements (bdg_sw2d_curved_enable_drifters): the affine check covers only the
+    /// elements NOT listed in curvedEls (numCurved entries, each once). curvedSlot (K): -1, or the element's row c in modal.
+    /// modal (numCurved, 6, Np): per listed element the modal coefficients Vinv f of the six nodal planes f = x, y, Dr x, Ds x,
+    /// Dr y, Ds y (formed in long double, rounded once): sum_m P_m(r, s) modal[c][p][m] is the nodal map and its Jacobian at
+    /// (r, s). vertices of a listed element are its corner nodes. std::invalid_argument also for a curvedEls entry out of
+    /// range or listed twice and for a listed element with a nodal Jacobian Dr x Ds y - Ds x Dr y that is not positive.
+    void curvedDrifterTables(const index_type* curvedEls, index_type numCurved, const index_type* mapO, index_type numOut,
+                             real_type* vertices, index_type* neighbours, real_type* vinv, real_type* jacobi,
+                             index_type* curvedSlot, real_type* modal) const;
 
     // ---- accessors
     const real_matrix_type& get_xGrid() const { return xGrid; }

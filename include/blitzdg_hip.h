@@ -754,8 +754,9 @@ int bdg_trinodes_interpolation_rows(const bdg_trinodes* nodes, const double* r, 
  * LDS tree, partials added in ascending order; no floating-point atomics): equal states give equal records bit for bit.
  * A solver that renumbered its elements (bdg_sw2d_is_renumbered) sums in the order of its device slots: the weights are
  * uploaded through the renumbering, and the records of a renumbered and a BDG_SW2D_KEEP_ORDER solver agree to the summation
- * bound, not bit for bit. Gauge elements are given in the caller's numbering. Straight-sided solvers only
- * (bdg_sw2d_curved has cubature weights and per-element mass matrices: no monitor). */
+ * bound, not bit for bit. Gauge elements are given in the caller's numbering. These weights serve straight-sided
+ * solvers; bdg_sw2d_curved has cubature weights and per-element mass matrices and takes the weights its own monitor states
+ * (bdg_sw2d_curved_enable_monitor below). */
 typedef struct bdg_sw2d_monitor_desc {
     const double* weights;      /* (Np, K), bdg_trinodes_quadrature_weights */
     const double* H;            /* (Np, K) or NULL (the solver's resident H if it has one) */
@@ -839,7 +840,7 @@ typedef struct bdg_sw2d_drifter_desc {
  * drifters_state: the current x, y, element, r, s, status (count entries each; any may be NULL). drifters_count: records
  * taken and drifters. drifters_read: records [first, first + num): t (num), x, y, status (num x count each, record-major; any
  * may be NULL); synchronises the solver's stream. drifters_reset drops the records only.
- * (bdg_sw2d_curved has curved elements: no drifters.) */
+ * (Curved elements: bdg_sw2d_curved_enable_drifters below.) */
 int bdg_sw2d_enable_drifters(bdg_sw2d* s, const bdg_sw2d_drifter_desc* desc);
 int bdg_sw2d_drifters_advance(bdg_sw2d* s, double dt, int num_steps);
 int bdg_sw2d_drifters_time(bdg_sw2d* s, double dt, int count, float* ms);
@@ -1059,6 +1060,72 @@ int bdg_sw2d_curved_output_fields(bdg_sw2d_curved* s, const double* IM, double* 
 /* Average device milliseconds (HIP events on the solver's stream, after 10 untimed launches) of `count` dt passes (which = 0) or
  * output launches of all six fields (which = 1; IM as above). */
 int bdg_sw2d_curved_time_driver(bdg_sw2d_curved* s, int which, const double* IM, int count, float* ms);
+
+/* ---- model time, run monitor, field statistics and drifters of the curved solver: the groups of bdg_sw2d_* above with the same
+ * record layouts, statuses and refusals (csrc/hip/run_records.hpp). Single domain only: every enable_* call refuses a solver
+ * with a partition or a communicator set, and set_partition and comm_init refuse a solver that has any of the three; the
+ * host-staged halves (rk2_phase) feed nothing. With nothing enabled every stepping call launches exactly what it did before.
+ * The columns of the state are the caller's elements: nothing is renumbered.
+ * Model time: + dt per completed step of step_rk2 (and time_rk2), per completed five-stage step of lserk4_stages; run_adaptive
+ * starts it from its t_inout and adds each step's dt. Only the records read it. */
+int bdg_sw2d_curved_set_time(bdg_sw2d_curved* s, double t);
+int bdg_sw2d_curved_get_time(const bdg_sw2d_curved* s, double* t);
+/* Run monitor: four fields, so a record is t, int h, int hu, int hv, int hN, E, min h, max h, max|hu|, max|hv|, NaN count, then
+ * per gauge eta, u, v, N. weights (Np, K): on the elements of curvedEls w[:, k] = cubV^T cubW[:, k], the column sums 1^T M_k of
+ * the element's mass matrix, which is the mass its Cholesky solve conserves; m[n] J[n, k] (bdg_trinodes_quadrature_weights) on
+ * the others (blitzdg_amd/sw2d_curved.py: quadratureWeights). gauge_row from bdg_trinodes_interpolation_rows at the (r, s)
+ * bdg_trinodes_locate_points gives on the deformed coordinates. H: the descriptor's if given, else the one
+ * bdg_sw2d_curved_enable_driver was given, else 0. Records after every stride-th completed step of step_rk2, lserk4_stages and
+ * run_adaptive (which checks the room before each step); a call that would overflow the capacity is refused before it launches
+ * anything. */
+int bdg_sw2d_curved_enable_monitor(bdg_sw2d_curved* s, const bdg_sw2d_monitor_desc* desc);
+int bdg_sw2d_curved_monitor_sample(bdg_sw2d_curved* s);
+int bdg_sw2d_curved_monitor_count(const bdg_sw2d_curved* s, int* n);
+int bdg_sw2d_curved_monitor_read(bdg_sw2d_curved* s, int first, int count, double* records);
+int bdg_sw2d_curved_monitor_width(const bdg_sw2d_curved* s, int* width);
+int bdg_sw2d_curved_monitor_reset(bdg_sw2d_curved* s);
+int bdg_sw2d_curved_monitor_time(bdg_sw2d_curved* s, int count, float* ms);
+/* Field statistics: bdg_sw2d_enable_field_stats and its group, H by the monitor's rule. */
+int bdg_sw2d_curved_enable_field_stats(bdg_sw2d_curved* s, const bdg_field_stats_desc* desc);
+int bdg_sw2d_curved_field_stats_sample(bdg_sw2d_curved* s);
+int bdg_sw2d_curved_field_stats_count(const bdg_sw2d_curved* s, int* samples, int* num_periods);
+int bdg_sw2d_curved_field_stats_read(bdg_sw2d_curved* s, int which, int index, double* plane);
+int bdg_sw2d_curved_field_stats_samples(const bdg_sw2d_curved* s, int first, int count, double* rows);
+int bdg_sw2d_curved_field_stats_reset(bdg_sw2d_curved* s);
+int bdg_sw2d_curved_field_stats_time(bdg_sw2d_curved* s, int count, float* ms);
+/* Drifters through curved elements and along curved walls (csrc/hip/sw2d_curved_drifter_kernel.hpp states the algorithm).
+ * Host set-up: bdg_trinodes_drifter_tables with the affine check on the elements NOT listed in curved_els alone, and the side
+ * tables of the listed ones: curved_slot (K): -1, or the element's row in modal; modal (num_curved, 6, Np): the modal
+ * coefficients (Vinv times the nodal values) of x, y, Dr x, Ds x, Dr y, Ds y of the provisioner's current coordinates. vertices
+ * of a listed element are its corner nodes. BDG_ERR_ARGUMENT also for a curved_els entry out of range or listed twice and for a
+ * listed element with a nodal Jacobian that is not positive. modal may be NULL when num_curved is 0. */
+int bdg_trinodes_curved_drifter_tables(const bdg_trinodes* nodes, const int* curved_els, int num_curved, const int* mapO, int num_out,
+                                       double* vertices, int* neighbours, double* vinv, double* jacobi, int* curved_slot,
+                                       double* modal);
+typedef struct bdg_sw2d_curved_drifter_desc {
+    int count;                  /* the fields of bdg_sw2d_drifter_desc ... */
+    const int* element;
+    const double* r;
+    const double* s;
+    const double* vertices;
+    const int* neighbours;
+    const double* vinv;
+    const double* jacobi;
+    int stride;
+    int capacity;
+    const int* curved_slot;     /* ... and (K), (num_curved, 6, Np): bdg_trinodes_curved_drifter_tables */
+    const double* modal;
+    int num_curved;
+} bdg_sw2d_curved_drifter_desc;
+/* The calls of the bdg_sw2d_*drifters* group: advanced after every completed step of step_rk2, lserk4_stages and run_adaptive,
+ * sampled again by set_state. BDG_ERR_ARGUMENT also for a curved_slot entry outside [-1, num_curved). */
+int bdg_sw2d_curved_enable_drifters(bdg_sw2d_curved* s, const bdg_sw2d_curved_drifter_desc* desc);
+int bdg_sw2d_curved_drifters_advance(bdg_sw2d_curved* s, double dt, int num_steps);
+int bdg_sw2d_curved_drifters_time(bdg_sw2d_curved* s, double dt, int count, float* ms);
+int bdg_sw2d_curved_drifters_state(bdg_sw2d_curved* s, double* x, double* y, int* element, double* r, double* sref, int* status);
+int bdg_sw2d_curved_drifters_count(const bdg_sw2d_curved* s, int* num_records, int* num_drifters);
+int bdg_sw2d_curved_drifters_read(bdg_sw2d_curved* s, int first, int num, double* t, double* x, double* y, int* status);
+int bdg_sw2d_curved_drifters_reset(bdg_sw2d_curved* s);
 
 #ifdef __cplusplus
 }
