@@ -230,6 +230,7 @@ _SIGNATURES = {
     "bdg_sw2d_rhs4": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
     "bdg_sw2d_num_fields": (c_int, [_P]),
     "bdg_sw2d_enable_variant_b": (c_int, [_P, POINTER(Sw2dVbDesc)]),
+    "bdg_sw2d_enable_variant_b4": (c_int, [_P, POINTER(Sw2dVbDesc), _P, c_int]),
     "bdg_sw2d_set_time": (c_int, [_P, c_double]),
     "bdg_sw2d_get_time": (c_int, [_P, POINTER(c_double)]),
     "bdg_sw2d_global_speed": (c_int, [_P, POINTER(c_double)]),

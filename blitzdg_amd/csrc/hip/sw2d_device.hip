@@ -12,6 +12,8 @@
 //   ops         Dr|Ds interleaved, Lift, Filter (copied to LDS by every workgroup)
 // Elements may be renumbered internally (BDG_SW2D_REORDER); all I/O is in the
 // caller's numbering.
+// After bdg_sw2d_enable_variant_b4 a four-field solver evaluates variant B with the tracer as a fourth equation: the three-field
+// variant-B launches, each followed by the tracer pass of sw2d_vb_tracer_kernel.hpp (per-order objects sw2d_vb4_order.hip).
 // After bdg_sw2d_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2d_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_drifter_kernel.hpp).
 #include "../host/capi_internal.hpp"
@@ -21,6 +23,7 @@
 #include "run_records.hpp"
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
+#include "sw2d_vb4_launch.hpp"
 #include "sw2d_drifter_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -54,6 +57,29 @@ const KernelTable* kernel_table(int order) {
     case 6: return kernel_table_order6();
     case 7: return kernel_table_order7();
     case 8: return kernel_table_order8();
+    default: return nullptr;
+    }
+}
+
+const Vb4KernelTable* vb4_kernel_table_order1();
+const Vb4KernelTable* vb4_kernel_table_order2();
+const Vb4KernelTable* vb4_kernel_table_order3();
+const Vb4KernelTable* vb4_kernel_table_order4();
+const Vb4KernelTable* vb4_kernel_table_order5();
+const Vb4KernelTable* vb4_kernel_table_order6();
+const Vb4KernelTable* vb4_kernel_table_order7();
+const Vb4KernelTable* vb4_kernel_table_order8();
+
+const Vb4KernelTable* vb4_kernel_table(int order) {
+    switch (order) {
+    case 1: return vb4_kernel_table_order1();
+    case 2: return vb4_kernel_table_order2();
+    case 3: return vb4_kernel_table_order3();
+    case 4: return vb4_kernel_table_order4();
+    case 5: return vb4_kernel_table_order5();
+    case 6: return vb4_kernel_table_order6();
+    case 7: return vb4_kernel_table_order7();
+    case 8: return vb4_kernel_table_order8();
     default: return nullptr;
     }
 }
@@ -255,6 +281,14 @@ struct bdg_sw2d {
     double tideAmp = 0.0, tidePeriod = 1.0, tideRamp = 0.0;
     double timeNow = 0.0;  // model time of the resident state (tide phase)
     bool lamExternal = false; // variant B, partitioned: lamBuf holds the all-rank speed of the state about to be evaluated
+    // variant B with the tracer (bdg_sw2d_enable_variant_b4): the tracer pass of sw2d_vb_tracer_kernel.hpp behind every three-field
+    // variant-B launch, and the concentration the open boundary feeds (a scalar, or a table per open-boundary node in device slots)
+    bool variantB4 = false;
+    bool evaluated = false; // a stage kernel or a speed pass has been launched
+    const bdg_dev::Vb4KernelTable* kt4 = nullptr;
+    bdg_dev::VbTracerParams vb4{};
+    DevBuf<int> openBase;
+    DevBuf<double> openN, opsRow, opsRowFiltered; // VnOps images of the tracer pass's general form (straight-sided elements)
     DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
     int lamSlot = 0;
     // Direction of the tile sweep of whole-mesh stage launches (StageParams::sweepBack, sw2d_stage_tile.hpp): it alternates from
@@ -468,6 +502,7 @@ struct bdg_sw2d {
         if (filter && !hasFilter) throw arg_error("filter requested but the solver was created without a Filter matrix");
         hipStream_t st = on ? on : stream;
         auto sweep = [&] { nextSweep(p, wholeMesh); };
+        evaluated = true;
         // Small launches (a rank's share of a many-way split, its partition-boundary strip) are bound by
         // the latency of one wavefront, not by HBM: the matrix-core kernel gives each wave 16 elements
         // instead of 64 (measured at N=4: 750 elements 7 us vs 19 us; 125 k elements 48 us vs 56 us;
@@ -489,6 +524,7 @@ struct bdg_sw2d {
                 vb.lamNext = nullptr;
                 lamStateFor = nullptr;
                 hipCheck(kt->stageVn(mode, true, p, vd, vb, opsVn.p, filt, vnRaw.p, vbPartials.p, lamBuf.p, !lamExternal, st), what);
+                if (variantB4) launchTracerB(mode, filter, p, what, st);
             } else {
                 bdg_dev::VdParams v = vd;
                 v.cbase = 0;
@@ -535,6 +571,10 @@ struct bdg_sw2d {
             } else {
                 p.opsAffine = filter ? opsVdFiltered.p : opsVd.p;
                 hipCheck(kt->stageVb(mode, p, vb, vbPartials.p, lamBuf.p, false, VbStage::Rolled, nullptr, st), what);
+            }
+            if (variantB4) { // the tracer pass walks the tiles against the launch before it, as every whole-mesh launch does
+                sweep();
+                launchTracerB(mode, filter, p, what, st);
             }
         } else if (variantD && fastSources) {
             // three conserved fields on the unrolled kernel with the sources folded in, the tracer (if
@@ -613,6 +653,20 @@ struct bdg_sw2d {
         } else {
             sweep();
             hipCheck(kt->stage(mode, filter, p, st), what);
+        }
+    }
+
+    // Variant B with the tracer: plane 3 of the evaluation whose three-field launch(es) were just issued on `st` -- same input
+    // state, same tide (vb.tide) and the speed that launch read (vb.lam; the speed it leaves for the next evaluation is in the
+    // other accumulator). The tracer has no source: the filter rides in the operators on straight-sided elements.
+    void launchTracerB(int mode, bool filter, bdg_dev::StageParams& p, const char* what, hipStream_t st) {
+        if (!affine) {
+            hipCheck(kt4->tracerGeneral(mode, true, p, vb, vb4, opsVn.p, filter ? filterRows.p : nullptr, vnRaw.p, st), what);
+        } else if (fastSources && kt4->unrolled) {
+            p.opsAffine = filter ? opsAffineFiltered.p : opsAffine.p;
+            hipCheck(kt4->tracerUnrolled(mode, p, vb, vb4, st), what);
+        } else {
+            hipCheck(kt4->tracerGeneral(mode, false, p, vb, vb4, filter ? opsRowFiltered.p : opsRow.p, nullptr, nullptr, st), what);
         }
     }
 
@@ -698,6 +752,7 @@ struct bdg_sw2d {
         p.qin = state;
         vb.tide = tideAt(timeNow);
         vb.lam = lamBuf.p;
+        evaluated = true;
         hipCheck(kt->stageVb(bdg_dev::MODE_RHS, p, vb, vbPartials.p, lamBuf.p, true, bdg_dev::VbStage::None, nullptr, stream), "sw2d_vb_speed_kernel");
         if (halo.comm && halo.world > 1)
             ncclCheck(rccl().AllReduce(lamBuf.p, lamBuf.p, 1, ncclDouble, ncclMax, halo.comm, stream), "ncclAllReduce");
@@ -1572,58 +1627,153 @@ int bdg_sw2d_set_bathymetry(bdg_sw2d* s, const double* H) {
     });
 }
 
+} // extern "C"
+
+namespace {
+
+// what bdg_sw2d_enable_variant_b and _b4 share: the checks on the descriptor (`fn` names the caller in the messages) ...
+void checkVariantB(const bdg_sw2d* s, const bdg_sw2d_vb_desc* d, const std::string& fn) {
+    // partitioned solvers: allowed -- their steppers are the *_exchanged ones, which reduce the global speed over all
+    // ranks before each evaluation (evaluateExchanged); the in-process group transport has no such reduction
+    if (s->localGroup) throw arg_error(fn + ": not available with the in-process group transport");
+    if (d->num_out < 0 || (d->num_out > 0 && !d->mapO)) throw arg_error(fn + ": bad open-boundary list");
+    if (!(d->tide_period > 0.0) && d->num_out > 0) throw arg_error(fn + ": tide_period must be > 0");
+    const size_t nFaceNodes = static_cast<size_t>(s->NFN) * s->K;
+    for (int i = 0; i < d->num_out; ++i)
+        if (d->mapO[i] < 0 || static_cast<size_t>(d->mapO[i]) >= nFaceNodes)
+            throw arg_error(fn + ": open-boundary node index out of range");
+}
+
+// ... and the set-up: operator images of the source-term kernels, the bed, the sponge, the open-boundary bit masks, the tide
+void enableVariantB(bdg_sw2d* s, const bdg_sw2d_vb_desc* d) {
+    s->buildSourceOps();
+    s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources();
+    if (s->N > bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources()) {
+        s->buildMfma2SourceOps();
+        s->mfmaSources = true;
+    }
+    if (s->fastSources) s->buildFilterT();
+    if (!s->Hbuf.p) s->Hbuf.alloc(s->planeSize(), s->bytes);
+    hipCheck(hipMemsetAsync(s->Hbuf.p, 0, s->Hbuf.n * sizeof(double), s->stream), "hipMemset");
+    // padding lanes are never computed, but give them a positive depth anyway
+    s->uploadRows(d->H, s->Hbuf.p, s->Np);
+    s->hasH = true;
+    s->vb.H = s->Hbuf.p;
+    s->vb.Hx = s->uploadPlane(d->Hx, s->HxBuf);
+    s->vb.Hy = s->uploadPlane(d->Hy, s->HyBuf);
+    s->vb.sponge = s->uploadPlane(d->sponge, s->spongeBuf);
+    // open-boundary face nodes as one bit mask per element, in device slots
+    std::vector<int> mask(static_cast<size_t>(s->ld), 0);
+    for (int i = 0; i < d->num_out; ++i) {
+        const int k = d->mapO[i] / s->NFN, j = d->mapO[i] % s->NFN;
+        mask[s->permHost.empty() ? k : s->permHost[k]] |= 1 << j;
+    }
+    if (!s->obcBuf.p) s->obcBuf.alloc(static_cast<size_t>(s->ld), s->bytes);
+    hipCheck(hipMemcpy(s->obcBuf.p, mask.data(), mask.size() * sizeof(int), hipMemcpyHostToDevice), "open-boundary upload");
+    s->vb.obc = s->obcBuf.p;
+    if (!s->lamBuf.p) s->lamBuf.alloc(1, s->bytes);
+    if (!s->lamPair.p) s->lamPair.alloc(2, s->bytes);
+    s->lamStateFor = nullptr;
+    if (!s->vbPartials.p) s->vbPartials.alloc(static_cast<size_t>((s->K + 255) / 256), s->bytes);
+    s->vb.lam = s->lamBuf.p;
+    s->vb.fcor = d->coriolis;
+    s->vb.cd = d->drag;
+    s->tideAmp = d->tide_amplitude;
+    s->tidePeriod = d->tide_period > 0.0 ? d->tide_period : 1.0;
+    s->tideRamp = d->tide_ramp;
+    s->variantB = true;
+}
+
+// VnOps image (row i = {Dr[i][m], Ds[i][m]} interleaved, then Lift[i][j]) of the tracer pass's general form
+std::vector<double> rowOpsImage(const double* Dr, const double* Ds, const double* Lift, int Np, int NFN) {
+    const int row = 2 * Np + NFN;
+    std::vector<double> img(static_cast<size_t>(row) * Np);
+    for (int i = 0; i < Np; ++i) {
+        for (int m = 0; m < Np; ++m) {
+            img[static_cast<size_t>(i) * row + 2 * m] = Dr[static_cast<size_t>(i) * Np + m];
+            img[static_cast<size_t>(i) * row + 2 * m + 1] = Ds[static_cast<size_t>(i) * Np + m];
+        }
+        for (int j = 0; j < NFN; ++j) img[static_cast<size_t>(i) * row + 2 * Np + j] = Lift[static_cast<size_t>(i) * NFN + j];
+    }
+    return img;
+}
+
+} // namespace
+
+extern "C" {
+
 int bdg_sw2d_enable_variant_b(bdg_sw2d* s, const bdg_sw2d_vb_desc* d) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_enable_variant_b");
         if (!d || !d->H || !d->Hx || !d->Hy) throw arg_error("bdg_sw2d_enable_variant_b: H, Hx and Hy are required");
         if (s->nf != 3 || s->variantD)
             throw arg_error("bdg_sw2d_enable_variant_b: the solver was created with tracer / variant-D sources");
-        // partitioned solvers: allowed -- their steppers are the *_exchanged ones, which reduce the global speed over all
-        // ranks before each evaluation (evaluateExchanged); the in-process group transport has no such reduction
-        if (s->localGroup) throw arg_error("bdg_sw2d_enable_variant_b: not available with the in-process group transport");
-        if (d->num_out < 0 || (d->num_out > 0 && !d->mapO)) throw arg_error("bdg_sw2d_enable_variant_b: bad open-boundary list");
-        if (!(d->tide_period > 0.0) && d->num_out > 0) throw arg_error("bdg_sw2d_enable_variant_b: tide_period must be > 0");
-        const size_t nFaceNodes = static_cast<size_t>(s->NFN) * s->K;
-        for (int i = 0; i < d->num_out; ++i)
-            if (d->mapO[i] < 0 || static_cast<size_t>(d->mapO[i]) >= nFaceNodes)
-                throw arg_error("bdg_sw2d_enable_variant_b: open-boundary node index out of range");
+        checkVariantB(s, d, "bdg_sw2d_enable_variant_b");
         s->use();
-        s->buildSourceOps();
-        s->fastSources = s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources();
-        if (s->N > bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources()) {
-            s->buildMfma2SourceOps();
-            s->mfmaSources = true;
+        enableVariantB(s, d);
+    });
+}
+
+int bdg_sw2d_enable_variant_b4(bdg_sw2d* s, const bdg_sw2d_vb_desc* d, const double* n_open, int n_open_count) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_enable_variant_b4";
+        requireSolver(s, fn.c_str());
+        if (!d || !d->H || !d->Hx || !d->Hy) throw arg_error(fn + ": H, Hx and Hy are required");
+        if (s->nf != 4) throw arg_error(fn + ": the solver was created with three fields; the tracer needs four (num_fields = 4)");
+        if (s->vd.sources) throw arg_error(fn + ": the solver was created with variant-D sources; variant B brings its own");
+        if (s->variantB) throw arg_error(fn + ": variant B is already enabled on this solver; the call is made once");
+        if (s->evaluated)
+            throw arg_error(fn + ": the solver has evaluated a right-hand side already; variant B is enabled before the first evaluation");
+        checkVariantB(s, d, fn);
+        // (without an open-boundary node no concentration is read: a count of 0 is then num_out, and n_open may be NULL)
+        const bool none = d->num_out == 0 && n_open_count == 0;
+        if (!none && (!n_open || (n_open_count != 1 && n_open_count != d->num_out)))
+            throw arg_error(fn + ": n_open must hold 1 value or one per open-boundary node (num_out)");
+        const bdg_dev::Vb4KernelTable* kt4 = bdg_dev::vb4_kernel_table(s->N);
+        if (!kt4) throw arg_error(fn + ": no tracer-pass kernels compiled for this order");
+        s->use();
+        bdg_dev::VbTracerParams tp{};
+        if (none || n_open_count == 1) { // (also a single open node given per node)
+            tp.nOpenC = none ? 0.0 : n_open[0];
+        } else {
+            // per element in DEVICE slots (as the bit masks of the open boundary are stored): the values of its open nodes in the
+            // order of its face nodes, from base[slot] on; the last entry of a node listed twice wins, as an assignment through
+            // mapO does
+            struct Entry { int slot, node, at; };
+            std::vector<Entry> entries(static_cast<size_t>(d->num_out));
+            for (int i = 0; i < d->num_out; ++i) {
+                const int k = d->mapO[i] / s->NFN;
+                entries[static_cast<size_t>(i)] = {s->permHost.empty() ? k : s->permHost[k], d->mapO[i] % s->NFN, i};
+            }
+            std::sort(entries.begin(), entries.end(), [](const Entry& a, const Entry& b) {
+                return a.slot != b.slot ? a.slot < b.slot : (a.node != b.node ? a.node < b.node : a.at < b.at);
+            });
+            std::vector<int> base(static_cast<size_t>(s->ld), 0);
+            std::vector<double> vals;
+            for (size_t e = 0; e < entries.size(); ++e) {
+                const bool again = e > 0 && entries[e - 1].slot == entries[e].slot && entries[e - 1].node == entries[e].node;
+                if (again) { vals.back() = n_open[entries[e].at]; continue; }
+                if (e == 0 || entries[e - 1].slot != entries[e].slot) base[static_cast<size_t>(entries[e].slot)] = static_cast<int>(vals.size());
+                vals.push_back(n_open[entries[e].at]);
+            }
+            if (vals.empty()) vals.push_back(0.0);
+            s->openBase.upload(base, s->bytes, "open-boundary tracer index upload");
+            s->openN.upload(vals, s->bytes, "open-boundary tracer upload");
+            tp.openBase = s->openBase.p;
+            tp.openN = s->openN.p;
         }
-        if (s->fastSources) s->buildFilterT();
-        if (!s->Hbuf.p) s->Hbuf.alloc(s->planeSize(), s->bytes);
-        hipCheck(hipMemsetAsync(s->Hbuf.p, 0, s->Hbuf.n * sizeof(double), s->stream), "hipMemset");
-        // padding lanes are never computed, but give them a positive depth anyway
-        s->uploadRows(d->H, s->Hbuf.p, s->Np);
-        s->hasH = true;
-        s->vb.H = s->Hbuf.p;
-        s->vb.Hx = s->uploadPlane(d->Hx, s->HxBuf);
-        s->vb.Hy = s->uploadPlane(d->Hy, s->HyBuf);
-        s->vb.sponge = s->uploadPlane(d->sponge, s->spongeBuf);
-        // open-boundary face nodes as one bit mask per element, in device slots
-        std::vector<int> mask(static_cast<size_t>(s->ld), 0);
-        for (int i = 0; i < d->num_out; ++i) {
-            const int k = d->mapO[i] / s->NFN, j = d->mapO[i] % s->NFN;
-            mask[s->permHost.empty() ? k : s->permHost[k]] |= 1 << j;
+        if (s->affine && !(s->N <= bdg_sw2d::kUnrolledSourcesMaxOrder && !env::rolledSources() && kt4->unrolled)) {
+            s->opsRow.upload(rowOpsImage(s->hostDr.data(), s->hostDs.data(), s->hostLift.data(), s->Np, s->NFN), s->bytes, "tracer row ops upload");
+            if (!s->hostFilter.empty())
+                s->opsRowFiltered.upload(rowOpsImage(s->hostFDr.data(), s->hostFDs.data(), s->hostFLift.data(), s->Np, s->NFN), s->bytes,
+                                         "filtered tracer row ops upload");
         }
-        if (!s->obcBuf.p) s->obcBuf.alloc(static_cast<size_t>(s->ld), s->bytes);
-        hipCheck(hipMemcpy(s->obcBuf.p, mask.data(), mask.size() * sizeof(int), hipMemcpyHostToDevice), "open-boundary upload");
-        s->vb.obc = s->obcBuf.p;
-        if (!s->lamBuf.p) s->lamBuf.alloc(1, s->bytes);
-        if (!s->lamPair.p) s->lamPair.alloc(2, s->bytes);
-        s->lamStateFor = nullptr;
-        if (!s->vbPartials.p) s->vbPartials.alloc(static_cast<size_t>((s->K + 255) / 256), s->bytes);
-        s->vb.lam = s->lamBuf.p;
-        s->vb.fcor = d->coriolis;
-        s->vb.cd = d->drag;
-        s->tideAmp = d->tide_amplitude;
-        s->tidePeriod = d->tide_period > 0.0 ? d->tide_period : 1.0;
-        s->tideRamp = d->tide_ramp;
-        s->variantB = true;
+        enableVariantB(s, d);
+        // from here on the solver is variant B with a tracer: the three-field variant-B launches, each followed by the tracer pass
+        s->variantD = false;
+        s->kt4 = kt4;
+        s->vb4 = tp;
+        s->variantB4 = true;
     });
 }
 

@@ -318,7 +318,8 @@ class NativeDistributedSw2d:
 
     def set_initial_state(self, fn):
         ctx = self.nodes.dgContext()
-        self.solver.setState(*fn(ctx.x, ctx.y))
+        q = fn(ctx.x, ctx.y)
+        (self.solver.setState4 if len(q) == 4 else self.solver.setState)(*q)
 
     def compute_dt(self, CFL):
         dt, em = self._c_double(), self._c_double()
@@ -338,16 +339,28 @@ class NativeDistributedSw2d:
         self._check(self._lib.bdg_sw2d_step_ssprk2_exchanged(self.solver._h, float(dt), int(nsteps), int(bool(filter)),
                                                              float(sponge)))
 
-    def enable_variant_b(self, fields_fn, **kwargs):
+    def enable_variant_b(self, fields_fn, tracer=None, **kwargs):
         """Variant B on this rank's part: fields_fn(x, y) -> H of the rank-local nodes (owned and ghost elements);
         bed slopes from this rank's operators, open boundary = this rank's BCmap[2] (owned elements keep the global
         mesh's tags). kwargs: CD, f, tide*, sponge (the coefficient array on the rank-local nodes), as
-        Sw2dSolver.enableVariantB."""
+        Sw2dSolver.enableVariantB.
+
+        ``tracer`` (a ``fields=4`` partition created without sources): the concentration the open boundary feeds -- a scalar,
+        one value per rank-local open-boundary node (the order of this rank's BCmap[2]), or a function (x, y) -> values of
+        those nodes' coordinates; variant B then carries the passive tracer hN as a fourth equation on every rank. An
+        evaluation runs in stream order: the four-field exchange, the speed pass, the all-reduce, the owned elements' stage,
+        the owned elements' tracer pass."""
         ctx = self.nodes.dgContext()
         H = fields_fn(ctx.x, ctx.y)
         Hx, Hy = self.nodes.bedSlopes(H)
         mapO = np.array(ctx.BCmap.get(2, []), dtype=np.int32)
-        self.solver.enableVariantB(H, Hx, Hy, mapO=mapO, **kwargs)
+        if tracer is None:
+            self.solver.enableVariantB(H, Hx, Hy, mapO=mapO, **kwargs)
+            return H
+        if callable(tracer):
+            at = np.asarray(ctx.vmapM).reshape(-1)[mapO]
+            tracer = np.asarray(tracer(ctx.x.flatten("F")[at], ctx.y.flatten("F")[at]), dtype=np.float64).reshape(-1)
+        self.solver.enableVariantB(H, Hx, Hy, mapO=mapO, tracer=tracer, **kwargs)
         return H
 
     def allreduce_max(self, value):

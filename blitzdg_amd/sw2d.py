@@ -132,17 +132,37 @@ class Sw2dSolver(RunRecords):
 
     # ---- variant B: physics of the reference's C++ sw2d driver (src/sw2d/main.cpp:279-484)
     def enableVariantB(self, H, Hx, Hy, mapO=(), CD=0.0, f=0.0, tideAmplitude=3.0, tidePeriod=3600 * 12.42,
-                       tideRamp=0.15 / 3600, sponge=None):
+                       tideRamp=0.15 / 3600, sponge=None, tracer=None):
         """Depth ``H`` with star states, open-boundary nodes ``mapO`` (BCmap[2]) following the tide, one
         global Lax-Friedrichs speed, bed-slope (``Hx, Hy``) / drag / Coriolis sources. Afterwards
         computeRHS and the steppers evaluate variant B at ``self.time``; ``sponge`` is the (Np, K)
-        coefficient field stepSSPRK2 relaxes hu, hv with. Defaults are the reference's constants."""
+        coefficient field stepSSPRK2 relaxes hu, hv with. Defaults are the reference's constants.
+
+        ``tracer``: on a ``fields=4`` solver created without ``sources`` (variant B brings its own), the concentration
+        N = hN / h the open-boundary nodes take on their outer side, a scalar or one value per entry of ``mapO``; variant B
+        then carries the passive tracer hN as a fourth equation (computeRHS4, setState4 / getState4, the steppers,
+        outputTracer), before the solver's first evaluation only. A wrong length and a three-field solver raise ValueError.
+        Without ``tracer`` a four-field solver is refused as before."""
         Hh, Hxh, Hyh = self._field(H, "H"), self._field(Hx, "Hx"), self._field(Hy, "Hy")
         mo = C.as_i32(mapO).reshape(-1)
         sp = self._field(sponge, "sponge") if sponge is not None else None
         d = C.Sw2dVbDesc(C.ptr(Hh), C.ptr(Hxh), C.ptr(Hyh), C.ptr(mo) if mo.size else None, mo.size, float(CD),
                          float(f), float(tideAmplitude), float(tidePeriod), float(tideRamp), C.ptr(sp))
-        check(lib.bdg_sw2d_enable_variant_b(self._h, byref(d)))
+        if tracer is None:
+            check(lib.bdg_sw2d_enable_variant_b(self._h, byref(d)))
+            return
+        if self.fields != 4:
+            raise ValueError("tracer needs a solver with fields=4")
+        scalar = np.ndim(tracer) == 0
+        if scalar:
+            tr = np.array([float(tracer)])
+        else:
+            tr = C.as_f64(tracer).reshape(-1)
+            if np.ndim(tracer) != 1 or tr.size != mo.size:
+                raise ValueError(f"tracer: expected a scalar or {mo.size} values, one per entry of mapO")
+        if tr.size == 0:                         # no open-boundary node (a rank away from the open side): nothing to feed
+            tr, scalar = np.zeros(1), True
+        check(lib.bdg_sw2d_enable_variant_b4(self._h, byref(d), C.ptr(tr), 1 if scalar else tr.size))
 
     @property
     def time(self):

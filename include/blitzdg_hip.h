@@ -343,6 +343,20 @@ typedef struct bdg_sw2d_vb_desc {
     const double* sponge;  /* (Np, K) or NULL                            */
 } bdg_sw2d_vb_desc;
 int bdg_sw2d_enable_variant_b(bdg_sw2d* s, const bdg_sw2d_vb_desc* desc);
+/* Variant B with a passive tracer hN as a fourth field (the reference's tidal driver has none; the definition is the one of
+ * bdg_sw2dq_enable_variant_b4). Concentrations are formed from the depths before the star states, NM = hN-/h-,
+ * NP = hN+/h+; a wall node takes NP = NM, an open-boundary node NP = n_open (it wins where a node is both); the star tracer is
+ * hM* NM, hP* NP, so a uniform concentration stays uniform over a discontinuous bed; F4 = hN* hu* / h*, G4 = hN* hv* / h*, the
+ * Lax-Friedrichs term with variant B's one global speed, which the tracer does not enter; no source term. n_open_count is 1
+ * (one concentration for every open-boundary node) or desc->num_out (n_open[i] belongs to mapO[i]; with num_out = 0 a count of
+ * 0 is accepted and n_open is not read); anything else, a NULL handle, descriptor or n_open is BDG_ERR_ARGUMENT, and so is a
+ * three-field solver, a solver created with sources, a second call, and a call after the solver's first evaluation; a refusal
+ * changes nothing. Once, on a solver created with num_fields = 4 and sources = 0: afterwards the four-field calls
+ * (bdg_sw2d_rhs4, _set_state4 / _get_state4) and every stepping entry evaluate the three-field variant-B launches exactly as a
+ * three-field solver does, each followed by the tracer pass (sw2d_vb_tracer_kernel.hpp); hN is stepped as h is (never sponged),
+ * the filter applies to all four right-hand sides. Orders 1 to 8, both geometry forms, partitioned solvers included.
+ * bdg_sw2d_enable_variant_b keeps refusing four-field solvers. */
+int bdg_sw2d_enable_variant_b4(bdg_sw2d* s, const bdg_sw2d_vb_desc* desc, const double* n_open, int n_open_count);
 int bdg_sw2d_set_time(bdg_sw2d* s, double t);
 int bdg_sw2d_get_time(const bdg_sw2d* s, double* t);
 /* The global Lax-Friedrichs speed of the most recent variant-B evaluation. */
