@@ -80,6 +80,10 @@ class Sw2dVbDesc(Structure):
                 ("tide_period", c_double), ("tide_ramp", c_double), ("sponge", c_void_p)]
 
 
+class Sw2dDiffusionDesc(Structure):
+    _fields_ = [("kappa", c_double), ("kappa_field", c_void_p), ("source", c_void_p), ("decay", c_double)]
+
+
 class Sw2dqMonitorDesc(Structure):
     _fields_ = [("weights", c_void_p), ("H", c_void_p), ("num_gauges", c_int), ("gauge_element", c_void_p),
                 ("gauge_r", c_void_p), ("gauge_s", c_void_p), ("stride", c_int), ("capacity", c_int)]
@@ -231,6 +235,8 @@ _SIGNATURES = {
     "bdg_sw2d_num_fields": (c_int, [_P]),
     "bdg_sw2d_enable_variant_b": (c_int, [_P, POINTER(Sw2dVbDesc)]),
     "bdg_sw2d_enable_variant_b4": (c_int, [_P, POINTER(Sw2dVbDesc), _P, c_int]),
+    "bdg_sw2d_enable_tracer_diffusion": (c_int, [_P, POINTER(Sw2dDiffusionDesc)]),
+    "bdg_sw2d_diffusion_dt": (c_int, [_P, POINTER(c_double)]),
     "bdg_sw2d_set_time": (c_int, [_P, c_double]),
     "bdg_sw2d_get_time": (c_int, [_P, POINTER(c_double)]),
     "bdg_sw2d_global_speed": (c_int, [_P, POINTER(c_double)]),

@@ -14,6 +14,8 @@
 // caller's numbering.
 // After bdg_sw2d_enable_variant_b4 a four-field solver evaluates variant B with the tracer as a fourth equation: the three-field
 // variant-B launches, each followed by the tracer pass of sw2d_vb_tracer_kernel.hpp (per-order objects sw2d_vb4_order.hip).
+// After bdg_sw2d_enable_tracer_diffusion every evaluation of a four-field solver is followed by the two passes of
+// sw2d_diffusion_kernel.hpp (per-order objects sw2d_diffusion_order.hip), which add the tracer's diffusion, source and decay.
 // After bdg_sw2d_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2d_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_drifter_kernel.hpp).
 #include "../host/capi_internal.hpp"
@@ -24,6 +26,7 @@
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
 #include "sw2d_vb4_launch.hpp"
+#include "sw2d_diffusion_launch.hpp"
 #include "sw2d_drifter_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -80,6 +83,29 @@ const Vb4KernelTable* vb4_kernel_table(int order) {
     case 6: return vb4_kernel_table_order6();
     case 7: return vb4_kernel_table_order7();
     case 8: return vb4_kernel_table_order8();
+    default: return nullptr;
+    }
+}
+
+const DiffusionKernelTable* diffusion_kernel_table_order1();
+const DiffusionKernelTable* diffusion_kernel_table_order2();
+const DiffusionKernelTable* diffusion_kernel_table_order3();
+const DiffusionKernelTable* diffusion_kernel_table_order4();
+const DiffusionKernelTable* diffusion_kernel_table_order5();
+const DiffusionKernelTable* diffusion_kernel_table_order6();
+const DiffusionKernelTable* diffusion_kernel_table_order7();
+const DiffusionKernelTable* diffusion_kernel_table_order8();
+
+const DiffusionKernelTable* diffusion_kernel_table(int order) {
+    switch (order) {
+    case 1: return diffusion_kernel_table_order1();
+    case 2: return diffusion_kernel_table_order2();
+    case 3: return diffusion_kernel_table_order3();
+    case 4: return diffusion_kernel_table_order4();
+    case 5: return diffusion_kernel_table_order5();
+    case 6: return diffusion_kernel_table_order6();
+    case 7: return diffusion_kernel_table_order7();
+    case 8: return diffusion_kernel_table_order8();
     default: return nullptr;
     }
 }
@@ -289,6 +315,16 @@ struct bdg_sw2d {
     bdg_dev::VbTracerParams vb4{};
     DevBuf<int> openBase;
     DevBuf<double> openN, opsRow, opsRowFiltered; // VnOps images of the tracer pass's general form (straight-sided elements)
+    // tracer diffusion, sources and decay (bdg_sw2d_enable_tracer_diffusion): the passes of sw2d_diffusion_kernel.hpp behind the
+    // last launch of every evaluation. difOps / difOpsFiltered: VnOps images (the second on straight-sided elements with a Filter),
+    // difFilter: the Filter's rows, difScratch: the flux planes fx, fy and, with a Filter, the plane of the unfiltered term
+    bool diffusion = false;
+    const bdg_dev::DiffusionKernelTable* ktd = nullptr;
+    bdg_dev::DiffusionParams dif{};
+    DevBuf<double> difKappa, difSource, difScratch, difOps, difOpsFiltered, difFilter;
+    double difDt = 0.0;                // c / (max kappa (N+1)^4 max(Fscale)^2), kDiffusionDtConstant below
+    // dt_diff <= 2 / rho(operator) at every order with this constant: the smallest bound measured is 4.30 (N = 1)
+    static constexpr double kDiffusionDtConstant = 4.0;
     DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
     int lamSlot = 0;
     // Direction of the tile sweep of whole-mesh stage launches (StageParams::sweepBack, sw2d_stage_tile.hpp): it alternates from
@@ -653,6 +689,32 @@ struct bdg_sw2d {
         } else {
             sweep();
             hipCheck(kt->stage(mode, filter, p, st), what);
+        }
+        if (diffusion) launchDiffusion(mode, filter, p, sweep, st);
+    }
+
+    // The tracer's diffusion, source and decay of the evaluation whose launches were just issued on `st`: T of p.qin -- which
+    // those launches read and did not write -- added to plane 3 of what they wrote. Each launch takes the next direction of the
+    // alternating sweep. A filtered evaluation: pre-filtered rows where T is linear in the fluxes and the metric is one per
+    // element; else the unfiltered T into a scratch plane and the Filter's rows over all of it in a third launch.
+    template <class Sweep>
+    void launchDiffusion(int mode, bool filter, bdg_dev::StageParams& p, Sweep&& sweep, hipStream_t st) {
+        const bool nodal = !affine;
+        // what the scheme rests on: the evaluation's own launches have not written the state they read
+        if (mode == bdg_dev::MODE_RHS ? p.qin == p.rhs : (p.qin == p.qout || p.qin == p.res))
+            throw std::logic_error("tracer diffusion: the stage's input state is one of its output buffers");
+        sweep();
+        hipCheck(ktd->gradient(nodal, p, dif, difOps.p, st), "sw2d_tracer_gradient_kernel");
+        sweep();
+        const char* what = "sw2d_tracer_diffusion_kernel";
+        if (!filter) {
+            hipCheck(ktd->divergence(mode, nodal, false, p, dif, difOps.p, st), what);
+        } else if (!nodal && !dif.source && dif.decay == 0.0) {
+            hipCheck(ktd->divergence(mode, false, false, p, dif, difOpsFiltered.p, st), what);
+        } else {
+            hipCheck(ktd->divergence(mode, nodal, true, p, dif, difOps.p, st), what);
+            sweep();
+            hipCheck(ktd->filter(mode, p, dif, difFilter.p, st), "sw2d_tracer_diffusion_filter_kernel");
         }
     }
 
@@ -1777,6 +1839,75 @@ int bdg_sw2d_enable_variant_b4(bdg_sw2d* s, const bdg_sw2d_vb_desc* d, const dou
     });
 }
 
+int bdg_sw2d_enable_tracer_diffusion(bdg_sw2d* s, const bdg_sw2d_diffusion_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_enable_tracer_diffusion";
+        requireSolver(s, fn.c_str());
+        if (!d) throw arg_error(fn + ": NULL descriptor");
+        if (s->nf != 4) throw arg_error(fn + ": the solver was created with three fields; the tracer needs four (num_fields = 4)");
+        if (s->diffusion) throw arg_error(fn + ": tracer diffusion is already enabled on this solver; the call is made once");
+        if (s->evaluated)
+            throw arg_error(fn + ": the solver has evaluated a right-hand side already; diffusion is enabled before the first evaluation");
+        if (s->partitionSet) throw arg_error(fn + ": the solver has a partition set; the diffusion passes cover a single domain only");
+        if (!(d->decay >= 0.0) || !std::isfinite(d->decay)) throw arg_error(fn + ": decay must be finite and >= 0");
+        const size_t nodesTotal = static_cast<size_t>(s->Np) * s->K;
+        double kmax = d->kappa;
+        if (d->kappa_field) {
+            kmax = 0.0;
+            for (size_t i = 0; i < nodesTotal; ++i) {
+                const double v = d->kappa_field[i];
+                if (!(v >= 0.0) || !std::isfinite(v)) throw arg_error(fn + ": kappa must be finite and >= 0 at every node");
+                kmax = std::max(kmax, v);
+            }
+        } else if (!(d->kappa >= 0.0) || !std::isfinite(d->kappa)) {
+            throw arg_error(fn + ": kappa must be finite and >= 0");
+        }
+        if (d->source)
+            for (size_t i = 0; i < nodesTotal; ++i)
+                if (!std::isfinite(d->source[i])) throw arg_error(fn + ": the source must be finite at every node");
+        const bdg_dev::DiffusionKernelTable* ktd = bdg_dev::diffusion_kernel_table(s->N);
+        if (!ktd) throw arg_error(fn + ": no diffusion kernels compiled for this order");
+        s->use();
+        bdg_dev::DiffusionParams dp{};
+        dp.kappa = d->kappa;
+        dp.decay = d->decay;
+        dp.kappaField = s->uploadPlane(d->kappa_field, s->difKappa);
+        dp.source = s->uploadPlane(d->source, s->difSource);
+        const size_t pl = s->planeSize();
+        s->difScratch.alloc((s->hasFilter ? 3 : 2) * pl, s->bytes);
+        hipCheck(hipMemsetAsync(s->difScratch.p, 0, s->difScratch.n * sizeof(double), s->stream), "hipMemset");
+        dp.flux = s->difScratch.p;
+        dp.raw = s->hasFilter ? s->difScratch.p + 2 * pl : nullptr;
+        s->difOps.upload(rowOpsImage(s->hostDr.data(), s->hostDs.data(), s->hostLift.data(), s->Np, s->NFN), s->bytes, "diffusion row ops upload");
+        if (s->hasFilter) {
+            s->difFilter.upload(s->hostFilter, s->bytes, "diffusion filter upload");
+            if (s->affine)
+                s->difOpsFiltered.upload(rowOpsImage(s->hostFDr.data(), s->hostFDs.data(), s->hostFLift.data(), s->Np, s->NFN), s->bytes,
+                                         "filtered diffusion row ops upload");
+        }
+        // max(Fscale) over the mesh, from the plane the time-step reduction reads (padding columns are zero)
+        std::vector<double> fs(static_cast<size_t>(s->NFN) * s->ld);
+        hipCheck(hipMemcpyAsync(fs.data(), s->fscaleNodal, fs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream), "D2H copy");
+        hipCheck(hipStreamSynchronize(s->stream), "sync");
+        double fmax = 0.0;
+        for (double v : fs) fmax = std::max(fmax, std::fabs(v));
+        const double n1 = static_cast<double>(s->N + 1);
+        s->difDt = kmax > 0.0 ? bdg_sw2d::kDiffusionDtConstant / (kmax * n1 * n1 * n1 * n1 * fmax * fmax) : std::numeric_limits<double>::infinity();
+        s->ktd = ktd;
+        s->dif = dp;
+        s->diffusion = true;
+    });
+}
+
+int bdg_sw2d_diffusion_dt(const bdg_sw2d* s, double* dt_diff) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2d_diffusion_dt");
+        if (!dt_diff) throw arg_error("bdg_sw2d_diffusion_dt: NULL argument");
+        if (!s->diffusion) throw arg_error("bdg_sw2d_diffusion_dt: tracer diffusion is not enabled");
+        *dt_diff = s->difDt;
+    });
+}
+
 int bdg_sw2d_set_time(bdg_sw2d* s, double t) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_set_time");
@@ -1894,6 +2025,7 @@ int bdg_sw2d_compute_dt(bdg_sw2d* s, double cfl, double* dt, double* eta_max) {
         s->reduceDt(r);
         if (eta_max) *eta_max = r[1];
         if (dt) *dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * r[0]);
+        if (dt && s->diffusion) *dt = std::min(*dt, cfl * s->difDt);
         if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
             throw unstable_error("A numerical instability has occurred!");
     });
@@ -1918,6 +2050,7 @@ int bdg_sw2d_run_adaptive(bdg_sw2d* s, double cfl, double final_time, int max_st
             if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
                 throw unstable_error("A numerical instability has occurred!");
             dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * r[0]);
+            if (s->diffusion) dt = std::min(dt, cfl * s->difDt);
             t += dt;
             ++done;
             *t_inout = t;
@@ -1950,6 +2083,8 @@ int bdg_sw2d_time_lserk4_stages(bdg_sw2d* s, double dt, int num_stages, float* m
 int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireSolver(s, "bdg_sw2d_set_partition");
+        if (s->diffusion)
+            throw arg_error("bdg_sw2d_set_partition: the solver has tracer diffusion, whose passes cover a single domain only");
         if (s->drf.on)
             throw arg_error("bdg_sw2d_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
         if (s->fst.on)

@@ -363,6 +363,15 @@ class NativeDistributedSw2d:
         self.solver.enableVariantB(H, Hx, Hy, mapO=mapO, tracer=tracer, **kwargs)
         return H
 
+    def enable_tracer_diffusion(self, *args, **kwargs):
+        """Not built: the diffusion passes of Sw2dSolver.enableTracerDiffusion read the neighbours' fluxes of the first pass,
+        which a partition would have to exchange between the two; they cover a single domain only."""
+        raise NotImplementedError("tracer diffusion is not available on a partitioned solver (NativeDistributedSw2d): the second "
+                                  "pass needs the neighbours' fluxes of the first, which are not exchanged; run a single domain "
+                                  "with Sw2dSolver.enableTracerDiffusion")
+
+    enableTracerDiffusion = enable_tracer_diffusion
+
     def allreduce_max(self, value):
         out = self._c_double()
         self._check(self._lib.bdg_sw2d_allreduce_max(self.solver._h, float(value), self._byref(out)))

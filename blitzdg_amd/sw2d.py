@@ -164,6 +164,27 @@ class Sw2dSolver(RunRecords):
             tr, scalar = np.zeros(1), True
         check(lib.bdg_sw2d_enable_variant_b4(self._h, byref(d), C.ptr(tr), 1 if scalar else tr.size))
 
+    # ---- tracer diffusion, sources and decay
+    def enableTracerDiffusion(self, kappa, source=None, decay=0.0):
+        """d(hN)/dt gains div(kappa h grad N) + S - k hN with N = hN / h (local DG, central fluxes; zero diffusive flux at walls
+        and at the open boundary). ``kappa``: a scalar or an (Np, K) array, >= 0; ``source``: (Np, K) S in hN per second, or
+        None; ``decay``: k >= 0. On a ``fields=4`` solver -- plain, with ``sources``, or variant B with a tracer (after
+        ``enableVariantB(..., tracer=)``) -- once, before its first evaluation; afterwards computeRHS4 and every stepper
+        include the term, and computeDt / runAdaptive return min(advective dt, CFL * diffusionDt()). A three-field solver
+        raises ValueError; the library refuses the rest (BdgError)."""
+        if self.fields != 4:
+            raise ValueError("tracer diffusion needs a solver with fields=4")
+        field = None if np.ndim(kappa) == 0 else self._field(kappa, "kappa")
+        src = self._field(source, "source") if source is not None else None
+        d = C.Sw2dDiffusionDesc(float(kappa) if field is None else 0.0, C.ptr(field), C.ptr(src), float(decay))
+        check(lib.bdg_sw2d_enable_tracer_diffusion(self._h, byref(d)))
+
+    def diffusionDt(self):
+        """dt_diff = 4 / (max kappa (N+1)^4 max(Fscale)^2) of the enabled tracer diffusion."""
+        v = c_double()
+        check(lib.bdg_sw2d_diffusion_dt(self._h, byref(v)))
+        return v.value
+
     @property
     def time(self):
         t = c_double()

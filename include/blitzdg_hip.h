@@ -357,6 +357,28 @@ int bdg_sw2d_enable_variant_b(bdg_sw2d* s, const bdg_sw2d_vb_desc* desc);
  * the filter applies to all four right-hand sides. Orders 1 to 8, both geometry forms, partitioned solvers included.
  * bdg_sw2d_enable_variant_b keeps refusing four-field solvers. */
 int bdg_sw2d_enable_variant_b4(bdg_sw2d* s, const bdg_sw2d_vb_desc* desc, const double* n_open, int n_open_count);
+/* Diffusion, sources and decay of the passive tracer of a four-field solver (tests/tridiff_ref.py):
+ *   d(hN)/dt = (advection, as before) + div(kappa h grad N) + S - k hN,   N = hN / h,
+ * local DG with central fluxes and no penalty. A face node without a neighbour (vmapP == vmapM: walls and the open boundary
+ * alike) is a boundary node with zero diffusive flux; the tracer crosses the open boundary by advection only. kappa_field: (Np, K)
+ * diffusivity or NULL (then the scalar kappa); source: (Np, K) S, hN per second, or NULL; decay: k >= 0. Once, before the solver's
+ * first evaluation, on a solver created with num_fields = 4: variant A's four-field form, variant D with or without sources, or
+ * variant B with a tracer (after bdg_sw2d_enable_variant_b4). From then on every evaluation's launches are followed on the same
+ * stream by the two passes of sw2d_diffusion_kernel.hpp, which add T to plane 3 of what the evaluation wrote (the right-hand
+ * side, or the LSERK / RK2 / Heun stage update); planes 0-2 and every existing kernel are untouched; a filtered evaluation adds
+ * Filter T. BDG_ERR_ARGUMENT, nothing changed: a NULL descriptor, three fields, kappa < 0 or not finite (scalar or any entry),
+ * decay < 0 or not finite, a source that is not finite, a second call, after the first evaluation, a solver with a partition set
+ * (bdg_sw2d_set_partition on a diffusing solver is refused as well). bdg_sw2d_compute_dt and bdg_sw2d_run_adaptive then return
+ * min(advective dt, cfl * dt_diff), dt_diff = 4 / (max kappa (N+1)^4 max(Fscale)^2) (infinite for kappa = 0);
+ * bdg_sw2d_diffusion_dt returns dt_diff (BDG_ERR_ARGUMENT without diffusion). */
+typedef struct bdg_sw2d_diffusion_desc {
+    double kappa;              /* used when kappa_field is NULL                */
+    const double* kappa_field; /* (Np, K) or NULL                              */
+    const double* source;      /* (Np, K) or NULL                              */
+    double decay;              /* k >= 0                                       */
+} bdg_sw2d_diffusion_desc;
+int bdg_sw2d_enable_tracer_diffusion(bdg_sw2d* s, const bdg_sw2d_diffusion_desc* desc);
+int bdg_sw2d_diffusion_dt(const bdg_sw2d* s, double* dt_diff);
 int bdg_sw2d_set_time(bdg_sw2d* s, double t);
 int bdg_sw2d_get_time(const bdg_sw2d* s, double* t);
 /* The global Lax-Friedrichs speed of the most recent variant-B evaluation. */
