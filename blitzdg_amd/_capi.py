@@ -278,6 +278,8 @@ _SIGNATURES = {
     "bdg_sw2dq_step_ssprk2_exchanged": (c_int, [_P, c_double, c_int, c_int, c_double]),
     "bdg_sw2dq_time_speed": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_sw2dq_enable_variant_b4": (c_int, [_P, POINTER(Sw2dVbDesc), _P, c_int]),
+    "bdg_sw2dq_enable_tracer_diffusion": (c_int, [_P, POINTER(Sw2dDiffusionDesc)]),
+    "bdg_sw2dq_diffusion_dt": (c_int, [_P, POINTER(c_double)]),
     "bdg_quadnodes_bed_slopes": (c_int, [_P, _P, _P, _P]),
     "bdg_quadnodes_sponge_coeff": (c_int, [_P, _P, c_int, c_double, c_double, _P]),
     "bdg_quadnodes_quadrature_weights": (c_int, [_P, _P]),

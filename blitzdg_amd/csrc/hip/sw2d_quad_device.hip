@@ -10,6 +10,11 @@
 // sw2d_quadb_speed_kernel, then sw2d_quadb_stage_kernel (sw2d_quadb_kernel.hpp), which reads the speed from device memory.
 // After bdg_sw2dq_enable_variant_b4 a four-field solver does the same with the tracer as a fourth equation
 // (sw2d_quadb4_stage_kernel, sw2d_quadb4_kernel.hpp; the speed pass is the three-field one).
+// After bdg_sw2dq_enable_tracer_diffusion every evaluation of a four-field solver is followed on the same stream by the two passes
+// of sw2d_quad_diffusion_kernel.hpp (per-order objects sw2d_quad_diffusion_order.hip), which add the tracer's diffusion, source
+// and decay, evaluated from the stage's input state, to plane 3 of what the stage wrote. That state is never one of the stage's
+// output buffers: rk2Step evaluates q into q1 and q1 into q, heunStep likewise, lserkStage q into q1 and res (then swaps), and
+// computeRhs io into ioOut.
 // After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2dq_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_quad_drifter_kernel.hpp).
 #include "device_buffer.hpp"
@@ -17,6 +22,7 @@
 #include "run_records.hpp"
 #include "sw2d_quad4_kernel.hpp"
 #include "sw2d_dispatch.hpp"
+#include "sw2d_quad_diffusion_launch.hpp"
 #include "sw2d_quad_drifter_kernel.hpp"
 #include "sw2d_quad_output_kernel.hpp"
 #include "sw2d_quadb4_kernel.hpp"
@@ -29,6 +35,7 @@
 #include <cstdlib>
 #include <limits>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -78,6 +85,38 @@ hipError_t sw2d_quadb_speed(int order, bool general, const QuadBParams& p, doubl
     else
         hipLaunchKernelGGL((sw2d_quadb_speed_kernel<false>), grid, block, 0, stream, p, order, bits);
     return hipGetLastError();
+}
+
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order1();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order2();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order3();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order4();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order5();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order6();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order7();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order8();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order9();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order10();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order11();
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table_order12();
+static_assert(BDG_SW2DQ_MAX_ORDER == 12, "one table per order of the Makefile's QUAD_ORDERS");
+
+const QuadDiffusionKernelTable* quad_diffusion_kernel_table(int order) {
+    switch (order) {
+    case 1: return quad_diffusion_kernel_table_order1();
+    case 2: return quad_diffusion_kernel_table_order2();
+    case 3: return quad_diffusion_kernel_table_order3();
+    case 4: return quad_diffusion_kernel_table_order4();
+    case 5: return quad_diffusion_kernel_table_order5();
+    case 6: return quad_diffusion_kernel_table_order6();
+    case 7: return quad_diffusion_kernel_table_order7();
+    case 8: return quad_diffusion_kernel_table_order8();
+    case 9: return quad_diffusion_kernel_table_order9();
+    case 10: return quad_diffusion_kernel_table_order10();
+    case 11: return quad_diffusion_kernel_table_order11();
+    case 12: return quad_diffusion_kernel_table_order12();
+    default: return nullptr;
+    }
 }
 
 int sw2d_quad_tile(int order) {
@@ -176,6 +215,17 @@ struct bdg_sw2dq {
     int numOpenN = 0;
     double nOpenC = 0.0;
     double vbF = 0.0, vbCD = 0.0, tideAmp = 0.0, tidePeriod = 1.0, tideRamp = 0.0;
+    // tracer diffusion, sources and decay (bdg_sw2dq_enable_tracer_diffusion): the two passes of sw2d_quad_diffusion_kernel.hpp
+    // behind the stage launch of every evaluation. difFlux: the planes fx, fy
+    bool diffusion = false;
+    const QuadDiffusionKernelTable* ktd = nullptr;
+    QuadDiffusionParams dif{};
+    DevBuf<double> difKappa, difSource, difFlux;
+    double fscaleMax = 0.0;   // max|Fscale| of the mesh (createQuad)
+    double difDt = 0.0;       // kDiffusionDtConstant / (max kappa (N+1)^4 max(Fscale)^2)
+    // every eigenvalue z = dt_diff lambda of the operator stays inside the RK2 stability region with this constant: the smallest
+    // bound measured is 4.02 (N = 1 on squares; DESIGN.md 3.8, tests/test_quaddiff_reference.py)
+    static constexpr double kDiffusionDtConstant = 4.0;
     double timeNow = 0.0;     // model time of the resident state (tide phase); the steppers advance it
     double spongeC = 0.0;     // scalar sponge coefficient of the Heun step in flight
     long long ld = 0;
@@ -249,18 +299,25 @@ struct bdg_sw2dq {
         if (variantB && fields == 4) {
             const QuadB4Params p4{paramsB(p), openKey.p, openN.p, numOpenN, nOpenC};
             hipCheck(sw2d_quadb4_stage(N, mode, filter, general, p4, on), "sw2d_quadb4_stage_kernel launch");
-            return;
-        }
-        if (variantB) {
+        } else if (variantB) {
             hipCheck(sw2d_quadb_stage(N, mode, filter, general, paramsB(p), on), "sw2d_quadb_stage_kernel launch");
-            return;
-        }
-        if (fields == 4) {
+        } else if (fields == 4) {
             const Quad4Params p4{p, zx.p, zy.p, fcor.p, fconst, CD};
             hipCheck(sw2d_quad4_stage(N, mode, filter, general, hasSources, p4, on), "sw2d_quad4_stage_kernel launch");
-            return;
+        } else {
+            hipCheck(sw2d_quad_stage(N, mode, filter, general, p, on), "sw2d_quad_stage_kernel launch");
         }
-        hipCheck(sw2d_quad_stage(N, mode, filter, general, p, on), "sw2d_quad_stage_kernel launch");
+        if (diffusion) launchDiffusion(mode, filter, p, on);
+    }
+    // The tracer's diffusion, source and decay of the evaluation whose stage launch was just issued on `on`: T of p.qin -- which
+    // that launch read and did not write -- added to plane 3 of what it wrote. p.gidx is the solver's first gather index (wall
+    // flags only), for variant B too: a boundary node is one that gathers itself.
+    void launchDiffusion(int mode, bool filter, const QuadParams& p, hipStream_t on) {
+        // what the scheme rests on
+        if (mode == QMODE_RHS ? p.qin == p.rhs : (p.qin == p.qout || (mode == QMODE_LSERK && p.qin == p.res)))
+            throw std::logic_error("tracer diffusion: the stage's input state is one of its output buffers");
+        hipCheck(ktd->gradient(general, p, dif, on), "sw2d_quad_tracer_gradient_kernel launch");
+        hipCheck(ktd->divergence(mode, filter, general, p, dif, on), "sw2d_quad_tracer_divergence_kernel launch");
     }
     // ---- how one evaluation (reads p.qin, writes its outputs) is carried out
     enum class Eval {
@@ -562,6 +619,7 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
 
     std::unique_ptr<bdg_sw2dq> s(new bdg_sw2dq());
     s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->g = d.g; s->device = d.device; s->fields = fields;
+    s->fscaleMax = maxAbs(d.Fscale, static_cast<size_t>(NFN) * K);
     s->ld = (static_cast<long long>(K) + 63) / 64 * 64;
     const long long ld = s->ld;
 
@@ -933,6 +991,73 @@ int bdg_sw2dq_enable_variant_b4(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* d, const 
     });
 }
 
+int bdg_sw2dq_enable_tracer_diffusion(bdg_sw2dq* s, const bdg_sw2d_diffusion_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2dq_enable_tracer_diffusion";
+        requireSolver(s, fn.c_str());
+        if (!d) throw arg_error(fn + ": NULL descriptor");
+        if (s->fields != 4)
+            throw arg_error(fn + ": the solver was created with three fields; the tracer needs four (bdg_sw2dq_create_fields)");
+        if (s->diffusion) throw arg_error(fn + ": tracer diffusion is already enabled on this solver; the call is made once");
+        if (s->evaluated)
+            throw arg_error(fn + ": the solver has evaluated a right-hand side already; diffusion is enabled before the first evaluation");
+        if (s->part.numOwned > 0 || s->halo.comm)
+            throw arg_error(fn + ": the solver has a partition set; the diffusion passes cover a single domain only");
+        if (!(d->decay >= 0.0) || !std::isfinite(d->decay)) throw arg_error(fn + ": decay must be finite and >= 0");
+        const size_t nodesTotal = static_cast<size_t>(s->Np) * s->K;
+        double kmax = d->kappa;
+        if (d->kappa_field) {
+            kmax = 0.0;
+            for (size_t i = 0; i < nodesTotal; ++i) {
+                const double v = d->kappa_field[i];
+                if (!(v >= 0.0) || !std::isfinite(v)) throw arg_error(fn + ": kappa must be finite and >= 0 at every node");
+                kmax = std::max(kmax, v);
+            }
+        } else if (!(d->kappa >= 0.0) || !std::isfinite(d->kappa)) {
+            throw arg_error(fn + ": kappa must be finite and >= 0");
+        }
+        if (d->source)
+            for (size_t i = 0; i < nodesTotal; ++i)
+                if (!(d->source[i] >= 0.0) || !std::isfinite(d->source[i]))
+                    throw arg_error(fn + ": the source must be finite and >= 0 at every node");
+        const QuadDiffusionKernelTable* ktd = quad_diffusion_kernel_table(s->N);
+        if (!ktd) throw arg_error(fn + ": no diffusion kernels compiled for this order");
+        s->use();
+        const long long plane = s->plane();
+        QuadDiffusionParams dp{};
+        dp.kappa = d->kappa;
+        dp.decay = d->decay;
+        if (d->kappa_field) {
+            s->difKappa.alloc(plane, s->bytes, s->stream);
+            s->upload(s->difKappa.p, d->kappa_field, s->Np);
+        }
+        if (d->source) {
+            s->difSource.alloc(plane, s->bytes, s->stream);
+            s->upload(s->difSource.p, d->source, s->Np);
+        }
+        s->difFlux.alloc(2 * plane, s->bytes, s->stream);
+        hipCheck(hipStreamSynchronize(s->stream), "hipStreamSynchronize"); // the caller's arrays are free again
+        dp.kappaField = s->difKappa.p;
+        dp.source = s->difSource.p;
+        dp.flux = s->difFlux.p;
+        const double n1 = static_cast<double>(s->N + 1);
+        s->difDt = kmax > 0.0 ? bdg_sw2dq::kDiffusionDtConstant / (kmax * n1 * n1 * n1 * n1 * s->fscaleMax * s->fscaleMax)
+                              : std::numeric_limits<double>::infinity();
+        s->ktd = ktd;
+        s->dif = dp;
+        s->diffusion = true;
+    });
+}
+
+int bdg_sw2dq_diffusion_dt(const bdg_sw2dq* s, double* dt_diff) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2dq_diffusion_dt");
+        if (!dt_diff) throw arg_error("bdg_sw2dq_diffusion_dt: NULL argument");
+        if (!s->diffusion) throw arg_error("bdg_sw2dq_diffusion_dt: tracer diffusion is not enabled");
+        *dt_diff = s->difDt;
+    });
+}
+
 int bdg_sw2dq_set_time(bdg_sw2dq* s, double t) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_time");
@@ -1013,6 +1138,7 @@ int bdg_sw2dq_compute_dt(bdg_sw2dq* s, double cfl, double* dt, double* speed) {
         }
         if (speed) *speed = m;
         if (dt) *dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * m);
+        if (dt && s->diffusion) *dt = std::min(*dt, cfl * s->difDt);
         if (std::isnan(m) || std::isinf(m)) throw unstable_error("A numerical instability has occurred!");
     });
 }
@@ -1079,6 +1205,8 @@ int bdg_sw2dq_synchronize(bdg_sw2dq* s) {
 int bdg_sw2dq_set_partition(bdg_sw2dq* s, int num_interior, int num_owned, const int* send_elements, int num_send) {
     return guard([&] {
         requireSolver(s, "bdg_sw2dq_set_partition");
+        if (s->diffusion)
+            throw arg_error("bdg_sw2dq_set_partition: the solver has tracer diffusion, whose passes cover a single domain only");
         if (s->drf.on)
             throw arg_error("bdg_sw2dq_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
         if (s->fst.on)

@@ -153,6 +153,27 @@ class Sw2dQuadSolver(RunRecords):
             check(lib.bdg_sw2dq_enable_variant_b4(self._h, byref(d), C.ptr(tr), 1 if scalar else tr.size))
         self.variantB = True
 
+    # ---- tracer diffusion, sources and decay
+    def enableTracerDiffusion(self, kappa, source=None, decay=0.0):
+        """d(hN)/dt gains div(kappa h grad N) + S - k hN with N = hN / h (local DG, central fluxes; zero diffusive flux at walls
+        and at the open boundary). ``kappa``: a scalar or an (Np, K) array, >= 0; ``source``: (Np, K) S in hN per second, >= 0, or
+        None; ``decay``: k >= 0. On a ``fields=4`` solver -- plain, with ``sources``, or variant B with a tracer (after
+        ``enableVariantB(..., tracer=)``) -- once, before its first evaluation; afterwards computeRHS4 and every stepper
+        include the term, and computeDt returns min(advective dt, CFL * diffusionDt()). A three-field solver raises ValueError;
+        the library refuses the rest (BdgError)."""
+        if self.fields != 4:
+            raise ValueError("tracer diffusion needs a solver with fields=4")
+        field = None if np.ndim(kappa) == 0 else self._field(kappa, "kappa")
+        src = self._field(source, "source") if source is not None else None
+        d = C.Sw2dDiffusionDesc(float(kappa) if field is None else 0.0, C.ptr(field), C.ptr(src), float(decay))
+        check(lib.bdg_sw2dq_enable_tracer_diffusion(self._h, byref(d)))
+
+    def diffusionDt(self):
+        """dt_diff = 4 / (max kappa (N+1)^4 max|Fscale|^2) of the enabled tracer diffusion."""
+        v = c_double()
+        check(lib.bdg_sw2dq_diffusion_dt(self._h, byref(v)))
+        return v.value
+
     def setTime(self, t):
         """Model time of the resident state (the tide phase of variant B); the steppers advance it."""
         check(lib.bdg_sw2dq_set_time(self._h, float(t)))
@@ -388,6 +409,15 @@ class NativeDistributedSw2dQuad:
         solver, self.solver = getattr(self, "solver", None), None
         if solver is not None:
             solver.close()
+
+    def enable_tracer_diffusion(self, *args, **kwargs):
+        """Not built: the diffusion passes of Sw2dQuadSolver.enableTracerDiffusion read the neighbours' fluxes of the first pass,
+        which a partition would have to exchange between the two; they cover a single domain only."""
+        raise NotImplementedError("tracer diffusion is not available on a partitioned solver (NativeDistributedSw2dQuad): the "
+                                  "second pass needs the neighbours' fluxes of the first, which are not exchanged; run a single "
+                                  "domain with Sw2dQuadSolver.enableTracerDiffusion")
+
+    enableTracerDiffusion = enable_tracer_diffusion
 
     def set_initial_state(self, fn):
         """fn(x, y) -> (h, hu, hv) (four fields: (h, hu, hv, hN)) on the rank-local nodes (owned and ghost elements: the

@@ -551,6 +551,25 @@ int bdg_sw2dq_time_speed(bdg_sw2dq* s, int count, float* ms);
  * evaluate it, the speed pass in front as on three fields; set_time, get_time, global_speed, time_speed, the monitor (int hN,
  * gauge N, the descriptor's H by default) and output_fields work as there. bdg_sw2dq_enable_variant_b still refuses four fields. */
 int bdg_sw2dq_enable_variant_b4(bdg_sw2dq* s, const bdg_sw2dq_vb_desc* desc, const double* n_open, int n_open_count);
+/* Diffusion, sources and decay of the passive tracer of a four-field quadrilateral solver: bdg_sw2d_enable_tracer_diffusion's
+ * term and descriptor (tests/tridiff_ref.py, tests/quaddiff_ref.py),
+ *   d(hN)/dt = (advection, as before) + div(kappa h grad N) + S - k hN,   N = hN / h,
+ * local DG with central fluxes and no penalty; a face node with vmapP == vmapM (walls and the open boundary alike) carries no
+ * diffusive flux. Once, before the solver's first evaluation, on a solver created with four fields: plain, with
+ * bdg_sw2dq_set_sources, or variant B with a tracer (after bdg_sw2dq_enable_variant_b4). Orders 1 to 12, both geometry forms.
+ * From then on the stage launch of every evaluation is followed on the same stream by the two passes of
+ * sw2d_quad_diffusion_kernel.hpp, which evaluate T from the stage's input state and add it to plane 3 of what the stage wrote
+ * (the right-hand side, or the RK2 / LSERK4 / Heun stage update); a filtered evaluation adds Filter T. The input state of a
+ * stage is never one of its output buffers (bdg_sw2dq_step_rk2 and _step_ssprk2 evaluate the state into the intermediate one
+ * and back, bdg_sw2dq_lserk4_stages into the other of two buffers), which is what the passes rest on. Planes 0-2, the global
+ * speed and every existing kernel are untouched. BDG_ERR_ARGUMENT, nothing changed: a NULL descriptor, three fields, kappa,
+ * decay or a source entry negative or not finite, a second call, after the first evaluation, a solver with a partition set
+ * (bdg_sw2dq_set_partition on a diffusing solver is refused as well). bdg_sw2dq_compute_dt then returns
+ * min(advective dt, cfl * dt_diff), dt_diff = 4 / (max kappa (N+1)^4 max|Fscale|^2) (infinite for kappa = 0);
+ * bdg_sw2dq_diffusion_dt returns dt_diff (BDG_ERR_ARGUMENT without diffusion). bdg_sw2dq_device_bytes counts the two flux planes
+ * and the planes of kappa and S. */
+int bdg_sw2dq_enable_tracer_diffusion(bdg_sw2dq* s, const bdg_sw2d_diffusion_desc* desc);
+int bdg_sw2dq_diffusion_dt(const bdg_sw2dq* s, double* dt_diff);
 /* Host helpers of the tidal set-up, argument lists as the bdg_trinodes_* ones: Hx, Hy = Filter (rx Dr H + sx Ds H,
  * ry Dr H + sy Ds H) (main.cpp:128-133; bdg_quadnodes_build_filter first), and buildSpongeCoeff (main.cpp:517-553). */
 int bdg_quadnodes_bed_slopes(const bdg_quadnodes* nodes, const double* H, double* Hx, double* Hy);

@@ -1,0 +1,42 @@
+"""Register use of the tracer's diffusion passes on quadrilaterals (csrc/hip/sw2d_quad_diffusion_kernel.hpp), from the compiler's
+own report: no instance may use scratch. sw2d_quad_diffusion_order.hip is cross-compiled for gfx950, device side only, with
+-Rpass-analysis=kernel-resource-usage at every order 1 .. 12; no GPU; only the compiler's remarks are read. The numbers
+themselves (VGPRs, LDS, waves per SIMD) are recorded in DESIGN.md 3.8; what is held here is the instance set -- the gradient
+pass on both geometry forms; the divergence pass for RHS, COMBINE and HEUN plain and filtered and LSERK plain, each on both
+geometry forms -- and ScratchSize = 0, VGPRs <= 256 and Occupancy >= 1 for each of them."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIP = os.path.join(ROOT, "blitzdg_amd", "csrc", "hip")
+
+
+def resource_usage(order, out):
+    cmd = ["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", f"-DBDG_ORDER={order}",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "blitzdg_amd", "csrc", "host"), "-I" + HIP,
+           "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(HIP, "sw2d_quad_diffusion_order.hip"),
+           "-o", str(out)]
+    run = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-3000:]
+    kernels = {}
+    for block in run.stderr.split("Function Name: ")[1:]:
+        name = block.split()[0]
+        kernels[name] = {key: int(value) for key, value in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", block)}
+    return kernels
+
+
+@pytest.mark.parametrize("order", range(1, 13))
+def test_no_instance_of_the_quad_diffusion_passes_uses_scratch(order, tmp_path):
+    kernels = resource_usage(order, tmp_path / "quad_diffusion.o")
+    forms = {"gradient": 0, "divergence": 0}
+    for name, use in kernels.items():
+        assert "sw2d_quad_tracer_" in name, name
+        forms["gradient" if "tracer_gradient" in name else "divergence"] += 1
+        assert use["ScratchSize"] == 0, (name, use)
+        assert use["VGPRs"] <= 256 and use["Occupancy"] >= 1, (name, use)
+    assert forms == {"gradient": 2, "divergence": 14}, sorted(kernels)
+    print(f"N{order}: " + "; ".join(f"{n[:70]} VGPRs {u['VGPRs']} AGPRs {u.get('AGPRs', 0)} LDS {u.get('LDS Size', 0)} occ {u['Occupancy']}"
+                                  for n, u in sorted(kernels.items())))
