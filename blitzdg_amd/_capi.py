@@ -84,6 +84,20 @@ class Sw2dDiffusionDesc(Structure):
     _fields_ = [("kappa", c_double), ("kappa_field", c_void_p), ("source", c_void_p), ("decay", c_double)]
 
 
+class Poisson2dDesc(Structure):
+    _fields_ = [("order", c_int), ("num_elements", c_int),
+                ("Dr", c_void_p), ("Ds", c_void_p), ("Lift", c_void_p), ("Vinv", c_void_p),
+                ("rx", c_void_p), ("sx", c_void_p), ("ry", c_void_p), ("sy", c_void_p), ("J", c_void_p),
+                ("nx", c_void_p), ("ny", c_void_p), ("Fscale", c_void_p),
+                ("vmapM", c_void_p), ("vmapP", c_void_p), ("mapD", c_void_p), ("num_dirichlet", c_int),
+                ("kappa", c_double), ("kappa_elements", c_void_p), ("sigma", c_double), ("tau_scale", c_double),
+                ("device", c_int), ("flags", c_int)]
+
+
+class Poisson2dResult(Structure):
+    _fields_ = [("iterations", c_int), ("relative_residual", c_double), ("converged", c_int), ("projected", c_int)]
+
+
 class Sw2dqMonitorDesc(Structure):
     _fields_ = [("weights", c_void_p), ("H", c_void_p), ("num_gauges", c_int), ("gauge_element", c_void_p),
                 ("gauge_r", c_void_p), ("gauge_s", c_void_p), ("stride", c_int), ("capacity", c_int)]
@@ -410,6 +424,17 @@ _SIGNATURES = {
     "bdg_sw2d_curved_drifters_count": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "bdg_sw2d_curved_drifters_read": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
     "bdg_sw2d_curved_drifters_reset": (c_int, [_P]),
+    "bdg_poisson2d_create": (c_int, [POINTER(Poisson2dDesc), POINTER(_P)]),
+    "bdg_poisson2d_create_from_nodes": (c_int, [_P, _P, c_int, c_double, _P, c_double, c_double, c_int, c_int, POINTER(_P)]),
+    "bdg_poisson2d_destroy": (None, [_P]),
+    "bdg_poisson2d_set_shift": (c_int, [_P, c_double]),
+    "bdg_poisson2d_set_boundary_data": (c_int, [_P, _P, _P]),
+    "bdg_poisson2d_apply": (c_int, [_P, _P, _P, c_int]),
+    "bdg_poisson2d_mass_dot": (c_int, [_P, _P, _P, POINTER(c_double)]),
+    "bdg_poisson2d_solve": (c_int, [_P, _P, _P, c_double, c_int, c_int, POINTER(Poisson2dResult)]),
+    "bdg_poisson2d_time_apply": (c_int, [_P, c_int, POINTER(c_float)]),
+    "bdg_poisson2d_time_iterations": (c_int, [_P, c_int, POINTER(c_float)]),
+    "bdg_poisson2d_device_bytes": (c_size_t, [_P]),
 }
 
 #: every symbol include/blitzdg_hip.h declares (checked by tests/test_capi_symbols.py)

@@ -1182,6 +1182,65 @@ int bdg_sw2d_curved_drifters_count(const bdg_sw2d_curved* s, int* num_records, i
 int bdg_sw2d_curved_drifters_read(bdg_sw2d_curved* s, int first, int num, double* t, double* x, double* y, int* status);
 int bdg_sw2d_curved_drifters_reset(bdg_sw2d_curved* s);
 
+/* ---------------------------------------------------------------- elliptic solver on straight-sided triangles
+ * A u = sigma u - div(kappa grad u) = f in Hesthaven and Warburton's stabilised central flux form (DESIGN.md 3.12 states it; the
+ * sign is opposite to an operator that returns the Laplacian), applied by two HIP passes, and conjugate gradients in the mass
+ * inner product <u, v> = sum_k J_k u_k^T (V V^T)^-1 v_k with alpha, beta and the residual norm resident in device memory.
+ * A face node is INTERIOR (vmapP != vmapM), DIRICHLET (a boundary node listed in mapD) or NEUMANN (any other boundary node).
+ * Tables as bdg_sw2d_desc, plus Vinv (Np, Np) and J (Np, K); vmapM is required (it tells boundary nodes from interior ones).
+ * kappa_elements: one value per element or NULL (then `kappa` everywhere); tau = tau_scale Np max(Fscale) / 2 max(kappa)
+ * (tau_scale 0 is read as 1). flags: BDG_SW2D_REORDER / BDG_SW2D_KEEP_ORDER as for bdg_sw2d_create.
+ * BDG_ERR_ARGUMENT, before a GPU is touched: a NULL argument or table, an order outside 1..8, BDG_SW2D_NODAL_GEOMETRY or tables
+ * that are not those of straight-sided elements, kappa <= 0 or not finite (scalar or any entry), sigma < 0, tau_scale < 0, a
+ * mapD entry that is not a boundary face node. All vectors are host (Np, K) row-major arrays in the caller's numbering. */
+typedef struct bdg_poisson2d bdg_poisson2d;
+typedef struct bdg_poisson2d_desc {
+    int order;
+    int num_elements;
+    const double* Dr; const double* Ds; const double* Lift; const double* Vinv;
+    const double* rx; const double* sx; const double* ry; const double* sy; const double* J; /* (Np, K) */
+    const double* nx; const double* ny; const double* Fscale;                                /* (3*Nfp, K) */
+    const int* vmapM; const int* vmapP;
+    const int* mapD;    /* flat face-node indices (3 Nfp k + j) of the Dirichlet nodes */
+    int num_dirichlet;
+    double kappa;
+    const double* kappa_elements;
+    double sigma;
+    double tau_scale;
+    int device;
+    int flags;
+} bdg_poisson2d_desc;
+typedef struct bdg_poisson2d_result {
+    int iterations;
+    double relative_residual; /* |r| / |b| in the mass norm, r the recursive residual, b = f - A(0; g, qn) */
+    int converged;
+    int projected;            /* 1: sigma = 0 and no Dirichlet node; means of b, r and the solution were removed */
+} bdg_poisson2d_result;
+int bdg_poisson2d_create(const bdg_poisson2d_desc* desc, bdg_poisson2d** out);
+/* Every table from a nodes provisioner; mapD NULL with num_dirichlet < 0: BCmap[Wall] + BCmap[Dirichlet]. */
+int bdg_poisson2d_create_from_nodes(const bdg_trinodes* nodes, const int* mapD, int num_dirichlet, double kappa,
+                                    const double* kappa_elements, double sigma, double tau_scale, int device, int flags,
+                                    bdg_poisson2d** out);
+void bdg_poisson2d_destroy(bdg_poisson2d* s);
+int bdg_poisson2d_set_shift(bdg_poisson2d* s, double sigma);
+/* g, qn: (3 Nfp, K) Dirichlet values and outward normal fluxes kappa du/dn (only the entries at nodes of their kind are read);
+ * either may be NULL (zero); both NULL clears the data. */
+int bdg_poisson2d_set_boundary_data(bdg_poisson2d* s, const double* g, const double* qn);
+/* out = A u, with_data != 0: A(u; g, qn). */
+int bdg_poisson2d_apply(bdg_poisson2d* s, const double* u, double* out, int with_data);
+int bdg_poisson2d_mass_dot(bdg_poisson2d* s, const double* u, const double* v, double* value);
+/* Solves A(x; g, qn) = f from x_inout: the data enter b = f - A(0; g, qn) and r0 = b - A x0 once, the iteration runs with the
+ * homogeneous operator; the host reads the residual norm every check_every iterations (and at max_iterations), so the
+ * iteration count is a multiple of check_every unless max_iterations ends it. b = 0 returns x = 0 in zero iterations.
+ * max_iterations <= 0: Np K. BDG_ERR_ARGUMENT for rel_tol <= 0 or check_every < 1; BDG_ERR_UNSTABLE for a residual norm that is
+ * not finite. */
+int bdg_poisson2d_solve(bdg_poisson2d* s, const double* f, double* x_inout, double rel_tol, int max_iterations, int check_every,
+                        bdg_poisson2d_result* result);
+/* Device milliseconds per operator application / per iteration of the loop (no host reads), averaged over count. */
+int bdg_poisson2d_time_apply(bdg_poisson2d* s, int count, float* ms);
+int bdg_poisson2d_time_iterations(bdg_poisson2d* s, int count, float* ms);
+size_t bdg_poisson2d_device_bytes(const bdg_poisson2d* s);
+
 #ifdef __cplusplus
 }
 #endif
