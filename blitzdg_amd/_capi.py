@@ -435,6 +435,8 @@ _SIGNATURES = {
     "bdg_poisson2d_time_apply": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_poisson2d_time_iterations": (c_int, [_P, c_int, POINTER(c_float)]),
     "bdg_poisson2d_device_bytes": (c_size_t, [_P]),
+    "bdg_poisson2d_create_quad": (c_int, [POINTER(Poisson2dDesc), POINTER(_P)]),
+    "bdg_poisson2d_create_from_quadnodes": (c_int, [_P, _P, c_int, c_double, _P, c_double, c_double, c_int, c_int, POINTER(_P)]),
 }
 
 #: every symbol include/blitzdg_hip.h declares (checked by tests/test_capi_symbols.py)

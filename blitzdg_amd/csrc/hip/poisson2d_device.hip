@@ -14,11 +14,18 @@
 //   gradient (p = r + beta p fused in)  ->  divergence  ->  mass product w = J M A p with the partials of p . w
 //   ->  finish: alpha  ->  x += alpha p, r -= alpha A p, s -= alpha w with the partials of r . s  ->  finish: beta, <r, r>
 // and the host reads <r, r> every check_every iterations.
+//
+// The same handle serves quadrilaterals in parallelogram form (bdg_poisson2d_create_quad): createQuadSolver fills
+// it with the launch table of poisson2d_quad_order.hip (a PoissonKernelTable as well), 16 numbers of geometry per element, (4 Nfp,
+// ld) index, kind and data planes, the tensor ops image and the 1-D mass matrix; the mass product then writes one partial per
+// tile of QuadElem<N>::E elements (tileElems). The loop, its vector kernels, the finishers and the projection are shared and
+// launch exactly what they launched for triangles.
 #include "../host/capi_internal.hpp"
 #include "../host/element_order.hpp"
 #include "../host/parallel_for.hpp"
 #include "device_buffer.hpp"
 #include "poisson2d_launch.hpp"
+#include "poisson2d_quad_launch.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -50,6 +57,33 @@ const PoissonKernelTable* poisson_kernel_table(int order) {
     default: return nullptr;
     }
 }
+
+#define BDG_PQ_DECL(n) \
+    const PoissonKernelTable* poisson_quad_kernel_table_order##n(); \
+    int poisson_quad_tile_elements_order##n();
+BDG_PQ_DECL(1) BDG_PQ_DECL(2) BDG_PQ_DECL(3) BDG_PQ_DECL(4) BDG_PQ_DECL(5) BDG_PQ_DECL(6)
+BDG_PQ_DECL(7) BDG_PQ_DECL(8) BDG_PQ_DECL(9) BDG_PQ_DECL(10) BDG_PQ_DECL(11) BDG_PQ_DECL(12)
+#undef BDG_PQ_DECL
+
+#define BDG_PQ_CASES(fn) \
+    case 1: return fn##1(); case 2: return fn##2(); case 3: return fn##3(); case 4: return fn##4(); \
+    case 5: return fn##5(); case 6: return fn##6(); case 7: return fn##7(); case 8: return fn##8(); \
+    case 9: return fn##9(); case 10: return fn##10(); case 11: return fn##11(); case 12: return fn##12();
+
+const PoissonKernelTable* poisson_quad_kernel_table(int order) {
+    switch (order) {
+    BDG_PQ_CASES(poisson_quad_kernel_table_order)
+    default: return nullptr;
+    }
+}
+
+int poisson_quad_tile_elements(int order) {
+    switch (order) {
+    BDG_PQ_CASES(poisson_quad_tile_elements_order)
+    default: return 0;
+    }
+}
+#undef BDG_PQ_CASES
 
 // (rows, K) caller-order image <-> padded, optionally renumbered device planes. perm[k_caller] = device slot (NULL = identity).
 template <typename T>
@@ -95,6 +129,7 @@ constexpr int kItems = 4;     // entries per thread of the reducing ones
 struct bdg_poisson2d {
     const bdg_dev::PoissonKernelTable* kt = nullptr;
     int N = 0, Np = 0, Nfp = 0, NFN = 0, K = 0, device = 0;
+    int tileElems = 64;                 // elements per partial of the mass product: a wave of triangles, a tile of quadrilaterals
     long long ld = 0;
     double sigma = 0.0, tau = 0.0, area = 0.0;
     bool hasDirichlet = false, hasData = false;
@@ -113,7 +148,7 @@ struct bdg_poisson2d {
     size_t planeSize() const { return static_cast<size_t>(Np) * static_cast<size_t>(ld); }
     long long planeEntries() const { return static_cast<long long>(Np) * ld; }
     bool singular() const { return sigma == 0.0 && !hasDirichlet; }
-    int tiles() const { return (K + 63) / 64; }
+    int tiles() const { return (K + tileElems - 1) / tileElems; }
     int flatBlocks() const { return static_cast<int>((planeEntries() + kBlock - 1) / kBlock); }
     int reduceBlocks() const { return static_cast<int>((planeEntries() + kBlock * kItems - 1) / (kBlock * kItems)); }
 
@@ -424,6 +459,274 @@ bdg_poisson2d* createSolver(const bdg_poisson2d_desc& d) {
     return s.release();
 }
 
+// ---- the quadrilateral family: the same handle, filled for poisson2d_quad_kernel.hpp
+
+// D1 | l0 | lN from Dr = D1 (x) I, Ds = I (x) D1 and the face-wise lift, each held to 1e-13 max|entry| as sw2d_quad_device.hip does.
+std::vector<double> quadTensorOps(const std::string& fn, int N, const double* Dr, const double* Ds, const double* Lift) {
+    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
+    std::vector<double> ops(static_cast<size_t>(Nq) * Nq + 2 * Nq);
+    double* D1 = ops.data();
+    double* l0 = D1 + Nq * Nq;
+    double* lN = l0 + Nq;
+    for (int j = 0; j < Nq; ++j)
+        for (int m = 0; m < Nq; ++m) D1[j * Nq + m] = Dr[static_cast<size_t>(Nq * j) * Np + Nq * m];
+    for (int i = 0; i < Nq; ++i) l0[i] = Lift[static_cast<size_t>(i) * NFN];
+    for (int j = 0; j < Nq; ++j) lN[j] = Lift[static_cast<size_t>(Nq * j) * NFN + Nq];
+    double maxD = 0.0, maxL = 0.0, errD = 0.0, errL = 0.0;
+    for (size_t i = 0; i < static_cast<size_t>(Np) * Np; ++i) maxD = std::max({maxD, std::fabs(Dr[i]), std::fabs(Ds[i])});
+    for (size_t i = 0; i < static_cast<size_t>(Np) * NFN; ++i) maxL = std::max(maxL, std::fabs(Lift[i]));
+    for (int j = 0; j < Nq; ++j)
+        for (int i = 0; i < Nq; ++i) {
+            const size_t row = static_cast<size_t>(Nq * j + i);
+            for (int jj = 0; jj < Nq; ++jj)
+                for (int ii = 0; ii < Nq; ++ii) {
+                    const int col = Nq * jj + ii;
+                    errD = std::max(errD, std::fabs(Dr[row * Np + col] - (ii == i ? D1[j * Nq + jj] : 0.0)));
+                    errD = std::max(errD, std::fabs(Ds[row * Np + col] - (jj == j ? D1[i * Nq + ii] : 0.0)));
+                }
+            for (int q = 0; q < Nq; ++q) {
+                errL = std::max(errL, std::fabs(Lift[row * NFN + q] - (q == j ? l0[i] : 0.0)));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + Nq + q] - (q == i ? lN[j] : 0.0)));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + 2 * Nq + q] - (q == j ? lN[i] : 0.0)));
+                errL = std::max(errL, std::fabs(Lift[row * NFN + 3 * Nq + q] - (q == i ? l0[j] : 0.0)));
+            }
+        }
+    if (!(maxD > 0.0) || !(maxL > 0.0) || !(errD <= 1e-13 * maxD) || !(errL <= 1e-13 * maxL))
+        throw arg_error(fn + ": Dr, Ds and Lift are not the tensor operators of the Gauss-Lobatto quadrilateral (D1 (x) I, I (x) D1, "
+                             "face-wise lifts); the quadrilateral kernels have no dense-operator form");
+    return ops;
+}
+
+// M = Vinv^T Vinv (Np, Np) and its 1-D factor M1 (Nq, Nq) with M = M1 (x) M1, held to 1e-12 max|entry|.
+void quadMassFactors(const std::string& fn, int N, const double* Vinv, std::vector<double>& M, std::vector<double>& M1) {
+    const int Nq = N + 1, Np = Nq * Nq;
+    M.assign(static_cast<size_t>(Np) * Np, 0.0);
+    for (int m = 0; m < Np; ++m)
+        for (int i = 0; i < Np; ++i) {
+            const double a = Vinv[static_cast<size_t>(m) * Np + i];
+            for (int j = 0; j < Np; ++j) M[static_cast<size_t>(i) * Np + j] += a * Vinv[static_cast<size_t>(m) * Np + j];
+        }
+    if (!(M[0] > 0.0)) throw arg_error(fn + ": Vinv does not give a positive definite mass matrix");
+    const double m00 = std::sqrt(M[0]);
+    M1.assign(static_cast<size_t>(Nq) * Nq, 0.0);
+    for (int a = 0; a < Nq; ++a)
+        for (int b = 0; b < Nq; ++b) M1[a * Nq + b] = M[static_cast<size_t>(Nq * a) * Np + Nq * b] / m00;
+    double maxM = 0.0, err = 0.0;
+    for (int j = 0; j < Nq; ++j)
+        for (int i = 0; i < Nq; ++i)
+            for (int jj = 0; jj < Nq; ++jj)
+                for (int ii = 0; ii < Nq; ++ii) {
+                    const double v = M[static_cast<size_t>(Nq * j + i) * Np + Nq * jj + ii];
+                    maxM = std::max(maxM, std::fabs(v));
+                    err = std::max(err, std::fabs(v - M1[j * Nq + jj] * M1[i * Nq + ii]));
+                }
+    if (!(err <= 1e-12 * maxM))
+        throw arg_error(fn + ": (V V^T)^-1 is not the tensor product of a 1-D mass matrix with itself (Vinv = V1^-1 (x) V1^-1 "
+                             "expected); the mass product is sum-factorised");
+}
+
+// Breadth-first numbering from the face-neighbour graph of a quadrilateral mesh: perm[k] = device slot.
+std::vector<int> quadBfsOrder(const int* vmapP, int K, int Np, int Nq) {
+    std::vector<int> perm(K, -1), frontier, nextFrontier;
+    int next = 0;
+    for (int seed = 0; seed < K; ++seed) {
+        if (perm[seed] >= 0) continue;
+        perm[seed] = next++;
+        frontier.assign(1, seed);
+        while (!frontier.empty()) {
+            nextFrontier.clear();
+            for (int k : frontier)
+                for (int f = 0; f < 4; ++f) {
+                    const int k2 = vmapP[(static_cast<size_t>(k) * 4 + f) * Nq] / Np;
+                    if (perm[k2] < 0) {
+                        perm[k2] = next++;
+                        nextFrontier.push_back(k2);
+                    }
+                }
+            frontier.swap(nextFrontier);
+        }
+    }
+    return perm;
+}
+
+bdg_poisson2d* createQuadSolver(const bdg_poisson2d_desc& d) {
+    const std::string fn = "bdg_poisson2d_create_quad";
+    if (d.order < 1 || d.order > bdg_dev::kPoissonQuadMaxOrder)
+        throw arg_error(fn + ": order must be 1.." + std::to_string(bdg_dev::kPoissonQuadMaxOrder));
+    if (d.flags & BDG_SW2D_NODAL_GEOMETRY)
+        throw arg_error(fn + ": per-node geometry is not supported (quadrilaterals in parallelogram form only)");
+    if (!d.kappa_elements && (!(d.kappa > 0.0) || !std::isfinite(d.kappa))) throw arg_error(fn + ": kappa must be finite and > 0");
+    requireSigma(d.sigma, fn.c_str());
+    if (!(d.tau_scale >= 0.0) || !std::isfinite(d.tau_scale)) throw arg_error(fn + ": tau_scale must be finite and >= 0");
+    if (d.num_elements < 1) throw arg_error(fn + ": num_elements must be >= 1");
+    if (!d.Dr || !d.Ds || !d.Lift || !d.Vinv || !d.rx || !d.sx || !d.ry || !d.sy || !d.J || !d.nx || !d.ny || !d.Fscale ||
+        !d.vmapM || !d.vmapP)
+        throw arg_error(fn + ": a required table pointer is NULL");
+    if (d.num_dirichlet < 0 || (d.num_dirichlet > 0 && !d.mapD)) throw arg_error(fn + ": bad Dirichlet-node list");
+    const bdg_dev::PoissonKernelTable* kt = bdg_dev::poisson_quad_kernel_table(d.order);
+    if (!kt) throw arg_error(fn + ": no kernels compiled for this order");
+
+    const int N = d.order, Nq = N + 1, Np = kt->Np, NFN = 4 * Nq, K = d.num_elements;
+    const long long ld = (static_cast<long long>(K) + 63) / 64 * 64;
+    if (static_cast<long long>(Np) * ld >= (1LL << 31)) throw arg_error(fn + ": Np*K exceeds 2^31 nodes (32-bit gather offsets)");
+    double kappaMax = 0.0;
+    if (d.kappa_elements) {
+        for (int k = 0; k < K; ++k) {
+            if (!(d.kappa_elements[k] > 0.0) || !std::isfinite(d.kappa_elements[k]))
+                throw arg_error(fn + ": every kappa must be finite and > 0");
+            kappaMax = std::max(kappaMax, d.kappa_elements[k]);
+        }
+    } else {
+        kappaMax = d.kappa;
+    }
+    const std::vector<double> opsHost = quadTensorOps(fn, N, d.Dr, d.Ds, d.Lift);
+    std::vector<double> M, M1;
+    quadMassFactors(fn, N, d.Vinv, M, M1);
+
+    // ---- the index tables, on the host
+    const size_t nFaceNodes = static_cast<size_t>(NFN) * K;
+    const long long totalNodes = static_cast<long long>(Np) * K;
+    for (int k = 0; k < K; ++k)
+        for (int f = 0; f < 4; ++f)
+            for (int n = 0; n < Nq; ++n)
+                if (d.vmapM[(static_cast<size_t>(k) * 4 + f) * Nq + n] != kt->fmask(f, n) + Np * k)
+                    throw arg_error(fn + ": vmapM is not the Gauss-Lobatto face numbering (faces s=-1, r=+1, s=+1, r=-1)");
+    for (size_t i = 0; i < nFaceNodes; ++i)
+        if (d.vmapP[i] < 0 || d.vmapP[i] >= totalNodes) throw arg_error(fn + ": vmapP entry out of range");
+    std::vector<unsigned char> kinds(nFaceNodes); // (NFN, K) rows
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < NFN; ++j) {
+            const size_t i = static_cast<size_t>(k) * NFN + j;
+            kinds[static_cast<size_t>(j) * K + k] = d.vmapP[i] == d.vmapM[i] ? bdg_dev::PK_NEUMANN : bdg_dev::PK_INTERIOR;
+        }
+    for (int i = 0; i < d.num_dirichlet; ++i) {
+        const int m = d.mapD[i];
+        if (m < 0 || static_cast<size_t>(m) >= nFaceNodes) throw arg_error(fn + ": Dirichlet-node index out of range");
+        unsigned char& e = kinds[static_cast<size_t>(m % NFN) * K + m / NFN];
+        if (e == bdg_dev::PK_INTERIOR) throw arg_error(fn + ": a mapD entry is not a boundary face node");
+        e = bdg_dev::PK_DIRICHLET;
+    }
+
+    // ---- geometry: the parallelogram form of sw2d_quad_device.hip (metric terms and J constant per element, nx, ny, Fscale per
+    // face, to 1e-10 relative), 16 numbers per element, and J_k
+    std::vector<double> ag(static_cast<size_t>(16) * K), jacHost(K);
+    {
+        std::atomic<bool> para{true}, positive{true};
+        const double* met[4] = {d.rx, d.sx, d.ry, d.sy};
+        const double* fg[3] = {d.nx, d.ny, d.Fscale};
+        blitzdg::detail::parallelFor(K, [&](int k) {
+            double scale = 0.0;
+            for (int a = 0; a < 4; ++a)
+                for (int n = 0; n < Np; ++n) scale = std::max(scale, std::fabs(met[a][static_cast<size_t>(n) * K + k]));
+            for (int a = 0; a < 5; ++a) {
+                const double* tab = a < 4 ? met[a] : d.J;
+                double mean = 0.0;
+                for (int n = 0; n < Np; ++n) mean += tab[static_cast<size_t>(n) * K + k];
+                mean /= Np;
+                const double sc = a < 4 ? scale : std::fabs(mean);
+                for (int n = 0; n < Np; ++n)
+                    if (!(std::fabs(tab[static_cast<size_t>(n) * K + k] - mean) <= 1e-10 * sc)) para = false;
+                if (a < 4) ag[static_cast<size_t>(a) * K + k] = mean;
+                else jacHost[k] = mean;
+            }
+            if (!(jacHost[k] > 0.0)) positive = false;
+            for (int c = 0; c < 3; ++c)
+                for (int f = 0; f < 4; ++f) {
+                    double mean = 0.0, sc = 0.0;
+                    for (int n = 0; n < Nq; ++n) {
+                        const double v = fg[c][static_cast<size_t>(f * Nq + n) * K + k];
+                        mean += v;
+                        sc = std::max(sc, std::fabs(v));
+                    }
+                    mean /= Nq;
+                    if (c < 2) sc = 1.0;
+                    for (int n = 0; n < Nq; ++n)
+                        if (!(std::fabs(fg[c][static_cast<size_t>(f * Nq + n) * K + k] - mean) <= 1e-10 * sc)) para = false;
+                    ag[static_cast<size_t>(4 + 4 * c + f) * K + k] = mean;
+                }
+        });
+        if (!para)
+            throw arg_error(fn + ": the mesh is not in parallelogram form (metric terms constant per element to 1e-10). On a general "
+                                 "bilinear quadrilateral the variable metric does not commute with the mass matrix, M A is not "
+                                 "symmetric and conjugate gradients has no licence (DESIGN.md 3.13)");
+        if (!positive) throw arg_error(fn + ": J must be positive");
+    }
+    double fscaleMax = 0.0;
+    for (size_t i = 0; i < nFaceNodes; ++i) fscaleMax = std::max(fscaleMax, std::fabs(d.Fscale[i]));
+    std::vector<double> colsum(Np, 0.0);
+    for (int i = 0; i < Np; ++i)
+        for (int j = 0; j < Np; ++j) colsum[i] += M[static_cast<size_t>(j) * Np + i];
+    std::vector<double> wtsHost(static_cast<size_t>(Np) * K);
+    for (int i = 0; i < Np; ++i)
+        for (int k = 0; k < K; ++k) wtsHost[static_cast<size_t>(i) * K + k] = colsum[i] * jacHost[k];
+    double area = 0.0, refArea = 0.0;
+    for (int i = 0; i < Np; ++i) refArea += colsum[i];
+    for (int k = 0; k < K; ++k) area += refArea * jacHost[k];
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        throw hip_error(fn + ": no HIP device available (the elliptic solver has no CPU fallback)");
+    if (d.device < 0 || d.device >= ndev) throw arg_error(fn + ": device ordinal out of range");
+
+    auto s = std::unique_ptr<bdg_poisson2d>(new bdg_poisson2d());
+    s->kt = kt;
+    s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->ld = ld;
+    s->tileElems = bdg_dev::poisson_quad_tile_elements(N);
+    s->device = d.device;
+    s->sigma = d.sigma;
+    s->tau = (d.tau_scale > 0.0 ? d.tau_scale : 1.0) * Np * fscaleMax / 2.0 * kappaMax;
+    s->area = area;
+    s->hasDirichlet = d.num_dirichlet > 0;
+    // Sw2dQuadSolver never renumbers: the caller's order stays unless BDG_SW2D_REORDER asks for the breadth-first one
+    if ((d.flags & BDG_SW2D_REORDER) != 0 && !(d.flags & BDG_SW2D_KEEP_ORDER)) s->permHost = quadBfsOrder(d.vmapP, K, Np, Nq);
+
+    s->use();
+    hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
+    hipStream_t st = s->stream;
+    const size_t pl = s->planeSize();
+    for (DevBuf<double>* b : {&s->x, &s->r, &s->s, &s->dirA, &s->dirB, &s->Ap, &s->w, &s->wts}) b->alloc(pl, s->bytes, st);
+    s->q.alloc(2 * pl, s->bytes, st);
+    s->ageo.alloc(16 * static_cast<size_t>(ld), s->bytes, st);
+    s->jac.alloc(static_cast<size_t>(ld), s->bytes, st);
+    s->kap.alloc(static_cast<size_t>(ld), s->bytes, st);
+    s->vmapP.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
+    s->kind.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
+    s->stage.alloc(static_cast<size_t>(std::max({Np, NFN, 16})) * K, s->bytes);
+    s->istage.alloc(nFaceNodes, s->bytes);
+    s->bstage.alloc(nFaceNodes, s->bytes);
+    s->partial.alloc(static_cast<size_t>(std::max(s->tiles(), s->reduceBlocks())), s->bytes, st);
+    s->scal.alloc(bdg_dev::PS_COUNT, s->bytes, st);
+    if (!s->permHost.empty()) s->perm.upload(s->permHost, s->bytes, "perm upload");
+
+    s->uploadRows(ag.data(), s->ageo.p, 16);
+    s->uploadRows(jacHost.data(), s->jac.p, 1);
+    {
+        std::vector<double> kapHost(K, d.kappa);
+        if (d.kappa_elements) kapHost.assign(d.kappa_elements, d.kappa_elements + K);
+        s->uploadRows(kapHost.data(), s->kap.p, 1);
+    }
+    s->uploadRows(wtsHost.data(), s->wts.p, Np);
+    s->uploadRowsT<unsigned char>(kinds.data(), s->kind.p, s->bstage.p, NFN);
+    s->ops.upload(opsHost, s->bytes, "ops upload");
+    s->mass.upload(M1, s->bytes, "mass upload");
+
+    // ---- gather offsets: reference numbering (n' + Np k') -> n' ld + slot(k'), as (NFN, K) rows; a boundary node gathers itself
+    {
+        std::vector<int> rows(nFaceNodes);
+        const int* perm = s->permHost.empty() ? nullptr : s->permHost.data();
+        for (int k = 0; k < K; ++k)
+            for (int j = 0; j < NFN; ++j) {
+                const int v = d.vmapP[static_cast<size_t>(k) * NFN + j];
+                const int n2 = v % Np, k2 = v / Np;
+                rows[static_cast<size_t>(j) * K + k] = static_cast<int>(n2 * ld + (perm ? perm[k2] : k2));
+            }
+        s->uploadRowsT<int>(rows.data(), s->vmapP.p, s->istage.p, NFN);
+    }
+    s->istage.release();
+    s->bstage.release();
+    return s.release();
+}
+
 void requireSolver(const bdg_poisson2d* s, const char* fn) {
     if (!s) throw arg_error(std::string(fn) + ": solver handle is NULL");
 }
@@ -469,6 +772,46 @@ int bdg_poisson2d_create_from_nodes(const bdg_trinodes* nodes, const int* mapD, 
         d.kappa = kappa; d.kappa_elements = kappa_elements; d.sigma = sigma; d.tau_scale = tau_scale;
         d.device = device; d.flags = flags;
         *out = createSolver(d);
+    });
+}
+
+int bdg_poisson2d_create_quad(const bdg_poisson2d_desc* desc, bdg_poisson2d** out) {
+    return guard([&] {
+        if (!desc || !out) throw arg_error("bdg_poisson2d_create_quad: NULL argument");
+        *out = createQuadSolver(*desc);
+    });
+}
+
+int bdg_poisson2d_create_from_quadnodes(const bdg_quadnodes* nodes, const int* mapD, int num_dirichlet, double kappa,
+                                        const double* kappa_elements, double sigma, double tau_scale, int device, int flags,
+                                        bdg_poisson2d** out) {
+    return guard([&] {
+        if (!nodes || !out) throw arg_error("bdg_poisson2d_create_from_quadnodes: NULL argument");
+        const blitzdg::QuadNodesProvisioner& p = nodes->prov;
+        bdg_poisson2d_desc d{};
+        d.order = p.get_NOrder();
+        d.num_elements = p.get_NumElements();
+        d.Dr = p.get_Dr().data(); d.Ds = p.get_Ds().data(); d.Lift = p.get_Lift().data(); d.Vinv = p.get_Vinv().data();
+        d.rx = p.get_rx().data(); d.sx = p.get_sx().data(); d.ry = p.get_ry().data(); d.sy = p.get_sy().data();
+        d.J = p.get_J().data();
+        d.nx = p.get_nx().data(); d.ny = p.get_ny().data(); d.Fscale = p.get_Fscale().data();
+        d.vmapM = p.get_vmapM().data(); d.vmapP = p.get_vmapP().data();
+        std::vector<int> walls;
+        if (!mapD && num_dirichlet < 0) {
+            const auto& bc = p.get_bcMap();
+            for (int tag : {static_cast<int>(blitzdg::BCTag::Wall), static_cast<int>(blitzdg::BCTag::Dirichlet)}) {
+                const auto it = bc.find(tag);
+                if (it != bc.end()) walls.insert(walls.end(), it->second.begin(), it->second.end());
+            }
+            d.mapD = walls.data();
+            d.num_dirichlet = static_cast<int>(walls.size());
+        } else {
+            d.mapD = mapD;
+            d.num_dirichlet = num_dirichlet;
+        }
+        d.kappa = kappa; d.kappa_elements = kappa_elements; d.sigma = sigma; d.tau_scale = tau_scale;
+        d.device = device; d.flags = flags;
+        *out = createQuadSolver(d);
     });
 }
 

@@ -33,6 +33,9 @@ SolveInfo = collections.namedtuple("SolveInfo", "iterations relativeResidual con
 class Poisson2dSolver:
     """Device-resident elliptic solver (one HIP device, one stream)."""
 
+    _FACES = 3
+    _CREATE, _CREATE_FROM_NODES = "bdg_poisson2d_create", "bdg_poisson2d_create_from_nodes"
+
     def __init__(self, nodes=None, tables=None, mapD=None, kappa=1.0, shift=0.0, tauScale=1.0, device=0, flags=0):
         """Create from a ``pyblitzdg.TriangleNodesProvisioner`` (``nodes``) or from a dict of host tables (``tables``: order, Dr,
         Ds, Lift, Vinv, rx, sx, ry, sy, J, nx, ny, Fscale, vmapM, vmapP).
@@ -56,17 +59,17 @@ class Poisson2dSolver:
             self.Np, self.K = rx.shape
             self.Nfp = self.order + 1
         else:
-            raise ValueError("Poisson2dSolver needs `nodes` or `tables`")
+            raise ValueError(f"{type(self).__name__} needs `nodes` or `tables`")
         kapK = None
         if kap.ndim == 1:
             kapK = C.as_f64(kap, (self.K,), "kappa")
         md = None if mapD is None else C.as_i32(mapD).reshape(-1)
         if nodes is not None:
-            check(lib.bdg_poisson2d_create_from_nodes(nodes._h, C.ptr(md) if md is not None and md.size else None,
-                                                      -1 if md is None else md.size, float(kap) if kapK is None else 0.0,
-                                                      C.ptr(kapK), float(shift), float(tauScale), int(device), int(flags), byref(h)))
+            check(getattr(lib, self._CREATE_FROM_NODES)(nodes._h, C.ptr(md) if md is not None and md.size else None,
+                                                        -1 if md is None else md.size, float(kap) if kapK is None else 0.0,
+                                                        C.ptr(kapK), float(shift), float(tauScale), int(device), int(flags), byref(h)))
         else:
-            Np, K, nfn = self.Np, self.K, 3 * self.Nfp
+            Np, K, nfn = self.Np, self.K, self._FACES * self.Nfp
             a = {
                 "Dr": C.as_f64(t["Dr"], (Np, Np), "Dr"), "Ds": C.as_f64(t["Ds"], (Np, Np), "Ds"),
                 "Lift": C.as_f64(t["Lift"], (Np, nfn), "Lift"), "Vinv": C.as_f64(t["Vinv"], (Np, Np), "Vinv"),
@@ -77,7 +80,7 @@ class Poisson2dSolver:
                 "vmapM": C.as_i32(t["vmapM"]).reshape(-1), "vmapP": C.as_i32(t["vmapP"]).reshape(-1),
             }
             if a["vmapP"].size != nfn * K or a["vmapM"].size != nfn * K:
-                raise ValueError("vmapM and vmapP must have 3*Nfp*K entries")
+                raise ValueError(f"vmapM and vmapP must have {self._FACES}*Nfp*K entries")
             if md is None:
                 md = np.zeros(0, dtype=np.int32)
             d = C.Poisson2dDesc(self.order, K, C.ptr(a["Dr"]), C.ptr(a["Ds"]), C.ptr(a["Lift"]), C.ptr(a["Vinv"]),
@@ -85,7 +88,7 @@ class Poisson2dSolver:
                                 C.ptr(a["nx"]), C.ptr(a["ny"]), C.ptr(a["Fscale"]), C.ptr(a["vmapM"]), C.ptr(a["vmapP"]),
                                 C.ptr(md) if md.size else None, md.size, float(kap) if kapK is None else 0.0, C.ptr(kapK),
                                 float(shift), float(tauScale), int(device), int(flags))
-            check(lib.bdg_poisson2d_create(byref(d), byref(h)))
+            check(getattr(lib, self._CREATE)(byref(d), byref(h)))
         self._h = h
         self.shift = float(shift)
         self._finalizer = weakref.finalize(self, lib.bdg_poisson2d_destroy, h)
@@ -98,7 +101,7 @@ class Poisson2dSolver:
         return C.as_f64(a, (self.Np, self.K), name)
 
     def _face(self, a, name):
-        return None if a is None else C.as_f64(a, (3 * self.Nfp, self.K), name)
+        return None if a is None else C.as_f64(a, (self._FACES * self.Nfp, self.K), name)
 
     def setShift(self, sigma):
         check(lib.bdg_poisson2d_set_shift(self._h, float(sigma)))
@@ -148,3 +151,18 @@ class Poisson2dSolver:
 
     def deviceBytes(self):
         return int(lib.bdg_poisson2d_device_bytes(self._h))
+
+
+class Poisson2dQuadSolver(Poisson2dSolver):
+    """The same solver on quadrilaterals in parallelogram form (csrc/hip/poisson2d_quad_kernel.hpp), orders 1
+    to 12: ``nodes`` a ``pyblitzdg.QuadNodesProvisioner`` or ``tables`` a dict with the same keys (``Vinv = V1^-1 (x) V1^-1`` and
+    ``J`` from ``dgContext()``). Face-node planes (``nx``, ``g``, ``qn``) are (4 Nfp, K) and ``mapD`` counts 4 Nfp k + j; by
+    default with ``nodes`` it is ``BCmap[Wall] + BCmap[Dirichlet]``. Every method is the triangle class's.
+
+    A mesh whose metric terms are not constant per element (a general bilinear quadrilateral) is refused at creation: there the
+    metric does not commute with the mass matrix, ``M A`` is not symmetric and conjugate gradients does not apply. The mass
+    matrix is the only preconditioner. ``REORDER`` renumbers the elements breadth-first on the device; by default, and with
+    ``KEEP_ORDER``, the caller's order is kept, as ``Sw2dQuadSolver`` keeps it."""
+
+    _FACES = 4
+    _CREATE, _CREATE_FROM_NODES = "bdg_poisson2d_create_quad", "bdg_poisson2d_create_from_quadnodes"

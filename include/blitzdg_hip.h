@@ -1241,6 +1241,22 @@ int bdg_poisson2d_time_apply(bdg_poisson2d* s, int count, float* ms);
 int bdg_poisson2d_time_iterations(bdg_poisson2d* s, int count, float* ms);
 size_t bdg_poisson2d_device_bytes(const bdg_poisson2d* s);
 
+/* ---- the same solver on quadrilaterals in parallelogram form: the two passes and the mass product in the
+ * tensor form of the quadrilateral kernels, orders 1..12, behind the same handle -- every bdg_poisson2d_* call above serves both
+ * families. The descriptor is bdg_poisson2d_desc with the tables of a QuadNodesProvisioner: Np = (N+1)^2, nx / ny / Fscale
+ * (4*Nfp, K), vmapM / vmapP and mapD in the face-node numbering 4 Nfp k + j, Vinv = V1^-1 (x) V1^-1; boundary data planes are
+ * (4 Nfp, K). flags: BDG_SW2D_REORDER renumbers the elements breadth-first (all I/O stays in the caller's numbering); without it,
+ * and with BDG_SW2D_KEEP_ORDER, the caller's order is kept, as bdg_sw2dq_* keeps it.
+ * BDG_ERR_ARGUMENT, before a GPU is touched, for what bdg_poisson2d_create refuses and for: an order outside 1..12; a mesh that is
+ * not in parallelogram form (rx, sx, ry, sy, J constant per element, nx, ny, Fscale per face, to 1e-10 relative: on a general
+ * bilinear quadrilateral M A is not symmetric, so conjugate gradients does not apply); Dr, Ds, Lift or Vinv that do not have the
+ * tensor form of the Gauss-Lobatto element. */
+int bdg_poisson2d_create_quad(const bdg_poisson2d_desc* desc, bdg_poisson2d** out);
+/* Every table from a quadrilateral nodes provisioner; mapD NULL with num_dirichlet < 0: BCmap[Wall] + BCmap[Dirichlet]. */
+int bdg_poisson2d_create_from_quadnodes(const bdg_quadnodes* nodes, const int* mapD, int num_dirichlet, double kappa,
+                                        const double* kappa_elements, double sigma, double tau_scale, int device, int flags,
+                                        bdg_poisson2d** out);
+
 #ifdef __cplusplus
 }
 #endif
