@@ -1,5 +1,5 @@
-// device_buffer.hpp -- the HIP error check, the owning device buffer and the event timer of the sw2d solvers
-// (sw2d_device.hip, sw2d_curved_device.hip, sw2d_quad_device.hip).
+// device_buffer.hpp -- the HIP error check, the owning device buffer and the event timer of the device solvers
+// (sw2d_device.hip, sw2d_curved_device.hip, sw2d_quad_device.hip, poisson2d_device.hip).
 #pragma once
 #include "../host/capi_internal.hpp"
 #include <hip/hip_runtime.h>

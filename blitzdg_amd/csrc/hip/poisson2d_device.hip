@@ -2,10 +2,12 @@
 // div(kappa grad u) on straight-sided triangles (the two passes of poisson2d_kernel.hpp, per-order objects poisson2d_order.hip)
 // and conjugate gradients in the mass inner product whose scalars live in device memory.
 //
-// Tables are set up the way the straight sw2d solver sets up its own (sw2d_device.hip): fp64 planes of ld = K rounded up to 64
+// Tables are laid out the way the straight sw2d solver lays out its own (sw2d_device.hip): fp64 planes of ld = K rounded up to 64
 // elements per nodal row, 13 numbers of affine geometry per element, int32 gather offsets n' ld + slot(k'), elements renumbered
 // internally by the same rule (element_order.hpp) with all I/O in the caller's numbering. On top of them: J_k, kappa_k, one
-// byte per face node for its kind, the reference mass matrix's rows, and the weights J M 1.
+// byte per face node for its kind, the reference mass matrix's rows, and the weights J M 1. The host builds all of them for both
+// element families in host/poisson_tables.cpp (its element-table checks are host/element_tables.cpp, shared with the sw2d solvers);
+// createFrom() here allocates and uploads them, through the row transposes of row_transfer.hpp.
 //
 // HBM layout (planes of Np ld doubles): x, r, s = J M r, two search directions (the fused first pass writes the new one beside
 // the old), A p, w = J M A p, the two flux planes; (3 Nfp, ld) data planes g and qn once data is set.
@@ -15,19 +17,17 @@
 //   ->  finish: alpha  ->  x += alpha p, r -= alpha A p, s -= alpha w with the partials of r . s  ->  finish: beta, <r, r>
 // and the host reads <r, r> every check_every iterations.
 //
-// The same handle serves quadrilaterals in parallelogram form (bdg_poisson2d_create_quad): createQuadSolver fills
-// it with the launch table of poisson2d_quad_order.hip (a PoissonKernelTable as well), 16 numbers of geometry per element, (4 Nfp,
+// The same handle serves quadrilaterals in parallelogram form (bdg_poisson2d_create_quad): it then holds
+// the launch table of poisson2d_quad_order.hip (a PoissonKernelTable as well), 16 numbers of geometry per element, (4 Nfp,
 // ld) index, kind and data planes, the tensor ops image and the 1-D mass matrix; the mass product then writes one partial per
 // tile of QuadElem<N>::E elements (tileElems). The loop, its vector kernels, the finishers and the projection are shared and
 // launch exactly what they launched for triangles.
 #include "../host/capi_internal.hpp"
-#include "../host/element_order.hpp"
-#include "../host/parallel_for.hpp"
-#include "device_buffer.hpp"
+#include "../host/poisson_tables.hpp"
 #include "poisson2d_launch.hpp"
 #include "poisson2d_quad_launch.hpp"
+#include "row_transfer.hpp"
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <memory>
 #include <string>
@@ -85,25 +85,6 @@ int poisson_quad_tile_elements(int order) {
 }
 #undef BDG_PQ_CASES
 
-// (rows, K) caller-order image <-> padded, optionally renumbered device planes. perm[k_caller] = device slot (NULL = identity).
-template <typename T>
-__global__ void poisson2d_scatter_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, int rows, int K, long long ld,
-                                              const int* __restrict__ perm) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(rows) * K) return;
-    const long long r = t / K, k = t % K;
-    dst[r * ld + (perm ? perm[k] : k)] = src[t];
-}
-
-template <typename T>
-__global__ void poisson2d_gather_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, int rows, int K, long long ld,
-                                             const int* __restrict__ perm) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(rows) * K) return;
-    const long long r = t / K, k = t % K;
-    dst[t] = src[r * ld + (perm ? perm[k] : k)];
-}
-
 // a reproducible nonzero right-hand side for bdg_poisson2d_time_iterations: values in (0.5, 1.5) at the nodes of real elements
 __global__ void poisson2d_fill_kernel(double* __restrict__ u, long long n, long long ld, int K) {
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -152,24 +133,10 @@ struct bdg_poisson2d {
     int flatBlocks() const { return static_cast<int>((planeEntries() + kBlock - 1) / kBlock); }
     int reduceBlocks() const { return static_cast<int>((planeEntries() + kBlock * kItems - 1) / (kBlock * kItems)); }
 
-    template <typename T>
-    void uploadRowsT(const T* host, T* dev, T* staging, int rows) {
-        const size_t n = static_cast<size_t>(rows) * K;
-        hipCheck(hipMemcpyAsync(staging, host, n * sizeof(T), hipMemcpyHostToDevice, stream), "H2D copy");
-        hipLaunchKernelGGL((bdg_dev::poisson2d_scatter_rows_kernel<T>), dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           stream, staging, dev, rows, K, ld, perm.p);
-        hipCheck(hipGetLastError(), "poisson2d_scatter_rows_kernel");
-        hipCheck(hipStreamSynchronize(stream), "upload sync"); // the staging buffer is reused
-    }
-    void uploadRows(const double* host, double* dev, int rows) { uploadRowsT<double>(host, dev, stage.p, rows); }
-    void downloadRows(const double* dev, double* host, int rows) {
-        const size_t n = static_cast<size_t>(rows) * K;
-        hipLaunchKernelGGL((bdg_dev::poisson2d_gather_rows_kernel<double>), dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                           stream, dev, stage.p, rows, K, ld, perm.p);
-        hipCheck(hipGetLastError(), "poisson2d_gather_rows_kernel");
-        hipCheck(hipMemcpyAsync(host, stage.p, n * sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
-        hipCheck(hipStreamSynchronize(stream), "download sync");
-    }
+    // host (rows, K) caller order <-> device planes (padded / renumbered): row_transfer.hpp
+    bdg_dev::RowLayout rowLayout() const { return {K, ld, perm.p, stream}; }
+    void uploadRows(const double* host, double* dev, int rows) { bdg_dev::uploadRows(rowLayout(), host, dev, stage.p, rows); }
+    void downloadRows(const double* dev, double* host, int rows) { bdg_dev::downloadRows(rowLayout(), dev, host, stage.p, rows); }
 
     bdg_dev::PoissonParams params(const double* u, double* out) {
         bdg_dev::PoissonParams p{};
@@ -259,472 +226,103 @@ struct bdg_poisson2d {
 
 namespace {
 
-// The straight solver's test (sw2d_device.hip): metric terms constant per element, face terms constant per face, to 1e-8.
-bool geometryIsAffine(const bdg_poisson2d_desc& d, int Np, int Nfp, int K) {
-    const double tol = 1e-8;
-    std::atomic<bool> ok{true};
-    blitzdg::detail::parallelFor(K, [&](int k) {
-        const double scale = std::fabs(d.rx[k]) + std::fabs(d.sx[k]) + std::fabs(d.ry[k]) + std::fabs(d.sy[k]);
-        for (int n = 1; n < Np; ++n) {
-            const size_t o = static_cast<size_t>(n) * K + k;
-            if (std::fabs(d.rx[o] - d.rx[k]) > tol * scale || std::fabs(d.sx[o] - d.sx[k]) > tol * scale ||
-                std::fabs(d.ry[o] - d.ry[k]) > tol * scale || std::fabs(d.sy[o] - d.sy[k]) > tol * scale ||
-                std::fabs(d.J[o] - d.J[k]) > tol * std::fabs(d.J[k]))
-                ok = false;
-        }
-        for (int f = 0; f < 3; ++f) {
-            const size_t o0 = static_cast<size_t>(f) * Nfp * K + k;
-            for (int n = 1; n < Nfp; ++n) {
-                const size_t o = o0 + static_cast<size_t>(n) * K;
-                if (std::fabs(d.nx[o] - d.nx[o0]) > tol || std::fabs(d.ny[o] - d.ny[o0]) > tol ||
-                    std::fabs(d.Fscale[o] - d.Fscale[o0]) > tol * std::fabs(d.Fscale[o0]))
-                    ok = false;
-            }
-        }
-    });
-    return ok;
-}
+namespace pt = blitzdg::poisson_tables;
+using pt::requireSigma;
+static_assert(int(pt::kInterior) == bdg_dev::PK_INTERIOR && int(pt::kDirichlet) == bdg_dev::PK_DIRICHLET &&
+                  int(pt::kNeumann) == bdg_dev::PK_NEUMANN, "poisson_tables.hpp writes the kind bytes the kernels read");
+static_assert(pt::kMaxOrder[pt::kQuadrilaterals] == bdg_dev::kPoissonQuadMaxOrder, "poisson_tables.hpp admits the compiled orders");
 
-void requireSigma(double sigma, const char* fn) {
-    if (!(sigma >= 0.0) || !std::isfinite(sigma)) throw arg_error(std::string(fn) + ": sigma must be finite and >= 0");
-}
-
-bdg_poisson2d* createSolver(const bdg_poisson2d_desc& d) {
-    const char* fn = "bdg_poisson2d_create";
-    if (d.order < 1 || d.order > 8) throw arg_error(std::string(fn) + ": order must be 1..8");
-    if (d.flags & BDG_SW2D_NODAL_GEOMETRY)
-        throw arg_error(std::string(fn) + ": per-node geometry is not supported (straight-sided triangles only)");
-    if (!d.kappa_elements && (!(d.kappa > 0.0) || !std::isfinite(d.kappa)))
-        throw arg_error(std::string(fn) + ": kappa must be finite and > 0");
-    requireSigma(d.sigma, fn);
-    if (!(d.tau_scale >= 0.0) || !std::isfinite(d.tau_scale)) throw arg_error(std::string(fn) + ": tau_scale must be finite and >= 0");
-    if (d.num_elements < 1) throw arg_error(std::string(fn) + ": num_elements must be >= 1");
-    if (!d.Dr || !d.Ds || !d.Lift || !d.Vinv || !d.rx || !d.sx || !d.ry || !d.sy || !d.J || !d.nx || !d.ny || !d.Fscale ||
-        !d.vmapM || !d.vmapP)
-        throw arg_error(std::string(fn) + ": a required table pointer is NULL");
-    if (d.num_dirichlet < 0 || (d.num_dirichlet > 0 && !d.mapD)) throw arg_error(std::string(fn) + ": bad Dirichlet-node list");
-    const bdg_dev::PoissonKernelTable* kt = bdg_dev::poisson_kernel_table(d.order);
-    if (!kt) throw arg_error(std::string(fn) + ": no kernels compiled for this order");
-
-    const int Np = kt->Np, Nfp = kt->Nfp, NFN = 3 * Nfp, K = d.num_elements;
-    const long long ld = (static_cast<long long>(K) + 63) / 64 * 64;
-    // Lane addresses are a wave-uniform row pointer plus a 32-bit unsigned BYTE offset (8 * node offset).
-    if (static_cast<long long>(Np) * ld * 8 > 4294967295LL)
-        throw arg_error(std::string(fn) + ": Np*K exceeds 2^29 nodes (32-bit byte offsets within a plane)");
-    double kappaMax = 0.0;
-    if (d.kappa_elements) {
-        for (int k = 0; k < K; ++k) {
-            if (!(d.kappa_elements[k] > 0.0) || !std::isfinite(d.kappa_elements[k]))
-                throw arg_error(std::string(fn) + ": every kappa must be finite and > 0");
-            kappaMax = std::max(kappaMax, d.kappa_elements[k]);
-        }
-    } else {
-        kappaMax = d.kappa;
-    }
-
-    // ---- the index tables, on the host
-    const size_t nFaceNodes = static_cast<size_t>(NFN) * K;
-    const long long totalNodes = static_cast<long long>(Np) * K;
-    for (int k = 0; k < K; ++k)
-        for (int f = 0; f < 3; ++f)
-            for (int n = 0; n < Nfp; ++n)
-                if (d.vmapM[(static_cast<size_t>(k) * 3 + f) * Nfp + n] != kt->fmask(f, n) + Np * k)
-                    throw arg_error(std::string(fn) + ": vmapM does not follow the warp&blend face-node ordering (Fmask) these "
-                                                      "kernels are specialised for");
-    for (size_t i = 0; i < nFaceNodes; ++i)
-        if (d.vmapP[i] < 0 || d.vmapP[i] >= totalNodes) throw arg_error(std::string(fn) + ": vmapP entry out of range");
-    std::vector<unsigned char> kinds(nFaceNodes); // (NFN, K) rows
-    for (int k = 0; k < K; ++k)
-        for (int j = 0; j < NFN; ++j) {
-            const size_t i = static_cast<size_t>(k) * NFN + j;
-            kinds[static_cast<size_t>(j) * K + k] = d.vmapP[i] == d.vmapM[i] ? bdg_dev::PK_NEUMANN : bdg_dev::PK_INTERIOR;
-        }
-    for (int i = 0; i < d.num_dirichlet; ++i) {
-        const int m = d.mapD[i];
-        if (m < 0 || static_cast<size_t>(m) >= nFaceNodes) throw arg_error(std::string(fn) + ": Dirichlet-node index out of range");
-        unsigned char& e = kinds[static_cast<size_t>(m % NFN) * K + m / NFN];
-        if (e == bdg_dev::PK_INTERIOR) throw arg_error(std::string(fn) + ": a mapD entry is not a boundary face node");
-        e = bdg_dev::PK_DIRICHLET;
-    }
-    if (!geometryIsAffine(d, Np, Nfp, K))
-        throw arg_error(std::string(fn) + ": the geometry tables are not those of straight-sided elements");
-    double fscaleMax = 0.0, area = 0.0;
-    for (size_t i = 0; i < nFaceNodes; ++i) fscaleMax = std::max(fscaleMax, std::fabs(d.Fscale[i]));
-    // reference mass matrix M = Vinv^T Vinv and its column sums (the nodal quadrature weights)
-    std::vector<double> M(static_cast<size_t>(Np) * Np, 0.0), colsum(Np, 0.0);
-    for (int i = 0; i < Np; ++i)
-        for (int j = 0; j < Np; ++j) {
-            double sum = 0.0;
-            for (int m = 0; m < Np; ++m) sum += d.Vinv[m * Np + i] * d.Vinv[m * Np + j];
-            M[static_cast<size_t>(i) * Np + j] = sum;
-        }
-    for (int i = 0; i < Np; ++i)
-        for (int j = 0; j < Np; ++j) colsum[i] += M[static_cast<size_t>(j) * Np + i];
-    std::vector<double> wtsHost(static_cast<size_t>(Np) * K);
-    for (int i = 0; i < Np; ++i)
-        for (int k = 0; k < K; ++k) wtsHost[static_cast<size_t>(i) * K + k] = colsum[i] * d.J[k];
-    for (int k = 0; k < K; ++k) {
-        if (!(d.J[k] > 0.0)) throw arg_error(std::string(fn) + ": J must be positive");
-        double a = 0.0;
-        for (int i = 0; i < Np; ++i) a += colsum[i];
-        area += a * d.J[k];
-    }
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        throw hip_error(std::string(fn) + ": no HIP device available (the elliptic solver has no CPU fallback)");
-    if (d.device < 0 || d.device >= ndev) throw arg_error(std::string(fn) + ": device ordinal out of range");
-
+// The handle of host tables `t`: allocations and uploads. tileElems: elements per partial of the family's mass product.
+bdg_poisson2d* createFrom(const pt::Tables& t, const bdg_dev::PoissonKernelTable* kt, int tileElems, double sigma, int device) {
     auto s = std::unique_ptr<bdg_poisson2d>(new bdg_poisson2d());
     s->kt = kt;
-    s->N = d.order; s->Np = Np; s->Nfp = Nfp; s->NFN = NFN; s->K = K; s->ld = ld;
-    s->device = d.device;
-    s->sigma = d.sigma;
-    s->tau = (d.tau_scale > 0.0 ? d.tau_scale : 1.0) * Np * fscaleMax / 2.0 * kappaMax;
-    s->area = area;
-    s->hasDirichlet = d.num_dirichlet > 0;
-
-    namespace eo = blitzdg::element_order;
-    const bool reorder = (d.flags & BDG_SW2D_REORDER) != 0 ||
-                         (!(d.flags & BDG_SW2D_KEEP_ORDER) && eo::renumberingWanted(d.vmapP, K, Np, Nfp, d.order));
-    if (reorder) s->permHost = eo::renumbering(d.vmapP, K, Np, Nfp, eo::patchSetting());
+    s->N = t.N; s->Np = t.Np; s->Nfp = t.Nfp; s->NFN = t.NFN; s->K = t.K; s->ld = t.ld;
+    s->tileElems = tileElems;
+    s->device = device;
+    s->sigma = sigma;
+    s->tau = t.tau;
+    s->area = t.area;
+    s->hasDirichlet = t.hasDirichlet;
+    s->permHost = t.perm;
 
     s->use();
     hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
     hipStream_t st = s->stream;
-    const size_t pl = s->planeSize();
+    const size_t pl = s->planeSize(), ld = static_cast<size_t>(t.ld), nFaceNodes = static_cast<size_t>(t.NFN) * t.K;
     for (DevBuf<double>* b : {&s->x, &s->r, &s->s, &s->dirA, &s->dirB, &s->Ap, &s->w, &s->wts}) b->alloc(pl, s->bytes, st);
     s->q.alloc(2 * pl, s->bytes, st);
-    s->ageo.alloc(13 * static_cast<size_t>(ld), s->bytes, st);
-    s->jac.alloc(static_cast<size_t>(ld), s->bytes, st);
-    s->kap.alloc(static_cast<size_t>(ld), s->bytes, st);
-    s->vmapP.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
-    s->kind.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
-    s->stage.alloc(static_cast<size_t>(std::max(Np, NFN)) * K, s->bytes);
+    s->ageo.alloc(t.geoRows * ld, s->bytes, st);
+    s->jac.alloc(ld, s->bytes, st);
+    s->kap.alloc(ld, s->bytes, st);
+    s->vmapP.alloc(t.NFN * ld, s->bytes, st);
+    s->kind.alloc(t.NFN * ld, s->bytes, st);
+    s->stage.alloc(static_cast<size_t>(std::max(t.Np, t.NFN)) * t.K, s->bytes);
     s->istage.alloc(nFaceNodes, s->bytes);
     s->bstage.alloc(nFaceNodes, s->bytes);
     s->partial.alloc(static_cast<size_t>(std::max(s->tiles(), s->reduceBlocks())), s->bytes, st);
     s->scal.alloc(bdg_dev::PS_COUNT, s->bytes, st);
     if (!s->permHost.empty()) s->perm.upload(s->permHost, s->bytes, "perm upload");
 
-    // ---- geometry: one metric value per element, one normal / scale per face (row 0 of each table, first node of each face)
-    s->uploadRows(d.rx, s->ageo.p, 1);
-    s->uploadRows(d.sx, s->ageo.p + ld, 1);
-    s->uploadRows(d.ry, s->ageo.p + 2 * ld, 1);
-    s->uploadRows(d.sy, s->ageo.p + 3 * ld, 1);
-    for (int f = 0; f < 3; ++f) {
-        const size_t row = static_cast<size_t>(f) * Nfp * K;
-        s->uploadRows(d.nx + row, s->ageo.p + (4 + f) * ld, 1);
-        s->uploadRows(d.ny + row, s->ageo.p + (7 + f) * ld, 1);
-        s->uploadRows(d.Fscale + row, s->ageo.p + (10 + f) * ld, 1);
-    }
-    s->uploadRows(d.J, s->jac.p, 1);
-    {
-        std::vector<double> kapHost(K, d.kappa);
-        if (d.kappa_elements) kapHost.assign(d.kappa_elements, d.kappa_elements + K);
-        s->uploadRows(kapHost.data(), s->kap.p, 1);
-    }
-    s->uploadRows(wtsHost.data(), s->wts.p, Np);
-    s->uploadRowsT<unsigned char>(kinds.data(), s->kind.p, s->bstage.p, NFN);
-
-    // ---- operator rows: VnOps image, row i = {Dr[i][m], Ds[i][m]} for m < Np, then Lift[i][j]
-    {
-        const int ROW = 2 * Np + NFN;
-        std::vector<double> img(static_cast<size_t>(ROW) * Np);
-        for (int i = 0; i < Np; ++i) {
-            for (int m = 0; m < Np; ++m) {
-                img[static_cast<size_t>(i) * ROW + 2 * m] = d.Dr[i * Np + m];
-                img[static_cast<size_t>(i) * ROW + 2 * m + 1] = d.Ds[i * Np + m];
-            }
-            for (int j = 0; j < NFN; ++j) img[static_cast<size_t>(i) * ROW + 2 * Np + j] = d.Lift[i * NFN + j];
-        }
-        s->ops.upload(img, s->bytes, "ops upload");
-        s->mass.upload(M, s->bytes, "mass upload");
-    }
-
-    // ---- gather offsets: reference numbering (n' + Np k') -> n' ld + slot(k'), as (NFN, K) rows
-    {
-        std::vector<int> rows(nFaceNodes);
-        const int* perm = s->permHost.empty() ? nullptr : s->permHost.data();
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < NFN; ++j) {
-                const int v = d.vmapP[static_cast<size_t>(k) * NFN + j];
-                const int n2 = v % Np, k2 = v / Np;
-                rows[static_cast<size_t>(j) * K + k] = static_cast<int>(n2 * ld + (perm ? perm[k2] : k2));
-            }
-        s->uploadRowsT<int>(rows.data(), s->vmapP.p, s->istage.p, NFN);
-    }
+    for (int r = 0; r < t.geoRows; ++r) s->uploadRows(t.geo[r], s->ageo.p + r * ld, 1);
+    s->uploadRows(t.jac, s->jac.p, 1);
+    s->uploadRows(t.kap.data(), s->kap.p, 1);
+    s->uploadRows(t.wts.data(), s->wts.p, t.Np);
+    s->ops.upload(t.ops, s->bytes, "ops upload");
+    s->mass.upload(t.mass, s->bytes, "mass upload");
+    bdg_dev::uploadRows(s->rowLayout(), t.kinds.data(), s->kind.p, s->bstage.p, t.NFN);
+    bdg_dev::uploadRows(s->rowLayout(), t.offP.data(), s->vmapP.p, s->istage.p, t.NFN);
     s->istage.release();
     s->bstage.release();
     return s.release();
 }
 
-// ---- the quadrilateral family: the same handle, filled for poisson2d_quad_kernel.hpp
+// Host tables, then the device: every refusal that needs no device comes first.
+bdg_poisson2d* create(const bdg_poisson2d_desc& d, pt::Family family) {
+    const bool quad = family == pt::kQuadrilaterals;
+    const bdg_dev::PoissonKernelTable* kt = quad ? bdg_dev::poisson_quad_kernel_table(d.order) : bdg_dev::poisson_kernel_table(d.order);
+    std::vector<int> fmask;
+    if (kt)
+        for (int f = 0; f < (quad ? 4 : 3); ++f)
+            for (int n = 0; n < kt->Nfp; ++n) fmask.push_back(kt->fmask(f, n));
+    const pt::Tables t = pt::build(d, family, fmask);
 
-// D1 | l0 | lN from Dr = D1 (x) I, Ds = I (x) D1 and the face-wise lift, each held to 1e-13 max|entry| as sw2d_quad_device.hip does.
-std::vector<double> quadTensorOps(const std::string& fn, int N, const double* Dr, const double* Ds, const double* Lift) {
-    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
-    std::vector<double> ops(static_cast<size_t>(Nq) * Nq + 2 * Nq);
-    double* D1 = ops.data();
-    double* l0 = D1 + Nq * Nq;
-    double* lN = l0 + Nq;
-    for (int j = 0; j < Nq; ++j)
-        for (int m = 0; m < Nq; ++m) D1[j * Nq + m] = Dr[static_cast<size_t>(Nq * j) * Np + Nq * m];
-    for (int i = 0; i < Nq; ++i) l0[i] = Lift[static_cast<size_t>(i) * NFN];
-    for (int j = 0; j < Nq; ++j) lN[j] = Lift[static_cast<size_t>(Nq * j) * NFN + Nq];
-    double maxD = 0.0, maxL = 0.0, errD = 0.0, errL = 0.0;
-    for (size_t i = 0; i < static_cast<size_t>(Np) * Np; ++i) maxD = std::max({maxD, std::fabs(Dr[i]), std::fabs(Ds[i])});
-    for (size_t i = 0; i < static_cast<size_t>(Np) * NFN; ++i) maxL = std::max(maxL, std::fabs(Lift[i]));
-    for (int j = 0; j < Nq; ++j)
-        for (int i = 0; i < Nq; ++i) {
-            const size_t row = static_cast<size_t>(Nq * j + i);
-            for (int jj = 0; jj < Nq; ++jj)
-                for (int ii = 0; ii < Nq; ++ii) {
-                    const int col = Nq * jj + ii;
-                    errD = std::max(errD, std::fabs(Dr[row * Np + col] - (ii == i ? D1[j * Nq + jj] : 0.0)));
-                    errD = std::max(errD, std::fabs(Ds[row * Np + col] - (jj == j ? D1[i * Nq + ii] : 0.0)));
-                }
-            for (int q = 0; q < Nq; ++q) {
-                errL = std::max(errL, std::fabs(Lift[row * NFN + q] - (q == j ? l0[i] : 0.0)));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + Nq + q] - (q == i ? lN[j] : 0.0)));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + 2 * Nq + q] - (q == j ? lN[i] : 0.0)));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + 3 * Nq + q] - (q == i ? l0[j] : 0.0)));
-            }
-        }
-    if (!(maxD > 0.0) || !(maxL > 0.0) || !(errD <= 1e-13 * maxD) || !(errL <= 1e-13 * maxL))
-        throw arg_error(fn + ": Dr, Ds and Lift are not the tensor operators of the Gauss-Lobatto quadrilateral (D1 (x) I, I (x) D1, "
-                             "face-wise lifts); the quadrilateral kernels have no dense-operator form");
-    return ops;
-}
-
-// M = Vinv^T Vinv (Np, Np) and its 1-D factor M1 (Nq, Nq) with M = M1 (x) M1, held to 1e-12 max|entry|.
-void quadMassFactors(const std::string& fn, int N, const double* Vinv, std::vector<double>& M, std::vector<double>& M1) {
-    const int Nq = N + 1, Np = Nq * Nq;
-    M.assign(static_cast<size_t>(Np) * Np, 0.0);
-    for (int m = 0; m < Np; ++m)
-        for (int i = 0; i < Np; ++i) {
-            const double a = Vinv[static_cast<size_t>(m) * Np + i];
-            for (int j = 0; j < Np; ++j) M[static_cast<size_t>(i) * Np + j] += a * Vinv[static_cast<size_t>(m) * Np + j];
-        }
-    if (!(M[0] > 0.0)) throw arg_error(fn + ": Vinv does not give a positive definite mass matrix");
-    const double m00 = std::sqrt(M[0]);
-    M1.assign(static_cast<size_t>(Nq) * Nq, 0.0);
-    for (int a = 0; a < Nq; ++a)
-        for (int b = 0; b < Nq; ++b) M1[a * Nq + b] = M[static_cast<size_t>(Nq * a) * Np + Nq * b] / m00;
-    double maxM = 0.0, err = 0.0;
-    for (int j = 0; j < Nq; ++j)
-        for (int i = 0; i < Nq; ++i)
-            for (int jj = 0; jj < Nq; ++jj)
-                for (int ii = 0; ii < Nq; ++ii) {
-                    const double v = M[static_cast<size_t>(Nq * j + i) * Np + Nq * jj + ii];
-                    maxM = std::max(maxM, std::fabs(v));
-                    err = std::max(err, std::fabs(v - M1[j * Nq + jj] * M1[i * Nq + ii]));
-                }
-    if (!(err <= 1e-12 * maxM))
-        throw arg_error(fn + ": (V V^T)^-1 is not the tensor product of a 1-D mass matrix with itself (Vinv = V1^-1 (x) V1^-1 "
-                             "expected); the mass product is sum-factorised");
-}
-
-// Breadth-first numbering from the face-neighbour graph of a quadrilateral mesh: perm[k] = device slot.
-std::vector<int> quadBfsOrder(const int* vmapP, int K, int Np, int Nq) {
-    std::vector<int> perm(K, -1), frontier, nextFrontier;
-    int next = 0;
-    for (int seed = 0; seed < K; ++seed) {
-        if (perm[seed] >= 0) continue;
-        perm[seed] = next++;
-        frontier.assign(1, seed);
-        while (!frontier.empty()) {
-            nextFrontier.clear();
-            for (int k : frontier)
-                for (int f = 0; f < 4; ++f) {
-                    const int k2 = vmapP[(static_cast<size_t>(k) * 4 + f) * Nq] / Np;
-                    if (perm[k2] < 0) {
-                        perm[k2] = next++;
-                        nextFrontier.push_back(k2);
-                    }
-                }
-            frontier.swap(nextFrontier);
-        }
-    }
-    return perm;
-}
-
-bdg_poisson2d* createQuadSolver(const bdg_poisson2d_desc& d) {
-    const std::string fn = "bdg_poisson2d_create_quad";
-    if (d.order < 1 || d.order > bdg_dev::kPoissonQuadMaxOrder)
-        throw arg_error(fn + ": order must be 1.." + std::to_string(bdg_dev::kPoissonQuadMaxOrder));
-    if (d.flags & BDG_SW2D_NODAL_GEOMETRY)
-        throw arg_error(fn + ": per-node geometry is not supported (quadrilaterals in parallelogram form only)");
-    if (!d.kappa_elements && (!(d.kappa > 0.0) || !std::isfinite(d.kappa))) throw arg_error(fn + ": kappa must be finite and > 0");
-    requireSigma(d.sigma, fn.c_str());
-    if (!(d.tau_scale >= 0.0) || !std::isfinite(d.tau_scale)) throw arg_error(fn + ": tau_scale must be finite and >= 0");
-    if (d.num_elements < 1) throw arg_error(fn + ": num_elements must be >= 1");
-    if (!d.Dr || !d.Ds || !d.Lift || !d.Vinv || !d.rx || !d.sx || !d.ry || !d.sy || !d.J || !d.nx || !d.ny || !d.Fscale ||
-        !d.vmapM || !d.vmapP)
-        throw arg_error(fn + ": a required table pointer is NULL");
-    if (d.num_dirichlet < 0 || (d.num_dirichlet > 0 && !d.mapD)) throw arg_error(fn + ": bad Dirichlet-node list");
-    const bdg_dev::PoissonKernelTable* kt = bdg_dev::poisson_quad_kernel_table(d.order);
-    if (!kt) throw arg_error(fn + ": no kernels compiled for this order");
-
-    const int N = d.order, Nq = N + 1, Np = kt->Np, NFN = 4 * Nq, K = d.num_elements;
-    const long long ld = (static_cast<long long>(K) + 63) / 64 * 64;
-    if (static_cast<long long>(Np) * ld >= (1LL << 31)) throw arg_error(fn + ": Np*K exceeds 2^31 nodes (32-bit gather offsets)");
-    double kappaMax = 0.0;
-    if (d.kappa_elements) {
-        for (int k = 0; k < K; ++k) {
-            if (!(d.kappa_elements[k] > 0.0) || !std::isfinite(d.kappa_elements[k]))
-                throw arg_error(fn + ": every kappa must be finite and > 0");
-            kappaMax = std::max(kappaMax, d.kappa_elements[k]);
-        }
-    } else {
-        kappaMax = d.kappa;
-    }
-    const std::vector<double> opsHost = quadTensorOps(fn, N, d.Dr, d.Ds, d.Lift);
-    std::vector<double> M, M1;
-    quadMassFactors(fn, N, d.Vinv, M, M1);
-
-    // ---- the index tables, on the host
-    const size_t nFaceNodes = static_cast<size_t>(NFN) * K;
-    const long long totalNodes = static_cast<long long>(Np) * K;
-    for (int k = 0; k < K; ++k)
-        for (int f = 0; f < 4; ++f)
-            for (int n = 0; n < Nq; ++n)
-                if (d.vmapM[(static_cast<size_t>(k) * 4 + f) * Nq + n] != kt->fmask(f, n) + Np * k)
-                    throw arg_error(fn + ": vmapM is not the Gauss-Lobatto face numbering (faces s=-1, r=+1, s=+1, r=-1)");
-    for (size_t i = 0; i < nFaceNodes; ++i)
-        if (d.vmapP[i] < 0 || d.vmapP[i] >= totalNodes) throw arg_error(fn + ": vmapP entry out of range");
-    std::vector<unsigned char> kinds(nFaceNodes); // (NFN, K) rows
-    for (int k = 0; k < K; ++k)
-        for (int j = 0; j < NFN; ++j) {
-            const size_t i = static_cast<size_t>(k) * NFN + j;
-            kinds[static_cast<size_t>(j) * K + k] = d.vmapP[i] == d.vmapM[i] ? bdg_dev::PK_NEUMANN : bdg_dev::PK_INTERIOR;
-        }
-    for (int i = 0; i < d.num_dirichlet; ++i) {
-        const int m = d.mapD[i];
-        if (m < 0 || static_cast<size_t>(m) >= nFaceNodes) throw arg_error(fn + ": Dirichlet-node index out of range");
-        unsigned char& e = kinds[static_cast<size_t>(m % NFN) * K + m / NFN];
-        if (e == bdg_dev::PK_INTERIOR) throw arg_error(fn + ": a mapD entry is not a boundary face node");
-        e = bdg_dev::PK_DIRICHLET;
-    }
-
-    // ---- geometry: the parallelogram form of sw2d_quad_device.hip (metric terms and J constant per element, nx, ny, Fscale per
-    // face, to 1e-10 relative), 16 numbers per element, and J_k
-    std::vector<double> ag(static_cast<size_t>(16) * K), jacHost(K);
-    {
-        std::atomic<bool> para{true}, positive{true};
-        const double* met[4] = {d.rx, d.sx, d.ry, d.sy};
-        const double* fg[3] = {d.nx, d.ny, d.Fscale};
-        blitzdg::detail::parallelFor(K, [&](int k) {
-            double scale = 0.0;
-            for (int a = 0; a < 4; ++a)
-                for (int n = 0; n < Np; ++n) scale = std::max(scale, std::fabs(met[a][static_cast<size_t>(n) * K + k]));
-            for (int a = 0; a < 5; ++a) {
-                const double* tab = a < 4 ? met[a] : d.J;
-                double mean = 0.0;
-                for (int n = 0; n < Np; ++n) mean += tab[static_cast<size_t>(n) * K + k];
-                mean /= Np;
-                const double sc = a < 4 ? scale : std::fabs(mean);
-                for (int n = 0; n < Np; ++n)
-                    if (!(std::fabs(tab[static_cast<size_t>(n) * K + k] - mean) <= 1e-10 * sc)) para = false;
-                if (a < 4) ag[static_cast<size_t>(a) * K + k] = mean;
-                else jacHost[k] = mean;
-            }
-            if (!(jacHost[k] > 0.0)) positive = false;
-            for (int c = 0; c < 3; ++c)
-                for (int f = 0; f < 4; ++f) {
-                    double mean = 0.0, sc = 0.0;
-                    for (int n = 0; n < Nq; ++n) {
-                        const double v = fg[c][static_cast<size_t>(f * Nq + n) * K + k];
-                        mean += v;
-                        sc = std::max(sc, std::fabs(v));
-                    }
-                    mean /= Nq;
-                    if (c < 2) sc = 1.0;
-                    for (int n = 0; n < Nq; ++n)
-                        if (!(std::fabs(fg[c][static_cast<size_t>(f * Nq + n) * K + k] - mean) <= 1e-10 * sc)) para = false;
-                    ag[static_cast<size_t>(4 + 4 * c + f) * K + k] = mean;
-                }
-        });
-        if (!para)
-            throw arg_error(fn + ": the mesh is not in parallelogram form (metric terms constant per element to 1e-10). On a general "
-                                 "bilinear quadrilateral the variable metric does not commute with the mass matrix, M A is not "
-                                 "symmetric and conjugate gradients has no licence (DESIGN.md 3.13)");
-        if (!positive) throw arg_error(fn + ": J must be positive");
-    }
-    double fscaleMax = 0.0;
-    for (size_t i = 0; i < nFaceNodes; ++i) fscaleMax = std::max(fscaleMax, std::fabs(d.Fscale[i]));
-    std::vector<double> colsum(Np, 0.0);
-    for (int i = 0; i < Np; ++i)
-        for (int j = 0; j < Np; ++j) colsum[i] += M[static_cast<size_t>(j) * Np + i];
-    std::vector<double> wtsHost(static_cast<size_t>(Np) * K);
-    for (int i = 0; i < Np; ++i)
-        for (int k = 0; k < K; ++k) wtsHost[static_cast<size_t>(i) * K + k] = colsum[i] * jacHost[k];
-    double area = 0.0, refArea = 0.0;
-    for (int i = 0; i < Np; ++i) refArea += colsum[i];
-    for (int k = 0; k < K; ++k) area += refArea * jacHost[k];
-
+    const std::string fn = quad ? "bdg_poisson2d_create_quad" : "bdg_poisson2d_create";
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         throw hip_error(fn + ": no HIP device available (the elliptic solver has no CPU fallback)");
     if (d.device < 0 || d.device >= ndev) throw arg_error(fn + ": device ordinal out of range");
+    return createFrom(t, kt, quad ? bdg_dev::poisson_quad_tile_elements(d.order) : 64, d.sigma, d.device);
+}
 
-    auto s = std::unique_ptr<bdg_poisson2d>(new bdg_poisson2d());
-    s->kt = kt;
-    s->N = N; s->Np = Np; s->Nfp = Nq; s->NFN = NFN; s->K = K; s->ld = ld;
-    s->tileElems = bdg_dev::poisson_quad_tile_elements(N);
-    s->device = d.device;
-    s->sigma = d.sigma;
-    s->tau = (d.tau_scale > 0.0 ? d.tau_scale : 1.0) * Np * fscaleMax / 2.0 * kappaMax;
-    s->area = area;
-    s->hasDirichlet = d.num_dirichlet > 0;
-    // Sw2dQuadSolver never renumbers: the caller's order stays unless BDG_SW2D_REORDER asks for the breadth-first one
-    if ((d.flags & BDG_SW2D_REORDER) != 0 && !(d.flags & BDG_SW2D_KEEP_ORDER)) s->permHost = quadBfsOrder(d.vmapP, K, Np, Nq);
-
-    s->use();
-    hipCheck(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
-    hipStream_t st = s->stream;
-    const size_t pl = s->planeSize();
-    for (DevBuf<double>* b : {&s->x, &s->r, &s->s, &s->dirA, &s->dirB, &s->Ap, &s->w, &s->wts}) b->alloc(pl, s->bytes, st);
-    s->q.alloc(2 * pl, s->bytes, st);
-    s->ageo.alloc(16 * static_cast<size_t>(ld), s->bytes, st);
-    s->jac.alloc(static_cast<size_t>(ld), s->bytes, st);
-    s->kap.alloc(static_cast<size_t>(ld), s->bytes, st);
-    s->vmapP.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
-    s->kind.alloc(static_cast<size_t>(NFN) * ld, s->bytes, st);
-    s->stage.alloc(static_cast<size_t>(std::max({Np, NFN, 16})) * K, s->bytes);
-    s->istage.alloc(nFaceNodes, s->bytes);
-    s->bstage.alloc(nFaceNodes, s->bytes);
-    s->partial.alloc(static_cast<size_t>(std::max(s->tiles(), s->reduceBlocks())), s->bytes, st);
-    s->scal.alloc(bdg_dev::PS_COUNT, s->bytes, st);
-    if (!s->permHost.empty()) s->perm.upload(s->permHost, s->bytes, "perm upload");
-
-    s->uploadRows(ag.data(), s->ageo.p, 16);
-    s->uploadRows(jacHost.data(), s->jac.p, 1);
-    {
-        std::vector<double> kapHost(K, d.kappa);
-        if (d.kappa_elements) kapHost.assign(d.kappa_elements, d.kappa_elements + K);
-        s->uploadRows(kapHost.data(), s->kap.p, 1);
+// The descriptor of a provisioner's tables (TriangleNodesProvisioner or QuadNodesProvisioner), and the solver from it. Without a
+// mapD and with num_dirichlet < 0 the Dirichlet nodes are the provisioner's wall and Dirichlet nodes.
+template <class Provisioner>
+bdg_poisson2d* createFromProvisioner(const Provisioner& p, pt::Family family, const int* mapD, int num_dirichlet, double kappa,
+                                     const double* kappa_elements, double sigma, double tau_scale, int device, int flags) {
+    bdg_poisson2d_desc d{};
+    d.order = p.get_NOrder();
+    d.num_elements = p.get_NumElements();
+    d.Dr = p.get_Dr().data(); d.Ds = p.get_Ds().data(); d.Lift = p.get_Lift().data(); d.Vinv = p.get_Vinv().data();
+    d.rx = p.get_rx().data(); d.sx = p.get_sx().data(); d.ry = p.get_ry().data(); d.sy = p.get_sy().data();
+    d.J = p.get_J().data();
+    d.nx = p.get_nx().data(); d.ny = p.get_ny().data(); d.Fscale = p.get_Fscale().data();
+    d.vmapM = p.get_vmapM().data(); d.vmapP = p.get_vmapP().data();
+    std::vector<int> walls;
+    if (!mapD && num_dirichlet < 0) {
+        const auto& bc = p.get_bcMap();
+        for (int tag : {static_cast<int>(blitzdg::BCTag::Wall), static_cast<int>(blitzdg::BCTag::Dirichlet)}) {
+            const auto it = bc.find(tag);
+            if (it != bc.end()) walls.insert(walls.end(), it->second.begin(), it->second.end());
+        }
+        d.mapD = walls.data();
+        d.num_dirichlet = static_cast<int>(walls.size());
+    } else {
+        d.mapD = mapD;
+        d.num_dirichlet = num_dirichlet;
     }
-    s->uploadRows(wtsHost.data(), s->wts.p, Np);
-    s->uploadRowsT<unsigned char>(kinds.data(), s->kind.p, s->bstage.p, NFN);
-    s->ops.upload(opsHost, s->bytes, "ops upload");
-    s->mass.upload(M1, s->bytes, "mass upload");
-
-    // ---- gather offsets: reference numbering (n' + Np k') -> n' ld + slot(k'), as (NFN, K) rows; a boundary node gathers itself
-    {
-        std::vector<int> rows(nFaceNodes);
-        const int* perm = s->permHost.empty() ? nullptr : s->permHost.data();
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < NFN; ++j) {
-                const int v = d.vmapP[static_cast<size_t>(k) * NFN + j];
-                const int n2 = v % Np, k2 = v / Np;
-                rows[static_cast<size_t>(j) * K + k] = static_cast<int>(n2 * ld + (perm ? perm[k2] : k2));
-            }
-        s->uploadRowsT<int>(rows.data(), s->vmapP.p, s->istage.p, NFN);
-    }
-    s->istage.release();
-    s->bstage.release();
-    return s.release();
+    d.kappa = kappa; d.kappa_elements = kappa_elements; d.sigma = sigma; d.tau_scale = tau_scale;
+    d.device = device; d.flags = flags;
+    return create(d, family);
 }
 
 void requireSolver(const bdg_poisson2d* s, const char* fn) {
@@ -738,7 +336,7 @@ extern "C" {
 int bdg_poisson2d_create(const bdg_poisson2d_desc* desc, bdg_poisson2d** out) {
     return guard([&] {
         if (!desc || !out) throw arg_error("bdg_poisson2d_create: NULL argument");
-        *out = createSolver(*desc);
+        *out = create(*desc, pt::kTriangles);
     });
 }
 
@@ -747,38 +345,15 @@ int bdg_poisson2d_create_from_nodes(const bdg_trinodes* nodes, const int* mapD, 
                                     bdg_poisson2d** out) {
     return guard([&] {
         if (!nodes || !out) throw arg_error("bdg_poisson2d_create_from_nodes: NULL argument");
-        const blitzdg::TriangleNodesProvisioner& p = nodes->prov;
-        bdg_poisson2d_desc d{};
-        d.order = p.get_NOrder();
-        d.num_elements = p.get_NumElements();
-        d.Dr = p.get_Dr().data(); d.Ds = p.get_Ds().data(); d.Lift = p.get_Lift().data(); d.Vinv = p.get_Vinv().data();
-        d.rx = p.get_rx().data(); d.sx = p.get_sx().data(); d.ry = p.get_ry().data(); d.sy = p.get_sy().data();
-        d.J = p.get_J().data();
-        d.nx = p.get_nx().data(); d.ny = p.get_ny().data(); d.Fscale = p.get_Fscale().data();
-        d.vmapM = p.get_vmapM().data(); d.vmapP = p.get_vmapP().data();
-        std::vector<int> walls;
-        if (!mapD && num_dirichlet < 0) {
-            const auto& bc = p.get_bcMap();
-            for (int tag : {static_cast<int>(blitzdg::BCTag::Wall), static_cast<int>(blitzdg::BCTag::Dirichlet)}) {
-                const auto it = bc.find(tag);
-                if (it != bc.end()) walls.insert(walls.end(), it->second.begin(), it->second.end());
-            }
-            d.mapD = walls.data();
-            d.num_dirichlet = static_cast<int>(walls.size());
-        } else {
-            d.mapD = mapD;
-            d.num_dirichlet = num_dirichlet;
-        }
-        d.kappa = kappa; d.kappa_elements = kappa_elements; d.sigma = sigma; d.tau_scale = tau_scale;
-        d.device = device; d.flags = flags;
-        *out = createSolver(d);
+        *out = createFromProvisioner(nodes->prov, pt::kTriangles, mapD, num_dirichlet, kappa, kappa_elements, sigma, tau_scale, device,
+                                     flags);
     });
 }
 
 int bdg_poisson2d_create_quad(const bdg_poisson2d_desc* desc, bdg_poisson2d** out) {
     return guard([&] {
         if (!desc || !out) throw arg_error("bdg_poisson2d_create_quad: NULL argument");
-        *out = createQuadSolver(*desc);
+        *out = create(*desc, pt::kQuadrilaterals);
     });
 }
 
@@ -787,31 +362,8 @@ int bdg_poisson2d_create_from_quadnodes(const bdg_quadnodes* nodes, const int* m
                                         bdg_poisson2d** out) {
     return guard([&] {
         if (!nodes || !out) throw arg_error("bdg_poisson2d_create_from_quadnodes: NULL argument");
-        const blitzdg::QuadNodesProvisioner& p = nodes->prov;
-        bdg_poisson2d_desc d{};
-        d.order = p.get_NOrder();
-        d.num_elements = p.get_NumElements();
-        d.Dr = p.get_Dr().data(); d.Ds = p.get_Ds().data(); d.Lift = p.get_Lift().data(); d.Vinv = p.get_Vinv().data();
-        d.rx = p.get_rx().data(); d.sx = p.get_sx().data(); d.ry = p.get_ry().data(); d.sy = p.get_sy().data();
-        d.J = p.get_J().data();
-        d.nx = p.get_nx().data(); d.ny = p.get_ny().data(); d.Fscale = p.get_Fscale().data();
-        d.vmapM = p.get_vmapM().data(); d.vmapP = p.get_vmapP().data();
-        std::vector<int> walls;
-        if (!mapD && num_dirichlet < 0) {
-            const auto& bc = p.get_bcMap();
-            for (int tag : {static_cast<int>(blitzdg::BCTag::Wall), static_cast<int>(blitzdg::BCTag::Dirichlet)}) {
-                const auto it = bc.find(tag);
-                if (it != bc.end()) walls.insert(walls.end(), it->second.begin(), it->second.end());
-            }
-            d.mapD = walls.data();
-            d.num_dirichlet = static_cast<int>(walls.size());
-        } else {
-            d.mapD = mapD;
-            d.num_dirichlet = num_dirichlet;
-        }
-        d.kappa = kappa; d.kappa_elements = kappa_elements; d.sigma = sigma; d.tau_scale = tau_scale;
-        d.device = device; d.flags = flags;
-        *out = createQuadSolver(d);
+        *out = createFromProvisioner(nodes->prov, pt::kQuadrilaterals, mapD, num_dirichlet, kappa, kappa_elements, sigma, tau_scale,
+                                     device, flags);
     });
 }
 

@@ -20,8 +20,10 @@
 // After bdg_sw2d_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_drifter_kernel.hpp).
 #include "../host/capi_internal.hpp"
 #include "../host/element_order.hpp"
+#include "../host/element_tables.hpp"
 #include "../host/parallel_for.hpp"
 #include "blitzdg/LSERK4.hpp"
+#include "row_transfer.hpp"
 #include "run_records.hpp"
 #include "sw2d_launch.hpp"
 #include "sw2d_launch_host.hpp"
@@ -139,26 +141,6 @@ __global__ __launch_bounds__(256) void sw2d_reduce_kernel(const double* __restri
         out2[0] = sBad ? nan : sA[0];
         out2[1] = sBad ? nan : sB[0];
     }
-}
-
-// (rows, K) caller-order image <-> padded, optionally renumbered device planes.
-// perm[k_caller] = device slot (NULL = identity). One thread per (row, element).
-template <typename T>
-__global__ void scatter_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, int rows, int K, long long ld,
-                                    const int* __restrict__ perm) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(rows) * K) return;
-    const long long r = t / K, k = t % K;
-    dst[r * ld + (perm ? perm[k] : k)] = src[t];
-}
-
-template <typename T>
-__global__ void gather_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, int rows, int K, long long ld,
-                                   const int* __restrict__ perm) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= static_cast<long long>(rows) * K) return;
-    const long long r = t / K, k = t % K;
-    dst[t] = src[r * ld + (perm ? perm[k] : k)];
 }
 
 // ---- bandwidth probes (measurement aids, not part of the solver)
@@ -405,25 +387,10 @@ struct bdg_sw2d {
     size_t planeSize() const { return static_cast<size_t>(Np) * static_cast<size_t>(ld); }
     const int* permDev() const { return perm.p; }
 
-    // host (rows, K) caller order -> device planes (padded / renumbered)
-    void uploadRows(const double* host, double* dev, int rows) {
-        const size_t n = static_cast<size_t>(rows) * K;
-        hipCheck(hipMemcpyAsync(stage.p, host, n * sizeof(double), hipMemcpyHostToDevice, stream), "H2D copy");
-        const unsigned grid = static_cast<unsigned>((n + 255) / 256);
-        hipLaunchKernelGGL((bdg_dev::scatter_rows_kernel<double>), dim3(grid), dim3(256), 0, stream, stage.p, dev, rows,
-                           K, ld, permDev());
-        hipCheck(hipGetLastError(), "scatter_rows_kernel");
-        hipCheck(hipStreamSynchronize(stream), "upload sync"); // staging buffer is reused
-    }
-    void downloadRows(const double* dev, double* host, int rows) {
-        const size_t n = static_cast<size_t>(rows) * K;
-        const unsigned grid = static_cast<unsigned>((n + 255) / 256);
-        hipLaunchKernelGGL((bdg_dev::gather_rows_kernel<double>), dim3(grid), dim3(256), 0, stream, dev, stage.p, rows,
-                           K, ld, permDev());
-        hipCheck(hipGetLastError(), "gather_rows_kernel");
-        hipCheck(hipMemcpyAsync(host, stage.p, n * sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
-        hipCheck(hipStreamSynchronize(stream), "download sync");
-    }
+    // host (rows, K) caller order <-> device planes (padded / renumbered): row_transfer.hpp
+    bdg_dev::RowLayout rowLayout() const { return {K, ld, permDev(), stream}; }
+    void uploadRows(const double* host, double* dev, int rows) { bdg_dev::uploadRows(rowLayout(), host, dev, stage.p, rows); }
+    void downloadRows(const double* dev, double* host, int rows) { bdg_dev::downloadRows(rowLayout(), dev, host, stage.p, rows); }
     // one (Np, K) host array per field, to / from the nf consecutive device planes at `dev`
     void uploadFields(const double* const* host, double* dev) {
         for (int c = 0; c < nf; ++c) uploadRows(host[c], dev + c * planeSize(), Np);
@@ -1184,35 +1151,6 @@ struct bdg_sw2d {
 
 namespace {
 
-// True when the metric terms are constant per element and the face terms constant per
-// face (straight-sided elements), to round-off: then one value per element/face suffices.
-// The tables themselves carry round-off from Dr*x on small elements (relative ~1e-16 * |Dr| / h:
-// 5e-11 at N=8 on a 500x250-cell box), so the test is 1e-8: far above that noise, far below any
-// real curvature.
-bool geometryIsAffine(const bdg_sw2d_desc& d, int Np, int Nfp, int K) {
-    const double tol = 1e-8;
-    std::atomic<bool> ok{true};
-    blitzdg::detail::parallelFor(K, [&](int k) {
-        const double scale = std::fabs(d.rx[k]) + std::fabs(d.sx[k]) + std::fabs(d.ry[k]) + std::fabs(d.sy[k]);
-        for (int n = 1; n < Np; ++n) {
-            const size_t o = static_cast<size_t>(n) * K + k;
-            if (std::fabs(d.rx[o] - d.rx[k]) > tol * scale || std::fabs(d.sx[o] - d.sx[k]) > tol * scale ||
-                std::fabs(d.ry[o] - d.ry[k]) > tol * scale || std::fabs(d.sy[o] - d.sy[k]) > tol * scale)
-                ok = false;
-        }
-        for (int f = 0; f < 3; ++f) {
-            const size_t o0 = static_cast<size_t>(f) * Nfp * K + k;
-            for (int n = 1; n < Nfp; ++n) {
-                const size_t o = o0 + static_cast<size_t>(n) * K;
-                if (std::fabs(d.nx[o] - d.nx[o0]) > tol || std::fabs(d.ny[o] - d.ny[o0]) > tol ||
-                    std::fabs(d.Fscale[o] - d.Fscale[o0]) > tol * std::fabs(d.Fscale[o0]))
-                    ok = false;
-            }
-        }
-    });
-    return ok;
-}
-
 // C = A (n x n) * B (n x c), row-major.
 std::vector<double> matmulHost(const double* A, const double* B, int n, int c) {
     std::vector<double> C(static_cast<size_t>(n) * c, 0.0);
@@ -1300,7 +1238,12 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
     const bool reorder = (d.flags & BDG_SW2D_REORDER) != 0 ||
                          (!(d.flags & BDG_SW2D_KEEP_ORDER) && eo::renumberingWanted(d.vmapP, K, Np, Nfp, d.order));
     if (reorder) s->permHost = eo::renumbering(d.vmapP, K, Np, Nfp, eo::patchSetting());
-    s->affine = !(d.flags & BDG_SW2D_NODAL_GEOMETRY) && geometryIsAffine(d, Np, Nfp, K);
+    // Affine: the metric terms are constant per element and the face terms constant per face (straight-sided elements), to
+    // round-off: then one value per element/face suffices. The tables themselves carry round-off from Dr*x on small elements
+    // (relative ~1e-16 * |Dr| / h: 5e-11 at N=8 on a 500x250-cell box), so the test (element_tables.hpp) is 1e-8: far above
+    // that noise, far below any real curvature. J is not held to it here.
+    s->affine = !(d.flags & BDG_SW2D_NODAL_GEOMETRY) &&
+                blitzdg::element_tables::trianglesAreAffine({d.rx, d.sx, d.ry, d.sy, nullptr, d.nx, d.ny, d.Fscale}, Np, Nfp, K);
     // Non-affine tables: the matrix-core kernel with per-node geometry (every order). BDG_SW2D_NODAL_VECTOR=1 keeps the
     // round-1 vector kernel (one lane per element, N <= 6) for A/B measurements and cross-checks.
     s->nodalMfma = !s->affine && !(env::nodalVector() && kt->ldsDoubles != 0);
@@ -1501,13 +1444,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
             int& e = rows[static_cast<size_t>(j) * K + k];
             if (e >= 0) e = -(e + 1);
         }
-        hipCheck(hipMemcpyAsync(s->istage.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s->stream),
-                 "vmapP upload");
-        const unsigned grid = static_cast<unsigned>((rows.size() + 255) / 256);
-        hipLaunchKernelGGL((bdg_dev::scatter_rows_kernel<int>), dim3(grid), dim3(256), 0, s->stream, s->istage.p,
-                           s->vmapP.p, NFN, K, ld, s->permDev());
-        hipCheck(hipGetLastError(), "scatter_rows_kernel<int>");
-        hipCheck(hipStreamSynchronize(s->stream), "vmapP sync");
+        bdg_dev::uploadRows(s->rowLayout(), rows.data(), s->vmapP.p, s->istage.p, NFN);
 
         // ---- face links: every face of every element must reproduce its Nfp rows above exactly (address and wall
         //      flag); one face that does not (periodic maps, non-conforming meshes, hand-made tables) keeps the whole
@@ -1547,12 +1484,7 @@ bdg_sw2d* createSolver(const bdg_sw2d_desc& d) {
             if (ok) {
                 s->faceLink.alloc(static_cast<size_t>(3) * ld, s->bytes);
                 hipCheck(hipMemsetAsync(s->faceLink.p, 0, s->faceLink.n * sizeof(int), s->stream), "hipMemset");
-                hipCheck(hipMemcpyAsync(s->istage.p, links.data(), links.size() * sizeof(int), hipMemcpyHostToDevice, s->stream),
-                         "face link upload");
-                hipLaunchKernelGGL((bdg_dev::scatter_rows_kernel<int>), dim3(static_cast<unsigned>((links.size() + 255) / 256)),
-                                   dim3(256), 0, s->stream, s->istage.p, s->faceLink.p, 3, K, ld, s->permDev());
-                hipCheck(hipGetLastError(), "scatter_rows_kernel<int>");
-                hipCheck(hipStreamSynchronize(s->stream), "face link sync");
+                bdg_dev::uploadRows(s->rowLayout(), links.data(), s->faceLink.p, s->istage.p, 3);
             }
         }
     }

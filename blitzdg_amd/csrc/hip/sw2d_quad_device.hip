@@ -1,6 +1,6 @@
 // sw2d_quad_device.hip -- the device-resident quadrilateral sw2d solver behind the bdg_sw2dq_* C ABI
 // (include/blitzdg_hip.h). Host side: checks that Dr, Ds and Lift have the Gauss-Lobatto tensor form and extracts
-// their 1-D factors, chooses the geometry form, builds the gather index; then launches sw2d_quad_stage_kernel
+// their 1-D factors, chooses the geometry form (both: host/element_tables.hpp), builds the gather index; then launches sw2d_quad_stage_kernel
 // (sw2d_quad_kernel.hpp) on its own stream. One device; results come back in the caller's numbering.
 // Partitioned runs (bdg_sw2dq_set_partition / _comm_init) add the ghost exchange and the two-chain schedule of
 // partition_schedule.hpp on a second stream. A solver created with four fields (bdg_sw2dq_create_fields) launches
@@ -17,6 +17,7 @@
 // computeRhs io into ioOut.
 // After bdg_sw2dq_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2dq_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_quad_drifter_kernel.hpp).
+#include "../host/element_tables.hpp"
 #include "device_buffer.hpp"
 #include "partition_schedule.hpp"
 #include "run_records.hpp"
@@ -548,52 +549,6 @@ double maxAbs(const double* a, size_t n) {
     return m;
 }
 
-// Dr = D1 (x) I, Ds = I (x) D1 and the face-wise lift structure, each to 1e-13 max|entry|; returns the ops image.
-std::vector<double> tensorFactors(int N, const double* Dr, const double* Ds, const double* Lift) {
-    const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
-    std::vector<double> ops(Nq * Nq + 2 * Nq);
-    double* D1 = ops.data();
-    double* l0 = D1 + Nq * Nq;
-    double* lN = l0 + Nq;
-    for (int j = 0; j < Nq; ++j)
-        for (int m = 0; m < Nq; ++m) D1[j * Nq + m] = Dr[static_cast<size_t>(Nq * j) * Np + Nq * m];
-    for (int i = 0; i < Nq; ++i) l0[i] = Lift[static_cast<size_t>(i) * NFN + 0];          // face 0, q = j = 0
-    for (int j = 0; j < Nq; ++j) lN[j] = Lift[static_cast<size_t>(Nq * j) * NFN + Nq];    // face 1, q = i = 0
-    const double tolD = 1e-13 * std::max(maxAbs(Dr, static_cast<size_t>(Np) * Np), maxAbs(Ds, static_cast<size_t>(Np) * Np));
-    const double tolL = 1e-13 * maxAbs(Lift, static_cast<size_t>(Np) * NFN);
-    // (a zero table would pass a tolerance relative to its own largest entry)
-    if (!(tolD > 0.0) || !(tolL > 0.0))
-        throw arg_error("bdg_sw2dq_create: Dr / Ds or Lift is identically zero or not finite: these are not the operators of an "
-                        "element of order " + std::to_string(N));
-    double errD = 0.0, errL = 0.0;
-    for (int j = 0; j < Nq; ++j)
-        for (int i = 0; i < Nq; ++i) {
-            const size_t row = static_cast<size_t>(Nq * j + i);
-            for (int jj = 0; jj < Nq; ++jj)
-                for (int ii = 0; ii < Nq; ++ii) {
-                    const int col = Nq * jj + ii;
-                    const double er = (ii == i ? D1[j * Nq + jj] : 0.0), es = (jj == j ? D1[i * Nq + ii] : 0.0);
-                    errD = std::max(errD, std::fabs(Dr[row * Np + col] - er));
-                    errD = std::max(errD, std::fabs(Ds[row * Np + col] - es));
-                }
-            for (int q = 0; q < Nq; ++q) {
-                const double e0 = q == j ? l0[i] : 0.0, e1 = q == i ? lN[j] : 0.0;
-                const double e2 = q == j ? lN[i] : 0.0, e3 = q == i ? l0[j] : 0.0;
-                errL = std::max(errL, std::fabs(Lift[row * NFN + q] - e0));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + Nq + q] - e1));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + 2 * Nq + q] - e2));
-                errL = std::max(errL, std::fabs(Lift[row * NFN + 3 * Nq + q] - e3));
-            }
-        }
-    if (!(errD <= tolD))
-        throw arg_error("bdg_sw2dq_create: Dr / Ds are not the Gauss-Lobatto tensor operators D1 (x) I, I (x) D1 (deviation " +
-                        std::to_string(errD) + "); the quadrilateral kernel has no dense-operator form");
-    if (!(errL <= tolL))
-        throw arg_error("bdg_sw2dq_create: Lift does not have the face-wise tensor form of the Gauss-Lobatto element (deviation " +
-                        std::to_string(errL) + "); the quadrilateral kernel has no dense-operator form");
-    return ops;
-}
-
 bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
     const int N = d.order, K = d.num_elements;
     if (fields != 3 && fields != 4) throw arg_error("bdg_sw2dq_create: num_fields must be 3 or 4");
@@ -605,7 +560,7 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
     if (d.num_wall < 0 || (d.num_wall > 0 && !d.mapW)) throw arg_error("bdg_sw2dq_create: bad wall list");
     const int Nq = N + 1, Np = Nq * Nq, NFN = 4 * Nq;
     if (static_cast<long long>(Np) * (K + 64) >= (1LL << 31)) throw arg_error("bdg_sw2dq_create: mesh too large for int32 gathers");
-    std::vector<double> opsHost = tensorFactors(N, d.Dr, d.Ds, d.Lift);
+    std::vector<double> opsHost = blitzdg::element_tables::tensorOperators("bdg_sw2dq_create", N, d.Dr, d.Ds, d.Lift);
 
     if (d.vmapM) {
         for (int k = 0; k < K; ++k)
@@ -641,40 +596,13 @@ bdg_sw2dq* createQuad(const bdg_sw2dq_desc& d, int fields) {
             s->maxNeighbourHost[static_cast<size_t>(k)] = std::max(s->maxNeighbourHost[static_cast<size_t>(k)], v / Np);
         }
 
-    // geometry form: parallelograms (metric terms constant per element, nx, ny, Fscale per face, to 1e-10 relative)
+    // geometry form: parallelograms (metric terms constant per element, nx, ny, Fscale per face, to 1e-10 relative), else general
     bool para = (d.flags & BDG_SW2DQ_GENERAL_GEOMETRY) == 0;
     std::vector<double> ag;
     if (para) {
         ag.assign(static_cast<size_t>(16) * ld, 0.0);
-        const double* met[4] = {d.rx, d.sx, d.ry, d.sy};
-        const double* fg[3] = {d.nx, d.ny, d.Fscale};
-        for (int k = 0; k < K && para; ++k) {
-            double scale = 0.0;
-            for (int a = 0; a < 4; ++a)
-                for (int n = 0; n < Np; ++n) scale = std::max(scale, std::fabs(met[a][static_cast<size_t>(n) * K + k]));
-            for (int a = 0; a < 4 && para; ++a) {
-                double mean = 0.0;
-                for (int n = 0; n < Np; ++n) mean += met[a][static_cast<size_t>(n) * K + k];
-                mean /= Np;
-                for (int n = 0; n < Np; ++n)
-                    if (std::fabs(met[a][static_cast<size_t>(n) * K + k] - mean) > 1e-10 * scale) para = false;
-                ag[static_cast<size_t>(a) * ld + k] = mean;
-            }
-            for (int c = 0; c < 3 && para; ++c)
-                for (int f = 0; f < 4 && para; ++f) {
-                    double mean = 0.0, sc = 0.0;
-                    for (int n = 0; n < Nq; ++n) {
-                        const double v = fg[c][static_cast<size_t>(f * Nq + n) * K + k];
-                        mean += v;
-                        sc = std::max(sc, std::fabs(v));
-                    }
-                    mean /= Nq;
-                    if (c < 2) sc = 1.0;
-                    for (int n = 0; n < Nq; ++n)
-                        if (std::fabs(fg[c][static_cast<size_t>(f * Nq + n) * K + k] - mean) > 1e-10 * sc) para = false;
-                    ag[static_cast<size_t>(4 + 4 * c + f) * ld + k] = mean;
-                }
-        }
+        para = blitzdg::element_tables::parallelogramForm({d.rx, d.sx, d.ry, d.sy, nullptr, d.nx, d.ny, d.Fscale}, Np, Nq, K,
+                                                          static_cast<size_t>(ld), ag.data(), nullptr);
     }
     s->general = !para;
 

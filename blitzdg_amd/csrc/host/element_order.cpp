@@ -12,7 +12,7 @@ namespace element_order {
 // Breadth-first (Cuthill-McKee style) renumbering from the face-neighbour graph:
 // neighbours end up within O(sqrt(K)) slots of each other, so the trace gather of
 // a wave hits lines its own or nearby waves stream. perm[k] = device slot.
-std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp) {
+std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp, int faces) {
     std::vector<int> perm(K, -1);
     int next = 0;
     std::vector<int> frontier, nextFrontier;
@@ -23,8 +23,8 @@ std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp) {
         while (!frontier.empty()) {
             nextFrontier.clear();
             for (int k : frontier)
-                for (int f = 0; f < 3; ++f) {
-                    const int k2 = vmapP[(static_cast<size_t>(k) * 3 + f) * Nfp] / Np;
+                for (int f = 0; f < faces; ++f) {
+                    const int k2 = vmapP[(static_cast<size_t>(k) * faces + f) * Nfp] / Np;
                     if (k2 >= 0 && k2 < K && perm[k2] < 0) {
                         perm[k2] = next++;
                         nextFrontier.push_back(k2);
@@ -97,7 +97,7 @@ int patchSetting() {
 }
 
 std::vector<int> renumbering(const int* vmapP, int K, int Np, int Nfp, int patch) {
-    return patch <= 0 ? bfsOrder(vmapP, K, Np, Nfp) : patchOrder(vmapP, K, Np, Nfp, patch);
+    return patch <= 0 ? bfsOrder(vmapP, K, Np, Nfp, 3) : patchOrder(vmapP, K, Np, Nfp, patch);
 }
 
 int stageBytesPerElement(int order) {

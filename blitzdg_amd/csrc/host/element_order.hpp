@@ -15,8 +15,9 @@ namespace element_order {
 // shuffled mesh the caller's index inside a patch means nothing (0.32 ms against 0.39 ... 0.53).
 constexpr int kDefaultPatch = 0;
 
-// Breadth-first numbering from element 0. perm[k] = device slot.
-std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp);
+// Breadth-first numbering from element 0. perm[k] = device slot. `faces` is 3, or 4 for a quadrilateral mesh, whose
+// neighbour of face f is vmapP[(4 k + f) Nfp] / Np; every other function here is for triangles.
+std::vector<int> bfsOrder(const int* vmapP, int K, int Np, int Nfp, int faces);
 
 // Compact patches of `patch` elements grown over the face graph, slots handed out patch by patch and
 // by caller index inside a patch. perm[k] = device slot. patch >= K on a connected mesh is the identity.

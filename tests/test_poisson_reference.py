@@ -265,3 +265,27 @@ def test_a_mapD_entry_off_the_boundary_is_refused_without_a_gpu():
     h = ctypes.c_void_p()
     assert C.lib.bdg_poisson2d_create(ctypes.byref(d), ctypes.byref(h)) == C.BDG_ERR_ARGUMENT and not h.value
     assert b"boundary" in C.lib.bdg_last_error()
+
+
+def test_curved_triangles_and_bad_arguments_are_refused_on_the_host():
+    """The twin of test_quadpoisson_reference's quadrilateral refusals: these come before a device is looked for."""
+    from blitzdg_amd import _capi as C
+    from blitzdg_amd import poisson2d
+    t = small_tables(2, "box")
+    K = t["rx"].shape[1]
+
+    def refused(tables=t, **kw):
+        with pytest.raises(C.BdgError) as e:
+            poisson2d.Poisson2dSolver(tables=tables, **kw)
+        assert e.value.code == C.BDG_ERR_ARGUMENT
+        return str(e.value)
+
+    bent = dict(t, rx=t["rx"].copy())    # one node's rx off by 1e-6 of the element's metric terms: no longer affine at 1e-8
+    bent["rx"][1, 0] += 1e-6 * sum(abs(t[k][0, 0]) for k in ("rx", "sx", "ry", "sy"))
+    assert "straight-sided" in refused(bent, mapD=P.all_boundary(t))
+    assert "boundary face node" in refused(mapD=np.nonzero(~P.boundary_nodes(t))[0][:1])
+    assert "order" in refused(P.tables(dg.TriangleNodesProvisioner(9, P.box(4, 3))))
+    assert "per-node geometry" in refused(flags=poisson2d.NODAL_GEOMETRY)
+    for kappa in (0.0, -1.0, np.zeros(K)):
+        assert "kappa" in refused(kappa=kappa)
+    assert "sigma" in refused(shift=-0.1)

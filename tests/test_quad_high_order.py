@@ -8,7 +8,7 @@
     over both meshes (the test prints them per regime): N = 9 8.6e-15, N = 10 9.2e-15, N = 11 8.8e-15, N = 12 9.7e-15 (deep
     regime each time; the other regimes stay below 2.5e-15), so no order needs a wider GPU tolerance than 1e-12.
   * Mesh checks: the shear mesh passes the solver's parallelogram test, the jitter mesh fails it, K = 143 is ragged for the
-    tiles of 8 and 16, and the provisioner's tables have the tensor form that tensorFactors (sw2d_quad_device.hip) demands.
+    tiles of 8 and 16, and the provisioner's tables have the tensor form that tensorOperators (csrc/host/element_tables.cpp) demands.
   * bdg_sw2dq_create refuses orders 0 and 13 before it touches a device, and says 1..12.
   * sw2d_quad_output_kernel<9..12> compiled alone: no scratch, 512 (N+1)^2 bytes of LDS with the lattice, none without.
 """
@@ -115,7 +115,7 @@ def test_meshes_are_ragged_at_the_tiles_of_8_and_16(mesh):
 
 
 def tensor_form_errors(t):
-    """tensorFactors of sw2d_quad_device.hip in NumPy: (errD, tolD, errL, tolL)."""
+    """tensorOperators of csrc/host/element_tables.cpp in NumPy: (errD, tolD, errL, tolL)."""
     Nq = t["order"] + 1
     Dr, Ds, L = t["Dr"], t["Ds"], t["Lift"]
     D1 = Dr[::Nq, ::Nq]                               # D1[j, m] = Dr[Nq j, Nq m]

@@ -153,3 +153,33 @@ def test_the_heat_reference_is_stable_and_first_order():
           f"{np.abs(h['explicit'] - h['exact']).max():.3e}, allowance {h['allowance']:.1e}, bound {h['bound']:.4e}")
     assert h["rho_dt"] < 2
     assert np.abs(h["explicit"] - h["implicit"]).max() <= h["bound"]
+
+
+SHARED_REFUSALS = {
+    "kappa": lambda t: dict(kappa=0.0),
+    "kappa-per-element": lambda t: dict(kappa=np.zeros(t["x"].shape[1])),
+    "shift": lambda t: dict(shift=-0.1),
+    "tau-scale": lambda t: dict(tauScale=-1.0),
+    "mapD-interior": lambda t: dict(mapD=np.nonzero(~P.boundary_nodes(t))[0][:1]),
+    "mapD-range": lambda t: dict(mapD=[np.asarray(t["vmapM"]).size]),
+    "vmapP-range": lambda t: dict(tables=dict(t, vmapP=np.where(np.arange(np.asarray(t["vmapP"]).size) == 5, t["x"].size,
+                                                                np.asarray(t["vmapP"]).reshape(-1)))),
+    "J": lambda t: dict(tables=dict(t, J=-t["J"])),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SHARED_REFUSALS))
+def test_both_families_refuse_a_shared_bad_argument_in_the_same_words(name):
+    """One table builder serves triangles and quadrilaterals: after the name of the function the refusal reads the same."""
+    said = []
+    for cls, t in ((poisson2d.Poisson2dSolver, P.nodes_tables(2, 4, 3)[1]), (poisson2d.Poisson2dQuadSolver, Q.mesh_tables("shear", 2, 3, 2)[1])):
+        kw = dict(tables=t)
+        kw.update(SHARED_REFUSALS[name](t))
+        with pytest.raises(C.BdgError) as e:
+            cls(**kw)
+        assert e.value.code == C.BDG_ERR_ARGUMENT
+        _, named, text = str(e.value).partition(cls._CREATE + ": ")
+        assert named and text
+        said.append(text)
+    print(f"{name}: {said[0]}")
+    assert said[0] == said[1]
