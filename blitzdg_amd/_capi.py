@@ -84,6 +84,10 @@ class Sw2dDiffusionDesc(Structure):
     _fields_ = [("kappa", c_double), ("kappa_field", c_void_p), ("source", c_void_p), ("decay", c_double)]
 
 
+class Sw2dViscosityDesc(Structure):
+    _fields_ = [("nu", c_double), ("nu_field", c_void_p), ("smagorinsky", c_double)]
+
+
 class Poisson2dDesc(Structure):
     _fields_ = [("order", c_int), ("num_elements", c_int),
                 ("Dr", c_void_p), ("Ds", c_void_p), ("Lift", c_void_p), ("Vinv", c_void_p),
@@ -251,6 +255,9 @@ _SIGNATURES = {
     "bdg_sw2d_enable_variant_b4": (c_int, [_P, POINTER(Sw2dVbDesc), _P, c_int]),
     "bdg_sw2d_enable_tracer_diffusion": (c_int, [_P, POINTER(Sw2dDiffusionDesc)]),
     "bdg_sw2d_diffusion_dt": (c_int, [_P, POINTER(c_double)]),
+    "bdg_sw2d_enable_viscosity": (c_int, [_P, POINTER(Sw2dViscosityDesc)]),
+    "bdg_sw2d_viscosity_dt": (c_int, [_P, POINTER(c_double)]),
+    "bdg_sw2d_eddy_viscosity": (c_int, [_P, _P]),
     "bdg_sw2d_set_time": (c_int, [_P, c_double]),
     "bdg_sw2d_get_time": (c_int, [_P, POINTER(c_double)]),
     "bdg_sw2d_global_speed": (c_int, [_P, POINTER(c_double)]),

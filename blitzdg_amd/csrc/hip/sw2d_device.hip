@@ -16,6 +16,8 @@
 // variant-B launches, each followed by the tracer pass of sw2d_vb_tracer_kernel.hpp (per-order objects sw2d_vb4_order.hip).
 // After bdg_sw2d_enable_tracer_diffusion every evaluation of a four-field solver is followed by the two passes of
 // sw2d_diffusion_kernel.hpp (per-order objects sw2d_diffusion_order.hip), which add the tracer's diffusion, source and decay.
+// After bdg_sw2d_enable_viscosity every evaluation is also followed by the two passes of sw2d_viscosity_kernel.hpp (per-order objects
+// sw2d_viscosity_order.hip), which add the eddy viscosity's terms to the momentum planes and make the Heun step's sponge division.
 // After bdg_sw2d_enable_monitor the stepping calls record diagnostics and gauges on the device (sw2d_monitor_kernel.hpp).
 // After bdg_sw2d_enable_drifters they also advance Lagrangian drifters after every completed step (sw2d_drifter_kernel.hpp).
 #include "../host/capi_internal.hpp"
@@ -29,6 +31,7 @@
 #include "sw2d_launch_host.hpp"
 #include "sw2d_vb4_launch.hpp"
 #include "sw2d_diffusion_launch.hpp"
+#include "sw2d_viscosity_launch.hpp"
 #include "sw2d_drifter_kernel.hpp"
 #include <algorithm>
 #include <atomic>
@@ -108,6 +111,29 @@ const DiffusionKernelTable* diffusion_kernel_table(int order) {
     case 6: return diffusion_kernel_table_order6();
     case 7: return diffusion_kernel_table_order7();
     case 8: return diffusion_kernel_table_order8();
+    default: return nullptr;
+    }
+}
+
+const ViscosityKernelTable* viscosity_kernel_table_order1();
+const ViscosityKernelTable* viscosity_kernel_table_order2();
+const ViscosityKernelTable* viscosity_kernel_table_order3();
+const ViscosityKernelTable* viscosity_kernel_table_order4();
+const ViscosityKernelTable* viscosity_kernel_table_order5();
+const ViscosityKernelTable* viscosity_kernel_table_order6();
+const ViscosityKernelTable* viscosity_kernel_table_order7();
+const ViscosityKernelTable* viscosity_kernel_table_order8();
+
+const ViscosityKernelTable* viscosity_kernel_table(int order) {
+    switch (order) {
+    case 1: return viscosity_kernel_table_order1();
+    case 2: return viscosity_kernel_table_order2();
+    case 3: return viscosity_kernel_table_order3();
+    case 4: return viscosity_kernel_table_order4();
+    case 5: return viscosity_kernel_table_order5();
+    case 6: return viscosity_kernel_table_order6();
+    case 7: return viscosity_kernel_table_order7();
+    case 8: return viscosity_kernel_table_order8();
     default: return nullptr;
     }
 }
@@ -307,6 +333,21 @@ struct bdg_sw2d {
     double difDt = 0.0;                // c / (max kappa (N+1)^4 max(Fscale)^2), kDiffusionDtConstant below
     // dt_diff <= 2 / rho(operator) at every order with this constant: the smallest bound measured is 4.30 (N = 1)
     static constexpr double kDiffusionDtConstant = 4.0;
+    // eddy viscosity (bdg_sw2d_enable_viscosity): the passes of sw2d_viscosity_kernel.hpp behind the last launch of every evaluation
+    // (behind the tracer's diffusion where both are on). visOps / visOpsFiltered: VnOps images (the second on straight-sided
+    // elements with a Filter), visFilter: the Filter's rows (per-node geometry), visScratch: the four flux planes, the plane of nu
+    // and, per-node geometry with a Filter, the two planes of the unfiltered terms; visRed: partials and result of max nu
+    bool viscosity = false;
+    const bdg_dev::ViscosityKernelTable* ktv = nullptr;
+    bdg_dev::ViscosityParams vis{};
+    DevBuf<double> visNu0, visScratch, visOps, visOpsFiltered, visFilter, visRed;
+    double* visNuPlane = nullptr;
+    bool visSmagorinsky = false;
+    double visNu0Max = 0.0;            // max nu0, on the host at set-up
+    double visDtScale = 0.0;           // c / ((N+1)^4 max(Fscale)^2): dt_visc = visDtScale / max nu
+    // dt_visc <= 2 / rho(operator) at every order with this constant, nu a nodal field (tests/test_triviscosity_reference.py,
+    // DESIGN.md 3.7)
+    static constexpr double kViscosityDtConstant = 4.0;
     DevBuf<double> lamPair;            // two accumulators for the fused next-evaluation speed (alternating)
     int lamSlot = 0;
     // Direction of the tile sweep of whole-mesh stage launches (StageParams::sweepBack, sw2d_stage_tile.hpp): it alternates from
@@ -506,6 +547,25 @@ struct bdg_sw2d {
         hipStream_t st = on ? on : stream;
         auto sweep = [&] { nextSweep(p, wholeMesh); };
         evaluated = true;
+        // Eddy viscosity and the Heun step's sponge: q1 = sponge(q + dt (R + T)), and T cannot be added behind a store that has
+        // divided already. The stage launches run with the sponge off (a coefficient of 0 divides by exactly 1, or takes the
+        // instance without the division) and the viscosity's update divides planes 1 and 2 after adding T.
+        struct SpongeHandOver {
+            bdg_dev::StageParams& p;
+            bdg_dev::VbParams& vb;
+            double scalar;
+            const double* field;
+            bool on;
+            ~SpongeHandOver() {
+                if (on) { p.sponge = scalar; vb.sponge = field; }
+            }
+        } handOver{p, vb, p.sponge, vb.sponge, viscosity && mode == bdg_dev::MODE_COMBINE};
+        if (handOver.on) {
+            vis.sponge = p.sponge;
+            vis.spongeField = variantB ? vb.sponge : nullptr;
+            p.sponge = 0.0;
+            vb.sponge = nullptr;
+        }
         // Small launches (a rank's share of a many-way split, its partition-boundary strip) are bound by
         // the latency of one wavefront, not by HBM: the matrix-core kernel gives each wave 16 elements
         // instead of 64 (measured at N=4: 750 elements 7 us vs 19 us; 125 k elements 48 us vs 56 us;
@@ -658,6 +718,7 @@ struct bdg_sw2d {
             hipCheck(kt->stage(mode, filter, p, st), what);
         }
         if (diffusion) launchDiffusion(mode, filter, p, sweep, st);
+        if (viscosity) launchViscosity(mode, filter, p, sweep, st);
     }
 
     // The tracer's diffusion, source and decay of the evaluation whose launches were just issued on `st`: T of p.qin -- which
@@ -683,6 +744,67 @@ struct bdg_sw2d {
             sweep();
             hipCheck(ktd->filter(mode, p, dif, difFilter.p, st), "sw2d_tracer_diffusion_filter_kernel");
         }
+    }
+
+    // The eddy viscosity's terms of the evaluation whose launches were just issued on `st`: T_u, T_v of p.qin -- which those
+    // launches read and did not write -- added to planes 1 and 2 of what they wrote, then (a Heun stage) the sponge division the
+    // stage launch left out. Each launch takes the next direction of the alternating sweep. A filtered evaluation: pre-filtered
+    // rows on straight-sided elements (T is linear in the fluxes); per-node geometry: the unfiltered terms into two scratch
+    // planes and the Filter's rows over them in a third launch.
+    template <class Sweep>
+    void launchViscosity(int mode, bool filter, bdg_dev::StageParams& p, Sweep&& sweep, hipStream_t st) {
+        const bool nodal = !affine;
+        if (mode == bdg_dev::MODE_RHS ? p.qin == p.rhs : (p.qin == p.qout || p.qin == p.res))
+            throw std::logic_error("eddy viscosity: the stage's input state is one of its output buffers");
+        bdg_dev::ViscosityParams v = vis;
+        v.nuOut = nullptr;
+        if (mode != bdg_dev::MODE_COMBINE) { v.sponge = 0.0; v.spongeField = nullptr; }
+        sweep();
+        hipCheck(ktv->gradient(nodal, p, v, visOps.p, st), "sw2d_viscosity_gradient_kernel");
+        sweep();
+        const char* what = "sw2d_viscosity_divergence_kernel";
+        if (!filter) {
+            hipCheck(ktv->divergence(mode, nodal, false, p, v, visOps.p, st), what);
+        } else if (!nodal) {
+            hipCheck(ktv->divergence(mode, false, false, p, v, visOpsFiltered.p, st), what);
+        } else {
+            hipCheck(ktv->divergence(mode, true, true, p, v, visOps.p, st), what);
+            sweep();
+            hipCheck(ktv->filter(mode, p, v, visFilter.p, st), "sw2d_viscosity_filter_kernel");
+        }
+        // variant B's unrolled stage kernel reduced the speed of the state it wrote for the next evaluation: that state's momentum
+        // has changed since, so the next evaluation runs its own speed pass
+        if (mode != bdg_dev::MODE_RHS) lamStateFor = nullptr;
+    }
+    // nu of the resident state into visNuPlane: the first pass alone (its fluxes are scratch between evaluations)
+    void launchEddyViscosity() {
+        bdg_dev::StageParams p = baseParams();
+        p.qin = qcur;
+        nextSweep(p, true);
+        bdg_dev::ViscosityParams v = vis;
+        v.nuOut = visNuPlane;
+        hipCheck(ktv->gradient(!affine, p, v, visOps.p, stream), "sw2d_viscosity_gradient_kernel");
+    }
+    // dt_visc = c / (max nu (N+1)^4 max(Fscale)^2), max nu of the resident state (Smagorinsky: a launch and a fixed-order reduction)
+    double viscosityDt() {
+        double numax = visNu0Max;
+        if (visSmagorinsky) {
+            launchEddyViscosity();
+            hipCheck(ktv->maxOf(visNuPlane, static_cast<long long>(planeSize()), visRed.p, visRed.p + bdg_dev::kViscosityMaxBlocks, stream),
+                     "sw2d_viscosity_max_kernel");
+            hipCheck(hipMemcpyAsync(&numax, visRed.p + bdg_dev::kViscosityMaxBlocks, sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
+            hipCheck(hipStreamSynchronize(stream), "sync");
+        }
+        return numax > 0.0 ? visDtScale / numax : std::numeric_limits<double>::infinity();
+    }
+    // max |Fscale| over the mesh, from the plane the time-step reduction reads (padding columns are zero)
+    double maxFscale() {
+        std::vector<double> fs(static_cast<size_t>(NFN) * ld);
+        hipCheck(hipMemcpyAsync(fs.data(), fscaleNodal, fs.size() * sizeof(double), hipMemcpyDeviceToHost, stream), "D2H copy");
+        hipCheck(hipStreamSynchronize(stream), "sync");
+        double fmax = 0.0;
+        for (double v : fs) fmax = std::max(fmax, std::fabs(v));
+        return fmax;
     }
 
     // Variant B with the tracer: plane 3 of the evaluation whose three-field launch(es) were just issued on `st` -- same input
@@ -1817,12 +1939,7 @@ int bdg_sw2d_enable_tracer_diffusion(bdg_sw2d* s, const bdg_sw2d_diffusion_desc*
                 s->difOpsFiltered.upload(rowOpsImage(s->hostFDr.data(), s->hostFDs.data(), s->hostFLift.data(), s->Np, s->NFN), s->bytes,
                                          "filtered diffusion row ops upload");
         }
-        // max(Fscale) over the mesh, from the plane the time-step reduction reads (padding columns are zero)
-        std::vector<double> fs(static_cast<size_t>(s->NFN) * s->ld);
-        hipCheck(hipMemcpyAsync(fs.data(), s->fscaleNodal, fs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream), "D2H copy");
-        hipCheck(hipStreamSynchronize(s->stream), "sync");
-        double fmax = 0.0;
-        for (double v : fs) fmax = std::max(fmax, std::fabs(v));
+        const double fmax = s->maxFscale();
         const double n1 = static_cast<double>(s->N + 1);
         s->difDt = kmax > 0.0 ? bdg_sw2d::kDiffusionDtConstant / (kmax * n1 * n1 * n1 * n1 * fmax * fmax) : std::numeric_limits<double>::infinity();
         s->ktd = ktd;
@@ -1837,6 +1954,84 @@ int bdg_sw2d_diffusion_dt(const bdg_sw2d* s, double* dt_diff) {
         if (!dt_diff) throw arg_error("bdg_sw2d_diffusion_dt: NULL argument");
         if (!s->diffusion) throw arg_error("bdg_sw2d_diffusion_dt: tracer diffusion is not enabled");
         *dt_diff = s->difDt;
+    });
+}
+
+int bdg_sw2d_enable_viscosity(bdg_sw2d* s, const bdg_sw2d_viscosity_desc* d) {
+    return guard([&] {
+        const std::string fn = "bdg_sw2d_enable_viscosity";
+        requireSolver(s, fn.c_str());
+        if (!d) throw arg_error(fn + ": NULL descriptor");
+        if (s->viscosity) throw arg_error(fn + ": eddy viscosity is already enabled on this solver; the call is made once");
+        if (s->evaluated)
+            throw arg_error(fn + ": the solver has evaluated a right-hand side already; viscosity is enabled before the first evaluation");
+        if (s->partitionSet) throw arg_error(fn + ": the solver has a partition set; the viscosity passes cover a single domain only");
+        if (!(d->smagorinsky >= 0.0) || !std::isfinite(d->smagorinsky)) throw arg_error(fn + ": smagorinsky must be finite and >= 0");
+        const size_t nodesTotal = static_cast<size_t>(s->Np) * s->K;
+        double numax = d->nu;
+        if (d->nu_field) {
+            numax = 0.0;
+            for (size_t i = 0; i < nodesTotal; ++i) {
+                const double v = d->nu_field[i];
+                if (!(v >= 0.0) || !std::isfinite(v)) throw arg_error(fn + ": nu must be finite and >= 0 at every node");
+                numax = std::max(numax, v);
+            }
+        } else if (!(d->nu >= 0.0) || !std::isfinite(d->nu)) {
+            throw arg_error(fn + ": nu must be finite and >= 0");
+        }
+        if (numax == 0.0 && d->smagorinsky == 0.0) throw arg_error(fn + ": nu and smagorinsky are both zero: there is no viscosity to enable");
+        const bdg_dev::ViscosityKernelTable* ktv = bdg_dev::viscosity_kernel_table(s->N);
+        if (!ktv) throw arg_error(fn + ": no viscosity kernels compiled for this order");
+        s->use();
+        const double n1 = static_cast<double>(s->N + 1);
+        bdg_dev::ViscosityParams vp{};
+        vp.nu = d->nu_field ? 0.0 : d->nu;
+        vp.cs2d2 = d->smagorinsky * d->smagorinsky * 2.0 / (n1 * n1);
+        vp.nuField = s->uploadPlane(d->nu_field, s->visNu0);
+        const size_t pl = s->planeSize();
+        const bool rawPlanes = s->hasFilter && !s->affine;
+        s->visScratch.alloc((rawPlanes ? 7 : 5) * pl, s->bytes);
+        hipCheck(hipMemsetAsync(s->visScratch.p, 0, s->visScratch.n * sizeof(double), s->stream), "hipMemset");
+        vp.flux = s->visScratch.p;
+        s->visNuPlane = s->visScratch.p + 4 * pl;
+        vp.raw = rawPlanes ? s->visScratch.p + 5 * pl : nullptr;
+        s->visRed.alloc(bdg_dev::kViscosityMaxBlocks + 1, s->bytes);
+        s->visOps.upload(rowOpsImage(s->hostDr.data(), s->hostDs.data(), s->hostLift.data(), s->Np, s->NFN), s->bytes, "viscosity row ops upload");
+        if (s->hasFilter) {
+            if (s->affine)
+                s->visOpsFiltered.upload(rowOpsImage(s->hostFDr.data(), s->hostFDs.data(), s->hostFLift.data(), s->Np, s->NFN), s->bytes,
+                                         "filtered viscosity row ops upload");
+            else
+                s->visFilter.upload(s->hostFilter, s->bytes, "viscosity filter upload");
+        }
+        const double fmax = s->maxFscale();
+        s->visDtScale = bdg_sw2d::kViscosityDtConstant / (n1 * n1 * n1 * n1 * fmax * fmax);
+        s->visNu0Max = numax;
+        s->visSmagorinsky = d->smagorinsky > 0.0;
+        s->ktv = ktv;
+        s->vis = vp;
+        s->viscosity = true;
+    });
+}
+
+int bdg_sw2d_viscosity_dt(bdg_sw2d* s, double* dt_visc) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2d_viscosity_dt");
+        if (!dt_visc) throw arg_error("bdg_sw2d_viscosity_dt: NULL argument");
+        if (!s->viscosity) throw arg_error("bdg_sw2d_viscosity_dt: eddy viscosity is not enabled");
+        s->use();
+        *dt_visc = s->viscosityDt();
+    });
+}
+
+int bdg_sw2d_eddy_viscosity(bdg_sw2d* s, double* nu) {
+    return guard([&] {
+        requireSolver(s, "bdg_sw2d_eddy_viscosity");
+        if (!nu) throw arg_error("bdg_sw2d_eddy_viscosity: NULL argument");
+        if (!s->viscosity) throw arg_error("bdg_sw2d_eddy_viscosity: eddy viscosity is not enabled");
+        s->use();
+        s->launchEddyViscosity();
+        s->downloadRows(s->visNuPlane, nu, s->Np);
     });
 }
 
@@ -1958,6 +2153,7 @@ int bdg_sw2d_compute_dt(bdg_sw2d* s, double cfl, double* dt, double* eta_max) {
         if (eta_max) *eta_max = r[1];
         if (dt) *dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * r[0]);
         if (dt && s->diffusion) *dt = std::min(*dt, cfl * s->difDt);
+        if (dt && s->viscosity) *dt = std::min(*dt, cfl * s->viscosityDt());
         if (std::isnan(r[0]) || std::isnan(r[1]) || std::fabs(r[1]) > 1e8)
             throw unstable_error("A numerical instability has occurred!");
     });
@@ -1983,6 +2179,7 @@ int bdg_sw2d_run_adaptive(bdg_sw2d* s, double cfl, double final_time, int max_st
                 throw unstable_error("A numerical instability has occurred!");
             dt = cfl / ((s->N + 1) * (s->N + 1) * 0.5 * r[0]);
             if (s->diffusion) dt = std::min(dt, cfl * s->difDt);
+            if (s->viscosity) dt = std::min(dt, cfl * s->viscosityDt());
             t += dt;
             ++done;
             *t_inout = t;
@@ -2017,6 +2214,8 @@ int bdg_sw2d_set_partition(bdg_sw2d* s, int num_interior, int num_owned, const i
         requireSolver(s, "bdg_sw2d_set_partition");
         if (s->diffusion)
             throw arg_error("bdg_sw2d_set_partition: the solver has tracer diffusion, whose passes cover a single domain only");
+        if (s->viscosity)
+            throw arg_error("bdg_sw2d_set_partition: the solver has eddy viscosity, whose passes cover a single domain only");
         if (s->drf.on)
             throw arg_error("bdg_sw2d_set_partition: the solver has drifters, which do not migrate between ranks (single domain only)");
         if (s->fst.on)

@@ -372,6 +372,15 @@ class NativeDistributedSw2d:
 
     enableTracerDiffusion = enable_tracer_diffusion
 
+    def enable_viscosity(self, *args, **kwargs):
+        """Not built: the viscosity passes of Sw2dSolver.enableViscosity read the neighbours' fluxes of the first pass, which a
+        partition would have to exchange between the two; they cover a single domain only."""
+        raise NotImplementedError("eddy viscosity is not available on a partitioned solver (NativeDistributedSw2d): the second "
+                                  "pass needs the neighbours' fluxes of the first, which are not exchanged; run a single domain "
+                                  "with Sw2dSolver.enableViscosity")
+
+    enableViscosity = enable_viscosity
+
     def allreduce_max(self, value):
         out = self._c_double()
         self._check(self._lib.bdg_sw2d_allreduce_max(self.solver._h, float(value), self._byref(out)))

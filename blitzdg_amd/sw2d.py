@@ -185,6 +185,30 @@ class Sw2dSolver(RunRecords):
         check(lib.bdg_sw2d_diffusion_dt(self._h, byref(v)))
         return v.value
 
+    # ---- eddy viscosity, constant or Smagorinsky
+    def enableViscosity(self, nu=0.0, smagorinsky=0.0):
+        """d(hu)/dt and d(hv)/dt gain div(nu h grad u) and div(nu h grad v) with u = hu / h, v = hv / h and
+        nu = nu0 + Cs^2 D^2 |S|, D^2 = 2 J / (N+1)^2 (local DG, central fluxes; free slip at walls and at the open boundary).
+        ``nu``: nu0, a scalar or an (Np, K) array, >= 0; ``smagorinsky``: Cs >= 0. On any solver kind, once, before its first
+        evaluation; afterwards computeRHS / computeRHS4 and every stepper include the terms, and computeDt / runAdaptive return
+        min(advective dt, CFL * viscosityDt(), CFL * diffusionDt() if the tracer diffuses). The library refuses bad values
+        (BdgError)."""
+        field = None if np.ndim(nu) == 0 else self._field(nu, "nu")
+        d = C.Sw2dViscosityDesc(float(nu) if field is None else 0.0, C.ptr(field), float(smagorinsky))
+        check(lib.bdg_sw2d_enable_viscosity(self._h, byref(d)))
+
+    def viscosityDt(self):
+        """dt_visc = 4 / (max nu (N+1)^4 max(Fscale)^2), max nu over the nodes of the current state."""
+        v = c_double()
+        check(lib.bdg_sw2d_viscosity_dt(self._h, byref(v)))
+        return v.value
+
+    def eddyViscosity(self):
+        """The (Np, K) field nu = nu0 + Cs^2 D^2 |S| of the current state."""
+        out = np.empty((self.Np, self.K))
+        check(lib.bdg_sw2d_eddy_viscosity(self._h, C.ptr(out)))
+        return out
+
     @property
     def time(self):
         t = c_double()

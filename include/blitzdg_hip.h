@@ -379,6 +379,34 @@ typedef struct bdg_sw2d_diffusion_desc {
 } bdg_sw2d_diffusion_desc;
 int bdg_sw2d_enable_tracer_diffusion(bdg_sw2d* s, const bdg_sw2d_diffusion_desc* desc);
 int bdg_sw2d_diffusion_dt(const bdg_sw2d* s, double* dt_diff);
+/* Horizontal eddy viscosity on the momentum of a triangle solver, constant or Smagorinsky (the definition is
+ * restated in tests/triviscosity_ref.py). With u = hu / h and v = hv / h at every node,
+ *   d(hu)/dt += div(nu h grad u),  d(hv)/dt += div(nu h grad v),
+ *   nu = nu0 + Cs^2 D^2 |S|,  |S| = sqrt(2 u_x^2 + 2 v_y^2 + (u_y + v_x)^2),  D^2 = 2 J / (N+1)^2,
+ * in the tracer diffusion's discretisation: local DG, central fluxes, no penalty; a face node with vmapP == vmapM (walls and the
+ * open boundary alike) carries no viscous stress (free slip). The gradients in |S| are the ones that diffuse, lifts included.
+ * nu: nu0 >= 0, used when nu_field is NULL; nu_field: (Np, K) nu0 >= 0 or NULL; smagorinsky: Cs >= 0 (0: off). Once, before the
+ * solver's first evaluation, on any solver kind: three or four fields, with or without sources, variant B with or without a
+ * tracer, with or without bdg_sw2d_enable_tracer_diffusion, in either order. From then on every evaluation's launches are
+ * followed on the same stream by the two passes of sw2d_viscosity_kernel.hpp, which add the terms to planes 1 and 2 of what the
+ * evaluation wrote (a filtered evaluation adds their filtered form); planes 0 and 3 and every existing kernel are untouched. A
+ * Heun step with a sponge is q1 = sponge(q + dt (R + T)): the stage launches run with the sponge off and the viscosity's update
+ * makes the division. BDG_ERR_ARGUMENT, nothing changed: a NULL handle or descriptor, nu or smagorinsky negative or not finite
+ * (scalar or any entry), both zero, a second call, after the first evaluation, a solver with a partition set
+ * (bdg_sw2d_set_partition on a viscous solver is refused as well). bdg_sw2d_compute_dt and bdg_sw2d_run_adaptive then return
+ * min(advective dt, cfl * dt_visc, cfl * dt_diff if the tracer diffuses), dt_visc = 4 / (max nu (N+1)^4 max(Fscale)^2) with max nu
+ * over the nodes of the CURRENT state (Cs > 0: one launch and a fixed-order reduction; Cs = 0: max nu0 from set-up).
+ * bdg_sw2d_viscosity_dt returns dt_visc; bdg_sw2d_eddy_viscosity writes the (Np, K) field nu of the current state (both
+ * BDG_ERR_ARGUMENT without viscosity). bdg_sw2d_device_bytes counts four flux planes, the plane of nu, the plane of nu0 if it is a
+ * field and, per-node geometry with a Filter, two planes of unfiltered terms. */
+typedef struct bdg_sw2d_viscosity_desc {
+    double nu;              /* used when nu_field is NULL                   */
+    const double* nu_field; /* (Np, K) or NULL                              */
+    double smagorinsky;     /* Cs >= 0                                      */
+} bdg_sw2d_viscosity_desc;
+int bdg_sw2d_enable_viscosity(bdg_sw2d* s, const bdg_sw2d_viscosity_desc* desc);
+int bdg_sw2d_viscosity_dt(bdg_sw2d* s, double* dt_visc);
+int bdg_sw2d_eddy_viscosity(bdg_sw2d* s, double* nu);
 int bdg_sw2d_set_time(bdg_sw2d* s, double t);
 int bdg_sw2d_get_time(const bdg_sw2d* s, double* t);
 /* The global Lax-Friedrichs speed of the most recent variant-B evaluation. */
